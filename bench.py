@@ -1,7 +1,14 @@
 """Benchmark of the hot path: DualGNN forward + loss + backward (+ optimiser step) on synthetic meshes.
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W     (N > 1: launched through
-torch.distributed.run, one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.
+torch.distributed.run, one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times
+the K steps and prints the line (`value`, `ms_per_step`, `config`); `roofline`, `roofline_mfma`, `extra` and
+`cpu_baseline` below are measured only with --full (each can then be dropped again with --no-roofline, --no-extra,
+--no-cpu-baseline).
+--dump-outputs DIR  after the timed steps, rank 0 writes what the last of them computed as DIR/<name>.npy (float32):
+          pred_vertices, pred_normals, loss, loss_v, loss_n, and the flat gradient bucket `grad` and parameters `params`
+          after the optimiser step (above 64 MB in all: a fixed, seeded sample of each array).  Inputs and initial
+          weights are seeded: the same arguments give the same inputs.
 
 Workload = BASELINE.json configs[2] "Synthetic train, batch=4 meshes (~20k faces each), fwd+bwd":
 per rank and step, 4 noisy icospheres of frequency 32 (F = 20 480, V = 10 242; 337 862 level-0
@@ -13,13 +20,13 @@ Timed region: forward, loss, backward, gradient all-reduce, optimiser step.  Inp
 in HBM before the clock starts.
 
 metric  M-edges/s = level-0 edge_index columns of all meshes of all ranks / wall seconds.
-roofline  the forward fused FeaSt kernel (aggregation -- the "scatter-add" of the path -- with the node
+roofline  (--full) the forward fused FeaSt kernel (aggregation -- the "scatter-add" of the path -- with the node
           transform fused behind it), its dominant instantiation: ALGORITHMIC bytes (SURVEY.md 8d,
           B_agg with the fused write term 4 N C_out) / launch time measured with HIP events on the
           launch stream in a separate pass; `traffic` / `frac_by_counters` quote the committed PMC passes.
-cpu_baseline  the PyG-shaped CPU oracle (same op decomposition as the reference) on ONE mesh of
+cpu_baseline  (--full) the PyG-shaped CPU oracle (same op decomposition as the reference) on ONE mesh of
           the same size, all host cores, rank 0 at N = 1 only.
-extra     rank 0 at N = 1, after the timed region (never part of `value`):
+extra     (--full) rank 0 at N = 1, after the timed region (never part of `value`):
           infer        BASELINE configs[1] (one mesh n = 32) and configs[3] (one unsplit scan n = 87): network ms,
                        M-edges/s and the fused kernel's algorithmic fraction of the HBM peak (test_dual.py:18-22,44-87)
           fresh_batch  ms/step when every step unions 4 OTHER pre-processed meshes from a pool of 12 (what a loader
@@ -70,17 +77,37 @@ def make_batch(rank, device, freq=FREQ, batch=BATCH, groups=1):
     return dv.to(device), df.to(device), edges, parts
 
 
-def grouped_step(tg, bucket, opt, collective=True):
+def grouped_step(tg, bucket, opt, collective=True, keep=None):
     """The same optimiser step with the batch's meshes as mesh groups in flight together (executor.TrainGroups: the
-    iterations of the reference's accumulation loop, train_dual.py:199-218, overlapped; gradients summed in group order)."""
+    iterations of the reference's accumulation loop, train_dual.py:199-218, overlapped; gradients summed in group order).
+    `keep` (a dict, or None) receives the step's per-group losses; grouped_outputs() turns them into the step's outputs
+    after the clock has stopped."""
+    seq = tg.sequential_steps
     losses = tg.step()
     if collective:
         bucket.all_reduce_mean()
     opt.step()
+    if keep is not None:
+        keep.update(group_losses=losses, sequential=tg.sequential_steps != seq)
     return losses
 
 
-def train_step(net, bucket, opt, dv0, df0, collective=True):
+def grouped_outputs(tg, keep):
+    """What grouped_step() kept of the last step -> the same outputs train_step() keeps: predictions of the groups
+    concatenated in mesh order (tg.prediction() views stay valid until the next step), summed losses."""
+    if keep.pop('sequential'):
+        raise SystemExit('bench.py --dump-outputs: the last grouped step ran group by group (module path), which '
+                         'keeps no predictions')
+    losses = keep.pop('group_losses')
+    preds = [tg.prediction(k) for k in range(len(tg.groups))]
+    lv, ln = losses[:, 0].sum(), losses[:, 1].sum()
+    keep.update(pred_vertices=torch.cat([p[0] for p in preds]), pred_normals=torch.cat([p[1] for p in preds]),
+                loss_v=lv, loss_n=ln, loss=lv + ln)
+    return keep
+
+
+def train_step(net, bucket, opt, dv0, df0, collective=True, keep=None):
+    """One optimiser step; `keep` (a dict, or None) receives the step's predictions and losses."""
     from geobi_gnn_amd import network
     from geobi_gnn_amd.parallel import batched_losses
     bucket.zero()
@@ -88,6 +115,8 @@ def train_step(net, bucket, opt, dv0, df0, collective=True):
     vp, npred, _ = net((dv, df))
     lv, ln = batched_losses(vp, npred, dv0, df0, 'L1', 'L1')
     loss = network.dual_loss(lv, ln)
+    if keep is not None:
+        keep.update(pred_vertices=vp, pred_normals=npred, loss_v=lv, loss_n=ln, loss=loss)
     split = collective and SPLIT_ALLREDUCE is not None
     if split:
         from geobi_gnn_amd import executor
@@ -540,6 +569,35 @@ def cpu_baseline(freq=FREQ, timed=3, warm=1):
                       (freq, 20 * freq * freq, edges, timed, warm, med, torch.__version__)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, kept, flat, bucket):
+    """--dump-outputs: what the last timed step handed its caller -- predicted vertices and normals of the batch, the
+    losses -- and the state it left behind: the flat gradient bucket (all-reduced at N > 1) and the flat parameters
+    after the optimiser step.  float32 .npy files, ~9 MB in all on the bench workload.  Above DUMP_LIMIT_BYTES in all,
+    every array is cut to the same seeded sample of its elements (flattened, in index order) for every run."""
+    import numpy as np
+    arrays = {k: np.atleast_1d(v.detach().float().cpu().numpy()) for k, v in kept.items()}
+    arrays['grad'] = bucket.flat.detach().float().cpu().numpy()
+    arrays['params'] = flat.flat_param.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(0)
+        share = (DUMP_LIMIT_BYTES - 4096) / float(total)      # the margin covers arrays too small to cut
+        for name in sorted(arrays):
+            a = arrays[name].reshape(-1)
+            n = max(1, int(a.size * share))
+            if n < a.size:
+                arrays[name] = a[np.sort(rng.choice(a.size, n, replace=False))]
+        log('outputs sampled: %.1f MB in all exceed the %.0f MB limit' % (total / 1e6, DUMP_LIMIT_BYTES / 2.0 ** 20))
+        total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    log('outputs of the last timed step: %s (%.1f MB) in %s' % (', '.join(sorted(arrays)), total / 1e6, out_dir))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -595,11 +653,18 @@ def main():
     ap.add_argument('--freq', type=int, default=FREQ, help=argparse.SUPPRESS)
     ap.add_argument('--groups', type=int, default=int(os.environ.get('GEOBI_BENCH_GROUPS', '1')),
                     help='mesh groups in flight together per step (1: the batch as one union graph on one stream)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip extra.infer / extra.fresh_batch')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure roofline / roofline_mfma, extra and cpu_baseline '
+                         '(a plain run reports the timed steps only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip roofline / roofline_mfma')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip extra')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32)')
     ap.add_argument('--plumbing', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -663,10 +728,10 @@ def main():
         from geobi_gnn_amd.executor import TrainGroups
         tg = TrainGroups(net, bucket, 'L1', 'L1').set_groups(parts)
 
-    def one_step():
+    def one_step(keep=None):
         if tg is not None:
-            return grouped_step(tg, bucket, opt)
-        return train_step(net, bucket, opt, dv, df)
+            return grouped_step(tg, bucket, opt, keep=keep)
+        return train_step(net, bucket, opt, dv, df, keep=keep)
 
     log('rank %d: batch resident (%d edges), warming up' % (rank, edges))
     for _ in range(args.warmup):
@@ -678,10 +743,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    kept = {} if args.dump_outputs else None
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = one_step()
+    for i in range(args.steps):
+        loss = one_step(kept if i == args.steps - 1 else None)
     fence()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -691,6 +757,10 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.SUM)
     my_ms = elapsed / args.steps * 1e3
     elapsed, total_edges = float(t.item()), float(e.item())
+    if kept is not None and rank == 0:
+        if tg is not None:
+            grouped_outputs(tg, kept)
+        dump_outputs(args.dump_outputs, kept, flat, bucket)        # before anything below moves the weights again
     mr = None
     if world > 1:
         # the line must explain a scaling loss by itself: every rank's own step time and the all-reduce alone
@@ -715,8 +785,8 @@ def main():
                                '[BASELINE.json configs[2]]: per rank 4 noisy icospheres n=%d (F=%d) as one '
                                'disjoint-union graph, L1/L1 loss, grad all-reduce + Adam step inside the timed '
                                'region; ONE resident batch replayed every step, its level-0 CSR / reverse-edge index / '
-                               'corner lists / loss weights built in warm-up and cached per mesh (extra.fresh_batch: '
-                               'other meshes every step)' % (args.freq, 20 * args.freq ** 2),
+                               'corner lists / loss weights built in warm-up and cached per mesh (with --full, '
+                               'extra.fresh_batch: other meshes every step)' % (args.freq, 20 * args.freq ** 2),
                    'meshes_per_rank': BATCH, 'edges_per_rank_step': edges, 'parallelism': 'dp%d' % world,
                    'mesh_groups_in_flight': args.groups, 'split_allreduce': SPLIT_ALLREDUCE is not None,
                    'collective': ('none' if world == 1 else
@@ -728,7 +798,7 @@ def main():
     if rehearsal:
         out['config']['rehearsal'] = ('%d ranks share device 0 over gloo (fewer devices than ranks): checks the '
                                       'multi-rank path, NOT a scaling measurement' % world)
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_roofline:
             out['roofline'] = measure_roofline(net, bucket, opt, dv, df)
             out['roofline_mfma'] = measure_mfma(net, bucket, opt, dv, df)

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*argv):
+def _bench(*argv, **kw):
+    """-> the JSON line of `bench.py argv` (and its stderr with stderr=True)."""
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
@@ -22,11 +23,11 @@ def _bench(*argv):
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
-    return json.loads(lines[0])
+    return (json.loads(lines[0]), r.stderr) if kw.get('stderr') else json.loads(lines[0])
 
 
 def test_bench_line_single_gpu():
-    out = _bench('--steps', '3', '--warmup', '1', '--no-cpu-baseline')
+    out = _bench('--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline')
     assert out['n_gpus'] == 1 and out['steps'] == 3 and out['warmup'] == 1
     assert out['unit'] == 'M-edges/s' and out['value'] > 0 and out['higher_is_better'] is True
     assert out['scaling'] == 'weak' and out['dtype'] == 'f32' and out['vs_baseline'] is None
@@ -46,6 +47,40 @@ def test_bench_line_single_gpu():
     assert fb['ms_per_step'] > 0 and fb['structure_build_ms_per_mesh'] > 0
     # 4 fresh meshes of the bench size per step: the same edge count as the replayed batch
     assert abs(fb['M_edges_per_s'] * fb['ms_per_step'] - out['config']['edges_per_rank_step'] / 1e3) < 1e-2 * out['config']['edges_per_rank_step'] / 1e3
+
+
+def _dumped(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times its steps and reports only them; --dump-outputs writes the last timed step's results, the same
+    ones run after run with the same arguments; --steps sets how many steps run after the warm-up."""
+    import numpy as np
+    out, err = _bench('--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path / 'a'), stderr=True)
+    assert out['n_gpus'] == 1 and out['steps'] == 2 and out['warmup'] == 1 and out['ms_per_step'] > 0
+    assert out['unit'] == 'M-edges/s' and out['value'] > 0 and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert not {'roofline', 'roofline_mfma', 'extra', 'cpu_baseline'} & set(out)
+    assert 'timed 2 steps' in err
+    arrays = _dumped(str(tmp_path / 'a'))
+    assert set(arrays) == {'pred_vertices', 'pred_normals', 'loss', 'loss_v', 'loss_n', 'grad', 'params'}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays['pred_vertices'].shape == (4 * 10242, 3) and arrays['pred_normals'].shape == (4 * 20480, 3)
+    assert arrays['grad'].shape == arrays['params'].shape == (939128,)
+    assert abs(float(arrays['loss'][0]) - out['config']['final_loss']) < 1e-5 * max(1.0, abs(out['config']['final_loss']))
+    assert abs(float(arrays['loss'][0]) - float(arrays['loss_v'][0] + arrays['loss_n'][0])) < 1e-5
+    # same arguments, same inputs: the second process computes the same outputs bit for bit
+    _bench('--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path / 'b'))
+    again = _dumped(str(tmp_path / 'b'))
+    assert set(again) == set(arrays) and all(np.array_equal(arrays[k], again[k]) for k in arrays)
+    # one more timed step is one more optimiser step; three steps split 2 + 1 (warm-up + timed) end where 1 + 2 did
+    more, err = _bench('--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / 'c'), stderr=True)
+    assert more['steps'] == 3 and 'timed 3 steps' in err
+    assert not np.array_equal(_dumped(str(tmp_path / 'c'))['params'], arrays['params'])
+    moved = _bench('--steps', '1', '--warmup', '2', '--dump-outputs', str(tmp_path / 'd'))
+    assert moved['steps'] == 1 and np.array_equal(_dumped(str(tmp_path / 'd'))['params'], arrays['params'])
 
 
 def test_bench_two_ranks_from_a_bare_shell():

@@ -433,6 +433,41 @@ def test_bench_relays_a_failing_child_and_checks_world_size():
     assert r.returncode != 0 and 'WORLD_SIZE=1 but --gpus 2' in r.stderr
 
 
+def test_bench_refuses_zero_timed_steps():
+    # --steps sets the number of timed steps; ms_per_step needs at least one
+    r = _run_bench('--steps', '0')
+    assert r.returncode == 2 and '--steps must be >= 1' in r.stderr and r.stdout.strip() == ''
+    r = _run_bench('--help')
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout
+
+
+def test_bench_dump_outputs_samples_above_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: whole arrays under the size limit; above it the same seeded sample of every
+    array's elements, within the limit, run after run."""
+    import types
+    import bench
+    g = torch.Generator().manual_seed(3)
+    kept = {'pred_vertices': torch.randn(5000, 3, generator=g), 'loss': torch.tensor(0.25)}
+    flat = types.SimpleNamespace(flat_param=torch.randn(20000, generator=g))
+    bucket = types.SimpleNamespace(flat=torch.randn(20000, generator=g))
+    bench.dump_outputs(str(tmp_path / 'whole'), kept, flat, bucket)
+    whole = {f[:-4]: np.load(str(tmp_path / 'whole' / f)) for f in os.listdir(str(tmp_path / 'whole'))}
+    assert set(whole) == {'pred_vertices', 'loss', 'grad', 'params'}
+    assert np.array_equal(whole['pred_vertices'], kept['pred_vertices'].numpy()) and whole['loss'].tolist() == [0.25]
+    assert np.array_equal(whole['params'], flat.flat_param.numpy()) and np.array_equal(whole['grad'], bucket.flat.numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 100000)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ('sampled%d' % k)
+        bench.dump_outputs(str(d), kept, flat, bucket)
+        runs.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    a, b = runs
+    assert sum(x.nbytes for x in a.values()) <= 100000
+    assert all(x.dtype == np.float32 for x in a.values()) and a['loss'].tolist() == [0.25]
+    assert 0 < a['params'].size < 20000 and np.isin(a['params'], flat.flat_param.numpy()).all()
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def _opt(**kw):
     import argparse
     from geobi_gnn_amd import train_util
