@@ -1,0 +1,139 @@
+"""Command line of the package: denoise a folder of OBJ meshes, score a folder of results.
+
+  python -m geobi_gnn_amd denoise --model net.pt --data_dir DIR [--out_dir DIR/result] [--sub_size 20000]
+  python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
+
+`denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
+present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
+and as face-weighted means; otherwise every DIR/*.obj is denoised without ground truth.  `eval` is
+data_util.eval_denoising_result (code/data_util.py:559-638).  All device work runs in this one process.
+"""
+import argparse
+import glob
+import os
+import sys
+import time
+
+import numpy as np
+
+
+def _denoise_list(data_dir):
+    """[(noisy file, ground-truth file or None)] in sorted order."""
+    original_dir, noisy_dir = os.path.join(data_dir, 'original'), os.path.join(data_dir, 'noisy')
+    if os.path.isdir(original_dir) and os.path.isdir(noisy_dir):
+        jobs = []
+        for gt in sorted(glob.glob(os.path.join(glob.escape(original_dir), '*.obj'))):
+            stem = os.path.basename(gt)[:-4]
+            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(stem) + '_n*.obj'))):
+                jobs.append((noisy, gt))
+        return jobs
+    return [(f, None) for f in sorted(glob.glob(os.path.join(glob.escape(data_dir), '*.obj')))]
+
+
+def _device(gpu):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('geobi_gnn_amd: no GPU visible -- this path runs on the MI355X only (there is no CPU fallback)')
+    dev = torch.device('cuda:%d' % gpu if gpu >= 0 else 'cuda:%d' % torch.cuda.current_device())
+    torch.cuda.set_device(dev)
+    return dev
+
+
+def denoise(opt):
+    import torch
+    from . import meshio, network, patches
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    torch.manual_seed(0)
+    net = network.DualGNN(force_depth=opt.force_depth, pool_type=opt.pool_type, wei_param=opt.wei_param)
+    if opt.model:
+        net.load_state_dict(torch.load(opt.model, map_location='cpu', weights_only=True))
+    net = net.to(dev).eval()
+    jobs = _denoise_list(opt.data_dir)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'result')
+    os.makedirs(out_dir, exist_ok=True)
+    print('\nInfer %s, sub_size:%d, %d files ...\n' % (opt.model or 'random init', opt.sub_size, len(jobs)), flush=True)
+    done, failed = [], 0
+    for noisy_file, gt_file in jobs:
+        t0 = time.time()
+        try:
+            points, faces = meshio.read_obj(noisy_file)
+            if faces.shape[0] == 0:
+                raise ValueError('%s: no faces' % noisy_file)
+            loose = meshio.unreferenced_vertices(points.shape[0], faces)
+            if loose:
+                raise ValueError('%s: %d of %d vertices are referenced by no face (the vertex update averages over a '
+                                 "vertex's faces)" % (noisy_file, loose, points.shape[0]))
+            gt_points = None
+            if gt_file is not None:
+                gt_points, gt_faces = meshio.read_obj(gt_file)
+                if gt_points.shape != points.shape or gt_faces.shape != faces.shape:
+                    raise ValueError('%s (V = %d, F = %d) and its ground truth %s (V = %d, F = %d) differ in size'
+                                     % (noisy_file, points.shape[0], faces.shape[0], gt_file, gt_points.shape[0],
+                                        gt_faces.shape[0]))
+            with torch.no_grad():
+                r = patches.predict_mesh(net, points, faces, sub_size=opt.sub_size, n_iter=opt.n_iter,
+                                         data_type=opt.data_type, gt_points=gt_points, distributed=False)
+            rst_file = os.path.join(out_dir, '%s-%d.obj' % (os.path.basename(noisy_file)[:-4], opt.n_iter))
+            meshio.write_obj(rst_file, r['V_updated'].cpu().numpy(), faces)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+            continue
+        angle1, angle2 = (r['angle1'], r['angle2']) if gt_file is not None else (0.0, 0.0)
+        done.append((faces.shape[0], angle1, angle2))
+        print("angle1: %9.6f,  angle2: %9.6f,  faces: %6d,  time: %7.4f s,  '%s'"
+              % (angle1, angle2, faces.shape[0], time.time() - t0, os.path.basename(rst_file)), flush=True)
+    if done:
+        err = np.asarray(done, dtype=np.float64).T
+        count = err[0].sum()
+        print('\nNum_face: %6d,  angle_mean1: %.6f,  angle_mean2: %.6f'
+              % (count, (err[0] * err[1]).sum() / count, (err[0] * err[2]).sum() / count))
+    print('\n--- end ---')
+    if failed:
+        print('%d of %d files skipped' % (failed, len(jobs)), file=sys.stderr)
+    return 1 if failed or not jobs else 0
+
+
+def evaluate(opt):
+    from . import mesheval
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    stats = {}
+    t0 = time.time()
+    try:
+        rows, _ = mesheval.eval_dirs(opt.result_dir, opt.original_dir, device=dev, stats=stats)
+    except (ValueError, OSError, GeobiError) as e:
+        print('eval failed: %s' % e, file=sys.stderr)
+        return 1
+    print('%d pairs in %.3f s (reading OBJ %.3f s, device work %.3f s)'
+          % (len(rows), time.time() - t0, stats.get('parse', 0.0), stats.get('device', 0.0)))
+    return 0 if rows else 1
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m geobi_gnn_amd', description=__doc__.split('\n')[0])
+    sub = ap.add_subparsers(dest='command', required=True)
+    d = sub.add_parser('denoise', help='denoise every OBJ mesh of a folder and write NAME-60.obj')
+    d.add_argument('--model', type=str, default='', help="state dict with the reference's keys; random init (seed 0) if empty")
+    d.add_argument('--data_dir', type=str, required=True)
+    d.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/result')
+    d.add_argument('--sub_size', type=int, default=20000, help='faces per patch')
+    d.add_argument('--n_iter', type=int, default=60, help='vertex-update sweeps')
+    d.add_argument('--data_type', type=str, default='Synthetic', choices=['Synthetic', 'Kinect_v1', 'Kinect_v2', 'Kinect_Fusion'])
+    d.add_argument('--wei_param', type=int, default=2)
+    d.add_argument('--force_depth', action='store_true')
+    d.add_argument('--pool_type', type=str, default='max', choices=['max', 'mean'])
+    d.add_argument('--gpu', type=int, default=-1, help='device index (default: the current device)')
+    d.set_defaults(fn=denoise)
+    e = sub.add_parser('eval', help='score result meshes against their originals, write ErrorInfo_h.txt')
+    e.add_argument('--result_dir', type=str, required=True)
+    e.add_argument('--original_dir', type=str, required=True)
+    e.add_argument('--gpu', type=int, default=-1)
+    e.set_defaults(fn=evaluate)
+    opt = ap.parse_args(argv)
+    return opt.fn(opt)
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -449,6 +449,28 @@ int geobi_row_loss_bwd(const float* a, const float* b, const float* w, const flo
   return row_loss_bwd(a, b, w, gout, n, kind, scale, ga, S(stream));
 }
 
+size_t geobi_nearest_ws_bytes(int64_t Q, int64_t T) { return nearest_ws_bytes(Q, T); }
+int geobi_nearest_slices(int64_t Q, int64_t T, int triangles) { return nearest_slices(Q, T, triangles); }
+int geobi_nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
+                        size_t ws_bytes, void* stream) {
+  SIZES(Q > T ? Q : T, 0);
+  NOTNULL(q); NOTNULL(t); NOTNULL(dist); NOTNULL(ws);
+  return nearest_point(q, t, Q, T, dist, idx, ws, ws_bytes, S(stream));
+}
+int geobi_nearest_triangle(const float* q, const float* verts, const int32_t* fv, int64_t Q, int64_t V, int64_t F,
+                           float* dist, int32_t* face, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(Q > V ? Q : V, 0);
+  SIZES(F, 0);
+  NOTNULL(q); NOTNULL(verts); NOTNULL(fv); NOTNULL(dist); NOTNULL(ws);
+  return nearest_triangle(q, verts, fv, Q, V, F, dist, face, ws, ws_bytes, S(stream));
+}
+size_t geobi_dist_summary_ws_bytes(int64_t n) { return dist_summary_ws_bytes(n); }
+int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(n, 0);
+  NOTNULL(dist); NOTNULL(out); NOTNULL(ws);
+  return dist_summary(dist, n, (double*)out, ws, ws_bytes, S(stream));
+}
+
 int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, float bias_corr1, float bias_corr2, void* stream) {
   NOTNULL(p); NOTNULL(g); NOTNULL(m); NOTNULL(v);

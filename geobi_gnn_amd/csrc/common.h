@@ -284,6 +284,15 @@ int patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, int64_
 // pool.hip: exclusive int scan shared with meshprep.hip (single launch below 2^18 elements)
 size_t scan_ws_bytes(int64_t n);
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s);
+// dist.hip (nearest point / nearest triangle by brute force, distance summary)
+int nearest_slices(int64_t Q, int64_t T, int triangles);
+size_t nearest_ws_bytes(int64_t Q, int64_t T);
+int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
+                  size_t ws_bytes, hipStream_t s);
+int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int64_t Q, int64_t V, int64_t F, float* dist,
+                     int32_t* face, void* ws, size_t ws_bytes, hipStream_t s);
+size_t dist_summary_ws_bytes(int64_t n);
+int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

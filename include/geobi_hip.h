@@ -277,6 +277,32 @@ int geobi_row_loss_fwd(const float* a, const float* b, const float* w, int64_t n
 int geobi_row_loss_bwd(const float* a, const float* b, const float* w, const float* gout, int64_t n, int kind,
                        float scale, float* ga, void* stream);
 
+/* ---------------------------------------------------------------- nearest distances (evaluation) ----
+ * The vertex metric of the denoising evaluation, data_util.eval_denoising_result (code/data_util.py:559-638), by brute
+ * force over all pairs: exact, deterministic (no atomics), fp32 with every pair's squared distance formed from coordinate
+ * DIFFERENCES (translation-invariant; no |q|^2 + |t|^2 - 2 q.t cancellation), one sqrt per query.  Among equally near
+ * targets the LOWEST index is returned.  The targets are cut into slices so that small query sets fill the chip
+ * (geobi_nearest_slices: how many the library picks for the sizes -- a pure host function); the results are bit-identical
+ * for every slice count.  A query with a NaN coordinate gets dist = +inf.
+ *   geobi_nearest_point     my_hausdorff.nearest_distance(XA, XB, 'euclidean') (code/data_util.py:604, code/my_hausdorff.py):
+ *                           dist[i] = min_j |q_i - t_j|, idx[i] = that j (idx may be NULL)
+ *   geobi_nearest_triangle  the point-to-surface form the reference keeps commented out beside it (p2m,
+ *                           code/data_util.py:601-603): distance from q_i to the closest point -- interior, edge or corner --
+ *                           of the closest triangle of (verts [V,3], fv [F,3]); face[i] = that triangle (may be NULL).
+ *                           Triangles without area count as their longest edge.  fv must index [0, V): range-check it
+ *                           first (the Python layer does; the kernel clamps what it reads, it does not report)
+ *   geobi_dist_summary      out (DEVICE double[2]) = sum and max of dist [n], accumulated in fp64 in a fixed order: the
+ *                           .sum() / .mean() of code/data_util.py:610-616 and the directed Hausdorff maximum
+ * ws: geobi_nearest_ws_bytes(Q, T) (T = targets: points or triangles) serves either nearest call.                       */
+size_t geobi_nearest_ws_bytes(int64_t Q, int64_t T);
+int geobi_nearest_slices(int64_t Q, int64_t T, int triangles);
+int geobi_nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
+                        size_t ws_bytes, void* stream);
+int geobi_nearest_triangle(const float* q, const float* verts, const int32_t* fv, int64_t Q, int64_t V, int64_t F,
+                           float* dist, int32_t* face, void* ws, size_t ws_bytes, void* stream);
+size_t geobi_dist_summary_ws_bytes(int64_t n);
+int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser step ----
  * torch.optim.Adam's update rule (code/train_dual.py:162, the reference's default optimiser; no amsgrad) over one flat
  * fp32 vector of n parameters, its gradient and the two moment vectors (16-byte aligned), one launch:
