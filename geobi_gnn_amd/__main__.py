@@ -1,12 +1,15 @@
-"""Command line of the package: denoise a folder of OBJ meshes, score a folder of results.
+"""Command line of the package: train on folders of OBJ meshes, denoise a folder, score a folder of results.
 
+  python -m geobi_gnn_amd train --data_dir dataset/Synthetic --out_dir log/run1 [--batch_size 4] [--max_epoch 100]
   python -m geobi_gnn_amd denoise --model net.pt --data_dir DIR [--out_dir DIR/result] [--sub_size 20000]
   python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
 and as face-weighted means; otherwise every DIR/*.obj is denoised without ground truth.  `eval` is
-data_util.eval_denoising_result (code/data_util.py:559-638).  All device work runs in this one process.
+data_util.eval_denoising_result (code/data_util.py:559-638).  `train` is code/train_dual.py:100-298 (trainer.py): DIR holds
+train/ and test/, each with original/ and noisy/; the best model, the options, the log, TensorBoard event files and the
+denoised test meshes go to --out_dir.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -111,7 +114,13 @@ def evaluate(opt):
     return 0 if rows else 1
 
 
-def main(argv=None):
+def train(opt):
+    from . import trainer
+    trainer.require_single_process()              # before the device is touched
+    return trainer.train(opt, _device(opt.gpu), predict=denoise)
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog='python -m geobi_gnn_amd', description=__doc__.split('\n')[0])
     sub = ap.add_subparsers(dest='command', required=True)
     d = sub.add_parser('denoise', help='denoise every OBJ mesh of a folder and write NAME-60.obj')
@@ -131,7 +140,15 @@ def main(argv=None):
     e.add_argument('--original_dir', type=str, required=True)
     e.add_argument('--gpu', type=int, default=-1)
     e.set_defaults(fn=evaluate)
-    opt = ap.parse_args(argv)
+    t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
+    from .trainer import add_train_flags
+    add_train_flags(t)
+    t.set_defaults(fn=train)
+    return ap
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
     return opt.fn(opt)
 
 

@@ -477,6 +477,23 @@ int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, flo
   return adam_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, S(stream));
 }
 
+int geobi_rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
+                       int64_t n, void* stream) {
+  SIZES(n, 0);
+  if (P < 1) return set_error("%s: P = %d parts (at least one)", __func__, P);
+  NOTNULL(part_ptr); NOTNULL(R);
+  if (x_triples < 0 || ldx < 3 * x_triples)
+    return set_error("%s: ldx = %d is shorter than the x_triples = %d column triples to turn", __func__, ldx, x_triples);
+  if (part_ptr[0] != 0 || part_ptr[P] != n)
+    return set_error("%s: part_ptr runs from %lld to %lld, not from 0 to n = %lld", __func__, (long long)part_ptr[0],
+                     (long long)part_ptr[P], (long long)n);
+  for (int p = 0; p < P; ++p)
+    if (part_ptr[p + 1] < part_ptr[p]) return set_error("%s: part_ptr decreases at part %d", __func__, p);
+  if (n == 0) return 0;
+  NOTNULL(x);
+  return rotate_parts(part_ptr, P, R, x, ldx, x_triples, y, dd, S(stream));
+}
+
 size_t geobi_update_position_ws_bytes(int64_t V, int64_t F) { return update_position_ws_bytes(V, F); }
 int geobi_update_position2(const float* points, const int32_t* fv, const int32_t* vf, int maxval,
                            const float* normals, const float* dd, int64_t V, int64_t F, int n_iter, float* out,

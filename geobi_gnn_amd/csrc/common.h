@@ -308,6 +308,8 @@ int row_loss_bwd(const float* a, const float* b, const float* w, const float* go
                  float scale, float* ga, hipStream_t s);
 int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
               float bias_corr1, float bias_corr2, hipStream_t s);
+int rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
+                 hipStream_t s);
 size_t update_position_ws_bytes(int64_t V, int64_t F);
 int update_position2(const float* points, const int32_t* fv, const int32_t* vf, int maxval, const float* normals,
                      const float* dd, int64_t V, int64_t F, int n_iter, float* out, void* ws, size_t ws_bytes,

@@ -471,4 +471,66 @@ int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr,
   return 0;
 }
 
+// ---------------------------------------------------------------------------- per-mesh rotation of a union batch
+// code/dataset.py:39-69 turns every training sample by its own random rotation before the loader hands it over; here the
+// samples are already one disjoint-union graph, so part p (rows ptr[p] .. ptr[p + 1]) takes matrix p: out = in @ R.  The
+// shape is concat32_kernel's (graph.hip): offsets and matrices ride in the kernel arguments, are staged in LDS once per
+// block and a lane finds its row's part by binary search -- no copy of the host arrays, nothing out of stream order.
+namespace {
+constexpr int kMaxParts = 32;
+struct RotateJob {
+  int64_t ptr[kMaxParts + 1];      // row offsets of this launch's parts (ptr[0] = first row of the launch)
+  float R[kMaxParts * 9];          // row-major 3x3 per part
+  int n;
+};
+
+__device__ __forceinline__ void rotate_triple(float* __restrict__ v, const float* __restrict__ R) {
+  const float a = v[0], b = v[1], c = v[2];       // the triple is read whole before it is written: in place is safe
+  v[0] = fmaf(c, R[6], fmaf(b, R[3], a * R[0]));
+  v[1] = fmaf(c, R[7], fmaf(b, R[4], a * R[1]));
+  v[2] = fmaf(c, R[8], fmaf(b, R[5], a * R[2]));
+}
+
+__global__ __launch_bounds__(256) void rotate_parts_kernel(RotateJob job, float* __restrict__ x, int ldx, int x_triples,
+                                                           float* __restrict__ y, float* __restrict__ dd) {
+  __shared__ int64_t s_ptr[kMaxParts + 1];
+  __shared__ float s_R[kMaxParts * 9];
+  for (int i = threadIdx.x; i <= job.n; i += 256) s_ptr[i] = job.ptr[i];
+  for (int i = threadIdx.x; i < job.n * 9; i += 256) s_R[i] = job.R[i];
+  __syncthreads();
+  const int64_t end = s_ptr[job.n];
+  for (int64_t i = s_ptr[0] + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)gridDim.x * 256) {
+    int lo = 0, hi = job.n - 1;
+    while (lo < hi) {                              // last part that starts at or before row i (empty parts never win)
+      const int mid = (lo + hi + 1) >> 1;
+      if (s_ptr[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    float R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = s_R[lo * 9 + k];
+    float* row = x + i * ldx;
+    for (int t = 0; t < x_triples; ++t) rotate_triple(row + 3 * t, R);
+    if (y != nullptr) rotate_triple(y + i * 3, R);
+    if (dd != nullptr) rotate_triple(dd + i * 3, R);
+  }
+}
+}  // namespace
+
+int rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
+                 hipStream_t s) {
+  for (int base = 0; base < P; base += kMaxParts) {
+    RotateJob job;
+    job.n = P - base < kMaxParts ? P - base : kMaxParts;
+    for (int i = 0; i <= job.n; ++i) job.ptr[i] = part_ptr[base + i];
+    for (int i = 0; i < job.n * 9; ++i) job.R[i] = R[(int64_t)base * 9 + i];
+    const int64_t rows = job.ptr[job.n] - job.ptr[0];
+    if (rows == 0) continue;
+    int64_t blocks = (rows + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    rotate_parts_kernel<<<(int)blocks, 256, 0, s>>>(job, x, ldx, x_triples, y, dd);
+    GEOBI_LAUNCH_OK();
+  }
+  return 0;
+}
+
 }  // namespace geobi

@@ -339,6 +339,12 @@ class RandomRotate(object):
         rz = np.array([[np.cos(a[2]), -np.sin(a[2]), 0], [np.sin(a[2]), np.cos(a[2]), 0], [0, 0, 1]])
         return rz if self.z_rotated else rz @ (ry @ rx)
 
+    def matrices(self, count):
+        """[count, 3, 3] float64: ``count`` sequential ``matrix()`` draws -- one draw of three angles per sample, in sample
+        order, as the reference's loader turns every sample it hands over (dataset.py:39-69 applied in ``get``)."""
+        import numpy as np
+        return np.stack([self.matrix() for _ in range(count)]) if count else np.zeros((0, 3, 3))
+
     def __call__(self, data):
         m = self.matrix()
         for d in data:
@@ -352,3 +358,32 @@ class RandomRotate(object):
                 if torch.is_tensor(v):
                     setattr(d, k, v @ r)
         return data
+
+
+def rotate_union(data_v, data_f, mats):
+    """Per-sample rotation of a union batch, in place: mesh ``k`` of the pair (rows ``mesh_ptr[k] .. mesh_ptr[k + 1]``
+    of either graph) is turned by ``mats[k]`` -- ``x[:, 0:3]``, ``x[:, 3:6]``, ``y`` and ``depth_direction``, row-vector
+    convention (``v @ R``) as ``RandomRotate.__call__``.  ONE ``geobi_rotate_parts`` launch per graph (per 32 meshes):
+    offsets and matrices travel in the kernel arguments, so there is no copy and no host loop over the meshes.  A pair
+    without ``mesh_ptr`` is one part.  mats: ``[B, 3, 3]`` (``RandomRotate.matrices``), rounded once to fp32."""
+    import numpy as np
+    from . import _lib as L
+    mats32 = np.ascontiguousarray(np.asarray(mats, dtype=np.float64).reshape(-1, 9).astype(np.float32))
+    P = mats32.shape[0]
+    for d in (data_v, data_f):
+        L.require_device(d.x, 'x')
+        n = int(d.x.shape[0])
+        mp = getattr(d, 'mesh_ptr', None)
+        ptr = [0, n] if mp is None else [int(v) for v in mp.tolist()]
+        if len(ptr) != P + 1:
+            raise ValueError('rotate_union: %d matrices for %d meshes' % (P, len(ptr) - 1))
+        dd = getattr(d, 'depth_direction', None)
+        for t in (d.x, d.y, dd):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError('rotate_union: contiguous float32 arrays only')
+        if d.x.shape[1] < 6 or any(t is not None and tuple(t.shape) != (n, 3) for t in (d.y, dd)):
+            raise ValueError('rotate_union: x is [n, >= 6], y and depth_direction are [n, 3]')
+        part_ptr = (ctypes.c_int64 * (P + 1))(*ptr)
+        L.call('geobi_rotate_parts', ctypes.cast(part_ptr, ctypes.c_void_p), P, mats32.ctypes.data, L.ptr(d.x),
+               int(d.x.shape[1]), 2, L.ptr(d.y), L.ptr(dd), n, L.stream())
+    return data_v, data_f

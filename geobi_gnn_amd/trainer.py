@@ -1,0 +1,213 @@
+"""Training on folders of OBJ meshes: the loop of code/train_dual.py:100-298 over a dataset.DualDataset, behind the
+``train`` command (``python -m geobi_gnn_amd train --data_dir dataset/Synthetic --out_dir log/run1``).
+
+It is the loop of tools/train_synthetic.py with files instead of generated meshes.  A step is: the batch as ONE
+disjoint-union graph (data.union_batch_graphs, two launches), every sample of it turned by its own random rotation
+(data.rotate_union, one launch per graph: the reference's RandomRotate, applied per sample by its loader), forward,
+per-mesh mean losses, backward, Adam over the flat parameter.  Per epoch: evaluation over the test split sample by
+sample, best-on-eval checkpoint, schedule, one log line, TensorBoard scalars read back once.
+
+Single process only.  Not taken over from the reference: the code backup (train_dual.py:131), the ``last_epoch = 500``
+of ``--restore``, the ``eval()`` of unknown flags, progress bars.
+"""
+import argparse
+import contextlib
+import json
+import os
+import sys
+import time
+
+import torch
+
+from . import network, train_util
+from .data import RandomRotate, rotate_union, union_batch_graphs
+from .dataset import DualDataset
+from .parallel import FlatParameters, batched_losses, shard_indices
+
+DATA_TYPES = ('Synthetic', 'Kinect_v1', 'Kinect_v2', 'Kinect_Fusion')
+TRAIN_TAGS = ('loss_v', 'loss_f', 'dual_loss', 'error_v', 'error_f')
+TEST_TAGS = (('loss_v', 'eval_loss_v'), ('loss_f', 'eval_loss_f'), ('error_v', 'eval_error_v'), ('error_f', 'eval_error_f'))
+
+
+def add_train_flags(parser):
+    """The flags of train_dual.py:39-82 that this loop honours, same names and defaults."""
+    train_util.add_training_flags(parser)
+    parser.add_argument('--data_dir', type=str, required=True,
+                        help="the reference's dataset/<data_type> folder: train/ and test/ (each original/ + noisy/), "
+                             'optional train_list.txt / test_list.txt')
+    parser.add_argument('--data_type', type=str, default='Synthetic', choices=list(DATA_TYPES))
+    parser.add_argument('--flag', type=str, default='train', help='free text, kept in the params file')
+    parser.add_argument('--seed', type=int, default=None, help='default: drawn, printed and kept in the params file')
+    parser.add_argument('--gpu', type=int, default=-1, help='device index (default: the current device)')
+    parser.add_argument('--filter_patch_count', type=int, default=100, help='patches of at most this many faces are dropped')
+    parser.add_argument('--sub_size', type=int, default=20000, help='faces per patch')
+    parser.add_argument('--model_path', type=str, default='', help='initial weights (state dict)')
+    parser.add_argument('--out_dir', type=str, required=True)
+    parser.add_argument('--rotate', type=str, default='full', choices=['full', 'z', 'none'],
+                        help="per-sample random rotation; full = the reference's RandomRotate(False)")
+    parser.add_argument('--no_cache', action='store_true', help='neither read nor write <split>/processed_data')
+    parser.add_argument('--no_predict', action='store_true', help='do not denoise the test folder after training')
+    return parser
+
+
+def make_rotation(mode, seed):
+    """RandomRotate for ``--rotate`` with a generator of its own, seeded: the same seed draws the same matrices."""
+    import numpy as np
+    if mode == 'none':
+        return None
+    return RandomRotate(z_rotated=mode == 'z', rng=np.random.default_rng(seed))
+
+
+def train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=None, scalars=None, iteration=0):
+    """One pass over ``samples`` (a DualDataset or a list of resident pairs) in parallel.shard_indices order (seed,
+    epoch), ``opt.batch_size`` samples per step; the last, short batch still steps.  scalars: optional list that takes
+    (iteration, device tensor of the five TRAIN_TAGS values) per step -- nothing is read back here.
+    -> (iteration, loss of the last step as a device scalar)"""
+    net.train()
+    order = shard_indices(len(samples), 0, 1, seed=opt.seed, epoch=epoch)
+    loss = None
+    for s in range(0, len(order), opt.batch_size):
+        batch = order[s:s + opt.batch_size]
+        dv, df = union_batch_graphs([samples[i] for i in batch])        # always a copy: the samples are never written
+        if rotate is not None:
+            rotate_union(dv, df, rotate.matrices(len(batch)))
+        flat.bucket.zero()
+        vp, npred, _ = net((dv.shallow_copy(), df.shallow_copy()))
+        lv, ln = batched_losses(vp, npred, dv, df, opt.loss_v, opt.loss_n)
+        loss = network.dual_loss(lv, ln, opt.loss_v_scale, opt.loss_n_scale)
+        loss.backward()
+        optimizer.step()
+        iteration += len(batch)
+        if scalars is not None:
+            with torch.no_grad():
+                scalars.append((iteration, torch.stack([lv.detach(), ln.detach(), loss.detach(),
+                                                        network.error_v(vp.detach(), dv.y),
+                                                        network.error_n(npred.detach(), df.y)])))
+    return iteration, loss
+
+
+def evaluate(net, samples, opt):
+    """train_dual.py:233-259: node-count-weighted means over the samples, one by one.
+    -> dict(eval_loss_v, eval_loss_f, eval_error_v, eval_error_f)"""
+    net.eval()
+    meter = train_util.EvalMeter()
+    with torch.no_grad():
+        for i in range(len(samples)):
+            a, b = samples[i]
+            vp, npred, _ = net((a.shallow_copy(), b.shallow_copy()))
+            meter.add_prediction(vp, npred, a, b, opt.loss_v, opt.loss_n)
+    return meter.result()
+
+
+class _Tee(object):
+    def __init__(self, stream, path):
+        self.stream, self.file = stream, open(path, 'w')
+
+    def write(self, text):
+        self.stream.write(text)
+        self.file.write(text)
+
+    def flush(self):
+        self.stream.flush()
+        self.file.flush()
+
+
+def require_single_process():
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('geobi_gnn_amd train runs in a single process (WORLD_SIZE = %s): the data-parallel loop is '
+                         'tools/train_synthetic.py' % os.environ['WORLD_SIZE'])
+
+
+def train(opt, dev, predict=None):
+    """The ``train`` command on device ``dev``.  Writes into ``opt.out_dir``: GeoBi-GNN_<data_type>_model.pth (best state dict, the
+    reference's keys), GeoBi-GNN_<data_type>_params.json (the options), training_info.txt (what was printed), train/ and
+    test/ event files and -- through ``predict`` (the ``denoise`` command's function) unless ``opt.no_predict`` --
+    result/ with the denoised test meshes (train_dual.py:297-298).  -> exit status"""
+    require_single_process()
+    if opt.seed is None:
+        import random
+        opt.seed = random.randint(1, 10000)
+    opt.force_depth = opt.data_type in ('Kinect_v1', 'Kinect_v2')          # train_dual.py:93-94
+    opt.pool_type = 'max'
+    os.makedirs(opt.out_dir, exist_ok=True)
+    name = 'GeoBi-GNN_%s' % opt.data_type
+    model_file = os.path.join(opt.out_dir, name + '_model.pth')
+    tee = _Tee(sys.stdout, os.path.join(opt.out_dir, 'training_info.txt'))
+    with contextlib.redirect_stdout(tee):
+        try:
+            return _train(opt, dev, name, model_file, predict)
+        finally:
+            tee.flush()
+            tee.file.close()
+
+
+def _train(opt, dev, name, model_file, predict):
+    print('Training flag: %s_%s' % (name, opt.flag))
+    print('Random seed: %d\n' % opt.seed)
+    torch.manual_seed(opt.seed)
+    options = {k: v for k, v in sorted(vars(opt).items()) if isinstance(v, (int, float, str, bool, list, type(None)))}
+    with open(os.path.join(opt.out_dir, name + '_params.json'), 'w') as fh:
+        json.dump(options, fh, indent=1)
+    print(json.dumps(options), flush=True)
+
+    def split(which):
+        lst = which + '_list.txt'
+        t0 = time.time()
+        ds = DualDataset(opt.data_dir, which, lst if os.path.isfile(os.path.join(opt.data_dir, lst)) else None,
+                         submesh_size=opt.sub_size, filter_patch_count=opt.filter_patch_count, data_type=opt.data_type,
+                         device=dev, cache=not opt.no_cache)
+        print('%s: %d samples from %d files (%d skipped) in %.2f s' % (which, len(ds), len(ds.pairs), ds.skipped,
+                                                                      time.time() - t0), flush=True)
+        return ds
+    train_set, test_set = split('train'), split('test')
+
+    net = network.DualGNN(force_depth=opt.force_depth, pool_type=opt.pool_type, wei_param=opt.wei_param)
+    if opt.model_path:
+        net.load_state_dict(torch.load(opt.model_path, map_location='cpu', weights_only=True))
+    net = net.to(dev)
+    flat = FlatParameters(net)
+    optimizer = train_util.make_optimizer(opt, flat.parameters(), fused=True if opt.optimizer == 'adam' else None)
+    sch = train_util.make_scheduler(opt, optimizer)
+    ckpt = train_util.BestCheckpoint(model_file)
+    rotate = make_rotation(opt.rotate, opt.seed)
+    train_writer = train_util.SummaryWriter(os.path.join(opt.out_dir, 'train'))
+    test_writer = train_util.SummaryWriter(os.path.join(opt.out_dir, 'test'))
+    test_writer.add_text('train_params', json.dumps(options))
+
+    # the net as initialised, before any step: what the best evaluation error is measured against
+    res = evaluate(net, test_set, opt)
+    print(json.dumps({'epoch': 0, 'eval_loss_v': res['eval_loss_v'], 'eval_loss_f': res['eval_loss_f'],
+                      'eval_error_v': res['eval_error_v'], 'eval_error_f_deg': res['eval_error_f']}), flush=True)
+    iteration = 0
+    for epoch in range(1, opt.max_epoch + 1):
+        t0 = time.time()
+        scalars = []
+        iteration, loss = train_epoch(net, flat, optimizer, train_set, opt, epoch, rotate, scalars, iteration)
+        # the reference reads five scalars back per iteration (.item()); here they stay on the device until the epoch ends
+        for (it, _), vals in zip(scalars, torch.stack([v for _, v in scalars]).tolist() if scalars else []):
+            for tag, v in zip(TRAIN_TAGS, vals):
+                train_writer.add_scalar(tag, v, it)
+        train_writer.flush()
+        res = evaluate(net, test_set, opt)
+        rec = {'epoch': epoch, 'train_loss': float(loss.detach()), 'eval_loss_v': res['eval_loss_v'],
+               'eval_loss_f': res['eval_loss_f'], 'eval_error_v': res['eval_error_v'],
+               'eval_error_f_deg': res['eval_error_f'], 'lr': optimizer.param_groups[0]['lr'],
+               'epoch_s': round(time.time() - t0, 3)}
+        rec['saved'] = ckpt.update(net, rec['eval_error_f_deg'])          # keys: gnn_v.l_conv1.lin.weight ... fc_f2.bias
+        print(json.dumps(rec), flush=True)
+        for tag, key in TEST_TAGS:
+            test_writer.add_scalar(tag, res[key], iteration)
+        test_writer.flush()
+        train_util.step_scheduler(opt, sch, rec['eval_error_f_deg'])
+    train_writer.close()
+    test_writer.close()
+    print('\n%s_%s\nbest error: %s' % (name, opt.flag, ckpt.best), flush=True)
+    if predict is None or opt.no_predict:
+        return 0
+    if not os.path.exists(model_file):
+        print('no model was saved (the evaluation error was never finite): nothing to predict with', file=sys.stderr)
+        return 1
+    return predict(argparse.Namespace(model=model_file, data_dir=os.path.join(opt.data_dir, 'test'),
+                                      out_dir=os.path.join(opt.out_dir, 'result'), sub_size=opt.sub_size, n_iter=60,
+                                      data_type=opt.data_type, wei_param=opt.wei_param, force_depth=opt.force_depth,
+                                      pool_type=opt.pool_type, gpu=opt.gpu))

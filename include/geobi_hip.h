@@ -311,6 +311,17 @@ int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t
 int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, float bias_corr1, float bias_corr2, void* stream);
 
+/* ---------------------------------------------------------------- per-mesh rotation of a union batch ----
+ * The training-time augmentation of code/dataset.py:39-69 (RandomRotate, applied per sample in `get`; the loop of
+ * code/train_dual.py:141 sees every sample under its own rotation) for a batch that is already ONE disjoint-union graph:
+ * rows part_ptr[p] .. part_ptr[p + 1] are turned in place by matrix p, row-vector convention as the reference's
+ * `x @ R`.  One call covers one graph's arrays: the first x_triples column triples of x [n, ldx] (2 for the
+ * [pos | normal] features), y [n, 3] (may be NULL) and depth_direction dd [n, 3] (may be NULL: Kinect types only); other
+ * columns are not touched.  part_ptr [P + 1] (0 .. n, non-decreasing) and R [P * 9] (row-major 3x3 each) are HOST arrays
+ * that travel in the kernel arguments, 32 parts per launch: no copy, no sync, stream order kept.  n == 0 is a no-op.   */
+int geobi_rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
+                       int64_t n, void* stream);
+
 /* ---------------------------------------------------------------- vertex update ----
  * data_util.update_position2 (code/data_util.py:529-556; called at code/test_dual.py:63-72 after the
  * network): n_iter Jacobi sweeps  p_v += mean_{f adj v} n_f (n_f . (c_f - p_v)), c_f = face centroid,
