@@ -3,13 +3,15 @@
   python -m geobi_gnn_amd train --data_dir dataset/Synthetic --out_dir log/run1 [--batch_size 4] [--max_epoch 100]
   python -m geobi_gnn_amd denoise --model net.pt --data_dir DIR [--out_dir DIR/result] [--sub_size 20000]
   python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
+  python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
 and as face-weighted means; otherwise every DIR/*.obj is denoised without ground truth.  `eval` is
 data_util.eval_denoising_result (code/data_util.py:559-638).  `train` is code/train_dual.py:100-298 (trainer.py): DIR holds
 train/ and test/, each with original/ and noisy/; the best model, the options, the log, TensorBoard event files and the
-denoised test meshes go to --out_dir.  All device work runs in this one process.
+denoised test meshes go to --out_dir.  `noise` has no counterpart in the reference (its dataset is a download): it writes
+DIR/noisy/NAME_n<k>.obj for every DIR/original/NAME.obj, the layout `train` and `denoise` read.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -20,9 +22,10 @@ import time
 import numpy as np
 
 
-def _denoise_list(data_dir):
-    """[(noisy file, ground-truth file or None)] in sorted order."""
-    original_dir, noisy_dir = os.path.join(data_dir, 'original'), os.path.join(data_dir, 'noisy')
+def _denoise_list(data_dir, noisy_dir=''):
+    """[(noisy file, ground-truth file or None)] in sorted order.  noisy_dir: where the NAME_n*.obj of DIR/original are,
+    if not in DIR/noisy (`train` hands over the test meshes it drew itself)."""
+    original_dir, noisy_dir = os.path.join(data_dir, 'original'), noisy_dir or os.path.join(data_dir, 'noisy')
     if os.path.isdir(original_dir) and os.path.isdir(noisy_dir):
         jobs = []
         for gt in sorted(glob.glob(os.path.join(glob.escape(original_dir), '*.obj'))):
@@ -52,7 +55,7 @@ def denoise(opt):
     if opt.model:
         net.load_state_dict(torch.load(opt.model, map_location='cpu', weights_only=True))
     net = net.to(dev).eval()
-    jobs = _denoise_list(opt.data_dir)
+    jobs = _denoise_list(opt.data_dir, getattr(opt, 'noisy_dir', ''))
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'result')
     os.makedirs(out_dir, exist_ok=True)
     print('\nInfer %s, sub_size:%d, %d files ...\n' % (opt.model or 'random init', opt.sub_size, len(jobs)), flush=True)
@@ -114,6 +117,46 @@ def evaluate(opt):
     return 0 if rows else 1
 
 
+def noise(opt):
+    """original/NAME.obj -> noisy/NAME_n<k>.obj for every level k = 1.., drawn on the device (meshnoise)."""
+    from . import meshio, meshnoise
+    from ._lib import GeobiError
+    from .dataset import read_original
+    dev = _device(opt.gpu)
+    try:
+        options = meshnoise.NoiseOptions(opt.levels, opt.kind, opt.direction, opt.fraction, opt.seed)
+    except ValueError as e:
+        print('noise: %s' % e, file=sys.stderr)
+        return 1
+    originals = sorted(glob.glob(os.path.join(glob.escape(os.path.join(opt.data_dir, 'original')), '*.obj')))
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'noisy')
+    os.makedirs(out_dir, exist_ok=True)
+    print('\nNoise %s / %s, levels %s, seed %d, %d files ...\n'
+          % (options.kind, options.direction, ','.join('%g' % v for v in options.levels), options.seed, len(originals)),
+          flush=True)
+    failed = 0
+    for original in originals:
+        name = os.path.basename(original)[:-4]
+        try:
+            points, faces = read_original(original)
+            geom = meshnoise.MeshGeometry(points, faces, dev)
+            for k, level in enumerate(options.levels, 1):
+                noisy = geom.draw(level, options.kind, options.direction, options.fraction, options.seed,
+                                  meshnoise.stream_of(name), k)
+                out_file = os.path.join(out_dir, meshnoise.noisy_name(name, k) + '.obj')
+                meshio.write_obj(out_file, noisy.cpu().numpy(), faces)
+                print("V: %7d,  F: %7d,  L: %.6g,  sigma: %.6g,  '%s'"
+                      % (points.shape[0], faces.shape[0], geom.mean_edge, geom.sigma(level), os.path.basename(out_file)),
+                      flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d of %d files skipped' % (failed, len(originals)), file=sys.stderr)
+    return 1 if failed or not originals else 0
+
+
 def train(opt):
     from . import trainer
     trainer.require_single_process()              # before the device is touched
@@ -140,6 +183,19 @@ def build_parser():
     e.add_argument('--original_dir', type=str, required=True)
     e.add_argument('--gpu', type=int, default=-1)
     e.set_defaults(fn=evaluate)
+    n = sub.add_parser('noise', help='write noisy/NAME_n<k>.obj for every original/NAME.obj, drawn on the device')
+    from .meshnoise import DIRECTIONS, KINDS
+    from .trainer import noise_levels_arg
+    n.add_argument('--data_dir', type=str, required=True, help='holds original/')
+    n.add_argument('--levels', type=noise_levels_arg, default=[0.1, 0.2, 0.3],
+                   help='noise levels as fractions of the mean edge length; level k of the list goes to NAME_n<k>.obj')
+    n.add_argument('--kind', type=str, default='gaussian', choices=list(KINDS))
+    n.add_argument('--direction', type=str, default='normal', choices=list(DIRECTIONS))
+    n.add_argument('--fraction', type=float, default=0.3, help='share of the vertices the impulsive kind moves')
+    n.add_argument('--seed', type=int, default=1)
+    n.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/noisy')
+    n.add_argument('--gpu', type=int, default=-1)
+    n.set_defaults(fn=noise)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)

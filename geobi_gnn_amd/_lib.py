@@ -23,6 +23,7 @@ class GeobiError(RuntimeError):
 _CTYPES = {
     'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double,
     'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32, 'size_t': ctypes.c_size_t,
+    'uint64_t': ctypes.c_uint64, 'uint32_t': ctypes.c_uint32,
 }
 
 

@@ -471,6 +471,14 @@ int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t
   return dist_summary(dist, n, (double*)out, ws, ws_bytes, S(stream));
 }
 
+int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction,
+                     float fraction, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, void* stream) {
+  SIZES(V, 0);
+  if (V == 0) return 0;
+  NOTNULL(points); NOTNULL(out);
+  return mesh_noise(points, vnormal, V, sigma, kind, direction, fraction, seed, stream_id, draw, out, S(stream));
+}
+
 int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, float bias_corr1, float bias_corr2, void* stream) {
   NOTNULL(p); NOTNULL(g); NOTNULL(m); NOTNULL(v);

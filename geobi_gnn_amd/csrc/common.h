@@ -293,6 +293,9 @@ int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int6
                      int32_t* face, void* ws, size_t ws_bytes, hipStream_t s);
 size_t dist_summary_ws_bytes(int64_t n);
 int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s);
+// noise.hip (synthetic mesh noise: counter-based Philox4x32-10, one counter per vertex)
+int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
+               uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

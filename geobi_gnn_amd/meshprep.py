@@ -244,3 +244,58 @@ def build_dual_data(points_noisy, faces, points_gt=None, name='mesh', data_type=
         data_v.mesh_ptr = torch.tensor(list(parts[0]), dtype=torch.long)
         data_f.mesh_ptr = torch.tensor(list(parts[1]), dtype=torch.long)
     return data_v, data_f
+
+
+def refresh_dual_data(data_v, data_f, points_noisy, points_gt, data_type='Synthetic', incidence=None, centroid=None,
+                      scale=None):
+    """New noisy points on the connectivity of an existing ``build_dual_data`` pair, in place: the graphs do not depend
+    on the points, so both ``Graph`` objects (with their reverse-edge index), the face table and its validation mark stay
+    as they are -- no CSR build, no host size read -- and only what moves is recomputed, by the calls ``build_dual_data``
+    makes and in its order, so every value equals a fresh build bit for bit: normals, centroid and scale, both bilateral
+    weight vectors, both feature matrices, ``depth_direction`` (Kinect types) and ``data_v.y``.  ``data_f.y`` (the
+    normals of the ground truth) does not move.  incidence: (rowptr, list) of meshprep.vertex_faces; default: that of
+    ``data_v.meta``, else recomputed.  ``data_v.meta`` -- where present -- takes the new centroid and scale (one host
+    read, as the build; without it the scale stays on the device).  -> (data_v, data_f)"""
+    g_v, g_f = data_v.graph(), data_f.graph()
+    if g_v.eid_out is not None or g_f.eid_out is not None:
+        raise L.GeobiError('refresh_dual_data: a pair in the reference layout (COO with self loops) is rebuilt, not refreshed')
+    dev = g_v.device
+    pts = torch.as_tensor(np.asarray(points_noisy) if not torch.is_tensor(points_noisy) else points_noisy)
+    pts = pts.to(device=dev, dtype=torch.float32).contiguous()
+    cache = getattr(data_f.fv_indices, '_geobi_fv', None)
+    V = g_v.N
+    if cache is None or cache[2] != V:
+        raise L.GeobiError('refresh_dual_data: the face table was not validated for %d vertices (not a build_dual_data pair)' % V)
+    fv = cache[0]
+    if pts.shape != (V, 3) or fv.shape[0] != g_f.N:
+        raise ValueError('refresh_dual_data: %s points for a pair of %d vertices and %d faces' % (tuple(pts.shape), V, g_f.N))
+    meta = getattr(data_v, 'meta', None)
+    if incidence is None:
+        incidence = meta['incidence'] if isinstance(meta, dict) and meta.get('incidence') is not None else vertex_faces(fv, V)
+    rowptr_vf, lst = incidence
+    fn, pos_f, vn = mesh_normals(pts, fv, rowptr_vf, lst)
+    if centroid is None:
+        cen = pts.mean(0, keepdim=True)
+    else:
+        cen = torch.as_tensor(centroid, dtype=torch.float32).reshape(1, 3).to(dev)
+    if scale is not None:
+        sc = float(scale)
+    else:
+        sc = 1.0 / mean_edge_length(pts, g_v)           # float32 [1]: the value build_dual_data reads back, used in place
+        if isinstance(meta, dict):
+            sc = float(sc.item())
+    ew_v = calc_weight(pts, vn, g_v)
+    ew_f = calc_weight(pos_f, fn, g_f)
+    data_v.x = torch.cat(((pts - cen) * sc, vn), 1)
+    data_f.x = torch.cat(((pos_f - cen) * sc, fn), 1)
+    data_v.edge_weight, data_f.edge_weight = ew_v, ew_f
+    data_v.depth_direction = None
+    if data_type in ('Kinect_v1', 'Kinect_v2'):
+        data_v.depth_direction = torch.nn.functional.normalize(pts, dim=1)
+    if points_gt is not None:
+        pg = torch.as_tensor(np.asarray(points_gt) if not torch.is_tensor(points_gt) else points_gt)
+        pg = pg.to(device=dev, dtype=torch.float32).contiguous()
+        data_v.y = (pg - cen) * sc
+    if isinstance(meta, dict):
+        meta['centroid'], meta['scale'] = cen, sc
+    return data_v, data_f

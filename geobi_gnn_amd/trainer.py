@@ -7,6 +7,9 @@ disjoint-union graph (data.union_batch_graphs, two launches), every sample of it
 per-mesh mean losses, backward, Adam over the flat parameter.  Per epoch: evaluation over the test split sample by
 sample, best-on-eval checkpoint, schedule, one log line, TensorBoard scalars read back once.
 
+With ``--noise_levels`` the train split needs clean meshes only: its noisy copies are drawn on the device
+(dataset.DualDataset(noise=...)), and ``--renoise_every K`` draws them afresh before every K-th epoch.
+
 Single process only.  Not taken over from the reference: the code backup (train_dual.py:131), the ``last_epoch = 500``
 of ``--restore``, the ``eval()`` of unknown flags, progress bars.
 """
@@ -19,7 +22,7 @@ import time
 
 import torch
 
-from . import network, train_util
+from . import meshnoise, network, train_util
 from .data import RandomRotate, rotate_union, union_batch_graphs
 from .dataset import DualDataset
 from .parallel import FlatParameters, batched_losses, shard_indices
@@ -47,7 +50,22 @@ def add_train_flags(parser):
                         help="per-sample random rotation; full = the reference's RandomRotate(False)")
     parser.add_argument('--no_cache', action='store_true', help='neither read nor write <split>/processed_data')
     parser.add_argument('--no_predict', action='store_true', help='do not denoise the test folder after training')
+    parser.add_argument('--noise_levels', type=noise_levels_arg, default=None,
+                        help='e.g. 0.1,0.2,0.3 (fractions of the mean edge length): draw the noisy copies of the train '
+                             'split on the device from <data_dir>/train/original alone; the noise seed is --seed.  The test '
+                             'split uses its noisy/ folder if there is one, else it is drawn once')
+    parser.add_argument('--noise_kind', type=str, default='gaussian', choices=list(meshnoise.KINDS))
+    parser.add_argument('--noise_direction', type=str, default='normal', choices=list(meshnoise.DIRECTIONS))
+    parser.add_argument('--noise_fraction', type=float, default=0.3, help='share of the vertices the impulsive kind moves')
+    parser.add_argument('--renoise_every', type=int, default=0,
+                        help='K > 0: before every epoch with epoch %% K == 0 the train split is drawn afresh (round epoch // K); '
+                             '0: the draw-0 noise for the whole run')
     return parser
+
+
+def noise_levels_arg(text):
+    """argparse type of a list of noise levels: '0.1,0.2' -> [0.1, 0.2] (a list, so that it goes into the params file)."""
+    return list(meshnoise.parse_levels(text))
 
 
 def make_rotation(mode, seed):
@@ -150,12 +168,21 @@ def _train(opt, dev, name, model_file, predict):
         json.dump(options, fh, indent=1)
     print(json.dumps(options), flush=True)
 
+    noise = None
+    if getattr(opt, 'noise_levels', None):
+        noise = meshnoise.NoiseOptions(opt.noise_levels, opt.noise_kind, opt.noise_direction, opt.noise_fraction, opt.seed)
+    renoise_every = int(getattr(opt, 'renoise_every', 0) or 0)
+    if renoise_every < 0 or (renoise_every and noise is None):
+        raise SystemExit('geobi_gnn_amd train: --renoise_every needs --noise_levels and K >= 0')
+
     def split(which):
         lst = which + '_list.txt'
         t0 = time.time()
+        # the test split keeps its noise files where it has some: only a split without noisy/ is drawn (once, round 0)
+        drawn = noise if which == 'train' or not os.path.isdir(os.path.join(opt.data_dir, which, 'noisy')) else None
         ds = DualDataset(opt.data_dir, which, lst if os.path.isfile(os.path.join(opt.data_dir, lst)) else None,
                          submesh_size=opt.sub_size, filter_patch_count=opt.filter_patch_count, data_type=opt.data_type,
-                         device=dev, cache=not opt.no_cache)
+                         device=dev, cache=not opt.no_cache, noise=drawn)
         print('%s: %d samples from %d files (%d skipped) in %.2f s' % (which, len(ds), len(ds.pairs), ds.skipped,
                                                                       time.time() - t0), flush=True)
         return ds
@@ -182,6 +209,8 @@ def _train(opt, dev, name, model_file, predict):
     for epoch in range(1, opt.max_epoch + 1):
         t0 = time.time()
         scalars = []
+        if renoise_every > 0 and epoch % renoise_every == 0:
+            train_set.resample(epoch // renoise_every)
         iteration, loss = train_epoch(net, flat, optimizer, train_set, opt, epoch, rotate, scalars, iteration)
         # the reference reads five scalars back per iteration (.item()); here they stay on the device until the epoch ends
         for (it, _), vals in zip(scalars, torch.stack([v for _, v in scalars]).tolist() if scalars else []):
@@ -207,7 +236,12 @@ def _train(opt, dev, name, model_file, predict):
     if not os.path.exists(model_file):
         print('no model was saved (the evaluation error was never finite): nothing to predict with', file=sys.stderr)
         return 1
-    return predict(argparse.Namespace(model=model_file, data_dir=os.path.join(opt.data_dir, 'test'),
+    noisy_dir = ''
+    if test_set.noise is not None:
+        # the inputs of result/: the round-0 test meshes the evaluation ran on, as files a user can look at
+        noisy_dir = os.path.join(opt.out_dir, 'test_noisy')
+        test_set.write_noisy(noisy_dir)
+    return predict(argparse.Namespace(model=model_file, data_dir=os.path.join(opt.data_dir, 'test'), noisy_dir=noisy_dir,
                                       out_dir=os.path.join(opt.out_dir, 'result'), sub_size=opt.sub_size, n_iter=60,
                                       data_type=opt.data_type, wei_param=opt.wei_param, force_depth=opt.force_depth,
                                       pool_type=opt.pool_type, gpu=opt.gpu))

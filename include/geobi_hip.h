@@ -303,6 +303,23 @@ int geobi_nearest_triangle(const float* q, const float* verts, const int32_t* fv
 size_t geobi_dist_summary_ws_bytes(int64_t n);
 int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- synthetic mesh noise ----
+ * The reference has NO call site for this: its dataset is an external download (README.md:7) and the generator of its
+ * noisy meshes is not in its tree.  out[v] = points[v] + displacement(v), v in [0, V); out may alias points; V == 0 is a
+ * no-op.
+ *   random numbers  Philox4x32-10 (Random123 constants), key = (seed & 0xffffffff, seed >> 32), counter =
+ *                   (v, stream_id, draw, block): the result depends on (seed, stream_id, draw, v) only -- v is the row index
+ *                   of this call -- never on grid shape, launch order or the number of calls
+ *   word -> uniform u = ((w >> 9) + 0.5) * 2^-23, exact in fp32, never 0 or 1
+ *   block 0         four standard normals g0..g3 by two Box-Muller pairs (words 0,1 and 2,3; cos first), precise
+ *                   logf / sincosf / sqrtf
+ *   direction       0 (normal): sigma * g0 * vnormal[v] (vnormal NULL is an error); 1 (random): sigma * g0 *
+ *                   normalize(g1, g2, g3), (0, 0, 1) for a vector without length; vnormal is not read
+ *   kind            0 (gaussian): every vertex moves; 1 (impulsive): only where u(block 1, word 0) < fraction
+ * sigma >= 0 (0 leaves every bit of points alone), fraction in [0, 1]; anything else is an error.                         */
+int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction,
+                     float fraction, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, void* stream);
+
 /* ---------------------------------------------------------------- optimiser step ----
  * torch.optim.Adam's update rule (code/train_dual.py:162, the reference's default optimiser; no amsgrad) over one flat
  * fp32 vector of n parameters, its gradient and the two moment vectors (16-byte aligned), one launch:
