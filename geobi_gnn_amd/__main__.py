@@ -160,6 +160,7 @@ def noise(opt):
 def train(opt):
     from . import trainer
     trainer.require_single_process()              # before the device is touched
+    trainer.require_known_losses(opt)
     return trainer.train(opt, _device(opt.gpu), predict=denoise)
 
 

@@ -293,6 +293,18 @@ int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int6
                      int32_t* face, void* ws, size_t ws_bytes, hipStream_t s);
 size_t dist_summary_ws_bytes(int64_t n);
 int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s);
+// dist.hip: the point search confined to the parts of a union batch (host part pointers, 32 parts per launch)
+int parts_ptr_ok(const char* fn, const char* what, const int64_t* ptr, int P);     // P >= 1, no empty part
+int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P);
+size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P);
+int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,
+                  void* ws, size_t ws_bytes, hipStream_t s);
+// chamfer.hip (Chamfer distance of a union batch: value and gradient on top of the two searches)
+size_t chamfer_ws_bytes(int P);
+int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out, void* ws,
+                size_t ws_bytes, hipStream_t s);
+int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
+                const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, hipStream_t s);
 // noise.hip (synthetic mesh noise: counter-based Philox4x32-10, one counter per vertex)
 int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
                uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s);

@@ -4,6 +4,8 @@
 //   nearest_point     code/data_util.py:604 (my_hausdorff.nearest_distance, numba prange on the CPU)
 //   nearest_triangle  data_util.py:601-603 (the commented-out p2m: point-to-surface distance)
 //   dist_summary      the .sum() / .mean() / max over the per-vertex distances, data_util.py:610-616
+//   nearest_parts     nearest_point confined to the meshes of a union batch: the search under the correspondence-free
+//                     losses, code/network.py:369-370 (chamfer_distance) and :385-388 (sided_distance)
 //
 // Shape of the two all-pairs kernels: a lane owns QPL queries in registers; the workgroup stages a tile of targets
 // in LDS (for triangles: a 16-float record per triangle, corners gathered once per tile); every lane walks the tile
@@ -123,6 +125,103 @@ __global__ void nearest_reduce_kernel(const float* __restrict__ part_d2, const i
   }
   dist[i] = sqrtf(best);
   if (idx) idx[i] = b;
+}
+
+// ---------------------------------------------------------------- point - point, confined to the parts of a union batch
+// The search the correspondence-free losses need (code/network.py:369-370 chamfer_distance, :385-388 sided_distance) on
+// a disjoint-union batch: queries of part p only meet targets of part p.  Same shape as nearest_point_kernel -- QPL
+// queries per lane, the target tile in LDS read by broadcast, target slices, a strict-< reduction in ascending slice
+// order -- and the same pair_d2, so for any part the answer is what nearest_point gives on that part's rows alone.  A
+// workgroup belongs to ONE part (blocks are formed per part); the part table rides in the kernel arguments as the
+// offsets of rotate_parts_kernel do (geom.hip): no copy of the host arrays, nothing out of stream order.
+constexpr int kMaxSearchParts = 32;
+struct PartsJob {
+  int q_begin[kMaxSearchParts + 1];     // query rows of part k: q_begin[k] .. q_begin[k + 1]
+  int t_begin[kMaxSearchParts + 1];     // target rows
+  int block_begin[kMaxSearchParts + 1]; // first workgroup (blockIdx.x) of part k
+  int tiles_per_slice[kMaxSearchParts];
+  int slices[kMaxSearchParts];          // >= 1, no empty slice
+  int n;
+};
+
+__global__ __launch_bounds__(kThreads) void nearest_parts_kernel(PartsJob job, const float* __restrict__ q,
+                                                                 const float* __restrict__ t, int ld_part,
+                                                                 float* __restrict__ part_d2, int* __restrict__ part_idx) {
+  __shared__ float4 tile[kPointTile];
+  const int tid = threadIdx.x;
+  int p = 0;
+  while (p + 1 < job.n && (int)blockIdx.x >= job.block_begin[p + 1]) ++p;      // wave-uniform
+  const int slice = blockIdx.y;
+  if (slice >= job.slices[p]) return;                                         // the whole workgroup leaves together
+  const int q0 = job.q_begin[p] + ((int)blockIdx.x - job.block_begin[p]) * (kThreads * kPointQpl);
+  const int q_end = job.q_begin[p + 1];
+  const int span = job.tiles_per_slice[p] * kPointTile;
+  const int t_begin = job.t_begin[p] + slice * span;
+  const int t_end = min(job.t_begin[p + 1], t_begin + span);
+  float qx[kPointQpl], qy[kPointQpl], qz[kPointQpl], best[kPointQpl];
+  int bidx[kPointQpl];
+#pragma unroll
+  for (int k = 0; k < kPointQpl; ++k) {
+    const int i = min(q0 + k * kThreads + tid, q_end - 1);    // tail lanes repeat the part's last query and write nothing
+    qx[k] = q[3 * (size_t)i]; qy[k] = q[3 * (size_t)i + 1]; qz[k] = q[3 * (size_t)i + 2];
+    best[k] = INFINITY;
+    bidx[k] = t_begin;                                        // in range whatever the coordinates are (NaN included)
+  }
+  for (int t0 = t_begin; t0 < t_end; t0 += kPointTile) {
+    const int n = min(kPointTile, t_end - t0);
+    __syncthreads();
+    for (int j = tid; j < n; j += kThreads) {
+      const float* pt = t + 3 * (size_t)(t0 + j);
+      tile[j] = make_float4(pt[0], pt[1], pt[2], 0.f);
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+      const float4 tj = tile[j];
+#pragma unroll
+      for (int k = 0; k < kPointQpl; ++k) {
+        const float d2 = pair_d2(qx[k], qy[k], qz[k], tj);
+        const bool lt = d2 < best[k];
+        best[k] = lt ? d2 : best[k];
+        bidx[k] = lt ? t0 + j : bidx[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kPointQpl; ++k) {
+    const int i = q0 + k * kThreads + tid;
+    if (i < q_end) {
+      part_d2[(size_t)slice * ld_part + i] = best[k];
+      part_idx[(size_t)slice * ld_part + i] = bidx[k];
+    }
+  }
+}
+
+// the partials of a query's own part, slices in ascending order, strict <; the SQUARED distance goes out
+__global__ __launch_bounds__(kThreads) void nearest_parts_reduce_kernel(PartsJob job, const float* __restrict__ part_d2,
+                                                                        const int* __restrict__ part_idx, int ld_part,
+                                                                        float* __restrict__ d2_out, int* __restrict__ idx) {
+  __shared__ int s_begin[kMaxSearchParts + 1], s_slices[kMaxSearchParts];     // a lane indexes them by ITS part
+  for (int k = threadIdx.x; k <= job.n; k += kThreads) s_begin[k] = job.q_begin[k];
+  for (int k = threadIdx.x; k < job.n; k += kThreads) s_slices[k] = job.slices[k];
+  __syncthreads();
+  const int i = s_begin[0] + blockIdx.x * kThreads + threadIdx.x;
+  if (i >= s_begin[job.n]) return;
+  int lo = 0, hi = job.n - 1;
+  while (lo < hi) {                                  // the part that holds row i (no part is empty)
+    const int mid = (lo + hi + 1) >> 1;
+    if (s_begin[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int S = s_slices[lo];
+  float best = part_d2[i];
+  int b = part_idx[i];
+  for (int s = 1; s < S; ++s) {
+    const float d2 = part_d2[(size_t)s * ld_part + i];
+    const int j = part_idx[(size_t)s * ld_part + i];
+    if (d2 < best) { best = d2; b = j; }
+  }
+  d2_out[i] = best;
+  idx[i] = b;
 }
 
 // ---------------------------------------------------------------- point - triangle
@@ -346,6 +445,97 @@ int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* d
   GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_point: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
   nearest_point_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, t, (int)Q, (int)T, c.tiles_per_slice, pd, pi);
   nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(pd, pi, (int)Q, c.slices, dist, idx);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+int parts_ptr_ok(const char* fn, const char* what, const int64_t* ptr, int P) {
+  GEOBI_REQUIRE(P >= 1, "%s: P = %d parts (at least one)", fn, P);
+  GEOBI_REQUIRE(ptr != nullptr && ptr[0] >= 0, "%s: %s is NULL or starts below 0", fn, what);
+  for (int p = 0; p < P; ++p)
+    GEOBI_REQUIRE(ptr[p + 1] > ptr[p], "%s: part %d of %s is empty (%lld .. %lld): an empty part is an error, not a launch", fn,
+                  p, what, (long long)ptr[p], (long long)ptr[p + 1]);
+  return 0;
+}
+
+namespace {
+// slices every part would like: the workgroups of ALL parts together should fill the chip
+int parts_want(const int64_t* qptr, int P) {
+  int64_t qblocks = 0;
+  for (int p = 0; p < P; ++p) qblocks += cdiv(qptr[p + 1] - qptr[p], (int64_t)kThreads * kPointQpl);
+  int64_t want = (kTargetBlocks + qblocks - 1) / qblocks;
+  return (int)(want > kMaxSlices ? kMaxSlices : (want < 1 ? 1 : want));
+}
+Slicing part_slices(int64_t Q, int64_t T, int want) {   // P = 1: exactly choose_slices
+  Slicing c;
+  c.qblocks = cdiv(Q, (int64_t)kThreads * kPointQpl);
+  const int ntiles = cdiv(T, kPointTile);
+  if (want > ntiles) want = ntiles;
+  c.tiles_per_slice = cdiv(ntiles, want);
+  c.slices = cdiv(ntiles, c.tiles_per_slice);
+  return c;
+}
+bool parts_sane(const int64_t* qptr, const int64_t* tptr, int P) {
+  if (P < 1 || !qptr || !tptr || qptr[0] < 0 || tptr[0] < 0) return false;
+  for (int p = 0; p < P; ++p)
+    if (qptr[p + 1] <= qptr[p] || tptr[p + 1] <= tptr[p]) return false;
+  return qptr[P] <= INT32_MAX / 4 && tptr[P] <= INT32_MAX / 4;
+}
+}  // namespace
+
+int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P) {
+  if (!parts_sane(qptr, tptr, P)) return 0;
+  const int want = parts_want(qptr, P);
+  int smax = 0;
+  for (int p = 0; p < P; ++p) {
+    const int sl = part_slices(qptr[p + 1] - qptr[p], tptr[p + 1] - tptr[p], want).slices;
+    smax = sl > smax ? sl : smax;
+  }
+  return smax;
+}
+
+size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
+  const int smax = nearest_parts_slices(qptr, tptr, P);
+  if (smax == 0) return 256;
+  return align_up((size_t)smax * qptr[P] * sizeof(float)) + align_up((size_t)smax * qptr[P] * sizeof(int)) + 256;
+}
+
+int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,
+                  void* ws, size_t ws_bytes, hipStream_t s) {
+  GEOBI_TRY(parts_ptr_ok("nearest_parts", "qptr", qptr, P));
+  GEOBI_TRY(parts_ptr_ok("nearest_parts", "tptr", tptr, P));
+  const int want = parts_want(qptr, P);
+  const int smax = nearest_parts_slices(qptr, tptr, P);
+  const int ld = (int)qptr[P];
+  Arena ar(ws, ws_bytes);
+  float* pd = ar.take<float>((size_t)smax * ld);
+  int* pi = ar.take<int>((size_t)smax * ld);
+  GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_parts: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
+  for (int base = 0; base < P; base += kMaxSearchParts) {
+    PartsJob job;
+    job.n = P - base < kMaxSearchParts ? P - base : kMaxSearchParts;
+    int blocks = 0, sl_max = 0;
+    for (int k = 0; k < job.n; ++k) {
+      const int p = base + k;
+      const Slicing c = part_slices(qptr[p + 1] - qptr[p], tptr[p + 1] - tptr[p], want);
+      job.q_begin[k] = (int)qptr[p];
+      job.t_begin[k] = (int)tptr[p];
+      job.block_begin[k] = blocks;
+      job.tiles_per_slice[k] = c.tiles_per_slice;
+      job.slices[k] = c.slices;
+      blocks += c.qblocks;
+      sl_max = c.slices > sl_max ? c.slices : sl_max;
+    }
+    for (int k = job.n; k <= kMaxSearchParts; ++k) {      // the unused tail repeats the end: nothing is left unset
+      job.q_begin[k] = (int)qptr[base + job.n];
+      job.t_begin[k] = (int)tptr[base + job.n];
+      job.block_begin[k] = blocks;
+      if (k < kMaxSearchParts) { job.tiles_per_slice[k] = 1; job.slices[k] = 1; }
+    }
+    nearest_parts_kernel<<<dim3(blocks, sl_max), kThreads, 0, s>>>(job, q, t, ld, pd, pi);
+    const int rows = job.q_begin[job.n] - job.q_begin[0];
+    nearest_parts_reduce_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(job, pd, pi, ld, d2, idx);
+  }
   GEOBI_LAUNCH_OK();
   return 0;
 }

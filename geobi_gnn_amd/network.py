@@ -191,21 +191,39 @@ class DualGNNFn(torch.autograd.Function):
 
 # ---------------------------------------------------------------------------------------
 _KIND = {'L1': 0, 'L2': 1}
+LOSS_V_NAMES = ('L1', 'L2', 'CD')
+LOSS_N_NAMES = ('L1', 'L2', 'sided')
+
+
+def check_loss_names(loss_v=None, loss_n=None):
+    """ValueError that lists the valid names for an unknown ``--loss_v`` / ``--loss_n``."""
+    if loss_v is not None and loss_v not in LOSS_V_NAMES:
+        raise ValueError('loss_v: unknown distance %r (valid: %s)' % (loss_v, ', '.join(LOSS_V_NAMES)))
+    if loss_n is not None and loss_n not in LOSS_N_NAMES:
+        raise ValueError('loss_n: unknown norm %r (valid: %s)' % (loss_n, ', '.join(LOSS_N_NAMES)))
 
 
 def loss_v(vp, v, dis='L2', apply_icp=False):
-    """network.py:364-377: mean over vertices of sum_c |d| ('L1') or sum_c d^2 ('L2')."""
+    """network.py:364-377: mean over vertices of sum_c |d| ('L1') or sum_c d^2 ('L2'); 'CD': the Chamfer distance
+    mean_i min_j |vp_i - v_j|^2 + mean_j min_i |vp_i - v_j|^2 (kaolin's chamfer_distance, :369-370; gradient to vp)."""
     if apply_icp:
         raise NotImplementedError('ICP alignment needs pytorch3d, which the reference treats as optional')
-    if dis not in _KIND:
-        raise NotImplementedError("loss_v: %r relies on kaolin, which the reference never imports" % (dis,))
+    if dis == 'EMD':
+        raise NotImplementedError("loss_v: 'EMD' is an empty branch in the reference (network.py:371-372)")
+    check_loss_names(loss_v=dis)
+    if dis == 'CD':
+        return ops.chamfer_loss(vp, v)
     return ops.row_loss(vp, v, _KIND[dis])
 
 
 def loss_n(np, n, norm='L1', fc_p=None, fc=None):
-    """network.py:380-389."""
-    if norm not in _KIND:
-        raise NotImplementedError("loss_n: %r relies on kaolin, which the reference never imports" % (norm,))
+    """network.py:380-389.  'sided': np_i against n[idx_i], idx_i the face whose centroid fc is nearest to the predicted
+    centroid fc_p[i] (kaolin's sided_distance, :385-388; data_util.face_centroids builds both; gradient to np)."""
+    check_loss_names(loss_n=norm)
+    if norm == 'sided':
+        if fc_p is None or fc is None:
+            raise ValueError("loss_n: norm='sided' needs the face centroids fc_p (predicted) and fc (ground truth)")
+        return ops.sided_loss(np, n, fc_p, fc)
     return ops.row_loss(np, n, _KIND[norm])
 
 

@@ -489,3 +489,106 @@ class RowLossFn(Function):
 def row_loss(a, b, kind, weights=None, scale=None):
     n = a.shape[0]
     return RowLossFn.apply(a, b, weights, kind, (1.0 / n) if scale is None else scale)
+
+
+# ------------------------------------------------------- correspondence-free losses (CD / sided)
+def _part_ptr(ptr, n, what):
+    """Host part pointer of a union batch -> list of ints; None is one part [0, n].  The ends must be 0 and n: the
+    kernels take the pointer's word for where the rows are."""
+    if ptr is None:
+        lst = [0, int(n)]
+    else:
+        lst = [int(v) for v in (ptr.tolist() if torch.is_tensor(ptr) else ptr)]
+    if len(lst) < 2 or lst[0] != 0 or lst[-1] != int(n):
+        raise L.GeobiError('%s %r does not cover the %d rows it cuts (it must run from 0 to %d)' % (what, lst, n, n))
+    return lst
+
+
+def _c_ptr(lst):
+    import ctypes
+    arr = (ctypes.c_int64 * len(lst))(*lst)
+    return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def _points3(t, what):
+    L.require_device(t, what)
+    t = _f32c(t.detach())
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise L.GeobiError('%s must be [n, 3], got %s' % (what, tuple(t.shape)))
+    return t
+
+
+def nearest_parts(q, t, qptr=None, tptr=None):
+    """For every row of q [Q, 3] the nearest row of t [T, 3] AMONG THE ROWS OF ITS OWN PART (geobi_nearest_parts; the
+    search under kaolin's chamfer_distance / sided_distance, code/network.py:370,386).  qptr / tptr: host part pointers
+    [P + 1] (list or CPU tensor; None: one part); no part may be empty.
+    -> (d2 float32 [Q]: SQUARED distance, idx int32 [Q]: row of t, the lowest among equally near ones)."""
+    q, t = _points3(q, 'query points'), _points3(t, 'target points')
+    Q, T = q.shape[0], t.shape[0]
+    qp, tp = _part_ptr(qptr, Q, 'qptr'), _part_ptr(tptr, T, 'tptr')
+    if len(qp) != len(tp):
+        raise L.GeobiError('nearest_parts: %d query parts but %d target parts' % (len(qp) - 1, len(tp) - 1))
+    P = len(qp) - 1
+    (qa, qc), (ta, tc) = _c_ptr(qp), _c_ptr(tp)
+    d2 = torch.empty(Q, dtype=torch.float32, device=q.device)
+    idx = torch.empty(Q, dtype=torch.int32, device=q.device)
+    ws = L.workspace(L.lib().geobi_nearest_parts_ws_bytes(qc, tc, P), q.device)
+    L.call('geobi_nearest_parts', L.ptr(q), L.ptr(t), qc, tc, P, L.ptr(d2), L.ptr(idx), L.ptr(ws), ws.numel(), L.stream())
+    return d2, idx
+
+
+def nearest_parts_slices(qptr, tptr):
+    """The largest number of target slices geobi_nearest_parts cuts a part into for these sizes (host computation)."""
+    (qa, qc), (ta, tc) = _c_ptr([int(v) for v in qptr]), _c_ptr([int(v) for v in tptr])
+    return int(L.lib().geobi_nearest_parts_slices(qc, tc, len(qptr) - 1))
+
+
+class ChamferFn(Function):
+    """kaolin's chamfer_distance(vp, v) as loss_v(..., dis='CD') calls it (code/network.py:369-370), per mesh of a union
+    batch and averaged over the meshes: mean_i min_j |p_i - t_j|^2 + mean_j min_i |p_i - t_j|^2.  The two arg-min maps are
+    constants of the gradient, which goes to the prediction only."""
+
+    @staticmethod
+    def forward(ctx, p, t, qptr, tptr):
+        p, t = _points3(p, 'prediction'), _points3(t, 'target')
+        qp, tp = _part_ptr(qptr, p.shape[0], 'qptr'), _part_ptr(tptr, t.shape[0], 'tptr')
+        d2a, ia = nearest_parts(p, t, qp, tp)
+        d2b, ib = nearest_parts(t, p, tp, qp)
+        P = len(qp) - 1
+        (qa, qc), (ta, tc) = _c_ptr(qp), _c_ptr(tp)
+        out = torch.empty(1, dtype=torch.float32, device=p.device)
+        ws = L.workspace(L.size_query('geobi_chamfer_ws_bytes', P), p.device)
+        L.call('geobi_chamfer_fwd', L.ptr(d2a), L.ptr(d2b), qc, tc, P, L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
+        ctx.qp, ctx.tp = qp, tp
+        ctx.save_for_backward(p, t, ia, ib)
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        p, t, ia, ib = ctx.saved_tensors
+        sidx = SegmentIndex(ib, p.shape[0])          # prediction row -> the targets that chose it, ascending
+        (qa, qc), (ta, tc) = _c_ptr(ctx.qp), _c_ptr(ctx.tp)
+        gp = torch.empty_like(p)
+        g = gout.reshape(1).float().contiguous()
+        L.call('geobi_chamfer_bwd', L.ptr(p), L.ptr(t), L.ptr(ia), L.ptr(sidx.segptr), L.ptr(sidx.members), qc, tc,
+               len(ctx.qp) - 1, L.ptr(g), L.ptr(gp), L.stream())
+        return gp, None, None, None
+
+
+def chamfer_loss(p, t, qptr=None, tptr=None):
+    return ChamferFn.apply(p, t, qptr, tptr)
+
+
+def sided_loss(np_, n, fc_p, fc, fptr=None, weights=None):
+    """loss_n(np, n, 'sided', fc_p, fc) (code/network.py:385-388): every predicted normal against the ground-truth normal
+    of the face whose centroid is nearest to the predicted face's, the search confined to the meshes of `fptr`;
+    `weights`: per-row 1 / (B n_mesh) of a union batch (None: plain mean).  The gradient goes to np only."""
+    L.require_device(np_, 'predicted normals')
+    n = _f32c(n.detach())
+    if n.dim() != 2 or n.shape[1] != 3 or n.shape[0] != fc.shape[0] or np_.shape[0] != fc_p.shape[0]:
+        raise L.GeobiError('sided loss: normals %s / %s do not match centroids %s / %s'
+                           % (tuple(np_.shape), tuple(n.shape), tuple(fc_p.shape), tuple(fc.shape)))
+    _, idx = nearest_parts(fc_p, fc, fptr, fptr)
+    ng = torch.empty((idx.shape[0], 3), dtype=torch.float32, device=n.device)
+    L.call('geobi_gather_rows', L.ptr(n), L.ptr(idx), 3, idx.shape[0], L.ptr(ng), L.stream())
+    return row_loss(np_, ng, 0, weights, 1.0 if weights is not None else None)

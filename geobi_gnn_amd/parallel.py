@@ -217,18 +217,48 @@ def _mesh_weights(data):
     return w
 
 
+def _cpu_nearest(q, t, chunk=2048):
+    """argmin_j |q_i - t_j|^2 by plain torch ops (the CPU statement of the search): chunks of queries against all the
+    targets, distances from coordinate differences, torch.argmin's first minimum = the lowest index."""
+    idx = torch.empty(q.shape[0], dtype=torch.long, device=q.device)
+    for s in range(0, q.shape[0], chunk):
+        d = q[s:s + chunk, None, :] - t[None, :, :]
+        idx[s:s + chunk] = d.pow(2).sum(2).argmin(1)
+    return idx
+
+
+def _cpu_chamfer(p, t):
+    """Chamfer distance of one mesh, gradient to p only with the two arg-min maps as constants."""
+    t = t.detach()
+    with torch.no_grad():
+        a, b = _cpu_nearest(p, t), _cpu_nearest(t, p)
+    return (p - t[a]).pow(2).sum(1).mean() + (p[b] - t).pow(2).sum(1).mean()
+
+
 def batched_losses(vp, npred, data_v, data_f, loss_v='L1', loss_n='L1'):
     """Per-mesh mean losses averaged over the meshes of a disjoint-union batch.
 
     Identical to accumulating ``loss / batch_size`` over sequential single-mesh steps
     (train_dual.py:204-212).  Without ``mesh_ptr`` it is the plain per-node mean.  On the MI355X
-    this is the fused reduction kernel (geobi_row_loss_*); CPU tensors (gloo tests) use torch ops."""
+    this is the fused reduction kernel (geobi_row_loss_*), for 'CD' / 'sided' on top of the per-mesh search
+    (geobi_nearest_parts, geobi_chamfer_*); CPU tensors (gloo tests) use torch ops."""
+    from . import network
+    network.check_loss_names(loss_v, loss_n)
     kinds = {'L1': 0, 'L2': 1}
+    ptr_v, ptr_f = getattr(data_v, 'mesh_ptr', None), getattr(data_f, 'mesh_ptr', None)
     if vp.is_cuda:
         from . import ops
         wv, wn = _mesh_weights(data_v), _mesh_weights(data_f)
-        lv = ops.row_loss(vp, data_v.y, kinds[loss_v], wv, 1.0 if wv is not None else None)
-        ln = ops.row_loss(npred, data_f.y, kinds[loss_n], wn, 1.0 if wn is not None else None)
+        if loss_v == 'CD':
+            lv = ops.chamfer_loss(vp, data_v.y, ptr_v, ptr_v)
+        else:
+            lv = ops.row_loss(vp, data_v.y, kinds[loss_v], wv, 1.0 if wv is not None else None)
+        if loss_n == 'sided':
+            from .data_util import face_centroids
+            fc_p, fc = face_centroids(vp, data_f.fv_indices), face_centroids(data_v.y, data_f.fv_indices)
+            ln = ops.sided_loss(npred, data_f.y, fc_p, fc, ptr_f, wn)
+        else:
+            ln = ops.row_loss(npred, data_f.y, kinds[loss_n], wn, 1.0 if wn is not None else None)
         return lv, ln
 
     def per_node(a, b, kind):
@@ -242,6 +272,21 @@ def batched_losses(vp, npred, data_v, data_f, loss_v='L1', loss_n='L1'):
         w = torch.repeat_interleave(1.0 / (counts.to(vals.dtype) * counts.numel()), counts)
         return (vals * w).sum()
 
-    lv = reduce(per_node(vp, data_v.y, loss_v), getattr(data_v, 'mesh_ptr', None))
-    ln = reduce(per_node(npred, data_f.y, loss_n), getattr(data_f, 'mesh_ptr', None))
+    def spans(ptr, n):
+        cut = [0, n] if ptr is None else [int(v) for v in ptr.tolist()]
+        return list(zip(cut[:-1], cut[1:]))
+
+    if loss_v == 'CD':
+        sp = spans(ptr_v, vp.shape[0])
+        lv = sum(_cpu_chamfer(vp[a:b], data_v.y[a:b]) for a, b in sp) / len(sp)
+    else:
+        lv = reduce(per_node(vp, data_v.y, loss_v), ptr_v)
+    if loss_n == 'sided':
+        fv = data_f.fv_indices.long()
+        with torch.no_grad():
+            fc_p, fc = vp.detach()[fv].sum(1) / 3.0, data_v.y[fv].sum(1) / 3.0
+            idx = torch.cat([a + _cpu_nearest(fc_p[a:b], fc[a:b]) for a, b in spans(ptr_f, fc.shape[0])])
+        ln = reduce(per_node(npred, data_f.y[idx], 'L1'), ptr_f)
+    else:
+        ln = reduce(per_node(npred, data_f.y, loss_n), ptr_f)
     return lv, ln

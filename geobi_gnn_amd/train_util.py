@@ -18,8 +18,12 @@ LR_SCHEDULES = ('step', 'multi_step', 'exp', 'auto', 'lmd')
 
 def add_training_flags(parser):
     """The optimiser / schedule / loss flags of train_dual.py:57-82, same names, types and defaults."""
-    parser.add_argument('--loss_v', type=str, default='L1')
-    parser.add_argument('--loss_n', type=str, default='L1')
+    parser.add_argument('--loss_v', type=str, default='L1',
+                        help="vertex loss: L1, L2 (row by row against the ground truth) or CD (Chamfer distance: squared "
+                             'distance to the nearest ground-truth vertex and back, no correspondence needed)')
+    parser.add_argument('--loss_n', type=str, default='L1',
+                        help='normal loss: L1, L2 (face by face) or sided (L1 against the normal of the ground-truth face '
+                             'whose centroid is nearest to the predicted face)')
     parser.add_argument('--loss_v_scale', type=float, default=1)
     parser.add_argument('--loss_n_scale', type=float, default=1)
     parser.add_argument('--wei_param', type=int, default=2)
@@ -134,7 +138,11 @@ class EvalMeter(object):
             self.sums[i] += v
 
     def add_prediction(self, vert_p, norm_p, data_v, data_f, loss_v='L1', loss_n='L1'):
-        self.add(network.loss_v(vert_p, data_v.y, loss_v), network.loss_n(norm_p, data_f.y, loss_n),
+        fc_p = fc = None
+        if loss_n == 'sided':
+            from .data_util import face_centroids
+            fc_p, fc = face_centroids(vert_p, data_f.fv_indices), face_centroids(data_v.y, data_f.fv_indices)
+        self.add(network.loss_v(vert_p, data_v.y, loss_v), network.loss_n(norm_p, data_f.y, loss_n, fc_p, fc),
                  network.error_v(vert_p, data_v.y), network.error_n(norm_p, data_f.y),
                  data_v.y.shape[0], data_f.y.shape[0])
 

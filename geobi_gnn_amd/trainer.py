@@ -136,12 +136,22 @@ def require_single_process():
                          'tools/train_synthetic.py' % os.environ['WORLD_SIZE'])
 
 
+def require_known_losses(opt):
+    """``--loss_v`` / ``--loss_n`` are free text to the parser (as in train_dual.py:57-58): a wrong name ends the command
+    here, before the device is touched or a mesh is read, with the valid names in the message."""
+    try:
+        network.check_loss_names(opt.loss_v, opt.loss_n)
+    except ValueError as e:
+        raise SystemExit('geobi_gnn_amd train: %s' % e)
+
+
 def train(opt, dev, predict=None):
     """The ``train`` command on device ``dev``.  Writes into ``opt.out_dir``: GeoBi-GNN_<data_type>_model.pth (best state dict, the
     reference's keys), GeoBi-GNN_<data_type>_params.json (the options), training_info.txt (what was printed), train/ and
     test/ event files and -- through ``predict`` (the ``denoise`` command's function) unless ``opt.no_predict`` --
     result/ with the denoised test meshes (train_dual.py:297-298).  -> exit status"""
     require_single_process()
+    require_known_losses(opt)
     if opt.seed is None:
         import random
         opt.seed = random.randint(1, 10000)

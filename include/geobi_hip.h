@@ -303,6 +303,41 @@ int geobi_nearest_triangle(const float* q, const float* verts, const int32_t* fv
 size_t geobi_dist_summary_ws_bytes(int64_t n);
 int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- correspondence-free losses ----
+ * The two loss options of the reference that need no vertex-to-vertex correspondence: loss_v(vp, v, dis='CD')
+ * (code/network.py:369-370, kaolin's chamfer_distance: squared distances, both directions, means) and
+ * loss_n(np, n, norm='sided', fc_p, fc) (code/network.py:385-388, kaolin's sided_distance: the index of the nearest
+ * ground-truth face centroid), for a disjoint-union batch of P meshes: every search stays inside its own mesh.
+ * qptr / tptr [P + 1] are HOST arrays (rows qptr[p] .. qptr[p + 1] of q and tptr[p] .. tptr[p + 1] of t are part p) that
+ * travel in the kernel arguments as geobi_rotate_parts' part_ptr does, 32 parts per launch: no copy, no sync.  P >= 1;
+ * an EMPTY part on either side is an error; qptr[P] and tptr[P] are bounded by GEOBI_MAX_NODES.
+ *   geobi_nearest_parts   d2[i] = min_j |q_i - t_j|^2 over the targets j of i's own part (SQUARED, no sqrt), idx[i] = that j
+ *                         as a row of t (the lowest among equally near ones).  Same kernel shape and the same pair
+ *                         arithmetic as geobi_nearest_point: for any part, idx - tptr[p] is what geobi_nearest_point
+ *                         returns on that part's rows alone (and d2 the square its dist is the root of), whatever the slicing
+ *                         (geobi_nearest_parts_slices: the largest slice count the library picks -- a pure host function).
+ *                         A query with a NaN coordinate gets d2 = +inf and the first row of its slice range: never an
+ *                         index outside its part.  ws: geobi_nearest_parts_ws_bytes(qptr, tptr, P)
+ *   geobi_chamfer_fwd     out[0] = sum_p (1/P) [ mean_{i in p} d2a[i] + mean_{j in p} d2b[j] ],  d2a [qptr[P]] / d2b [tptr[P]]
+ *                         = geobi_nearest_parts prediction -> target / target -> prediction; fp64 sums in a fixed order.
+ *                         ws: geobi_chamfer_ws_bytes(P)
+ *   geobi_chamfer_bwd     gp[i] = gout[0] * ( 2 / (P Q_p) (p_i - t_idx_a[i]) + 2 / (P M_p) sum_{j : b(j) = i} (p_i - t_j) ):
+ *                         the arg-min maps are constants, the gradient goes to the prediction only.  idx_a [Q]: the
+ *                         indices of the first search; (segptr [Q + 1], members [M]) = geobi_segment_csr of the second
+ *                         search's indices b with nseg = Q (members ascending).  Every row of gp is written once, no
+ *                         atomics; needs qptr[0] == tptr[0] == 0.
+ * The sided normal loss needs no arithmetic of its own: geobi_nearest_parts on the face centroids, geobi_gather_rows of
+ * the ground-truth normals, geobi_row_loss_* (kind 0) with the per-mesh weights.                                          */
+size_t geobi_nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P);
+int geobi_nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P);
+int geobi_nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2,
+                        int32_t* idx, void* ws, size_t ws_bytes, void* stream);
+size_t geobi_chamfer_ws_bytes(int P);
+int geobi_chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out,
+                      void* ws, size_t ws_bytes, void* stream);
+int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
+                      const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, void* stream);
+
 /* ---------------------------------------------------------------- synthetic mesh noise ----
  * The reference has NO call site for this: its dataset is an external download (README.md:7) and the generator of its
  * noisy meshes is not in its tree.  out[v] = points[v] + displacement(v), v in [0, V); out may alias points; V == 0 is a
