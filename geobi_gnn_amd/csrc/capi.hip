@@ -509,6 +509,26 @@ int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float
   return mesh_noise(points, vnormal, V, sigma, kind, direction, fraction, seed, stream_id, draw, out, S(stream));
 }
 
+int geobi_bnf_prepare(const float* points, const int32_t* fv, int64_t F, int64_t V, float* rec_c, float* rec_n,
+                      void* stream) {
+  SIZES(F > V ? F : V, 0);
+  if (F == 0) return 0;
+  NOTNULL(points); NOTNULL(fv); NOTNULL(rec_c); NOTNULL(rec_n);
+  return bnf_prepare(points, fv, F, rec_c, rec_n, S(stream));
+}
+
+size_t geobi_bnf_filter_ws_bytes(int64_t F, int64_t E) { return bnf_filter_ws_bytes(F, E); }
+
+int geobi_bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F,
+                     int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes,
+                     void* stream) {
+  SIZES(F, E);
+  if (F == 0) return 0;
+  NOTNULL(rec_c); NOTNULL(rec_n); NOTNULL(rowptr); NOTNULL(inv2ss); NOTNULL(out); NOTNULL(ws);
+  if (E > 0) NOTNULL(col);
+  return bnf_filter(rec_c, rec_n, rowptr, col, F, E, inv2ss, inv2sr, n_sweeps, out, ws, ws_bytes, S(stream));
+}
+
 int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, float bias_corr1, float bias_corr2, void* stream) {
   NOTNULL(p); NOTNULL(g); NOTNULL(m); NOTNULL(v);

@@ -308,6 +308,11 @@ int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int3
 // noise.hip (synthetic mesh noise: counter-based Philox4x32-10, one counter per vertex)
 int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
                uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s);
+// filter.hip (bilateral normal filter over the facet graph: the model-free baseline of `denoise`)
+int bnf_prepare(const float* points, const int32_t* fv, int64_t F, float* rec_c, float* rec_n, hipStream_t s);
+size_t bnf_filter_ws_bytes(int64_t F, int64_t E);
+int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
+               const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

@@ -355,6 +355,31 @@ int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, cons
 int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction,
                      float fraction, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, void* stream);
 
+/* ---------------------------------------------------------------- bilateral normal filter ----
+ * The reference has NO call site for this: its scratch code only lists result folders of classical filters beside its own
+ * (code/data_util.py:732-745).  Zheng et al. 2011, local iterative scheme, over the loop-free (row, col)-sorted facet graph
+ * (geobi_ring_graph_*, kind 1); the neighbourhood N(i) of face i is its row PLUS i itself.
+ *   geobi_bnf_prepare    face records as 16-byte rows: rec_c [F, 4] = (centroid, area A = |cr| / 2), rec_n [F, 4] = (start
+ *                        normal cr / max(|cr|, 1e-12), 0), cr = (b - a) x (c - a); fp64 inside, fp32 out.  A face of exactly
+ *                        zero area gets A = 0 and the zero vector.  fv must index [0, V): range-check it first
+ *   geobi_bnf_filter     n_sweeps Jacobi sweeps (ping-pong buffers, one launch per sweep: k sweeps in one call are k calls of
+ *                        one sweep, bit for bit)
+ *                          w_ij = A_j exp(-inv2ss |c_i - c_j|^2 - inv2sr |n_i - n_j|^2)     (differences, never expanded)
+ *                          s_i = sum_{j in N(i)} w_ij n_j,  W_i = sum w_ij,  n_i' = s_i / |s_i| if |s_i| > 1e-6 W_i, else n_i
+ *                        inv2ss = 1 / (2 sigma_s^2) is a DEVICE scalar (sigma_s comes from the mesh's mean centroid distance
+ *                        and never visits the host; 0 for a graph without edges), inv2sr = 1 / (2 sigma_r^2).  rec_n holds
+ *                        the normals to start from, out [F, 4] receives rows of rec_n's layout (so a result can be handed
+ *                        back as rec_n) and must not alias a record array; n_sweeps = 0 copies rec_n.  A fixed group of 16
+ *                        lanes per face with a fixed-shape reduction, no atomics: two runs give the same bits.
+ *                        The spatial factor A_j exp(-inv2ss d^2), which no sweep changes, is computed once per call into
+ *                        a per-edge array of the workspace.                                                             */
+int geobi_bnf_prepare(const float* points, const int32_t* fv, int64_t F, int64_t V, float* rec_c, float* rec_n,
+                      void* stream);
+size_t geobi_bnf_filter_ws_bytes(int64_t F, int64_t E);
+int geobi_bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F,
+                     int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* ---------------------------------------------------------------- optimiser step ----
  * torch.optim.Adam's update rule (code/train_dual.py:162, the reference's default optimiser; no amsgrad) over one flat
  * fp32 vector of n parameters, its gradient and the two moment vectors (16-byte aligned), one launch:
