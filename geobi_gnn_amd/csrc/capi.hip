@@ -192,6 +192,18 @@ static int sizes_ok(const char* fn, int64_t nodes, int64_t edges) {
 }
 #define SIZES(nodes, edges) GEOBI_TRY(sizes_ok(__func__, (int64_t)(nodes), (int64_t)(edges)))
 
+// the host part pointers of a union batch (common.h): every entry point that takes them checks them here, once
+int geobi::parts_check(const char* fn, const int64_t* qptr, const int64_t* tptr, int P) {
+  GEOBI_REQUIRE(P >= 1, "%s: P = %d parts (at least one)", fn, P);
+  GEOBI_REQUIRE(qptr != nullptr && tptr != nullptr, "%s: qptr / tptr is NULL", fn);
+  GEOBI_REQUIRE(qptr[0] >= 0 && tptr[0] >= 0, "%s: qptr / tptr starts below 0", fn);
+  for (int p = 0; p < P; ++p)
+    for (const int64_t* ptr : {qptr, tptr})
+      GEOBI_REQUIRE(ptr[p + 1] > ptr[p], "%s: part %d of %s is empty (%lld .. %lld): an empty part is an error, not a launch", fn,
+                    p, ptr == qptr ? "qptr" : "tptr", (long long)ptr[p], (long long)ptr[p + 1]);
+  return sizes_ok(fn, qptr[P] > tptr[P] ? qptr[P] : tptr[P], 0);
+}
+
 extern "C" {
 
 int geobi_version(void) { return 100; }
@@ -464,33 +476,26 @@ int geobi_nearest_triangle(const float* q, const float* verts, const int32_t* fv
   NOTNULL(q); NOTNULL(verts); NOTNULL(fv); NOTNULL(dist); NOTNULL(ws);
   return nearest_triangle(q, verts, fv, Q, V, F, dist, face, ws, ws_bytes, S(stream));
 }
-// every entry point that takes host part pointers: P >= 1, no empty part, the row counts inside the size limits
-static int parts_ok(const char* fn, const int64_t* qptr, const int64_t* tptr, int P) {
-  if (P < 1) return set_error("%s: P = %d parts (at least one)", fn, P);
-  if (qptr == nullptr || tptr == nullptr) return set_error("%s: qptr / tptr is NULL", fn);
-  if (parts_ptr_ok(fn, "qptr", qptr, P) != 0 || parts_ptr_ok(fn, "tptr", tptr, P) != 0) return 1;
-  return sizes_ok(fn, qptr[P] > tptr[P] ? qptr[P] : tptr[P], 0);
-}
 size_t geobi_nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
   return nearest_parts_ws_bytes(qptr, tptr, P);
 }
 int geobi_nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P) { return nearest_parts_slices(qptr, tptr, P); }
 int geobi_nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2,
                         int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
-  if (parts_ok(__func__, qptr, tptr, P) != 0) return 1;
+  GEOBI_TRY(parts_check(__func__, qptr, tptr, P));
   NOTNULL(q); NOTNULL(t); NOTNULL(d2); NOTNULL(idx); NOTNULL(ws);
   return nearest_parts(q, t, qptr, tptr, P, d2, idx, ws, ws_bytes, S(stream));
 }
 size_t geobi_chamfer_ws_bytes(int P) { return chamfer_ws_bytes(P); }
 int geobi_chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out,
                       void* ws, size_t ws_bytes, void* stream) {
-  if (parts_ok(__func__, qptr, tptr, P) != 0) return 1;
+  GEOBI_TRY(parts_check(__func__, qptr, tptr, P));
   NOTNULL(d2a); NOTNULL(d2b); NOTNULL(out); NOTNULL(ws);
   return chamfer_fwd(d2a, d2b, qptr, tptr, P, out, ws, ws_bytes, S(stream));
 }
 int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
                       const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, void* stream) {
-  if (parts_ok(__func__, qptr, tptr, P) != 0) return 1;
+  GEOBI_TRY(parts_check(__func__, qptr, tptr, P));
   NOTNULL(p); NOTNULL(t); NOTNULL(idx_a); NOTNULL(segptr); NOTNULL(members); NOTNULL(gout); NOTNULL(gp);
   return chamfer_bwd(p, t, idx_a, segptr, members, qptr, tptr, P, gout, gp, S(stream));
 }

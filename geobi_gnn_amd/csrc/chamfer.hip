@@ -6,10 +6,11 @@
 //   backward  gp_i = gout (2 / (B Q_p)) (p_i - t_a(i)) + gout (2 / (B M_p)) sum_{j : b(j) = i} (p_i - t_j)
 //
 // Both are free of atomics and of any order that depends on timing.  The sum is fp64 in a fixed order: a grid of a size
-// that depends on the row counts only walks the rows with a grid stride, an LDS tree folds a block, one thread adds
-// the block sums in ascending order.  The backward writes every row of gp exactly once: the targets that chose row i
+// that depends on the row counts only walks the rows with a grid stride, block_sum_fp64 folds a block, one thread adds
+// the block sums in ascending order (fold_ascending; both in common.h).  The backward writes every row of gp exactly once: the targets that chose row i
 // come from the inverse lists of b (geobi_segment_csr: members ascending), gathered and summed by the row's own lane.
-// The part table rides in the kernel arguments, 32 parts per launch, as in rotate_parts / nearest_parts.
+// The part tables ride in the kernel arguments (PartTable, common.h), kMaxParts parts per launch, with the weights.
+// The part pointers were checked once, by the entry point (parts_check).
 #include "common.h"
 
 namespace geobi {
@@ -17,60 +18,41 @@ namespace geobi {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxParts = 32;
 constexpr int kMaxBlocks = 256;
 
 struct ChamferJob {
-  int q_begin[kMaxParts + 1];     // prediction rows of part k
-  int t_begin[kMaxParts + 1];     // target rows
+  PartTable<int> q, t;            // prediction / target rows of part k
   float wq[kMaxParts];            // 1 / (B Q_p), rounded once from fp64
   float wt[kMaxParts];            // 1 / (B M_p)
-  int n;
 };
-
-__device__ __forceinline__ int find_part(const int* begin, int n, int i) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {               // last part that starts at or before row i (no part is empty)
-    const int mid = (lo + hi + 1) >> 1;
-    if (begin[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __global__ __launch_bounds__(kThreads) void chamfer_partial_kernel(ChamferJob job, const float* __restrict__ d2a,
                                                                    const float* __restrict__ d2b,
                                                                    double* __restrict__ partial) {
   __shared__ int s_q[kMaxParts + 1], s_t[kMaxParts + 1];
   __shared__ float s_wq[kMaxParts], s_wt[kMaxParts];
-  __shared__ double ssum[kThreads];
-  for (int k = threadIdx.x; k <= job.n; k += kThreads) { s_q[k] = job.q_begin[k]; s_t[k] = job.t_begin[k]; }
-  for (int k = threadIdx.x; k < job.n; k += kThreads) { s_wq[k] = job.wq[k]; s_wt[k] = job.wt[k]; }
+  const int n = job.q.n;
+  stage_parts(s_q, job.q);
+  stage_parts(s_t, job.t);
+  for (int k = threadIdx.x; k < n; k += kThreads) { s_wq[k] = job.wq[k]; s_wt[k] = job.wt[k]; }
   __syncthreads();
-  const int nq = s_q[job.n] - s_q[0], nt = s_t[job.n] - s_t[0];
+  const int nq = s_q[n] - s_q[0], nt = s_t[n] - s_t[0];
   double acc = 0.0;
   for (int r = blockIdx.x * kThreads + threadIdx.x; r < nq + nt; r += gridDim.x * kThreads) {
     if (r < nq) {
       const int i = s_q[0] + r;
-      acc += (double)s_wq[find_part(s_q, job.n, i)] * (double)d2a[i];
+      acc += (double)s_wq[find_part(s_q, n, i)] * (double)d2a[i];
     } else {
       const int j = s_t[0] + (r - nq);
-      acc += (double)s_wt[find_part(s_t, job.n, j)] * (double)d2b[j];
+      acc += (double)s_wt[find_part(s_t, n, j)] * (double)d2b[j];
     }
   }
-  ssum[threadIdx.x] = acc;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) ssum[threadIdx.x] += ssum[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = ssum[0];
+  const double sum = block_sum_fp64<kThreads>(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 __global__ void chamfer_final_kernel(const double* __restrict__ partial, int n, float* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double s = 0.0;
-  for (int b = 0; b < n; ++b) s += partial[b];
-  out[0] = (float)s;
+  if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = (float)fold_ascending(partial, n);
 }
 
 __global__ __launch_bounds__(kThreads) void chamfer_bwd_kernel(ChamferJob job, const float* __restrict__ p,
@@ -80,13 +62,14 @@ __global__ __launch_bounds__(kThreads) void chamfer_bwd_kernel(ChamferJob job, c
                                                                float* __restrict__ gp) {
   __shared__ int s_q[kMaxParts + 1];
   __shared__ float s_wq[kMaxParts], s_wt[kMaxParts];
-  for (int k = threadIdx.x; k <= job.n; k += kThreads) s_q[k] = job.q_begin[k];
-  for (int k = threadIdx.x; k < job.n; k += kThreads) { s_wq[k] = job.wq[k]; s_wt[k] = job.wt[k]; }
+  const int n = job.q.n;
+  stage_parts(s_q, job.q);
+  for (int k = threadIdx.x; k < n; k += kThreads) { s_wq[k] = job.wq[k]; s_wt[k] = job.wt[k]; }
   __syncthreads();
   const int i = s_q[0] + blockIdx.x * kThreads + threadIdx.x;
-  if (i >= s_q[job.n]) return;
-  const int part = find_part(s_q, job.n, i);
-  const int t_lo = job.t_begin[0], t_hi = job.t_begin[job.n];            // uniform: rows this launch may gather
+  if (i >= s_q[n]) return;
+  const int part = find_part(s_q, n, i);
+  const int t_lo = job.t.begin[0], t_hi = job.t.begin[n];            // uniform: rows this launch may gather
   const float g = gout[0];
   const float px = p[3 * (size_t)i], py = p[3 * (size_t)i + 1], pz = p[3 * (size_t)i + 2];
   // direction a: the row's own nearest target (an index the search wrote: inside the part; the clamp keeps a foreign
@@ -113,16 +96,12 @@ int partial_blocks(int64_t rows) {
 }
 
 void fill_job(ChamferJob* job, const int64_t* qptr, const int64_t* tptr, int base, int P) {
-  job->n = P - base < kMaxParts ? P - base : kMaxParts;
-  for (int k = 0; k <= kMaxParts; ++k) {             // the unused tail repeats the end: nothing is left unset
-    const int p = base + (k < job->n ? k : job->n);
-    job->q_begin[k] = (int)qptr[p];
-    job->t_begin[k] = (int)tptr[p];
-    if (k < kMaxParts) {
-      const bool used = k < job->n;
-      job->wq[k] = used ? (float)(1.0 / ((double)P * (double)(qptr[p + 1] - qptr[p]))) : 0.f;
-      job->wt[k] = used ? (float)(1.0 / ((double)P * (double)(tptr[p + 1] - tptr[p]))) : 0.f;
-    }
+  fill_parts(&job->q, qptr, base, P);
+  fill_parts(&job->t, tptr, base, P);
+  for (int k = 0; k < kMaxParts; ++k) {              // the unused tail weighs nothing
+    const bool used = k < job->q.n;
+    job->wq[k] = used ? (float)(1.0 / ((double)P * (double)(job->q.begin[k + 1] - job->q.begin[k]))) : 0.f;
+    job->wt[k] = used ? (float)(1.0 / ((double)P * (double)(job->t.begin[k + 1] - job->t.begin[k]))) : 0.f;
   }
 }
 
@@ -136,8 +115,6 @@ size_t chamfer_ws_bytes(int P) {
 
 int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out, void* ws,
                 size_t ws_bytes, hipStream_t s) {
-  GEOBI_TRY(parts_ptr_ok("chamfer_fwd", "qptr", qptr, P));
-  GEOBI_TRY(parts_ptr_ok("chamfer_fwd", "tptr", tptr, P));
   Arena ar(ws, ws_bytes);
   const int launches = (P + kMaxParts - 1) / kMaxParts;
   double* partial = ar.take<double>((size_t)launches * kMaxBlocks);
@@ -146,7 +123,7 @@ int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const i
   for (int base = 0; base < P; base += kMaxParts) {
     ChamferJob job;
     fill_job(&job, qptr, tptr, base, P);
-    const int64_t rows = (int64_t)(job.q_begin[job.n] - job.q_begin[0]) + (job.t_begin[job.n] - job.t_begin[0]);
+    const int64_t rows = (int64_t)(job.q.begin[job.q.n] - job.q.begin[0]) + (job.t.begin[job.t.n] - job.t.begin[0]);
     const int blocks = partial_blocks(rows);
     chamfer_partial_kernel<<<blocks, kThreads, 0, s>>>(job, d2a, d2b, partial + used);
     used += blocks;
@@ -158,14 +135,12 @@ int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const i
 
 int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
                 const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, hipStream_t s) {
-  GEOBI_TRY(parts_ptr_ok("chamfer_bwd", "qptr", qptr, P));
-  GEOBI_TRY(parts_ptr_ok("chamfer_bwd", "tptr", tptr, P));
   GEOBI_REQUIRE(qptr[0] == 0 && tptr[0] == 0, "chamfer_bwd: qptr / tptr start at %lld / %lld (the inverse lists are indexed by "
                 "the rows themselves: both 0)", (long long)qptr[0], (long long)tptr[0]);
   for (int base = 0; base < P; base += kMaxParts) {
     ChamferJob job;
     fill_job(&job, qptr, tptr, base, P);
-    const int rows = job.q_begin[job.n] - job.q_begin[0];
+    const int rows = job.q.begin[job.q.n] - job.q.begin[0];
     chamfer_bwd_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(job, p, t, idx_a, segptr, members, (int)tptr[P], gout, gp);
   }
   GEOBI_LAUNCH_OK();

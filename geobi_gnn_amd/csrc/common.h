@@ -50,6 +50,63 @@ struct Arena {
   bool ok() const { return dry || off <= cap; }
 };
 
+// ---- part table of a disjoint-union batch, carried in the kernel arguments: no copy of the host arrays, nothing out
+// of stream order.  A launch takes kMaxParts parts; begin[k] .. begin[k + 1] are the rows of its part k.
+constexpr int kMaxParts = 32;
+template <typename T>
+struct PartTable {
+  T begin[kMaxParts + 1];
+  int n;
+};
+// the parts base .. base + n of a host part pointer with P parts; the unused tail repeats the end: nothing is left unset
+template <typename T>
+static inline void fill_parts(PartTable<T>* tab, const int64_t* ptr, int base, int P) {
+  tab->n = P - base < kMaxParts ? P - base : kMaxParts;
+  for (int k = 0; k <= kMaxParts; ++k) tab->begin[k] = (T)ptr[base + (k < tab->n ? k : tab->n)];
+}
+// the table into LDS, where a lane indexes it by ITS part (the caller places the barrier)
+template <typename T>
+__device__ __forceinline__ void stage_parts(T* s_begin, const PartTable<T>& tab) {
+  for (int k = threadIdx.x; k <= tab.n; k += blockDim.x) s_begin[k] = tab.begin[k];
+}
+// last part that starts at or before row i: an empty part never wins
+template <typename T>
+__device__ __forceinline__ int find_part(const T* begin, int n, T i) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (begin[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// ---- fp64 sum in a fixed order: an LDS tree over the kN threads of a block (halve from kN / 2 down to 1, a barrier
+// per level), then the blocks' sums in ascending order.  The tree shape and the block order ARE the bits.
+// `beside(h)` runs in the lanes below h at every level, for a second quantity folded by the same barriers.
+template <int kN, typename Beside>
+__device__ __forceinline__ double block_sum_fp64(double v, Beside beside) {
+  __shared__ double s[kN];
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = kN / 2; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      s[threadIdx.x] += s[threadIdx.x + h];
+      beside(h);
+    }
+    __syncthreads();
+  }
+  return s[0];
+}
+template <int kN>
+__device__ __forceinline__ double block_sum_fp64(double v) {
+  return block_sum_fp64<kN>(v, [](int) {});
+}
+__device__ __forceinline__ double fold_ascending(const double* __restrict__ partial, int n, int stride = 1) {
+  double s = 0.0;
+  for (int b = 0; b < n; ++b) s += partial[(size_t)b * stride];
+  return s;
+}
+
 // ---- optional per-kernel timing for bench.py's roofline object (events on the launch stream)
 enum ProfKernel { PROF_NONE = 0, PROF_AGG_FWD = 1, PROF_AGG_BWD = 2, PROF_ROWPASS = 3, PROF_GEMM = 4 };
 void prof_begin(int kernel, hipStream_t s, double alg_bytes, int tag);
@@ -294,7 +351,9 @@ int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int6
 size_t dist_summary_ws_bytes(int64_t n);
 int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s);
 // dist.hip: the point search confined to the parts of a union batch (host part pointers, 32 parts per launch)
-int parts_ptr_ok(const char* fn, const char* what, const int64_t* ptr, int P);     // P >= 1, no empty part
+// capi.hip: the one check of host part pointers (P >= 1, not NULL, start >= 0, no empty part, GEOBI_MAX_NODES rows);
+// the entry points run it once, the functions below rely on it
+int parts_check(const char* fn, const int64_t* qptr, const int64_t* tptr, int P);
 int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P);
 size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P);
 int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,

@@ -7,19 +7,27 @@
 //   nearest_parts     nearest_point confined to the meshes of a union batch: the search under the correspondence-free
 //                     losses, code/network.py:369-370 (chamfer_distance) and :385-388 (sided_distance)
 //
-// Shape of the two all-pairs kernels: a lane owns QPL queries in registers; the workgroup stages a tile of targets
-// in LDS (for triangles: a 16-float record per triangle, corners gathered once per tile); every lane walks the tile
-// reading the SAME address (LDS broadcast, no bank conflict), so one 16-byte LDS read feeds QPL pair tests.
+// ONE all-pairs walk (nearest_walk) serves the three searches: a lane owns QPL queries in registers; the workgroup
+// stages a tile of targets in LDS (for triangles: a 16-float record per triangle, corners gathered once per tile); every
+// lane walks the tile reading the SAME address (LDS broadcast, no bank conflict), so one LDS record feeds QPL pair
+// tests.  What differs between points and triangles is a target policy (PointTargets, TriangleTargets: tile size, LDS
+// record, staging, pair test); what differs between the single-mesh and the per-part search is where the kernel takes
+// the row ranges q0, q_end, t_begin, t_end from.  So for any part the answer is what nearest_point gives on that part's
+// rows alone: it is the same text.
 //
-// Determinism: the target set is cut into S slices of whole tiles so that a small query set still fills the chip; a
-// (query block, slice) workgroup writes per query its partial (d2, index) and a second kernel reduces the S partials in
-// ascending slice order.  Comparisons are strict (<) in ascending target order at both stages, so ties go to the LOWEST
-// index, and since min is exact and a pair's d2 is formed by the same instruction sequence whatever the slicing
-// (contraction is off in the pair functions; every fused multiply-add is written out), the result is bit-identical
-// for every S.  d2 is formed from coordinate DIFFERENCES, never |q|^2 + |t|^2 - 2 q.t; one sqrt per query at the end.
+// Determinism: the target set is cut into S slices of whole tiles so that a small query set still fills the chip
+// (slice_targets: the one slicing rule); a (query block, slice) workgroup writes per query its partial (d2, index) and
+// nearest_reduce_kernel reduces the S partials in ascending slice order.  Comparisons are strict (<) in ascending
+// target order at both stages, so ties go to the LOWEST index, and since min is exact and a pair's d2 is formed by the
+// same instruction sequence whatever the slicing (contraction is off in the pair functions; every fused multiply-add is
+// written out), the result is bit-identical for every S.  d2 is formed from coordinate DIFFERENCES, never
+// |q|^2 + |t|^2 - 2 q.t; one sqrt per query at the end.
 #include "common.h"
 
 #include <math.h>
+
+#include <algorithm>
+#include <type_traits>
 
 namespace geobi {
 
@@ -36,17 +44,72 @@ constexpr int kMaxSlices = 1024;
 
 struct Slicing { int qblocks, slices, tiles_per_slice; };
 
-Slicing choose_slices(int64_t Q, int64_t T, int qpl, int tile) {
+// slices a launch with `qblocks` query blocks in all would like: its workgroups together should fill the chip
+int want_slices(int64_t qblocks) {
+  const int64_t want = (kTargetBlocks + qblocks - 1) / qblocks;
+  return (int)(want > kMaxSlices ? kMaxSlices : (want < 1 ? 1 : want));
+}
+
+// THE slicing rule: T targets in whole tiles, at most `want` slices, no empty slice
+Slicing slice_targets(int64_t Q, int64_t T, int qpl, int tile, int want) {
   Slicing c;
   c.qblocks = cdiv(Q, (int64_t)kThreads * qpl);
   const int ntiles = cdiv(T, tile);
-  int want = cdiv(kTargetBlocks, c.qblocks);
-  if (want > kMaxSlices) want = kMaxSlices;
   if (want > ntiles) want = ntiles;
-  if (want < 1) want = 1;
   c.tiles_per_slice = cdiv(ntiles, want);
-  c.slices = cdiv(ntiles, c.tiles_per_slice);       // no empty slice
+  c.slices = cdiv(ntiles, c.tiles_per_slice);
   return c;
+}
+
+Slicing choose_slices(int64_t Q, int64_t T, int qpl, int tile) {
+  return slice_targets(Q, T, qpl, tile, want_slices(cdiv(Q, (int64_t)kThreads * qpl)));
+}
+
+// ---------------------------------------------------------------- the walk
+// Queries q0 .. q_end of this workgroup (QPL per lane, kThreads apart) against targets t_begin .. t_end; the partial
+// (d2, index) of query i goes to part_*[slice * ld_part + i].  Tail lanes repeat the range's last query and write
+// nothing.  bidx starts at t_begin: in range whatever the coordinates are (a NaN query never passes the <).
+template <class Targets>
+__device__ __forceinline__ void nearest_walk(const Targets& tg, const float* __restrict__ q, int q0, int q_end, int t_begin,
+                                             int t_end, int slice, int ld_part, float* __restrict__ part_d2,
+                                             int* __restrict__ part_idx) {
+  constexpr int kQpl = Targets::kQpl, kTile = Targets::kTile;
+  __shared__ typename Targets::Tile tile;
+  const int tid = threadIdx.x;
+  float qx[kQpl], qy[kQpl], qz[kQpl], best[kQpl];
+  int bidx[kQpl];
+#pragma unroll
+  for (int k = 0; k < kQpl; ++k) {
+    const int i = min(q0 + k * kThreads + tid, q_end - 1);
+    qx[k] = q[3 * (size_t)i]; qy[k] = q[3 * (size_t)i + 1]; qz[k] = q[3 * (size_t)i + 2];
+    best[k] = INFINITY;
+    bidx[k] = t_begin;
+  }
+  for (int t0 = t_begin; t0 < t_end; t0 += kTile) {
+    const int n = min(kTile, t_end - t0);
+    __syncthreads();
+    tg.stage(tile, t0, n, tid);
+    __syncthreads();
+#pragma unroll Targets::kUnroll
+    for (int j = 0; j < n; ++j) {
+      const typename Targets::Record r = Targets::load(tile, j);
+#pragma unroll
+      for (int k = 0; k < kQpl; ++k) {
+        const float d2 = Targets::d2(qx[k], qy[k], qz[k], r);
+        const bool lt = d2 < best[k];
+        best[k] = lt ? d2 : best[k];
+        bidx[k] = lt ? t0 + j : bidx[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kQpl; ++k) {
+    const int i = q0 + k * kThreads + tid;
+    if (i < q_end) {
+      part_d2[(size_t)slice * ld_part + i] = best[k];
+      part_idx[(size_t)slice * ld_part + i] = bidx[k];
+    }
+  }
 }
 
 // ---------------------------------------------------------------- point - point
@@ -56,163 +119,76 @@ __device__ __forceinline__ float pair_d2(float qx, float qy, float qz, float4 t)
   return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
 }
 
+struct PointTargets {                               // LDS: one float4 per target point
+  static constexpr int kQpl = kPointQpl, kTile = kPointTile, kUnroll = 4;
+  struct Tile { float4 p[kTile]; };
+  using Record = float4;
+  const float* __restrict__ t;
+  __device__ __forceinline__ void stage(Tile& tile, int t0, int n, int tid) const {
+    for (int j = tid; j < n; j += kThreads) {
+      const float* p = t + 3 * (size_t)(t0 + j);
+      tile.p[j] = make_float4(p[0], p[1], p[2], 0.f);
+    }
+  }
+  static __device__ __forceinline__ Record load(const Tile& tile, int j) { return tile.p[j]; }
+  static __device__ __forceinline__ float d2(float qx, float qy, float qz, const Record& r) { return pair_d2(qx, qy, qz, r); }
+};
+
 __global__ __launch_bounds__(kThreads) void nearest_point_kernel(const float* __restrict__ q, const float* __restrict__ t,
                                                                  int Q, int T, int tiles_per_slice,
                                                                  float* __restrict__ part_d2, int* __restrict__ part_idx) {
-  __shared__ float4 tile[kPointTile];
-  const int tid = threadIdx.x;
-  const int q0 = blockIdx.x * (kThreads * kPointQpl);
   const int slice = blockIdx.y;
-  float qx[kPointQpl], qy[kPointQpl], qz[kPointQpl], best[kPointQpl];
-  int bidx[kPointQpl];
   const int t_begin = slice * tiles_per_slice * kPointTile;
-  const int t_end = min(T, t_begin + tiles_per_slice * kPointTile);
-#pragma unroll
-  for (int k = 0; k < kPointQpl; ++k) {
-    const int i = min(q0 + k * kThreads + tid, Q - 1);        // tail lanes repeat the last query and write nothing
-    qx[k] = q[3 * (size_t)i]; qy[k] = q[3 * (size_t)i + 1]; qz[k] = q[3 * (size_t)i + 2];
-    best[k] = INFINITY;
-    bidx[k] = t_begin;
-  }
-  for (int t0 = t_begin; t0 < t_end; t0 += kPointTile) {
-    const int n = min(kPointTile, t_end - t0);
-#ifndef GEOBI_DIST_UNIFORM_LOADS
-    __syncthreads();
-    for (int j = tid; j < n; j += kThreads) {
-      const float* p = t + 3 * (size_t)(t0 + j);
-      tile[j] = make_float4(p[0], p[1], p[2], 0.f);
-    }
-    __syncthreads();
-#endif
-#pragma unroll 4
-    for (int j = 0; j < n; ++j) {
-#ifndef GEOBI_DIST_UNIFORM_LOADS
-      const float4 tj = tile[j];
-#else   // A/B variant (tools/build_variant.sh): no LDS tile, the wave-uniform target index makes these scalar loads
-      const float* p = t + 3 * (size_t)(t0 + j);
-      const float4 tj = make_float4(p[0], p[1], p[2], 0.f);
-#endif
-#pragma unroll
-      for (int k = 0; k < kPointQpl; ++k) {
-        const float d2 = pair_d2(qx[k], qy[k], qz[k], tj);
-        const bool lt = d2 < best[k];
-        best[k] = lt ? d2 : best[k];
-        bidx[k] = lt ? t0 + j : bidx[k];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kPointQpl; ++k) {
-    const int i = q0 + k * kThreads + tid;
-    if (i < Q) {
-      part_d2[(size_t)slice * Q + i] = best[k];
-      part_idx[(size_t)slice * Q + i] = bidx[k];
-    }
-  }
+  nearest_walk(PointTargets{t}, q, blockIdx.x * (kThreads * kPointQpl), Q, t_begin,
+               min(T, t_begin + tiles_per_slice * kPointTile), slice, Q, part_d2, part_idx);
 }
 
-// partials of the S slices in ascending order, strict <: the lowest index among equal distances survives
-__global__ void nearest_reduce_kernel(const float* __restrict__ part_d2, const int* __restrict__ part_idx, int Q, int S,
-                                      float* __restrict__ dist, int* __restrict__ idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Q) return;
-  float best = part_d2[i];
-  int b = part_idx[i];
-  for (int s = 1; s < S; ++s) {
-    const float d2 = part_d2[(size_t)s * Q + i];
-    const int j = part_idx[(size_t)s * Q + i];
-    if (d2 < best) { best = d2; b = j; }
-  }
-  dist[i] = sqrtf(best);
-  if (idx) idx[i] = b;
-}
-
-// ---------------------------------------------------------------- point - point, confined to the parts of a union batch
-// The search the correspondence-free losses need (code/network.py:369-370 chamfer_distance, :385-388 sided_distance) on
-// a disjoint-union batch: queries of part p only meet targets of part p.  Same shape as nearest_point_kernel -- QPL
-// queries per lane, the target tile in LDS read by broadcast, target slices, a strict-< reduction in ascending slice
-// order -- and the same pair_d2, so for any part the answer is what nearest_point gives on that part's rows alone.  A
-// workgroup belongs to ONE part (blocks are formed per part); the part table rides in the kernel arguments as the
-// offsets of rotate_parts_kernel do (geom.hip): no copy of the host arrays, nothing out of stream order.
-constexpr int kMaxSearchParts = 32;
+// The same search confined to the parts of a disjoint-union batch (code/network.py:369-370 chamfer_distance, :385-388
+// sided_distance): queries of part p only meet targets of part p.  A workgroup belongs to ONE part (blocks are formed
+// per part); the part tables ride in the kernel arguments (common.h).
 struct PartsJob {
-  int q_begin[kMaxSearchParts + 1];     // query rows of part k: q_begin[k] .. q_begin[k + 1]
-  int t_begin[kMaxSearchParts + 1];     // target rows
-  int block_begin[kMaxSearchParts + 1]; // first workgroup (blockIdx.x) of part k
-  int tiles_per_slice[kMaxSearchParts];
-  int slices[kMaxSearchParts];          // >= 1, no empty slice
-  int n;
+  PartTable<int> q, t;                  // query / target rows of part k
+  int block_begin[kMaxParts + 1];       // first workgroup (blockIdx.x) of part k
+  int tiles_per_slice[kMaxParts];
+  int slices[kMaxParts];                // >= 1, no empty slice
 };
 
 __global__ __launch_bounds__(kThreads) void nearest_parts_kernel(PartsJob job, const float* __restrict__ q,
                                                                  const float* __restrict__ t, int ld_part,
                                                                  float* __restrict__ part_d2, int* __restrict__ part_idx) {
-  __shared__ float4 tile[kPointTile];
-  const int tid = threadIdx.x;
   int p = 0;
-  while (p + 1 < job.n && (int)blockIdx.x >= job.block_begin[p + 1]) ++p;      // wave-uniform
+  while (p + 1 < job.q.n && (int)blockIdx.x >= job.block_begin[p + 1]) ++p;    // wave-uniform
   const int slice = blockIdx.y;
   if (slice >= job.slices[p]) return;                                         // the whole workgroup leaves together
-  const int q0 = job.q_begin[p] + ((int)blockIdx.x - job.block_begin[p]) * (kThreads * kPointQpl);
-  const int q_end = job.q_begin[p + 1];
   const int span = job.tiles_per_slice[p] * kPointTile;
-  const int t_begin = job.t_begin[p] + slice * span;
-  const int t_end = min(job.t_begin[p + 1], t_begin + span);
-  float qx[kPointQpl], qy[kPointQpl], qz[kPointQpl], best[kPointQpl];
-  int bidx[kPointQpl];
-#pragma unroll
-  for (int k = 0; k < kPointQpl; ++k) {
-    const int i = min(q0 + k * kThreads + tid, q_end - 1);    // tail lanes repeat the part's last query and write nothing
-    qx[k] = q[3 * (size_t)i]; qy[k] = q[3 * (size_t)i + 1]; qz[k] = q[3 * (size_t)i + 2];
-    best[k] = INFINITY;
-    bidx[k] = t_begin;                                        // in range whatever the coordinates are (NaN included)
-  }
-  for (int t0 = t_begin; t0 < t_end; t0 += kPointTile) {
-    const int n = min(kPointTile, t_end - t0);
-    __syncthreads();
-    for (int j = tid; j < n; j += kThreads) {
-      const float* pt = t + 3 * (size_t)(t0 + j);
-      tile[j] = make_float4(pt[0], pt[1], pt[2], 0.f);
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int j = 0; j < n; ++j) {
-      const float4 tj = tile[j];
-#pragma unroll
-      for (int k = 0; k < kPointQpl; ++k) {
-        const float d2 = pair_d2(qx[k], qy[k], qz[k], tj);
-        const bool lt = d2 < best[k];
-        best[k] = lt ? d2 : best[k];
-        bidx[k] = lt ? t0 + j : bidx[k];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kPointQpl; ++k) {
-    const int i = q0 + k * kThreads + tid;
-    if (i < q_end) {
-      part_d2[(size_t)slice * ld_part + i] = best[k];
-      part_idx[(size_t)slice * ld_part + i] = bidx[k];
-    }
-  }
+  const int t_begin = job.t.begin[p] + slice * span;
+  nearest_walk(PointTargets{t}, q, job.q.begin[p] + ((int)blockIdx.x - job.block_begin[p]) * (kThreads * kPointQpl),
+               job.q.begin[p + 1], t_begin, min(job.t.begin[p + 1], t_begin + span), slice, ld_part, part_d2, part_idx);
 }
 
-// the partials of a query's own part, slices in ascending order, strict <; the SQUARED distance goes out
-__global__ __launch_bounds__(kThreads) void nearest_parts_reduce_kernel(PartsJob job, const float* __restrict__ part_d2,
-                                                                        const int* __restrict__ part_idx, int ld_part,
-                                                                        float* __restrict__ d2_out, int* __restrict__ idx) {
-  __shared__ int s_begin[kMaxSearchParts + 1], s_slices[kMaxSearchParts];     // a lane indexes them by ITS part
-  for (int k = threadIdx.x; k <= job.n; k += kThreads) s_begin[k] = job.q_begin[k];
-  for (int k = threadIdx.x; k < job.n; k += kThreads) s_slices[k] = job.slices[k];
-  __syncthreads();
-  const int i = s_begin[0] + blockIdx.x * kThreads + threadIdx.x;
-  if (i >= s_begin[job.n]) return;
-  int lo = 0, hi = job.n - 1;
-  while (lo < hi) {                                  // the part that holds row i (no part is empty)
-    const int mid = (lo + hi + 1) >> 1;
-    if (s_begin[mid] <= i) lo = mid; else hi = mid - 1;
+// The partials of a query's slices in ascending order, strict <: the lowest index among equal distances survives.
+// OneRange: rows 0 .. rows with S slices each, the distance (sqrt) goes out and idx may be NULL; PartsJob: a query
+// has the slice count of its own part and the SQUARED distance goes out.
+struct OneRange { int rows, slices; };
+
+template <class Job>
+__global__ __launch_bounds__(kThreads) void nearest_reduce_kernel(Job job, const float* __restrict__ part_d2,
+                                                                  const int* __restrict__ part_idx, int ld_part,
+                                                                  float* __restrict__ out, int* __restrict__ idx) {
+  constexpr bool kParts = std::is_same<Job, PartsJob>::value;
+  int i = blockIdx.x * kThreads + threadIdx.x, S;
+  if constexpr (kParts) {
+    __shared__ int s_begin[kMaxParts + 1], s_slices[kMaxParts];
+    stage_parts(s_begin, job.q);
+    for (int k = threadIdx.x; k < job.q.n; k += kThreads) s_slices[k] = job.slices[k];
+    __syncthreads();
+    i += s_begin[0];
+    if (i >= s_begin[job.q.n]) return;
+    S = s_slices[find_part(s_begin, job.q.n, i)];
+  } else {
+    if (i >= job.rows) return;
+    S = job.slices;
   }
-  const int S = s_slices[lo];
   float best = part_d2[i];
   int b = part_idx[i];
   for (int s = 1; s < S; ++s) {
@@ -220,8 +196,8 @@ __global__ __launch_bounds__(kThreads) void nearest_parts_reduce_kernel(PartsJob
     const int j = part_idx[(size_t)s * ld_part + i];
     if (d2 < best) { best = d2; b = j; }
   }
-  d2_out[i] = best;
-  idx[i] = b;
+  out[i] = kParts ? best : sqrtf(best);
+  if (kParts || idx) idx[i] = b;
 }
 
 // ---------------------------------------------------------------- point - triangle
@@ -324,59 +300,40 @@ __device__ __forceinline__ float tri_d2(float px, float py, float pz, float4 r0,
   return __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
 }
 
+struct TriangleTargets {                            // 16 KB of LDS: four float4 per triangle
+  static constexpr int kQpl = kTriQpl, kTile = kTriTile, kUnroll = 2;
+  static_assert(kTile == kThreads, "one thread stages one triangle of the tile");
+  struct Tile { float4 r[4][kTile]; };
+  struct Record { float4 r0, r1, r2, r3; };
+  const float* __restrict__ verts;
+  const int* __restrict__ fv;
+  int V;
+  __device__ __forceinline__ void stage(Tile& tile, int f0, int n, int tid) const {
+    if (tid < n) triangle_record(verts, fv, V, f0 + tid, &tile.r[0][tid], &tile.r[1][tid], &tile.r[2][tid], &tile.r[3][tid]);
+  }
+  static __device__ __forceinline__ Record load(const Tile& tile, int j) {
+    return {tile.r[0][j], tile.r[1][j], tile.r[2][j], tile.r[3][j]};
+  }
+  static __device__ __forceinline__ float d2(float qx, float qy, float qz, const Record& r) {
+    return tri_d2(qx, qy, qz, r.r0, r.r1, r.r2, r.r3);
+  }
+};
+
 __global__ __launch_bounds__(kThreads) void nearest_triangle_kernel(const float* __restrict__ q,
                                                                     const float* __restrict__ verts,
                                                                     const int* __restrict__ fv, int Q, int V, int F,
                                                                     int tiles_per_slice, float* __restrict__ part_d2,
                                                                     int* __restrict__ part_idx) {
-  __shared__ float4 rec[4][kTriTile];
-  const int tid = threadIdx.x;
-  const int q0 = blockIdx.x * (kThreads * kTriQpl);
   const int slice = blockIdx.y;
-  float qx[kTriQpl], qy[kTriQpl], qz[kTriQpl], best[kTriQpl];
-  int bidx[kTriQpl];
   const int f_begin = slice * tiles_per_slice * kTriTile;
-  const int f_end = min(F, f_begin + tiles_per_slice * kTriTile);
-#pragma unroll
-  for (int k = 0; k < kTriQpl; ++k) {
-    const int i = min(q0 + k * kThreads + tid, Q - 1);
-    qx[k] = q[3 * (size_t)i]; qy[k] = q[3 * (size_t)i + 1]; qz[k] = q[3 * (size_t)i + 2];
-    best[k] = INFINITY;
-    bidx[k] = f_begin;
-  }
-  static_assert(kTriTile == kThreads, "one thread stages one triangle of the tile");
-  for (int f0 = f_begin; f0 < f_end; f0 += kTriTile) {
-    const int n = min(kTriTile, f_end - f0);
-    __syncthreads();
-    if (tid < n) triangle_record(verts, fv, V, f0 + tid, &rec[0][tid], &rec[1][tid], &rec[2][tid], &rec[3][tid]);
-    __syncthreads();
-#pragma unroll 2
-    for (int j = 0; j < n; ++j) {
-      const float4 r0 = rec[0][j], r1 = rec[1][j], r2 = rec[2][j], r3 = rec[3][j];
-#pragma unroll
-      for (int k = 0; k < kTriQpl; ++k) {
-        const float d2 = tri_d2(qx[k], qy[k], qz[k], r0, r1, r2, r3);
-        const bool lt = d2 < best[k];
-        best[k] = lt ? d2 : best[k];
-        bidx[k] = lt ? f0 + j : bidx[k];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kTriQpl; ++k) {
-    const int i = q0 + k * kThreads + tid;
-    if (i < Q) {
-      part_d2[(size_t)slice * Q + i] = best[k];
-      part_idx[(size_t)slice * Q + i] = bidx[k];
-    }
-  }
+  nearest_walk(TriangleTargets{verts, fv, V}, q, blockIdx.x * (kThreads * kTriQpl), Q, f_begin,
+               min(F, f_begin + tiles_per_slice * kTriTile), slice, Q, part_d2, part_idx);
 }
 
 // ---------------------------------------------------------------- sum / max of a distance vector
-// fp64 accumulation, fixed order: thread-strided partial sums, an LDS tree per block, the blocks in ascending order.
+// fp64 accumulation, fixed order: thread-strided partial sums, block_sum_fp64, the blocks in ascending order.
 __global__ __launch_bounds__(kThreads) void dist_summary_partial_kernel(const float* __restrict__ d, int64_t n,
                                                                         double* __restrict__ partial) {
-  __shared__ double ssum[kThreads];
   __shared__ float smax[kThreads];
   double s = 0.0;
   float m = -INFINITY;
@@ -385,30 +342,19 @@ __global__ __launch_bounds__(kThreads) void dist_summary_partial_kernel(const fl
     s += (double)x;
     m = fmaxf(m, x);
   }
-  ssum[threadIdx.x] = s;
   smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      ssum[threadIdx.x] += ssum[threadIdx.x + h];
-      smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + h]);
-    }
-    __syncthreads();
-  }
+  const double sum = block_sum_fp64<kThreads>(s, [&](int h) { smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + h]); });
   if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = ssum[0];
+    partial[2 * blockIdx.x] = sum;
     partial[2 * blockIdx.x + 1] = (double)smax[0];
   }
 }
 
 __global__ void dist_summary_final_kernel(const double* __restrict__ partial, int blocks, double* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double s = 0.0, m = -INFINITY;
-  for (int b = 0; b < blocks; ++b) {
-    s += partial[2 * b];
-    m = fmax(m, partial[2 * b + 1]);
-  }
-  out[0] = s;
+  double m = -INFINITY;
+  for (int b = 0; b < blocks; ++b) m = fmax(m, partial[2 * b + 1]);
+  out[0] = fold_ascending(partial, blocks, 2);
   out[1] = m;
 }
 
@@ -444,54 +390,31 @@ int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* d
   int* pi = ar.take<int>((size_t)c.slices * Q);
   GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_point: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
   nearest_point_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, t, (int)Q, (int)T, c.tiles_per_slice, pd, pi);
-  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(pd, pi, (int)Q, c.slices, dist, idx);
+  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, pd, pi, (int)Q, dist, idx);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-int parts_ptr_ok(const char* fn, const char* what, const int64_t* ptr, int P) {
-  GEOBI_REQUIRE(P >= 1, "%s: P = %d parts (at least one)", fn, P);
-  GEOBI_REQUIRE(ptr != nullptr && ptr[0] >= 0, "%s: %s is NULL or starts below 0", fn, what);
-  for (int p = 0; p < P; ++p)
-    GEOBI_REQUIRE(ptr[p + 1] > ptr[p], "%s: part %d of %s is empty (%lld .. %lld): an empty part is an error, not a launch", fn,
-                  p, what, (long long)ptr[p], (long long)ptr[p + 1]);
-  return 0;
-}
-
 namespace {
-// slices every part would like: the workgroups of ALL parts together should fill the chip
+// every part is sliced as a single mesh would be, but for the workgroups of ALL parts together (P = 1: choose_slices)
 int parts_want(const int64_t* qptr, int P) {
   int64_t qblocks = 0;
   for (int p = 0; p < P; ++p) qblocks += cdiv(qptr[p + 1] - qptr[p], (int64_t)kThreads * kPointQpl);
-  int64_t want = (kTargetBlocks + qblocks - 1) / qblocks;
-  return (int)(want > kMaxSlices ? kMaxSlices : (want < 1 ? 1 : want));
+  return want_slices(qblocks);
 }
-Slicing part_slices(int64_t Q, int64_t T, int want) {   // P = 1: exactly choose_slices
-  Slicing c;
-  c.qblocks = cdiv(Q, (int64_t)kThreads * kPointQpl);
-  const int ntiles = cdiv(T, kPointTile);
-  if (want > ntiles) want = ntiles;
-  c.tiles_per_slice = cdiv(ntiles, want);
-  c.slices = cdiv(ntiles, c.tiles_per_slice);
-  return c;
+Slicing part_slices(const int64_t* qptr, const int64_t* tptr, int p, int want) {
+  return slice_targets(qptr[p + 1] - qptr[p], tptr[p + 1] - tptr[p], kPointQpl, kPointTile, want);
 }
-bool parts_sane(const int64_t* qptr, const int64_t* tptr, int P) {
-  if (P < 1 || !qptr || !tptr || qptr[0] < 0 || tptr[0] < 0) return false;
-  for (int p = 0; p < P; ++p)
-    if (qptr[p + 1] <= qptr[p] || tptr[p + 1] <= tptr[p]) return false;
-  return qptr[P] <= INT32_MAX / 4 && tptr[P] <= INT32_MAX / 4;
+int max_part_slices(const int64_t* qptr, const int64_t* tptr, int P) {
+  const int want = parts_want(qptr, P);
+  int smax = 0;
+  for (int p = 0; p < P; ++p) smax = std::max(smax, part_slices(qptr, tptr, p, want).slices);
+  return smax;
 }
 }  // namespace
 
 int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P) {
-  if (!parts_sane(qptr, tptr, P)) return 0;
-  const int want = parts_want(qptr, P);
-  int smax = 0;
-  for (int p = 0; p < P; ++p) {
-    const int sl = part_slices(qptr[p + 1] - qptr[p], tptr[p + 1] - tptr[p], want).slices;
-    smax = sl > smax ? sl : smax;
-  }
-  return smax;
+  return parts_check("nearest_parts_slices", qptr, tptr, P) == 0 ? max_part_slices(qptr, tptr, P) : 0;
 }
 
 size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
@@ -502,39 +425,28 @@ size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
 
 int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,
                   void* ws, size_t ws_bytes, hipStream_t s) {
-  GEOBI_TRY(parts_ptr_ok("nearest_parts", "qptr", qptr, P));
-  GEOBI_TRY(parts_ptr_ok("nearest_parts", "tptr", tptr, P));
   const int want = parts_want(qptr, P);
-  const int smax = nearest_parts_slices(qptr, tptr, P);
+  const int smax = max_part_slices(qptr, tptr, P);
   const int ld = (int)qptr[P];
   Arena ar(ws, ws_bytes);
   float* pd = ar.take<float>((size_t)smax * ld);
   int* pi = ar.take<int>((size_t)smax * ld);
   GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_parts: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
-  for (int base = 0; base < P; base += kMaxSearchParts) {
+  for (int base = 0; base < P; base += kMaxParts) {
     PartsJob job;
-    job.n = P - base < kMaxSearchParts ? P - base : kMaxSearchParts;
+    fill_parts(&job.q, qptr, base, P);
+    fill_parts(&job.t, tptr, base, P);
     int blocks = 0, sl_max = 0;
-    for (int k = 0; k < job.n; ++k) {
-      const int p = base + k;
-      const Slicing c = part_slices(qptr[p + 1] - qptr[p], tptr[p + 1] - tptr[p], want);
-      job.q_begin[k] = (int)qptr[p];
-      job.t_begin[k] = (int)tptr[p];
+    for (int k = 0; k <= kMaxParts; ++k) {                // the unused tail: no blocks, one slice
+      const Slicing c = k < job.q.n ? part_slices(qptr, tptr, base + k, want) : Slicing{0, 1, 1};
       job.block_begin[k] = blocks;
-      job.tiles_per_slice[k] = c.tiles_per_slice;
-      job.slices[k] = c.slices;
+      if (k < kMaxParts) { job.tiles_per_slice[k] = c.tiles_per_slice; job.slices[k] = c.slices; }
       blocks += c.qblocks;
-      sl_max = c.slices > sl_max ? c.slices : sl_max;
-    }
-    for (int k = job.n; k <= kMaxSearchParts; ++k) {      // the unused tail repeats the end: nothing is left unset
-      job.q_begin[k] = (int)qptr[base + job.n];
-      job.t_begin[k] = (int)tptr[base + job.n];
-      job.block_begin[k] = blocks;
-      if (k < kMaxSearchParts) { job.tiles_per_slice[k] = 1; job.slices[k] = 1; }
+      if (k < job.q.n) sl_max = std::max(sl_max, c.slices);
     }
     nearest_parts_kernel<<<dim3(blocks, sl_max), kThreads, 0, s>>>(job, q, t, ld, pd, pi);
-    const int rows = job.q_begin[job.n] - job.q_begin[0];
-    nearest_parts_reduce_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(job, pd, pi, ld, d2, idx);
+    const int rows = job.q.begin[job.q.n] - job.q.begin[0];
+    nearest_reduce_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(job, pd, pi, ld, d2, idx);
   }
   GEOBI_LAUNCH_OK();
   return 0;
@@ -551,7 +463,7 @@ int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int6
   GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_triangle: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
   nearest_triangle_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, verts, fv, (int)Q, (int)V, (int)F,
                                                                          c.tiles_per_slice, pd, pi);
-  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(pd, pi, (int)Q, c.slices, dist, face);
+  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, pd, pi, (int)Q, dist, face);
   GEOBI_LAUNCH_OK();
   return 0;
 }

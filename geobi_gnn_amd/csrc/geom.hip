@@ -474,14 +474,12 @@ int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr,
 // ---------------------------------------------------------------------------- per-mesh rotation of a union batch
 // code/dataset.py:39-69 turns every training sample by its own random rotation before the loader hands it over; here the
 // samples are already one disjoint-union graph, so part p (rows ptr[p] .. ptr[p + 1]) takes matrix p: out = in @ R.  The
-// shape is concat32_kernel's (graph.hip): offsets and matrices ride in the kernel arguments, are staged in LDS once per
-// block and a lane finds its row's part by binary search -- no copy of the host arrays, nothing out of stream order.
+// part table (common.h) and the matrices ride in the kernel arguments, are staged in LDS once per block and a lane finds
+// its row's part with find_part, which skips the empty parts this call allows.
 namespace {
-constexpr int kMaxParts = 32;
 struct RotateJob {
-  int64_t ptr[kMaxParts + 1];      // row offsets of this launch's parts (ptr[0] = first row of the launch)
+  PartTable<int64_t> rows;         // row offsets of this launch's parts
   float R[kMaxParts * 9];          // row-major 3x3 per part
-  int n;
 };
 
 __device__ __forceinline__ void rotate_triple(float* __restrict__ v, const float* __restrict__ R) {
@@ -495,16 +493,13 @@ __global__ __launch_bounds__(256) void rotate_parts_kernel(RotateJob job, float*
                                                            float* __restrict__ y, float* __restrict__ dd) {
   __shared__ int64_t s_ptr[kMaxParts + 1];
   __shared__ float s_R[kMaxParts * 9];
-  for (int i = threadIdx.x; i <= job.n; i += 256) s_ptr[i] = job.ptr[i];
-  for (int i = threadIdx.x; i < job.n * 9; i += 256) s_R[i] = job.R[i];
+  const int n = job.rows.n;
+  stage_parts(s_ptr, job.rows);
+  for (int i = threadIdx.x; i < n * 9; i += 256) s_R[i] = job.R[i];
   __syncthreads();
-  const int64_t end = s_ptr[job.n];
+  const int64_t end = s_ptr[n];
   for (int64_t i = s_ptr[0] + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)gridDim.x * 256) {
-    int lo = 0, hi = job.n - 1;
-    while (lo < hi) {                              // last part that starts at or before row i (empty parts never win)
-      const int mid = (lo + hi + 1) >> 1;
-      if (s_ptr[mid] <= i) lo = mid; else hi = mid - 1;
-    }
+    const int lo = find_part(s_ptr, n, i);
     float R[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = s_R[lo * 9 + k];
@@ -520,10 +515,9 @@ int rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int l
                  hipStream_t s) {
   for (int base = 0; base < P; base += kMaxParts) {
     RotateJob job;
-    job.n = P - base < kMaxParts ? P - base : kMaxParts;
-    for (int i = 0; i <= job.n; ++i) job.ptr[i] = part_ptr[base + i];
-    for (int i = 0; i < job.n * 9; ++i) job.R[i] = R[(int64_t)base * 9 + i];
-    const int64_t rows = job.ptr[job.n] - job.ptr[0];
+    fill_parts(&job.rows, part_ptr, base, P);
+    for (int i = 0; i < job.rows.n * 9; ++i) job.R[i] = R[(int64_t)base * 9 + i];
+    const int64_t rows = job.rows.begin[job.rows.n] - job.rows.begin[0];
     if (rows == 0) continue;
     int64_t blocks = (rows + 255) / 256;
     if (blocks > 4096) blocks = 4096;

@@ -226,18 +226,14 @@ struct ConcatJob {
 };
 
 // One launch for every array of a union batch: 4 elements per thread and step; the job of an element is found by a
-// binary search over <= 96 start offsets held in LDS.
+// binary search (find_part, common.h) over <= 96 start offsets held in LDS.
 __global__ __launch_bounds__(256) void concat32_kernel(ConcatJob job) {
   __shared__ int64_t s_start[kMaxSegs + 1];
   for (int i = threadIdx.x; i <= job.n; i += 256) s_start[i] = job.start[i];
   __syncthreads();
   const int64_t total = s_start[job.n];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    int lo = 0, hi = job.n - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (s_start[mid] <= i) lo = mid; else hi = mid - 1;
-    }
+    const int lo = find_part(s_start, job.n, i);
     const int64_t k = i - s_start[lo];
     const uint32_t* src = job.src[lo];
     uint32_t v = job.fill[lo];

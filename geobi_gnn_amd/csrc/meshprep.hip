@@ -156,31 +156,23 @@ __global__ void ring_graph_kernel(const int* __restrict__ fv, const int* __restr
   if (PASS == 0) cnt[node] = pos;
 }
 
-// sum of edge lengths, fixed blocking -> deterministic; double accumulation
+// sum of edge lengths, fixed blocking -> deterministic; double accumulation (block_sum_fp64 / fold_ascending, common.h)
 __global__ __launch_bounds__(256) void edge_length_partial_kernel(const float* __restrict__ pos,
                                                                   const int* __restrict__ row,
                                                                   const int* __restrict__ col, int64_t E,
                                                                   double* __restrict__ partial) {
-  __shared__ double red[256];
   double s = 0.0;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < E; e += (int64_t)gridDim.x * 256) {
     const int i = row[e], j = col[e];
     const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
     s += (double)sqrtf((dx * dx + dy * dy) + dz * dz);
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  const double sum = block_sum_fp64<256>(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 __device__ __forceinline__ float mean_from_partials(const double* __restrict__ partial, int64_t denom) {
-  double s = 0.0;
-  for (int b = 0; b < kPartials; ++b) s += partial[b];
-  return (float)(s / (double)(denom > 0 ? denom : 1));
+  return (float)(fold_ascending(partial, kPartials) / (double)(denom > 0 ? denom : 1));
 }
 
 __global__ void mean_edge_length_kernel(const double* __restrict__ partial, int64_t denom, float* __restrict__ out) {
@@ -212,7 +204,6 @@ __global__ __launch_bounds__(256) void edge_length_partial_parts_kernel(const fl
                                                                         const int* __restrict__ col,
                                                                         const int* __restrict__ node_ptr,
                                                                         double* __restrict__ partial) {
-  __shared__ double red[256];
   const int part = blockIdx.y;
   const int64_t e0 = rowptr[node_ptr[part]], E = (int64_t)rowptr[node_ptr[part + 1]] - e0;
   double s = 0.0;
@@ -222,13 +213,8 @@ __global__ __launch_bounds__(256) void edge_length_partial_parts_kernel(const fl
     const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
     s += (double)sqrtf((dx * dx + dy * dy) + dz * dz);
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[(size_t)part * kPartials + blockIdx.x] = red[0];
+  const double sum = block_sum_fp64<256>(s);
+  if (threadIdx.x == 0) partial[(size_t)part * kPartials + blockIdx.x] = sum;
 }
 
 __global__ void calc_weight_parts_kernel(const float* __restrict__ pos, const float* __restrict__ nrm,

@@ -6,52 +6,15 @@ import numpy as np
 import pytest
 import torch
 
+from chamfer_model import _argmin64, _cd64, _input, _sided64
+
 TOL = 1e-5                      # the project's bar (tests/test_gpu_kernels.py)
 
 
 # ------------------------------------------------------------------------------------------------ fp64 statements
-def _argmin64(q, t, chunk=512):
-    """For every row of q the index of the nearest row of t (lowest among equals) and the squared distance, fp64."""
-    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
-    idx, d2 = np.empty(len(q), np.int64), np.empty(len(q))
-    for s in range(0, len(q), chunk):
-        d = ((q[s:s + chunk, None, :] - t[None, :, :]) ** 2).sum(2)
-        idx[s:s + chunk] = d.argmin(1)
-        d2[s:s + chunk] = d.min(1)
-    return idx, d2
-
-
-def _cd64(p, t):
-    """Chamfer distance of one mesh (squared distances, both directions, means) and its gradient to p."""
-    p, t = np.asarray(p, np.float64), np.asarray(t, np.float64)
-    a, d2a = _argmin64(p, t)
-    b, d2b = _argmin64(t, p)
-    grad = (2.0 / len(p)) * (p - t[a])
-    np.add.at(grad, b, (2.0 / len(t)) * (p[b] - t))
-    return d2a.mean() + d2b.mean(), grad
-
-
-def _sided64(normals_p, normals, fc_p, fc):
-    """mean_i sum_c |np_i - n[idx_i]|, idx_i = nearest ground-truth centroid; gradient to np."""
-    normals_p, normals = np.asarray(normals_p, np.float64), np.asarray(normals, np.float64)
-    idx, _ = _argmin64(fc_p, fc)
-    d = normals_p - normals[idx]
-    return np.abs(d).sum(1).mean(), np.sign(d) / len(d)
-
-
 def _normals64(pts, faces):
     n = np.cross(pts[faces[:, 1]] - pts[faces[:, 0]], pts[faces[:, 2]] - pts[faces[:, 0]])
     return n / np.linalg.norm(n, axis=1, keepdims=True)
-
-
-def _input(n, s):
-    """The issue's input: the frequency-n icosphere as target, a copy jittered by s mean edge lengths as prediction."""
-    from geobi_gnn_amd import meshgen
-    pts, faces = meshgen.icosphere(n)
-    ev = meshgen.mesh_edges(faces)
-    mean_len = np.linalg.norm(pts[ev[:, 0]] - pts[ev[:, 1]], axis=1).mean()
-    q = (pts + s * mean_len * np.random.default_rng(5).standard_normal(pts.shape)).astype(np.float32)
-    return q, pts.astype(np.float32), faces
 
 
 def _bags(parts):
@@ -119,7 +82,7 @@ def test_torch_branch_matches_fp64(batch):
 def test_cd_differs_from_l2_on_these_inputs():
     """Only part of the noisy vertices have their own clean vertex as the nearest one: CD is not L2 in disguise."""
     q, t, _ = _input(8, 0.5)
-    a, _ = _argmin64(q, t)
+    a, _, _ = _argmin64(q, t)
     own = float((a == np.arange(len(q))).mean())
     print('share of vertices whose nearest target is their own: %.3f' % own)
     assert 0.1 < own < 0.9

@@ -11,18 +11,17 @@ may be at most 0.1 % of the rows."""
 import argparse
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from chamfer_model import _argmin64, _cd64, _input, _sided64, _union
 from helpers import rel_err
+from train_cases import _epoch, _options, _train_command, _write_split
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-5                      # the project's bar (tests/test_gpu_kernels.py)
 INPUTS = ((8, 0.5), (16, 0.5), (24, 0.3))
 
@@ -34,61 +33,6 @@ def dev():
 
 
 # ------------------------------------------------------------------------------------------------ fp64 statements
-def _argmin64(q, t, chunk=256):
-    """Per row of q: index of the nearest row of t (lowest among equals), its squared distance and the relative gap to
-    the second-best squared distance, all in fp64."""
-    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
-    idx, d2, gap = np.empty(len(q), np.int64), np.empty(len(q)), np.ones(len(q))
-    for s in range(0, len(q), chunk):
-        d = ((q[s:s + chunk, None, :] - t[None, :, :]) ** 2).sum(2)
-        idx[s:s + chunk] = d.argmin(1)
-        d2[s:s + chunk] = d.min(1)
-        if t.shape[0] > 1:
-            two = np.partition(d, 1, axis=1)[:, :2]
-            gap[s:s + chunk] = (two[:, 1] - two[:, 0]) / np.maximum(two[:, 1], 1e-300)
-    return idx, d2, gap
-
-
-def _cd64(p, t):
-    p, t = np.asarray(p, np.float64), np.asarray(t, np.float64)
-    a, d2a, _ = _argmin64(p, t)
-    b, d2b, _ = _argmin64(t, p)
-    grad = (2.0 / len(p)) * (p - t[a])
-    np.add.at(grad, b, (2.0 / len(t)) * (p[b] - t))
-    return d2a.mean() + d2b.mean(), grad
-
-
-def _sided64(normals_p, normals, fc_p, fc):
-    normals_p, normals = np.asarray(normals_p, np.float64), np.asarray(normals, np.float64)
-    idx, _, _ = _argmin64(fc_p, fc)
-    d = normals_p - normals[idx]
-    return np.abs(d).sum(1).mean(), np.sign(d) / len(d)
-
-
-_CACHE = {}
-
-
-def _input(n, s):
-    if (n, s) not in _CACHE:
-        from geobi_gnn_amd import meshgen
-        pts, faces = meshgen.icosphere(n)
-        ev = meshgen.mesh_edges(faces)
-        mean_len = np.linalg.norm(pts[ev[:, 0]] - pts[ev[:, 1]], axis=1).mean()
-        q = (pts + s * mean_len * np.random.default_rng(5).standard_normal(pts.shape)).astype(np.float32)
-        _CACHE[(n, s)] = (q, pts.astype(np.float32), faces)
-    return _CACHE[(n, s)]
-
-
-def _union(parts):
-    """[(q, t, faces)] -> q, t, faces of the disjoint union and the vertex / face pointers."""
-    vptr = np.cumsum([0] + [len(q) for q, _, _ in parts]).tolist()
-    fptr = np.cumsum([0] + [len(f) for _, _, f in parts]).tolist()
-    q = np.concatenate([q for q, _, _ in parts])
-    t = np.concatenate([t for _, t, _ in parts])
-    faces = np.concatenate([f + o for (_, _, f), o in zip(parts, vptr)])
-    return q, t, faces, vptr, fptr
-
-
 def _assert_indices(got, ref, gap, what):
     keep = gap >= 1e-5
     left_out = int((~keep).sum())
@@ -381,40 +325,6 @@ def test_documented_errors(dev):
 
 
 # ------------------------------------------------------------------------------------------------ 6. one training epoch
-def _write_split(root, split, names, freq, sigmas, seed0):
-    from geobi_gnn_amd import meshgen, meshio
-    for sub in ('original', 'noisy'):
-        os.makedirs(os.path.join(root, split, sub), exist_ok=True)
-    for i, name in enumerate(names):
-        for k, sigma in enumerate(sigmas, 1):
-            noisy, clean, faces = meshgen.noisy_icosphere(freq, sigma, seed=seed0 + 10 * i + k)
-            meshio.write_obj(os.path.join(root, split, 'noisy', '%s_n%d.obj' % (name, k)), noisy, faces)
-        meshio.write_obj(os.path.join(root, split, 'original', name + '.obj'), clean, faces)
-
-
-def _options(**kw):
-    from geobi_gnn_amd import train_util
-    opt = train_util.add_training_flags(argparse.ArgumentParser()).parse_args([])
-    opt.seed = 7
-    for k, v in kw.items():
-        setattr(opt, k, v)
-    return opt
-
-
-def _epoch(samples, dev, opt, rotate=None, epochs=1):
-    """Flat parameters after `epochs` passes of trainer.train_epoch from a seed-initialised net."""
-    from geobi_gnn_amd import network, train_util, trainer
-    from geobi_gnn_amd.parallel import FlatParameters
-    torch.manual_seed(11)
-    net = network.DualGNN().to(dev)
-    flat = FlatParameters(net)
-    optimizer = train_util.make_optimizer(opt, flat.parameters(), fused=True)
-    for epoch in range(1, epochs + 1):
-        trainer.train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=rotate)
-    torch.cuda.synchronize()
-    return flat.flat_param.detach().clone()
-
-
 def test_train_epoch_with_cd_and_sided_equals_the_loop_written_out(dev, tmp_path):
     """4 frequency-8 samples, batch 2: trainer.train_epoch with loss_v='CD', loss_n='sided' leaves the flat parameters
     bit-identical to forward, batched_losses, dual_loss, backward, step called one after the other; two runs agree bit
@@ -455,15 +365,6 @@ def test_train_epoch_with_cd_and_sided_equals_the_loop_written_out(dev, tmp_path
 
 
 # ------------------------------------------------------------------------------------------------ 7. command
-def _train_command(data_dir, out_dir, extra=()):
-    cmd = [sys.executable, '-m', 'geobi_gnn_amd', 'train', '--data_dir', data_dir, '--out_dir', out_dir, '--max_epoch', '5',
-           '--batch_size', '2', '--seed', '31', '--no_predict'] + list(extra)
-    run = subprocess.run(cmd, cwd=ROOT, timeout=600, capture_output=True, text=True)       # a cold `import torch` alone can take a minute
-    print(run.stdout)
-    print(run.stderr)
-    return run
-
-
 def test_train_command_with_cd_and_sided(dev, tmp_path):
     """python -m geobi_gnn_amd train --loss_v CD --loss_n sided on the tiny split of test_train_command_end_to_end
     (frequency-8 icospheres, 6 train files, 2 test files), 5 epochs, batch 2.  Child processes one after the other, each
@@ -472,12 +373,12 @@ def test_train_command_with_cd_and_sided(dev, tmp_path):
     _write_split(data, 'train', ('s1', 's2', 's3'), 8, (0.1, 0.3), seed0=700)
     _write_split(data, 'test', ('t1',), 8, (0.1, 0.3), seed0=800)
 
-    bad = _train_command(data, str(tmp_path / 'bad'), extra=('--loss_v', 'nonsense'))
+    bad = _train_command(data, str(tmp_path / 'bad'), extra=('--no_predict', '--loss_v', 'nonsense'))
     assert bad.returncode != 0
     assert 'L1, L2, CD' in bad.stderr and 'samples from' not in bad.stdout          # before any mesh was read
     assert not os.path.exists(str(tmp_path / 'bad'))
 
-    losses = ('--loss_v', 'CD', '--loss_n', 'sided')
+    losses = ('--no_predict', '--loss_v', 'CD', '--loss_n', 'sided')
     out = str(tmp_path / 'run1')
     run = _train_command(data, out, extra=losses)
     assert run.returncode == 0, run.stderr[-2000:]

@@ -11,8 +11,6 @@ Observed after 5 sweeps, kernel / d32 (every figure is printed by the tests): on
 after 20 sweeps: 1.1e-6 and 1.5e-7 (test_bnf_model_host.test_fp32_model_stays_near_the_fp64_model)."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,10 +18,10 @@ import torch
 
 import bnf_model as M
 import geom_model as G
+from train_cases import _run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
 SWEEPS = (0, 1, 2, 5)
 FAN_VALENCES = (3, 4, 5, 8, 9, 16, 17, 33, 64, 65, 200)
@@ -304,14 +302,6 @@ def test_errors(dev):
 
 
 # ------------------------------------------------------------------------------------------------ command
-def _run(args, timeout=600):
-    run = subprocess.run([sys.executable, '-m', 'geobi_gnn_amd'] + list(args), cwd=ROOT, timeout=timeout, capture_output=True,
-                         text=True)                                     # a cold `import torch` alone can take a minute
-    print(run.stdout)
-    print(run.stderr)
-    return run
-
-
 def test_denoise_command_with_the_filter(dev, tmp_path):
     from geobi_gnn_amd import filters, meshgen, meshio
     data = str(tmp_path / 'set')

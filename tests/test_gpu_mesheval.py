@@ -241,6 +241,126 @@ def test_properties(dev):
     assert one[0] == float(x[-1]) and one[1] == float(x[-1])
 
 
+# ------------------------------------------------------------------ the edges of the shared all-pairs walk
+# Points: integer lattice coordinates in [-9, 9], so every squared distance (<= 3 * 18^2 = 972) is exact in fp32 and the
+# reference is int64 numpy, whose arg-min is the lowest index.  Q sits around one query block (256 lanes x 4), T around
+# one tile (512); (1025, 513) and (1025, 1025) are cut into 2 and 3 slices.
+_WALK_Q, _WALK_T = (1, 1023, 1024, 1025), (1, 511, 512, 513, 1025)
+_LATTICE = {}
+
+
+def _lattice():
+    """q, t [1025, 3] and the int64 squared distances of all pairs; a case takes the first Q / T rows."""
+    if not _LATTICE:
+        rng = np.random.default_rng(23)
+        q = rng.integers(-9, 10, (1025, 3))
+        t = rng.integers(-9, 10, (1025, 3))
+        _LATTICE['qtd'] = (q.astype(np.float32), t.astype(np.float32), ((q[:, None, :] - t[None, :, :]) ** 2).sum(2))
+    return _LATTICE['qtd']
+
+
+@pytest.mark.parametrize('T', _WALK_T)
+@pytest.mark.parametrize('Q', _WALK_Q)
+def test_point_walk_edges_are_bit_exact(dev, Q, T):
+    """nearest_parts with one part, the same rows as the second of two parts (behind a 7-row first part: q_begin and
+    t_begin are not 0) and nearest_point: the index and d2 are the int64 statement's, bit for bit."""
+    from geobi_gnn_amd import mesheval, ops
+    q, t, d_all = _lattice()
+    q, t, d = q[:Q], t[:T], d_all[:Q, :T]
+    ref_idx, ref_d2 = d.argmin(1), d.min(1).astype(np.float32)
+    ties = float(((d == d.min(1, keepdims=True)).sum(1) > 1).mean())
+    slices = ops.nearest_parts_slices([0, Q], [0, T])
+    print('Q = %d, T = %d: %d slices, %.0f %% of the queries have several equally near targets' % (Q, T, slices, 100 * ties))
+    if T >= 511 and Q > 1:
+        assert ties > 0.2                                     # the tie rule is exercised
+    if Q == 1025 and T >= 513:
+        assert slices == (2 if T == 513 else 3)               # and so is the slice reduction
+    qd, td = _t(q, dev), _t(t, dev)
+    d2, idx = ops.nearest_parts(qd, td)
+    assert np.array_equal(idx.cpu().numpy(), ref_idx) and np.array_equal(d2.cpu().numpy(), ref_d2)
+    head_q, head_t = _lattice()[0][500:507], _lattice()[1][600:607]
+    d2, idx = ops.nearest_parts(_t(np.concatenate([head_q, q]), dev), _t(np.concatenate([head_t, t]), dev), [0, 7, 7 + Q],
+                                [0, 7, 7 + T])
+    assert np.array_equal(idx.cpu().numpy()[7:], ref_idx + 7) and np.array_equal(d2.cpu().numpy()[7:], ref_d2)
+    assert int(idx[:7].min()) >= 0 and int(idx[:7].max()) < 7
+    dist, idx = mesheval.nearest_point(qd, td)
+    assert np.array_equal(idx.cpu().numpy(), ref_idx)
+    ref = np.sqrt(d.min(1).astype(np.float64))
+    assert (np.abs(dist.cpu().numpy().astype(np.float64) - ref) <= TOL * ref).all()
+
+
+_SPHERE8 = {}
+
+
+def _sphere8():
+    """The frequency-8 icosphere (V = 642, F = 1280) and its noisy vertices as queries; fp64 surface distances per F'."""
+    if not _SPHERE8:
+        from geobi_gnn_amd import meshgen
+        noisy, clean, faces = meshgen.noisy_icosphere(8, 0.2, seed=3)
+        faces = np.asarray(faces)
+        _SPHERE8['mesh'] = (noisy.astype(np.float32), clean.astype(np.float32), faces, _mean_edge(clean, faces))
+    return _SPHERE8['mesh']
+
+
+@pytest.mark.parametrize('F', (1, 255, 256, 257, 513))
+def test_triangle_walk_edges_against_fp64(dev, F):
+    """Q around one query block (256 lanes x 2), F' = faces[:F'] around one tile (256): every row within TOL of the
+    fp64 surface distance, and so is the fp64 distance to the returned face."""
+    from geobi_gnn_amd import mesheval
+    q_all, verts, faces, e = _sphere8()
+    assert verts.shape[0] == 642 and faces.shape[0] == 1280
+    s_ref_all = _surface_fp64(q_all[:513], verts, faces[:F])          # once per F', shared by the four Q
+    td, fd = _t(verts, dev), _t(faces[:F], dev, torch.int32)
+    for Q in (1, 511, 512, 513):
+        q, s_ref = q_all[:Q], s_ref_all[:Q]
+        s, face = mesheval.point_to_mesh(_t(q, dev), td, fd)
+        s, face = s.cpu().numpy(), face.cpu().numpy()
+        assert s.shape == (Q,) and face.min() >= 0 and face.max() < F
+        f = faces[face]
+        s_at = _tri_dist_fp64(q, verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]])
+        print('Q = %d, F = %d: rel err %.3e, at the returned face %.3e' % (Q, F, _rel(s, s_ref, e), _rel(s_at, s_ref, e)))
+        assert _rel(s, s_ref, e) <= TOL
+        assert _rel(s_at, s_ref, e) <= TOL
+
+
+def _summary_vector(n=100000):
+    """Fixed fp32 values over 2^-21 .. 2^21.  Their fp64 sum rounds at almost every addition (numpy's pairwise sum differs
+    from the kernel's order in the last bit), so the two doubles of tests/golden/dist_summary_100k.npz pin the tree shape
+    and the block order of the sum.  PROVENANCE: the file holds a numpy fp64 replay of the kernel's order (98 blocks,
+    thread-strided sums, the 256-lane tree, blocks ascending); a run of the build before the shared helpers on an
+    MI355X, which is where the value should come from, has not been possible yet."""
+    i = np.arange(n, dtype=np.int64)
+    u = ((i * 2654435761) % 1000003).astype(np.float32) / np.float32(1000003)
+    return (u + np.float32(0.5)) * np.exp2(((i % 41) - 20).astype(np.float32))
+
+
+@pytest.mark.parametrize('n', (1, 255, 256, 257, 1025))
+def test_fixed_order_sums_at_the_block_edges(dev, n):
+    """dist_summary and the Chamfer forward on n rows, around one block of 256 and its grid of cdiv(n, 1024) blocks."""
+    from chamfer_model import _cd64
+    from geobi_gnn_amd import mesheval, ops
+    x = _summary_vector()[:n]
+    got = mesheval.dist_summary(_t(x, dev)).cpu().numpy()
+    ref = x.astype(np.float64)
+    assert abs(got[0] - ref.sum()) <= 1e-12 * ref.sum() and got[1] == ref.max()
+    q, verts, _, _ = _case('n13_on_n12')
+    q, t = q[:n], verts[:n]
+    cd = float(ops.chamfer_loss(_t(q, dev), _t(t, dev)))
+    ref_cd, _ = _cd64(q, t)
+    print('n = %d: CD %.9g (fp64 %.9g)' % (n, cd, ref_cd))
+    assert abs(cd - ref_cd) <= TOL * abs(ref_cd)
+
+
+def test_dist_summary_keeps_its_recorded_bits(dev):
+    from geobi_gnn_amd import mesheval
+    x = _summary_vector()
+    got = mesheval.dist_summary(_t(x, dev)).cpu().numpy()
+    want = np.load(os.path.join(ROOT, 'tests', 'golden', 'dist_summary_100k.npz'))['summary']
+    ref = x.astype(np.float64)
+    assert abs(got[0] - ref.sum()) <= 1e-12 * ref.sum() and got[1] == ref.max()
+    assert got.dtype == np.float64 and np.array_equal(got, want), (got[0].hex(), want[0].hex())
+
+
 def _eval_fp64(pr, po, faces):
     """code/data_util.py:591-611 in fp64 from the float32 inputs (+ surface distance and Hausdorff)."""
     pr, po = pr.astype(np.float64), po.astype(np.float64)

@@ -4,18 +4,16 @@ written from the same draws, meshprep.refresh_dual_data, and `train --noise_leve
 import json
 import os
 import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import noise_model as M
+from train_cases import _assert_same_sample, _run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24                  # unit roundoff of fp32
 # ulp bounds taken for the HIP math API's precise functions: its tables give logf 1, sincosf 1 (sine and cosine each) and
 # sqrtf 1; 2 is taken for the two transcendentals so that the bar does not hang on the last digit of a table
@@ -231,14 +229,6 @@ def test_add_noise(dev):
 
 
 # ------------------------------------------------------------------------------------------------ command
-def _run(args, timeout=600):
-    run = subprocess.run([sys.executable, '-m', 'geobi_gnn_amd'] + list(args), cwd=ROOT, timeout=timeout, capture_output=True,
-                         text=True)                                     # a cold `import torch` alone can take a minute
-    print(run.stdout)
-    print(run.stderr)
-    return run
-
-
 def _write_originals(folder, spheres):
     from geobi_gnn_amd import meshio
     os.makedirs(folder, exist_ok=True)
@@ -287,22 +277,6 @@ def test_noise_command_end_to_end(dev, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ dataset
-def _csr(d):
-    g = d.graph()
-    return g.rowptr_out, g.col_out, g.weights_sorted(d.edge_weight)
-
-
-def _assert_same_sample(got, want):
-    for a, b in zip(got, want):
-        assert torch.equal(a.x, b.x) and torch.equal(a.y, b.y)
-        for s, t in zip(_csr(a), _csr(b)):
-            assert torch.equal(s, t)
-        assert torch.equal(a.edge_weight, b.edge_weight)
-        da, db = getattr(a, 'depth_direction', None), getattr(b, 'depth_direction', None)
-        assert (da is None) == (db is None) and (da is None or torch.equal(da, db))
-    assert torch.equal(got[1].fv_indices, want[1].fv_indices)
-
-
 def _file_mode_twin(synthetic, root, tmp, tag, **kw):
     """A file-mode DualDataset(cache=False) over the files `synthetic` writes from its current draw."""
     from geobi_gnn_amd.dataset import DualDataset

@@ -1,20 +1,18 @@
 """Training from OBJ folders on the device: the per-mesh rotation kernel (geobi_rotate_parts) against fp64, the
 resident dataset (dataset.DualDataset: unsplit, split and filtered, cached), the package loop (trainer.train_epoch)
 against a loop written out here, and the `train` command end to end."""
-import argparse
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from train_cases import _assert_same_sample, _epoch, _options, _train_command, _write_split
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24                  # unit roundoff of fp32
 
 
@@ -155,61 +153,6 @@ def test_rotate_union_turns_every_mesh_by_its_own_matrix(dev):
 
 
 # ------------------------------------------------------------------------------------------------ dataset
-def _write_split(root, split, names, freq, sigmas, seed0):
-    """original/NAME.obj + noisy/NAME_n<k>.obj per sigma -> {sample name: (noisy file, original file)}"""
-    from geobi_gnn_amd import meshgen, meshio
-    files = {}
-    for sub in ('original', 'noisy'):
-        os.makedirs(os.path.join(root, split, sub), exist_ok=True)
-    for i, name in enumerate(names):
-        original = os.path.join(root, split, 'original', name + '.obj')
-        for k, sigma in enumerate(sigmas, 1):
-            noisy, clean, faces = meshgen.noisy_icosphere(freq, sigma, seed=seed0 + 10 * i + k)
-            noisy_file = os.path.join(root, split, 'noisy', '%s_n%d.obj' % (name, k))
-            meshio.write_obj(noisy_file, noisy, faces)
-            files['%s_n%d' % (name, k)] = (noisy_file, original)
-        meshio.write_obj(original, clean, faces)
-    return files
-
-
-def _csr(d):
-    g = d.graph()
-    return g.rowptr_out, g.col_out, g.weights_sorted(d.edge_weight)
-
-
-def _assert_same_sample(got, want, edge_weight_as_stored=True):
-    for a, b in zip(got, want):
-        assert torch.equal(a.x, b.x) and torch.equal(a.y, b.y)
-        for s, t in zip(_csr(a), _csr(b)):
-            assert torch.equal(s, t)
-        if edge_weight_as_stored:
-            assert torch.equal(a.edge_weight, b.edge_weight)
-    assert torch.equal(got[1].fv_indices, want[1].fv_indices)
-
-
-def _options(**kw):
-    from geobi_gnn_amd import train_util
-    opt = train_util.add_training_flags(argparse.ArgumentParser()).parse_args([])
-    opt.seed = 7
-    for k, v in kw.items():
-        setattr(opt, k, v)
-    return opt
-
-
-def _epoch(samples, dev, opt, rotate=None, epochs=1):
-    """Flat parameters after `epochs` passes of trainer.train_epoch from a seed-initialised net."""
-    from geobi_gnn_amd import network, train_util, trainer
-    from geobi_gnn_amd.parallel import FlatParameters
-    torch.manual_seed(11)
-    net = network.DualGNN().to(dev)
-    flat = FlatParameters(net)
-    optimizer = train_util.make_optimizer(opt, flat.parameters(), fused=True)
-    for epoch in range(1, epochs + 1):
-        trainer.train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=rotate)
-    torch.cuda.synchronize()
-    return flat.flat_param.detach().clone()
-
-
 def test_dataset_unsplit_fresh_cached_and_uncached(dev, tmp_path):
     """Two names x two noise files, every mesh below the patch size: each sample is bit-identical to a direct
     meshprep.build_dual_data on the arrays read back from its files; a second construction loads processed_data/ (file
@@ -367,15 +310,6 @@ def test_short_last_batch_steps_and_samples_are_never_written(dev, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ command
-def _train_command(data_dir, out_dir, extra=()):
-    cmd = [sys.executable, '-m', 'geobi_gnn_amd', 'train', '--data_dir', data_dir, '--out_dir', out_dir, '--max_epoch', '5',
-           '--batch_size', '2', '--seed', '31'] + list(extra)
-    run = subprocess.run(cmd, cwd=ROOT, timeout=600, capture_output=True, text=True)       # a cold `import torch` alone can take a minute
-    print(run.stdout)
-    print(run.stderr)
-    return run
-
-
 def test_train_command_end_to_end(dev, tmp_path):
     """python -m geobi_gnn_amd train on frequency-8 icospheres (6 train files, 2 test files), 5 epochs, batch 2: exit
     status, model, params, log, event files, denoised test meshes; a second run with the same seed gives the same state
