@@ -3,13 +3,15 @@
   python -m geobi_gnn_amd train --data_dir dataset/Synthetic --out_dir log/run1 [--batch_size 4] [--max_epoch 100]
   python -m geobi_gnn_amd denoise --model net.pt --data_dir DIR [--out_dir DIR/result] [--sub_size 20000]
   python -m geobi_gnn_amd denoise --method bnf --data_dir DIR [--normal_iters 20] [--sigma_r 0.35] [--sigma_s 1.0] [--n_iter 20]
+  python -m geobi_gnn_amd denoise --method gnf --data_dir DIR [the same flags]
   python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
 and as face-weighted means; otherwise every DIR/*.obj is denoised without ground truth.  `--method bnf` needs no model: it
-runs the bilateral normal filter (filters.py) on the same files and writes the same outputs -- the baseline row.  `eval` is
+runs the bilateral normal filter (filters.py) on the same files and writes the same outputs -- the baseline row; `--method
+gnf` is the guided normal filter, the model-free method for high noise, through the same loop and flags.  `eval` is
 data_util.eval_denoising_result (code/data_util.py:559-638).  `train` is code/train_dual.py:100-298 (trainer.py): DIR holds
 train/ and test/, each with original/ and noisy/; the best model, the options, the log, TensorBoard event files and the
 denoised test meshes go to --out_dir.  `noise` has no counterpart in the reference (its dataset is a download): it writes
@@ -24,7 +26,7 @@ import time
 import numpy as np
 
 
-BNF_N_ITER = 20          # vertex-update sweeps of --method bnf when --n_iter is not given (filters.bilateral_denoise's default)
+BNF_N_ITER = 20          # vertex-update sweeps of --method bnf / gnf when --n_iter is not given (filters.bilateral_denoise's default)
 
 
 class _StoreGiven(argparse.Action):
@@ -70,16 +72,17 @@ def denoise(opt):
     jobs = _denoise_list(opt.data_dir, getattr(opt, 'noisy_dir', ''))
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'result')
     os.makedirs(out_dir, exist_ok=True)
-    if method == 'bnf':
+    if method in ('bnf', 'gnf'):
         from . import filters
+        filter_fn = filters.bilateral_denoise if method == 'bnf' else filters.guided_denoise
         normal_iters, sigma_r, sigma_s = (getattr(opt, 'normal_iters', 20), getattr(opt, 'sigma_r', 0.35),
                                           getattr(opt, 'sigma_s', 1.0))
-        print('\nBilateral normal filter, normal_iters:%d, sigma_r:%g, sigma_s:%g, %d files ...\n'
-              % (normal_iters, sigma_r, sigma_s, len(jobs)), flush=True)
+        print('\n%s normal filter, normal_iters:%d, sigma_r:%g, sigma_s:%g, %d files ...\n'
+              % ('Bilateral' if method == 'bnf' else 'Guided', normal_iters, sigma_r, sigma_s, len(jobs)), flush=True)
 
         def run(points, faces, gt_points):
-            return filters.bilateral_denoise(points, faces, normal_iters=normal_iters, sigma_r=sigma_r, sigma_s=sigma_s,
-                                             n_iter=n_iter, data_type=opt.data_type, gt_points=gt_points, device=dev)
+            return filter_fn(points, faces, normal_iters=normal_iters, sigma_r=sigma_r, sigma_s=sigma_s, n_iter=n_iter,
+                             data_type=opt.data_type, gt_points=gt_points, device=dev)
     else:
         from . import network, patches
         torch.manual_seed(0)
@@ -200,17 +203,18 @@ def build_parser():
     ap = argparse.ArgumentParser(prog='python -m geobi_gnn_amd', description=__doc__.split('\n')[0])
     sub = ap.add_subparsers(dest='command', required=True)
     d = sub.add_parser('denoise', help='denoise every OBJ mesh of a folder and write NAME-<n_iter>.obj')
-    d.add_argument('--method', type=str, default='gnn', choices=['gnn', 'bnf'],
-                   help='gnn: the network (default); bnf: bilateral normal filter, needs no model')
+    d.add_argument('--method', type=str, default='gnn', choices=['gnn', 'bnf', 'gnf'],
+                   help='gnn: the network (default); bnf: bilateral normal filter; gnf: guided normal filter; the filters '
+                        'need no model')
     d.add_argument('--model', type=str, default='', help="state dict with the reference's keys; random init (seed 0) if empty")
     d.add_argument('--data_dir', type=str, required=True)
     d.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/result')
     d.add_argument('--sub_size', type=int, default=20000, help='faces per patch')
     d.add_argument('--n_iter', type=int, default=60, action=_StoreGiven,
-                   help='vertex-update sweeps (--method bnf: 20 unless given)')
-    d.add_argument('--normal_iters', type=int, default=20, help='bnf: sweeps of the normal filter')
-    d.add_argument('--sigma_r', type=float, default=0.35, help='bnf: range width, on |n_i - n_j|')
-    d.add_argument('--sigma_s', type=float, default=1.0, help='bnf: spatial width in units of the mean centroid distance')
+                   help='vertex-update sweeps (--method bnf / gnf: 20 unless given)')
+    d.add_argument('--normal_iters', type=int, default=20, help='bnf, gnf: sweeps of the normal filter')
+    d.add_argument('--sigma_r', type=float, default=0.35, help='bnf, gnf: range width, on |n_i - n_j| (gnf: of the guidance normals)')
+    d.add_argument('--sigma_s', type=float, default=1.0, help='bnf, gnf: spatial width in units of the mean centroid distance')
     d.add_argument('--data_type', type=str, default='Synthetic', choices=['Synthetic', 'Kinect_v1', 'Kinect_v2', 'Kinect_Fusion'])
     d.add_argument('--wei_param', type=int, default=2)
     d.add_argument('--force_depth', action='store_true')
@@ -246,9 +250,9 @@ def parse_args(argv=None):
     ap = build_parser()
     opt = ap.parse_args(argv)
     if opt.command == 'denoise':
-        if opt.method == 'bnf' and opt.model:
-            ap.error('denoise: --model cannot be combined with --method bnf (the filter has no model)')
-        if opt.method == 'bnf' and (opt.normal_iters < 0 or not opt.sigma_r > 0 or not opt.sigma_s > 0 or opt.n_iter < 0):
+        if opt.method in ('bnf', 'gnf') and opt.model:
+            ap.error('denoise: --model cannot be combined with --method %s (the filter has no model)' % opt.method)
+        if opt.method in ('bnf', 'gnf') and (opt.normal_iters < 0 or not opt.sigma_r > 0 or not opt.sigma_s > 0 or opt.n_iter < 0):
             ap.error('denoise: --normal_iters and --n_iter are not negative, --sigma_r and --sigma_s positive')
     return opt
 

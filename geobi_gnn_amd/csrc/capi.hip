@@ -534,6 +534,36 @@ int geobi_bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowp
   return bnf_filter(rec_c, rec_n, rowptr, col, F, E, inv2ss, inv2sr, n_sweeps, out, ws, ws_bytes, S(stream));
 }
 
+int geobi_gnf_edge_flags(const int32_t* fv, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E, uint8_t* flags,
+                         void* stream) {
+  SIZES(F, E);
+  if (F == 0 || E == 0) return 0;
+  NOTNULL(fv); NOTNULL(rowptr); NOTNULL(col); NOTNULL(flags);
+  return gnf_edge_flags(fv, rowptr, col, F, E, flags, S(stream));
+}
+
+int geobi_gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* rowptr, const int32_t* col,
+                            const uint8_t* flags, int64_t F, int64_t E, float* H, void* stream) {
+  SIZES(F, E);
+  if (F == 0) return 0;
+  NOTNULL(rec_c); NOTNULL(normals); NOTNULL(rowptr); NOTNULL(H);
+  if (E > 0) { NOTNULL(col); NOTNULL(flags); }
+  if ((const float*)H == rec_c || (const float*)H == normals) return set_error("%s: H aliases an input", __func__);
+  return gnf_patch_measure(rec_c, normals, rowptr, col, flags, F, H, nullptr, S(stream));
+}
+
+size_t geobi_gnf_filter_ws_bytes(int64_t F, int64_t E) { return gnf_filter_ws_bytes(F, E); }
+
+int geobi_gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
+                     int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out,
+                     void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F, E);
+  if (F == 0) return 0;
+  NOTNULL(rec_c); NOTNULL(rec_n); NOTNULL(fv); NOTNULL(rowptr); NOTNULL(inv2ss); NOTNULL(out); NOTNULL(ws);
+  if (E > 0) NOTNULL(col);
+  return gnf_filter(rec_c, rec_n, fv, rowptr, col, F, E, inv2ss, inv2sr, n_sweeps, out, sel_out, ws, ws_bytes, S(stream));
+}
+
 int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, float bias_corr1, float bias_corr2, void* stream) {
   NOTNULL(p); NOTNULL(g); NOTNULL(m); NOTNULL(v);

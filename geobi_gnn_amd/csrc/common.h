@@ -372,6 +372,17 @@ int bnf_prepare(const float* points, const int32_t* fv, int64_t F, float* rec_c,
 size_t bnf_filter_ws_bytes(int64_t F, int64_t E);
 int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
                const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes, hipStream_t s);
+int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
+                        const float* inv2ss, float* wsp, hipStream_t s);
+// guided.hip (guided normal filter: patch search, selection and guidance, the sweep with the range term on the guidance)
+int gnf_edge_flags(const int32_t* fv, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E, uint8_t* flags,
+                   hipStream_t s);
+int gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* rowptr, const int32_t* col,
+                      const uint8_t* flags, int64_t F, float* H, float* pmean, hipStream_t s);
+size_t gnf_filter_ws_bytes(int64_t F, int64_t E);
+int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
+               int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out, void* ws,
+               size_t ws_bytes, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

@@ -131,6 +131,15 @@ int bnf_prepare(const float* points, const int32_t* fv, int64_t F, float* rec_c,
   return 0;
 }
 
+// wsp [E]: the per-edge spatial factors, once per call (guided.hip's sweep reads the same array)
+int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
+                        const float* inv2ss, float* wsp, hipStream_t s) {
+  if (F == 0 || E == 0) return 0;
+  bnf_spatial_kernel<<<cdiv(F, kFacesPerBlock), kThreads, 0, s>>>((const float4*)rec_c, rowptr, col, (int)F, inv2ss, wsp);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
 // one buffer of normals (the sweeps alternate between it and `out`) and the per-edge spatial factors
 size_t bnf_filter_ws_bytes(int64_t F, int64_t E) {
   return align_up((size_t)F * sizeof(float4)) + align_up((size_t)E * sizeof(float)) + 256;
@@ -151,10 +160,7 @@ int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, co
   float* wsp = a.take<float>(E > 0 ? E : 1);
   GEOBI_REQUIRE(a.ok() && tmp && wsp, "bnf_filter: workspace too small (%zu < %zu)", ws_bytes, a.off);
   const int blocks = cdiv(F, kFacesPerBlock);
-  if (E > 0) {
-    bnf_spatial_kernel<<<blocks, kThreads, 0, s>>>((const float4*)rec_c, rowptr, col, (int)F, inv2ss, wsp);
-    GEOBI_LAUNCH_OK();
-  }
+  GEOBI_TRY(bnf_spatial_factors(rec_c, rowptr, col, F, E, inv2ss, wsp, s));
   const float4* src = (const float4*)rec_n;
   for (int k = 1; k <= n_sweeps; ++k) {
     float4* dst = ((n_sweeps - k) & 1) ? tmp : (float4*)out;     // the last sweep lands in `out`

@@ -16,12 +16,32 @@ Per face i of the mesh (points P, faces (a, b, c)):
 
 Sweeps are Jacobi (ping-pong buffers); the kernels are csrc/filter.hip.  The filtered normals go to the vertex update the
 network path uses (data_util.update_position2).  The whole mesh goes in one pass: there is no patch split.
+
+Guided normal filtering (Zhang, Deng, Zhang, Bouaziz, Liu, "Guided Mesh Normal Filtering", Pacific Graphics 2015;
+`denoise --method gnf`, csrc/guided.hip) is the same sweep with the range weight measured on a guidance normal g instead of
+the noisy normal, which is what keeps an edge at high noise.  With the patch P_k = N(k) and an "edge pair" a pair of
+different faces that share at least 2 distinct vertex ids, every sweep makes from the current normals n
+
+    Phi_k = max_{j, m in P_k} |n_j - n_m|
+    R_k   = max |n_j - n_m| / (1e-9 + sum |n_j - n_m|) over the edge pairs with both faces in P_k (0 without one)
+    H_k   = Phi_k R_k,   sel_i = argmin_{k in N(i)} H_k (ties: the lowest index) -- the patches that contain i
+    g_i   = normalised sum_{j in P_sel_i} A_j n_j (n_i when that sum has no length)
+    w_ij  = A_j exp(-|c_i - c_j|^2 / (2 sigma_s^2) - |g_i - g_j|^2 / (2 sigma_r^2)),  then s_i, W_i, n_i' as above
+
+The patch search costs sum_k |P_k|^2 normal comparisons per sweep; a call whose sum x sweeps exceeds GNF_COST_BUDGET is
+refused before the first kernel of the filter runs.
 """
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import meshprep
+
+
+# Normal comparisons (sum_k |P_k|^2 x sweeps) one guided call may ask for: about one second of gnf_measure_kernel at the
+# 1.0e11 per second it was measured to sustain on its slowest shape, a fan of valence 2048 whose every patch is the whole
+# fan; on spheres it does 3 to 4.5e11 per second (DESIGN.md 4g, profiles/filter_gnf.txt).
+GNF_COST_BUDGET = 1.0e11
 
 
 def _check_params(normal_iters, sigma_r, sigma_s):
@@ -114,6 +134,10 @@ def bilateral_denoise(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0,
     V_updated the moved vertices; with gt_points, angle1 = mean angle (degrees) of Np against the ground truth's face
     normals, angle2 = that of the updated mesh's normals (None without).  Kinect data types move vertices along
     normalize(points) only, as predict_mesh does."""
+    return _denoise(_bilateral_normals, points, faces, normal_iters, sigma_r, sigma_s, n_iter, data_type, gt_points, device)
+
+
+def _denoise(normals_fn, points, faces, normal_iters, sigma_r, sigma_s, n_iter, data_type, gt_points, device):
     from . import network
     from .data_util import computer_face_normal, update_position2
     _check_params(normal_iters, sigma_r, sigma_s)
@@ -123,7 +147,7 @@ def bilateral_denoise(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0,
     with torch.cuda.device(pts.device):
         V = pts.shape[0]
         rowptr, lst = meshprep.vertex_faces(fv, V)
-        Np = _bilateral_normals(pts, fv, normal_iters, sigma_r, sigma_s, (rowptr, lst))
+        Np = normals_fn(pts, fv, normal_iters, sigma_r, sigma_s, (rowptr, lst))
         dd = torch.nn.functional.normalize(pts, dim=1) if data_type in ('Kinect_v1', 'Kinect_v2') else None
         vf = meshprep.vf_padded32(rowptr, lst, V)
         Vu = update_position2(pts, fv, vf, Np, n_iter=int(n_iter), depth_direction=dd)
@@ -137,3 +161,79 @@ def bilateral_denoise(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0,
             out['angle1'] = float(network.error_n(Np, Nt))
             out['angle2'] = float(network.error_n(computer_face_normal(Vu, fv), Nt))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ guided normal filter
+def edge_flags(fv, graph):
+    """geobi_gnf_edge_flags: uint8 [E], 1 where the two faces of the CSR entry share at least 2 distinct vertex ids."""
+    flags = torch.empty(max(graph.E, 1), dtype=torch.uint8, device=fv.device)
+    L.call('geobi_gnf_edge_flags', L.ptr(fv), L.ptr(graph.rowptr_out), L.ptr(graph.col_out), fv.shape[0], graph.E,
+           L.ptr(flags), L.stream())
+    return flags[:graph.E]
+
+
+def patch_measure(rec_c, normals, graph, flags):
+    """geobi_gnf_patch_measure: H [F] of the normals [F,4] (rows of rec_n's layout)."""
+    F = rec_c.shape[0]
+    H = torch.empty(F, dtype=torch.float32, device=rec_c.device)
+    L.call('geobi_gnf_patch_measure', L.ptr(rec_c), L.ptr(normals), L.ptr(graph.rowptr_out), L.ptr(graph.col_out),
+           L.ptr(flags), F, graph.E, L.ptr(H), L.stream())
+    return H
+
+
+def patch_cost(graph, F):
+    """sum_k (deg_k + 1)^2, the normal comparisons of one patch search: summed on the device, one host read."""
+    deg = (graph.rowptr_out[1:F + 1] - graph.rowptr_out[:F]).long() + 1
+    total = (deg * deg).sum()
+    lo, hi = L.read_i32(torch.stack([total & 0x7fffffff, total >> 31]).to(torch.int32))
+    return (hi << 31) | lo
+
+
+def _check_cost(graph, F, n_sweeps):
+    cost = patch_cost(graph, F) * max(int(n_sweeps), 1)
+    if cost > GNF_COST_BUDGET:
+        raise L.GeobiError('guided filter: the patch search would take %d normal comparisons (sum of squared patch sizes '
+                           'x %d sweeps), the budget is %d: a vertex of very high valence; use the bilateral filter'
+                           % (cost, max(int(n_sweeps), 1), int(GNF_COST_BUDGET)))
+
+
+def guided_records(rec_c, rec_n, fv, graph, inv2ss, sigma_r, n_sweeps, return_selection=False):
+    """geobi_gnf_filter: `n_sweeps` sweeps starting from the normals in rec_n -> [F,4] rows of rec_n's layout; with
+    return_selection also every sweep's selection, int32 [n_sweeps, F]."""
+    F = rec_c.shape[0]
+    out = torch.empty_like(rec_n)
+    sel = torch.empty((int(n_sweeps), F), dtype=torch.int32, device=rec_c.device) if return_selection else None
+    ws = L.workspace(L.size_query('geobi_gnf_filter_ws_bytes', F, graph.E), rec_c.device)
+    L.call('geobi_gnf_filter', L.ptr(rec_c), L.ptr(rec_n), L.ptr(fv), L.ptr(graph.rowptr_out), L.ptr(graph.col_out), F,
+           graph.E, L.ptr(inv2ss), 0.5 / (float(sigma_r) * float(sigma_r)), int(n_sweeps), L.ptr(out),
+           L.ptr(sel) if sel is not None and sel.numel() else None, L.ptr(ws), ws.numel(), L.stream())
+    return (out, sel) if return_selection else out
+
+
+def _guided_normals(pts, fv, normal_iters, sigma_r, sigma_s, incidence, return_selection=False):
+    rowptr, lst = incidence if incidence is not None else meshprep.vertex_faces(fv, pts.shape[0])
+    graph = meshprep.ring_graph(1, fv, rowptr, lst, fv.shape[0])
+    _check_cost(graph, fv.shape[0], normal_iters)
+    rec_c, rec_n = face_records(pts, fv)
+    inv2ss = spatial_scale(pts, fv, graph, sigma_s)
+    r = guided_records(rec_c, rec_n, fv, graph, inv2ss, sigma_r, int(normal_iters), return_selection)
+    if return_selection:
+        return r[0][:, :3].contiguous(), r[1]
+    return r[:, :3].contiguous()
+
+
+def guided_normals(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0, incidence=None, return_selection=False):
+    """Guided-filtered unit face normals [F,3] (fp32, on the device) of the mesh (points [V,3], faces [F,3]).
+    incidence: (rowptr, list) of meshprep.vertex_faces for these faces, if the caller has it already.
+    normal_iters = 0 returns the start normals.  return_selection: -> (normals, int32 [normal_iters, F]: the patch every
+    face took its guidance from, per sweep)."""
+    _check_params(normal_iters, sigma_r, sigma_s)
+    pts, fv = _device_mesh(points, faces, None)
+    with torch.cuda.device(pts.device):
+        return _guided_normals(pts, fv, normal_iters, sigma_r, sigma_s, incidence, return_selection)
+
+
+def guided_denoise(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0, n_iter=20, data_type='Synthetic',
+                   gt_points=None, device=None):
+    """Guided normal filtering, then `n_iter` sweeps of the vertex update: bilateral_denoise's arguments and result."""
+    return _denoise(_guided_normals, points, faces, normal_iters, sigma_r, sigma_s, n_iter, data_type, gt_points, device)

@@ -380,6 +380,39 @@ int geobi_bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowp
                      int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------- guided normal filter ----
+ * The reference has NO call site for this either (same list of result folders).  Zhang, Deng, Zhang, Bouaziz, Liu,
+ * "Guided Mesh Normal Filtering" (Pacific Graphics 2015) over the same records, facet graph and inv2ss as the bilateral
+ * filter above; the patch of face k is P_k = row k PLUS k.
+ *   geobi_gnf_edge_flags     flags [E] (one byte per CSR entry): 1 when the two faces of the entry have at least 2 DISTINCT
+ *                            vertex ids in common (an "edge pair": non-manifold edges, duplicate faces, faces with a
+ *                            repeated vertex included), else 0.  Reads fv [F, 3] only; does not depend on the points
+ *   geobi_gnf_patch_measure  H [F] from normals [F, 4] (rows of rec_n's layout):
+ *                              Phi_k = max_{j, m in P_k} |n_j - n_m|;  over the edge pairs {j, m} with both faces in P_k
+ *                              R_k = max |n_j - n_m| / (1e-9 + sum |n_j - n_m|), 0 without such a pair;  H_k = Phi_k R_k
+ *                            16 lanes per face; the patch is staged in LDS up to 64 entries, a longer row is read through
+ *                            the CSR; m in P_k is a bisection of the ascending row; the edge sum is kept in fp64; fixed-shape
+ *                            reductions, no atomics: the same input gives the same bits.  H must not alias an input
+ *   geobi_gnf_filter         n_sweeps Jacobi sweeps; every sweep makes H from the current normals n, then
+ *                              sel_i = argmin_{k in row i or k = i} H_k, ties to the lowest face index
+ *                              s = sum_{j in P_sel_i} A_j n_j,  g_i = s / |s| if |s| > 1e-6 sum A_j, else n_i
+ *                              w_ij = A_j exp(-inv2ss |c_i - c_j|^2 - inv2sr |g_i - g_j|^2) over row i and j = i
+ *                              s_i = sum w_ij n_j,  W_i = sum w_ij,  n_i' = s_i / |s_i| if |s_i| > 1e-6 W_i, else n_i
+ *                            The edge flags (from fv) and the spatial factors are made once per call in the workspace.
+ *                            sel_out: NULL, or int32 [n_sweeps, F] that receives every sweep's selection (4 B per face and
+ *                            sweep).  rec_n, out, n_sweeps = 0 and the aliasing rule as geobi_bnf_filter; k sweeps in one
+ *                            call are k calls of one sweep, bit for bit.
+ * The patch search costs sum_k (deg_k + 1)^2 normal comparisons per sweep: a caller that admits arbitrary meshes bounds that
+ * sum first (geobi_gnn_amd/filters.py does).                                                                              */
+int geobi_gnf_edge_flags(const int32_t* fv, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E, uint8_t* flags,
+                         void* stream);
+int geobi_gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* rowptr, const int32_t* col,
+                            const uint8_t* flags, int64_t F, int64_t E, float* H, void* stream);
+size_t geobi_gnf_filter_ws_bytes(int64_t F, int64_t E);
+int geobi_gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
+                     int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out,
+                     void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser step ----
  * torch.optim.Adam's update rule (code/train_dual.py:162, the reference's default optimiser; no amsgrad) over one flat
  * fp32 vector of n parameters, its gradient and the two moment vectors (16-byte aligned), one launch:

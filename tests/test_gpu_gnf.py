@@ -1,0 +1,468 @@
+"""The guided normal filter on the device (csrc/guided.hip, geobi_gnn_amd/filters.py) against the fp64 model of
+tests/gnf_model.py: edge-pair flags, the patch measure H, selections, the normals after every sweep, determinism, the entry
+points' refusals, filters.guided_denoise and `denoise --method gnf` end to end.
+
+Bars, per component: 8 x max(d32, 4 x 2^-24), d32 = max |fp32 model - fp64 model| on the same input, computed here on the
+CPU -- measured against the model, never against the kernel (tests/test_gpu_filter.py's rule).  For H the two models read
+the same normals; for the normals after a sweep both models replay the KERNEL's selections, each selection only after it
+passed its own check:
+
+  a selection is discrete -- a near-tie of two patches may legitimately go either way -- so it is checked as (i) valid:
+  sel_t[i] is a patch that contains i and, in the fp64 model's H of the model's normals at sweep t, no further above the
+  row's minimum than the H bar (the bar from the two replaying models' H at that sweep); and (ii) exact where the model's H
+  over the row are exactly equal (flat meshes, the clean cube): the lowest index.
+
+Observed on the MI355X after 5 sweeps, kernel / d32 (every figure is printed by the tests): one face 5.5e-8 / 6.4e-8;
+icosahedron 1.1e-7 / 7.9e-8; n = 8 sphere 1.1e-7 / 1.6e-7; fans 64, 65, 200 8.9e-8 / 8.9e-8, 1.0e-7 / 6.0e-8, 1.0e-7 / 9.0e-8;
+degenerate sphere 2.0e-7 / 1.6e-7; translated n = 8 sphere 4.5e-5 / 1.8e-4.  H: n = 8 sphere 2.0e-8 / 2.7e-8, noisy cube(4)
+9.2e-8 / 9.3e-8.  Largest ratio to the bar: 0.20 (normals, degenerate sphere), 0.06 (H).  One selection of all was not the
+fp64 model's minimum: 5.4e-10 above it (icosahedron, sweep 0; bar 1.9e-6)."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import bnf_model as B
+import geom_model as G
+import gnf_model as M
+from train_cases import _run
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+SWEEPS = (0, 1, 2, 5)
+FAN_VALENCES = (3, 4, 5, 8, 9, 16, 17, 33, 64, 65, 200)
+
+
+@pytest.fixture(scope='module')
+def dev():
+    assert torch.cuda.is_available(), 'GPU tests need the MI355X'
+    return torch.device('cuda:0')
+
+
+# ------------------------------------------------------------------------------------------------ meshes and references
+def _one_face():
+    return G._f32_values([[0.1, 0.2, 0.3], [1.3, 0.1, 0.2], [0.4, 1.1, 0.9]]), torch.tensor([[0, 1, 2]])
+
+
+def _two_faces():
+    return (G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 2.0, 0.0], [0.5, -1.0, 1.0]]),
+            torch.tensor([[0, 1, 2], [1, 0, 3]]))
+
+
+def _tetrahedron():
+    return (G._f32_values([[0.0, 0.0, 0.0], [1.1, 0.1, 0.0], [0.2, 0.9, 0.1], [0.3, 0.2, 1.2]]),
+            torch.tensor([[0, 2, 1], [0, 1, 3], [1, 2, 3], [2, 0, 3]]))
+
+
+def _icosahedron():
+    from geobi_gnn_amd import meshgen
+    pts, faces = meshgen.icosphere(1)
+    return G._f32_values(pts), torch.from_numpy(np.asarray(faces, dtype=np.int64))
+
+
+def _all_degenerate():
+    pts = G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [2.0, 0.0, 0.0], [4.0, 0.0, 0.0]])
+    return pts, torch.tensor([[0, 1, 2], [1, 2, 3], [0, 0, 3]])
+
+
+def _opposite():
+    return G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), torch.tensor([[0, 1, 2], [0, 2, 1]])
+
+
+def _shifted():
+    pts, faces = G.sphere(8, 0.3, 1)
+    return G._f32_values((pts + torch.tensor([1000.0, -2000.0, 500.0], dtype=torch.float64)).numpy()), faces
+
+
+def _three_on_an_edge():
+    pts, faces = M.three_on_an_edge()
+    return G._f32_values(pts.numpy()), faces
+
+
+MESHES = {'one_face': _one_face, 'two_faces': _two_faces, 'tetrahedron': _tetrahedron, 'icosahedron': _icosahedron,
+          'cube2': lambda: M.cube(2), 'cube4_noisy': lambda: M.noisy_cube(4, 0.3, 1)[::2],
+          'sphere4': lambda: G.sphere(4, 0.3, 1), 'sphere8': lambda: G.sphere(8, 0.3, 1),
+          'degenerate': lambda: G.degenerate_sphere()[:2], 'all_degenerate': _all_degenerate, 'opposite': _opposite,
+          'three_on_an_edge': _three_on_an_edge, 'shifted': _shifted}
+MESHES.update({'fan%d' % v: (lambda v_=v: G.fan(v_)) for v in FAN_VALENCES})
+_CACHE = {}
+
+
+def _case(name):
+    """(points f64 with f32 values, faces, the model's topology): built once, never changed."""
+    if name not in _CACHE:
+        pts, faces = MESHES[name]()
+        _CACHE[name] = (pts, faces, M.Topology(faces, pts.shape[0]))
+    return _CACHE[name]
+
+
+def _bar(d32):
+    return 8 * max(d32, 4 * U)
+
+
+class _Device(object):
+    """The filter's device inputs for one mesh: records, facet graph, the spatial scale, the edge-pair flags."""
+
+    def __init__(self, pts, faces, dev, sigma_s=1.0):
+        from geobi_gnn_amd import filters, meshprep
+        self.filters = filters
+        self.pts = pts.float().to(dev).contiguous()
+        self.fv = faces.to(device=dev, dtype=torch.int32).contiguous()
+        rowptr, lst = meshprep.vertex_faces(self.fv, self.pts.shape[0])
+        self.graph = meshprep.ring_graph(1, self.fv, rowptr, lst, self.fv.shape[0])
+        self.rec_c, self.rec_n = filters.face_records(self.pts, self.fv)
+        self.inv2ss = filters.spatial_scale(self.pts, self.fv, self.graph, sigma_s)
+        self.flags = filters.edge_flags(self.fv, self.graph)
+
+    def run(self, n_sweeps, start=None, sigma_r=0.35):
+        out, sel = self.filters.guided_records(self.rec_c, self.rec_n if start is None else start, self.fv, self.graph,
+                                               self.inv2ss, sigma_r, n_sweeps, return_selection=True)
+        torch.cuda.synchronize()
+        return out, sel
+
+    def measure(self, normals):
+        H = self.filters.patch_measure(self.rec_c, normals, self.graph, self.flags)
+        torch.cuda.synchronize()
+        return H
+
+
+def _rows_all_equal(H, topo):
+    """Faces whose H values over the row (the patches that contain the face) are exactly equal."""
+    Hrow = torch.where(topo.valid, H[topo.safe], H[topo.patch[:, :1]].expand_as(topo.safe))
+    return (Hrow == Hrow[:, :1]).all(1)
+
+
+def _check_selection(name, t, sel, H64, hbar, topo, strong_ties=False):
+    """(i) validity and (ii) ties of one sweep's selection `sel` [F] against the fp64 model's H."""
+    sel = sel.long()
+    assert bool(((sel >= 0) & (sel < topo.F)).all()), (name, t)
+    member = (topo.patch == sel[:, None]).any(1)
+    assert bool(member.all()), (name, t, 'a selected patch does not contain its face')
+    least = torch.where(topo.valid, H64[topo.safe], torch.full((), float('inf'), dtype=H64.dtype)).min(1).values
+    excess = float((H64[sel] - least).max())
+    print('%-16s sweep %d: selection excess over the least H %.3g, H bar %.3g' % (name, t, excess, hbar))
+    assert excess <= hbar, (name, t, excess, hbar)
+    want = M.select(H64, topo)
+    tied = _rows_all_equal(H64, topo)
+    if strong_ties:                                     # every exact tie at the minimum, not only whole rows
+        tied = torch.ones_like(tied)
+        assert excess == 0.0
+    assert torch.equal(sel[tied], want[tied]), (name, t, 'a tie did not go to the lowest index')
+    return int(tied.sum())
+
+
+def _check_mesh(dev, name, sigma_r=0.35):
+    pts, faces, topo = _case(name)
+    d = _Device(pts, faces, dev)
+    F = faces.shape[0]
+    K = max(SWEEPS)
+    # the facet graph the kernels walk is the model's, loops aside; the flags are the model's, exactly
+    off = topo.row != topo.col
+    assert d.graph.E == int(off.sum()) and torch.equal(d.graph.col_out.cpu().long(), topo.col[off])
+    assert d.flags.dtype == torch.uint8 and torch.equal(d.flags.cpu(), topo.csr_flags())
+    # one sweep per call, chained
+    singles, single_sel = [d.rec_n], []
+    for _ in range(K):
+        out, sel = d.run(1, start=singles[-1], sigma_r=sigma_r)
+        assert tuple(sel.shape) == (1, F) and sel.dtype == torch.int32
+        singles.append(out)
+        single_sel.append(sel[0])
+    # determinism: two runs, k sweeps against k calls, sel_out included; 0 sweeps are the start normals
+    for k in SWEEPS:
+        got, sel = d.run(k, sigma_r=sigma_r)
+        again, sel_again = d.run(k, sigma_r=sigma_r)
+        assert tuple(got.shape) == (F, 4) and float(got[:, 3].abs().max()) == 0.0 and tuple(sel.shape) == (k, F)
+        assert torch.equal(got, again) and torch.equal(sel, sel_again), 'two runs of %d sweeps differ' % k
+        assert torch.equal(got, singles[k]), '%d sweeps in one call differ from %d calls of one sweep' % (k, k)
+        if k:
+            assert torch.equal(sel, torch.stack(single_sel[:k]))
+        plain = d.filters.guided_records(d.rec_c, d.rec_n, d.fv, d.graph, d.inv2ss, sigma_r, k)      # sel_out NULL
+        assert torch.equal(plain, got)
+    assert torch.equal(singles[0], d.rec_n)
+    # H on the kernel's own normals after 0, 1, 2, 5 sweeps: the two models read the same fp32 values
+    worst_h = 0.0
+    for k in SWEEPS:
+        n = singles[k][:, :3].cpu()
+        H64, H32 = M.patch_measure(n.double(), topo), M.patch_measure(n, topo)
+        dH = float((H32.double() - H64).abs().max())
+        got = d.measure(singles[k]).cpu().double()
+        assert torch.equal(d.measure(singles[k]).cpu().double(), got)
+        err = float((got - H64).abs().max())
+        worst_h = max(worst_h, err / _bar(dH))
+        print('%-16s F %5d after %d sweeps: |H kernel - H fp64 model| %.3g, d32 %.3g, bar %.3g' % (name, F, k, err, dH, _bar(dH)))
+        assert err <= _bar(dH), (name, k, err, dH)
+    # replay: both models follow the kernel's selections, each one checked before it is used
+    m64 = M.Filter(pts, faces, sigma_r=sigma_r, topo=topo)
+    m32 = M.Filter(pts.float(), faces, sigma_r=sigma_r, topo=topo)
+    worst_n, ties = 0.0, 0
+    for t in range(K + 1):
+        d32 = float((m32.n.double() - m64.n).abs().max())
+        err = float((singles[t][:, :3].cpu().double() - m64.n).abs().max())              # every face, every component
+        worst_n = max(worst_n, err / _bar(d32))
+        print('%-16s F %5d sweeps %d: |kernel - fp64 model| %.3g, d32 %.3g, bar %.3g' % (name, F, t, err, d32, _bar(d32)))
+        assert err <= _bar(d32), (name, t, err, d32)
+        if t > 0:
+            # every row is a unit vector, or exactly the row it was (kept: cancellation, all-degenerate neighbourhood)
+            length = singles[t][:, :3].cpu().double().norm(dim=1)
+            kept = (singles[t] == singles[t - 1]).all(1).cpu()
+            assert bool((((length - 1).abs() <= 4 * U * np.sqrt(3.0)) | kept).all()), (name, t)
+        if t == K:
+            break
+        H64, H32 = m64.measure(), m32.measure()
+        hbar = _bar(float((H32.double() - H64).abs().max()))
+        sel = single_sel[t].cpu()
+        ties += _check_selection(name, t, sel, H64, hbar, topo, strong_ties=name == 'cube2' and t == 0)
+        m64.step(sel)
+        m32.step(sel)
+    print('%-16s largest ratio to the bar: H %.2f, normals %.2f; %d rows of exactly equal H' % (name, worst_h, worst_n, ties))
+    # the public function: same bits as the steps above, [F, 3], and the selections on request
+    for k in (0, 5):
+        pub = d.filters.guided_normals(d.pts, d.fv, normal_iters=k, sigma_r=sigma_r)
+        assert tuple(pub.shape) == (F, 3) and pub.is_contiguous() and torch.equal(pub, singles[k][:, :3])
+    pub, sel = d.filters.guided_normals(d.pts, d.fv, normal_iters=K, sigma_r=sigma_r, return_selection=True)
+    assert torch.equal(pub, singles[K][:, :3]) and torch.equal(sel, torch.stack(single_sel))
+    return d, singles, single_sel, ties
+
+
+@pytest.mark.parametrize('name', ['one_face', 'two_faces', 'tetrahedron', 'icosahedron', 'cube4_noisy', 'sphere4', 'sphere8',
+                                  'three_on_an_edge', 'shifted'])
+def test_kernels_against_the_fp64_model(dev, name):
+    """F = 1 (a one-face patch: H = 0, g = n), two faces over an edge (one patch, an exact tie), the tetrahedron (every
+    face in every patch), the icosahedron, a noisy cube (creases), noisy spheres (F = 1280 is 80 full blocks; the smaller
+    meshes end in a tail block), three faces on one edge, and the n = 8 sphere far from the origin (differences only)."""
+    d, singles, sel, _ = _check_mesh(dev, name)
+    if name == 'one_face':
+        assert d.graph.E == 0 and float(d.measure(d.rec_n).abs().max()) == 0.0
+        assert all(s.tolist() == [0] for s in sel)
+    if name == 'two_faces':
+        assert all(s.tolist() == [0, 0] for s in sel)
+    if name == 'tetrahedron':
+        deg = (d.graph.rowptr_out[1:] - d.graph.rowptr_out[:-1]).cpu()
+        assert bool((deg == 3).all()) and bool((d.flags == 1).all())
+        H = d.measure(d.rec_n)
+        assert bool((H == H[0]).all())                                          # one patch, seen from four faces
+
+
+def test_clean_cube_ties(dev):
+    """cube(2), clean: the start normals are exact axis vectors, so congruent patches tie exactly (fp64 edge sums of equal
+    fp32 terms) and in the first sweep every tie at the minimum goes to the lowest index (_check_mesh asks that of the whole
+    selection, not only of rows that are equal throughout).  Later sweeps read normals that carry roundings: near-ties,
+    held to the validity check."""
+    d, singles, sel, ties = _check_mesh(dev, 'cube2')
+    topo = _case('cube2')[2]
+    H = d.measure(d.rec_n).cpu()
+    assert torch.unique(H).numel() == torch.unique(M.patch_measure(B.face_records(*_case('cube2')[:2])[2], topo)).numel()
+    assert torch.equal(sel[0].cpu().long(), M.select(H.double(), topo))
+
+
+@pytest.mark.parametrize('valence', FAN_VALENCES)
+def test_fan_rows(dev, valence):
+    """geom_model.fan(v): every patch is the whole fan, v entries -- below, at and above the 16-lane group (15, 16, 17), at
+    and above the 64 entries a group stages in LDS (fan64 staged, fan65 and fan200 through the CSR), several passes."""
+    d, _, _, _ = _check_mesh(dev, 'fan%d' % valence)
+    deg = (d.graph.rowptr_out[1:] - d.graph.rowptr_out[:-1]).cpu()
+    assert bool((deg == valence - 1).all())
+    assert int(d.flags.sum()) == 2 * valence                                    # a closed fan: v interior edges
+
+
+def test_degenerate_and_flat_meshes(dev):
+    """Zero-area faces (weight 0, zero start normal), a mesh of nothing but those (H = 0, W = 0: everything is kept and
+    every selection is the lowest index), and one triangle with both orientations (the guidance sum cancels: g = n)."""
+    _check_mesh(dev, 'degenerate')
+    d, singles, sel, ties = _check_mesh(dev, 'all_degenerate')
+    assert ties == 3 * max(SWEEPS)
+    for s in singles:
+        assert float(s.abs().max()) == 0.0
+    d, singles, sel, _ = _check_mesh(dev, 'opposite')
+    assert torch.equal(d.rec_n[0], -d.rec_n[1]) and all(s.tolist() == [0, 0] for s in sel)
+    # a flat triangulated square: H = 0, the lowest index everywhere, the normals come back bit for bit
+    from test_bnf_model_host import _flat_patch
+    pts, faces = _flat_patch()
+    pts = G._f32_values(pts.numpy())
+    topo = M.Topology(faces, pts.shape[0])
+    dd = _Device(pts, faces, dev)
+    assert float(dd.measure(dd.rec_n).abs().max()) == 0.0
+    out, sel = dd.run(3)
+    assert torch.equal(out, dd.rec_n) and torch.equal(sel.cpu().long(), topo.patch[:, 0].expand(3, -1))
+
+
+def test_bilateral_filter_is_untouched(dev):
+    from geobi_gnn_amd import filters
+    pts, faces = G.sphere(8, 0.3, 1)
+    before = filters.bilateral_normals(pts.float(), faces)
+    filters.guided_normals(pts.float(), faces, normal_iters=2)
+    after = filters.bilateral_normals(pts.float(), faces)
+    assert torch.equal(before, after)
+    want = B.bilateral_normals(pts, faces)
+    assert float((before.cpu().double() - want).abs().max()) <= 1e-5
+
+
+# ------------------------------------------------------------------------------------------------ guided_denoise
+def _sphere8_with_truth():
+    from geobi_gnn_amd import meshgen
+    noisy, clean, faces = meshgen.noisy_icosphere(8, 0.3, seed=1)
+    return noisy, clean, np.asarray(faces, dtype=np.int64)
+
+
+def _angle(a, b):
+    return float(G.row_terms(a, b, 3).mean())
+
+
+def test_guided_denoise_against_the_model(dev):
+    """n = 8, sigma 0.3, defaults: angle1 and angle2 within 0.01 degrees of the model's normals (replaying the device's
+    selections, 20 sweeps) pushed through the fp64 vertex update."""
+    from geobi_gnn_amd import filters
+    noisy, clean, faces = _sphere8_with_truth()
+    r = filters.guided_denoise(noisy, faces, gt_points=clean, device=dev)
+    assert sorted(r) == ['Np', 'V_updated', 'angle1', 'angle2']
+    assert tuple(r['Np'].shape) == (faces.shape[0], 3) and tuple(r['V_updated'].shape) == noisy.shape
+    Np, sel = filters.guided_normals(noisy, faces, return_selection=True)
+    assert torch.equal(r['Np'], Np) and tuple(sel.shape) == (20, faces.shape[0])
+    p64, f64 = torch.from_numpy(noisy.astype(np.float64)), torch.from_numpy(faces)
+    nt = B.face_records(torch.from_numpy(clean.astype(np.float64)), f64)[2]
+    np_model = M.guided_normals(p64, f64, selection=sel.cpu().long())
+    vu = G.update_position2(p64, f64, G.vertex_faces(f64, noisy.shape[0]), np_model, n_iter=20)
+    want1, want2 = _angle(np_model, nt), _angle(B.face_records(vu, f64)[2], nt)
+    before = _angle(B.face_records(p64, f64)[2], nt)
+    print('angle1 %.6f (model %.6f), angle2 %.6f (model %.6f), input %.3f' % (r['angle1'], want1, r['angle2'], want2, before))
+    assert abs(r['angle1'] - want1) <= 0.01 and abs(r['angle2'] - want2) <= 0.01
+    assert r['angle1'] < before / 4
+    assert float((r['V_updated'].cpu().double() - vu).abs().max()) <= 1e-5
+    none = filters.guided_denoise(noisy, faces, n_iter=0, device=dev)
+    assert none['angle1'] is None and none['angle2'] is None
+    assert torch.equal(none['V_updated'], torch.from_numpy(noisy).to(dev))
+
+
+def test_guided_denoise_kinect_moves_along_the_viewing_ray(dev):
+    """data_type Kinect_v1: every vertex moves along normalize(points) only; the bar is tests/test_gpu_filter.py's (20
+    sweeps, one rounding of p + step per coordinate each, the fp32 ray within 2u per coordinate of the exact one)."""
+    from geobi_gnn_amd import filters
+    noisy, clean, faces = _sphere8_with_truth()
+    r = filters.guided_denoise(noisy, faces, data_type='Kinect_v1', gt_points=clean, device=dev)
+    free = filters.guided_denoise(noisy, faces, gt_points=clean, device=dev)
+    assert torch.equal(r['Np'], free['Np'])
+    p = torch.from_numpy(noisy.astype(np.float64))
+    ray = torch.nn.functional.normalize(p, dim=1)
+    d = r['V_updated'].cpu().double() - p
+    across = (d - (d * ray).sum(1, keepdim=True) * ray).norm(dim=1)
+    bar = 20 * 2 * np.sqrt(3.0) * U * float(p.norm(dim=1).max()) + 8 * U * d.norm(dim=1)
+    print('largest displacement %.3g, largest part across the ray %.3g' % (float(d.norm(dim=1).max()), float(across.max())))
+    assert float(d.norm(dim=1).max()) > 1e-3 and bool((across <= bar).all())
+    assert not torch.equal(r['V_updated'], free['V_updated'])
+
+
+def test_errors(dev, monkeypatch):
+    from geobi_gnn_amd import _lib as L
+    from geobi_gnn_amd import filters
+    noisy, _, faces = _sphere8_with_truth()
+    bad = faces.copy()
+    bad[3, 1] = noisy.shape[0]
+    for fn in (filters.guided_normals, filters.guided_denoise):
+        with pytest.raises(L.GeobiError, match='outside'):
+            fn(noisy, bad)
+        neg = faces.copy()
+        neg[0, 0] = -1
+        with pytest.raises(L.GeobiError, match='outside'):
+            fn(noisy, neg)
+        with pytest.raises(ValueError, match='sigma_r'):
+            fn(noisy, faces, sigma_r=0)
+        with pytest.raises(ValueError, match='sigma_s'):
+            fn(noisy, faces, sigma_s=-1.0)
+        with pytest.raises(ValueError, match='normal_iters'):
+            fn(noisy, faces, normal_iters=-1)
+    with pytest.raises(ValueError, match='n_iter'):
+        filters.guided_denoise(noisy, faces, n_iter=-1)
+    # the cost guard: sum of squared patch sizes x sweeps against the module's budget, both named in the refusal
+    d = _Device(*_case('fan200')[:2], dev)
+    assert filters.patch_cost(d.graph, 200) == 200 ** 3
+    filters.guided_normals(d.pts, d.fv)                                        # the 200-fan is admitted as it is
+    monkeypatch.setattr(filters, 'GNF_COST_BUDGET', 200 ** 3 * 20 - 1)
+    with pytest.raises(L.GeobiError, match=r'160000000 normal comparisons.*budget is 159999999'):
+        filters.guided_normals(d.pts, d.fv)
+    filters.guided_normals(d.pts, d.fv, normal_iters=19)
+    monkeypatch.undo()
+    # the C entry points enforce the size limits and their own arguments
+    d = _Device(*_case('icosahedron')[:2], dev)
+    out = torch.empty_like(d.rec_n)
+    H = torch.empty(20, dtype=torch.float32, device=dev)
+    ws = L.workspace(1 << 16, dev)
+    args = (L.ptr(d.rec_c), L.ptr(d.rec_n), L.ptr(d.fv), L.ptr(d.graph.rowptr_out), L.ptr(d.graph.col_out))
+    tail = (L.ptr(out), None, L.ptr(ws), ws.numel(), L.stream())
+    with pytest.raises(L.GeobiError, match='GEOBI_MAX_NODES'):
+        L.call('geobi_gnf_filter', *args, 1 << 24, d.graph.E, L.ptr(d.inv2ss), 4.0, 1, *tail)
+    with pytest.raises(L.GeobiError, match='GEOBI_MAX_EDGES'):
+        L.call('geobi_gnf_filter', *args, 20, 1 << 28, L.ptr(d.inv2ss), 4.0, 1, *tail)
+    with pytest.raises(L.GeobiError, match='n_sweeps'):
+        L.call('geobi_gnf_filter', *args, 20, d.graph.E, L.ptr(d.inv2ss), 4.0, -1, *tail)
+    with pytest.raises(L.GeobiError, match='workspace'):
+        L.call('geobi_gnf_filter', *args, 20, d.graph.E, L.ptr(d.inv2ss), 4.0, 1, L.ptr(out), None, L.ptr(ws), 64, L.stream())
+    with pytest.raises(L.GeobiError, match='aliases'):
+        L.call('geobi_gnf_filter', *args, 20, d.graph.E, L.ptr(d.inv2ss), 4.0, 1, L.ptr(d.rec_n), None, L.ptr(ws), ws.numel(),
+               L.stream())
+    graph = (L.ptr(d.graph.rowptr_out), L.ptr(d.graph.col_out))
+    with pytest.raises(L.GeobiError, match='GEOBI_MAX_NODES'):
+        L.call('geobi_gnf_edge_flags', L.ptr(d.fv), *graph, 1 << 24, d.graph.E, L.ptr(d.flags), L.stream())
+    with pytest.raises(L.GeobiError, match='GEOBI_MAX_EDGES'):
+        L.call('geobi_gnf_edge_flags', L.ptr(d.fv), *graph, 20, 1 << 28, L.ptr(d.flags), L.stream())
+    with pytest.raises(L.GeobiError, match='GEOBI_MAX_NODES'):
+        L.call('geobi_gnf_patch_measure', L.ptr(d.rec_c), L.ptr(d.rec_n), *graph, L.ptr(d.flags), 1 << 24, d.graph.E, L.ptr(H),
+               L.stream())
+    with pytest.raises(L.GeobiError, match='GEOBI_MAX_EDGES'):
+        L.call('geobi_gnf_patch_measure', L.ptr(d.rec_c), L.ptr(d.rec_n), *graph, L.ptr(d.flags), 20, 1 << 28, L.ptr(H),
+               L.stream())
+    with pytest.raises(L.GeobiError, match='aliases'):
+        L.call('geobi_gnf_patch_measure', L.ptr(d.rec_c), L.ptr(d.rec_n), *graph, L.ptr(d.flags), 20, d.graph.E,
+               L.ptr(d.rec_n), L.stream())
+
+
+# ------------------------------------------------------------------------------------------------ command
+def test_denoise_command_with_the_guided_filter(dev, tmp_path):
+    from geobi_gnn_amd import filters, meshgen, meshio
+    data = str(tmp_path / 'set')
+    os.makedirs(os.path.join(data, 'original'))
+    os.makedirs(os.path.join(data, 'noisy'))
+    for name, seed in (('ball', 1), ('ball2', 2)):
+        noisy, clean, faces = meshgen.noisy_icosphere(4, 0.3, seed=seed)
+        meshio.write_obj(os.path.join(data, 'original', name + '.obj'), clean, np.asarray(faces, dtype=np.int32))
+        meshio.write_obj(os.path.join(data, 'noisy', name + '_n1.obj'), noisy, np.asarray(faces, dtype=np.int32))
+
+    def check(run, out_dir, fn, n_iter, **kw):
+        lines = [ln for ln in run.stdout.splitlines() if ln.startswith('angle1:')]
+        assert len(lines) == 2 and 'angle_mean1' in run.stdout and 'random init' not in run.stdout
+        for name in ('ball', 'ball2'):
+            ln, = [x for x in lines if "'%s_n1-%d.obj'" % (name, n_iter) in x]
+            pts, faces = meshio.read_obj(os.path.join(data, 'noisy', name + '_n1.obj'))
+            gt, _ = meshio.read_obj(os.path.join(data, 'original', name + '.obj'))
+            r = fn(pts, faces, gt_points=gt, device=dev, n_iter=n_iter, **kw)
+            assert ln.startswith('angle1: %9.6f,  angle2: %9.6f,  faces: %6d,' % (r['angle1'], r['angle2'], faces.shape[0])), ln
+            got, got_faces = meshio.read_obj(os.path.join(out_dir, '%s_n1-%d.obj' % (name, n_iter)))
+            assert (got_faces == faces).all()
+            assert (got.view(np.uint32) == r['V_updated'].cpu().numpy().view(np.uint32)).all()  # nine digits: bit for bit
+
+    run = _run(['denoise', '--method', 'gnf', '--data_dir', data])
+    assert run.returncode == 0, run.stderr[-2000:]
+    result = os.path.join(data, 'result')
+    assert sorted(os.listdir(result)) == ['ball2_n1-20.obj', 'ball_n1-20.obj'] and 'Guided normal filter' in run.stdout
+    check(run, result, filters.guided_denoise, 20)
+    mean = re.search(r'Num_face:\s*(\d+),\s*angle_mean1: ([0-9.]+),\s*angle_mean2: ([0-9.]+)', run.stdout)
+    assert mean and int(mean.group(1)) == 2 * 320
+    # `eval` pairs the results with their originals as it does for the network's
+    run = _run(['eval', '--result_dir', result, '--original_dir', os.path.join(data, 'original')])
+    assert run.returncode == 0 and '2 pairs' in run.stdout, run.stderr[-2000:]
+    # --model with the filter is an argument error, before anything runs
+    run = _run(['denoise', '--method', 'gnf', '--model', 'net.pt', '--data_dir', data])
+    assert run.returncode == 2 and '--model' in run.stderr
+    # --method bnf is what it was: the bilateral filter's own results, its own banner
+    bnf = str(tmp_path / 'bnf')
+    run = _run(['denoise', '--method', 'bnf', '--data_dir', data, '--out_dir', bnf])
+    assert run.returncode == 0 and sorted(os.listdir(bnf)) == ['ball2_n1-20.obj', 'ball_n1-20.obj']
+    assert 'Bilateral normal filter, normal_iters:20, sigma_r:0.35, sigma_s:1, 2 files' in run.stdout
+    check(run, bnf, filters.bilateral_denoise, 20)
+    # without --method the command is what it was: the network (random init), NAME-60.obj
+    plain = str(tmp_path / 'plain')
+    run = _run(['denoise', '--data_dir', data, '--out_dir', plain])
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert sorted(os.listdir(plain)) == ['ball2_n1-60.obj', 'ball_n1-60.obj'] and 'random init' in run.stdout
