@@ -6,6 +6,8 @@
   python -m geobi_gnn_amd denoise --method gnf --data_dir DIR [the same flags]
   python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
+  python -m geobi_gnn_amd clean --data_dir DIR [--out_dir DIR/clean] [--weld_tol 0] [--no_weld] [--no_manifold]
+  python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -15,7 +17,13 @@ gnf` is the guided normal filter, the model-free method for high noise, through 
 data_util.eval_denoising_result (code/data_util.py:559-638).  `train` is code/train_dual.py:100-298 (trainer.py): DIR holds
 train/ and test/, each with original/ and noisy/; the best model, the options, the log, TensorBoard event files and the
 denoised test meshes go to --out_dir.  `noise` has no counterpart in the reference (its dataset is a download): it writes
-DIR/noisy/NAME_n<k>.obj for every DIR/original/NAME.obj, the layout `train` and `denoise` read.  All device work runs in this one process.
+DIR/noisy/NAME_n<k>.obj for every DIR/original/NAME.obj, the layout `train` and `denoise` read.  `clean` (meshclean.py)
+repairs files that are no clean triangle meshes -- welds vertices, drops degenerate faces and faces that would give a
+directed edge a second owner, drops unused vertices -- which openmesh does for the reference while it reads a file; with
+DIR/original present the cleaning is computed from original/NAME.obj and the SAME maps are applied to every
+noisy/NAME_n*.obj of equal size (welding noisy coordinates would be wrong: duplicates carry independent noise).  `denoise
+--clean` cleans every file before it is denoised and writes the result in the file's own numbering.  All device work runs
+in this one process.
 """
 import argparse
 import glob
@@ -95,6 +103,9 @@ def denoise(opt):
         def run(points, faces, gt_points):
             return patches.predict_mesh(net, points, faces, sub_size=opt.sub_size, n_iter=n_iter,
                                         data_type=opt.data_type, gt_points=gt_points, distributed=False)
+    clean = getattr(opt, 'clean', False)
+    if clean:
+        from . import meshclean
     done, failed = [], 0
     for noisy_file, gt_file in jobs:
         t0 = time.time()
@@ -102,7 +113,7 @@ def denoise(opt):
             points, faces = meshio.read_obj(noisy_file)
             if faces.shape[0] == 0:
                 raise ValueError('%s: no faces' % noisy_file)
-            loose = meshio.unreferenced_vertices(points.shape[0], faces)
+            loose = 0 if clean else meshio.unreferenced_vertices(points.shape[0], faces)
             if loose:
                 raise ValueError('%s: %d of %d vertices are referenced by no face (the vertex update averages over a '
                                  "vertex's faces)" % (noisy_file, loose, points.shape[0]))
@@ -113,18 +124,33 @@ def denoise(opt):
                     raise ValueError('%s (V = %d, F = %d) and its ground truth %s (V = %d, F = %d) differ in size'
                                      % (noisy_file, points.shape[0], faces.shape[0], gt_file, gt_points.shape[0],
                                         gt_faces.shape[0]))
-            with torch.no_grad():
-                r = run(points, faces, gt_points)
+            if clean:
+                # the cleaning comes from the file itself; the ground truth follows its maps, the result goes back to the
+                # file's numbering and faces (welded duplicates share one position, unused vertices keep theirs)
+                cleaned = meshclean.clean_mesh(points, faces, weld_tol=_weld_tol(opt), manifold=not opt.no_manifold, device=dev)
+                n_faces = cleaned.faces.shape[0]
+                if n_faces == 0:
+                    raise ValueError('%s: no faces left after cleaning' % noisy_file)
+                if gt_points is not None:
+                    gt_points = meshclean.apply(cleaned, gt_points)
+                with torch.no_grad():
+                    r = run(cleaned.points.cpu().numpy(), cleaned.faces.cpu().numpy(), gt_points)
+                updated = meshclean.scatter_back(cleaned, r['V_updated'].to(dev), torch.from_numpy(points).to(dev))
+            else:
+                n_faces = faces.shape[0]
+                with torch.no_grad():
+                    r = run(points, faces, gt_points)
+                updated = r['V_updated']
             rst_file = os.path.join(out_dir, '%s-%d.obj' % (os.path.basename(noisy_file)[:-4], n_iter))
-            meshio.write_obj(rst_file, r['V_updated'].cpu().numpy(), faces)
+            meshio.write_obj(rst_file, updated.cpu().numpy(), faces)
         except (ValueError, OSError, GeobiError) as e:
             failed += 1
             print('skipped: %s' % e, file=sys.stderr, flush=True)
             continue
         angle1, angle2 = (r['angle1'], r['angle2']) if gt_file is not None else (0.0, 0.0)
-        done.append((faces.shape[0], angle1, angle2))
+        done.append((n_faces, angle1, angle2))
         print("angle1: %9.6f,  angle2: %9.6f,  faces: %6d,  time: %7.4f s,  '%s'"
-              % (angle1, angle2, faces.shape[0], time.time() - t0, os.path.basename(rst_file)), flush=True)
+              % (angle1, angle2, n_faces, time.time() - t0, os.path.basename(rst_file)), flush=True)
     if done:
         err = np.asarray(done, dtype=np.float64).T
         count = err[0].sum()
@@ -192,11 +218,101 @@ def noise(opt):
     return 1 if failed or not originals else 0
 
 
+def _weld_tol(opt):
+    return None if opt.no_weld else opt.weld_tol
+
+
+def _clean_line(cleaned, V, F, out_file):
+    c = cleaned.counts
+    return ("V: %7d -> %7d,  F: %7d -> %7d,  welded: %d,  degenerate: %d,  nonmanifold: %d,  unreferenced: %d,  rounds: %d,  '%s'"
+            % (V, cleaned.points.shape[0], F, cleaned.faces.shape[0], c['welded'], c['degenerate'], c['nonmanifold'],
+               c['unreferenced'], c['rounds'], os.path.basename(out_file)))
+
+
+def clean(opt):
+    """Repair every mesh of a folder on the device (meshclean): with DIR/original, original/NAME.obj -> OUT/original/NAME.obj
+    and the same maps on every noisy/NAME_n*.obj of the same size -> OUT/noisy/; else DIR/*.obj -> OUT/NAME.obj."""
+    from . import meshclean, meshio
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'clean')
+    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
+    paired = os.path.isdir(original_dir)
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
+    out_original = os.path.join(out_dir, 'original') if paired else out_dir
+    os.makedirs(out_original, exist_ok=True)
+    if paired:
+        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
+    weld_tol = _weld_tol(opt)
+    print('\nClean, weld %s, half-edge rule %s, %d files ...\n'
+          % ('off' if weld_tol is None else ('exact' if weld_tol == 0 else 'grid %g' % weld_tol),
+             'off' if opt.no_manifold else 'on', len(files)), flush=True)
+    failed = 0
+    for path in files:
+        name = os.path.basename(path)[:-4]
+        try:
+            points, faces = meshio.read_obj(path)
+            cleaned = meshclean.clean_mesh(points, faces, weld_tol=weld_tol, manifold=not opt.no_manifold, device=dev)
+            if cleaned.faces.shape[0] == 0:
+                raise ValueError('%s: no faces left after cleaning' % path)
+            faces_out = cleaned.faces.cpu().numpy()
+            out_file = os.path.join(out_original, name + '.obj')
+            meshio.write_obj(out_file, cleaned.points.cpu().numpy(), faces_out)
+            print(_clean_line(cleaned, points.shape[0], faces.shape[0], out_file), flush=True)
+            if not paired:
+                continue
+            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
+                try:
+                    n_points, n_faces = meshio.read_obj(noisy)
+                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
+                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
+                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
+                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
+                    meshio.write_obj(out_file, meshclean.apply(cleaned, n_points), faces_out)
+                    print(_clean_line(cleaned, points.shape[0], faces.shape[0], out_file), flush=True)
+                except (ValueError, OSError) as e:
+                    failed += 1
+                    print('skipped: %s' % e, file=sys.stderr, flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d files skipped' % failed, file=sys.stderr)
+    return 1 if failed or not files else 0
+
+
 def train(opt):
     from . import trainer
     trainer.require_single_process()              # before the device is touched
     trainer.require_known_losses(opt)
     return trainer.train(opt, _device(opt.gpu), predict=denoise)
+
+
+def _weld_tol_arg(text):
+    v = float(text)
+    if not (v >= 0.0 and v < float('inf')):
+        raise argparse.ArgumentTypeError('--weld_tol is 0 (equal coordinates) or a positive cell size, not %r' % text)
+    return v
+
+
+class _TrueGiven(argparse.Action):
+    """store_true, and note in <dest>_given that the flag was on the command line"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, True)
+        setattr(namespace, self.dest + '_given', True)
+
+
+def _add_clean_flags(p, given=False):
+    p.add_argument('--weld_tol', type=_weld_tol_arg, default=0.0, action=_StoreGiven if given else 'store',
+                   help='0: weld vertices with equal coordinates (default); > 0: weld the vertices of one grid cell of this '
+                        'side (a snap to a grid, not an epsilon-merge)')
+    p.add_argument('--no_weld', action=_TrueGiven, help='keep every vertex apart')
+    p.add_argument('--no_manifold', action=_TrueGiven, help='keep faces that give a directed edge a second owner')
 
 
 def build_parser():
@@ -220,6 +336,10 @@ def build_parser():
     d.add_argument('--force_depth', action='store_true')
     d.add_argument('--pool_type', type=str, default='max', choices=['max', 'mean'])
     d.add_argument('--gpu', type=int, default=-1, help='device index (default: the current device)')
+    d.add_argument('--clean', action='store_true',
+                   help='repair every file first (meshclean: weld, degenerate and non-manifold faces, unused vertices); the '
+                        "result keeps the file's numbering and faces")
+    _add_clean_flags(d, given=True)
     d.set_defaults(fn=denoise)
     e = sub.add_parser('eval', help='score result meshes against their originals, write ErrorInfo_h.txt')
     e.add_argument('--result_dir', type=str, required=True)
@@ -239,6 +359,12 @@ def build_parser():
     n.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/noisy')
     n.add_argument('--gpu', type=int, default=-1)
     n.set_defaults(fn=noise)
+    c = sub.add_parser('clean', help='weld vertices, drop degenerate / non-manifold faces and unused vertices, on the device')
+    c.add_argument('--data_dir', type=str, required=True, help='holds original/ (and noisy/), or the OBJ files themselves')
+    c.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/clean')
+    _add_clean_flags(c)
+    c.add_argument('--gpu', type=int, default=-1)
+    c.set_defaults(fn=clean)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)
@@ -254,6 +380,10 @@ def parse_args(argv=None):
             ap.error('denoise: --model cannot be combined with --method %s (the filter has no model)' % opt.method)
         if opt.method in ('bnf', 'gnf') and (opt.normal_iters < 0 or not opt.sigma_r > 0 or not opt.sigma_s > 0 or opt.n_iter < 0):
             ap.error('denoise: --normal_iters and --n_iter are not negative, --sigma_r and --sigma_s positive')
+        if not opt.clean:
+            for flag in ('weld_tol', 'no_weld', 'no_manifold'):
+                if getattr(opt, flag + '_given', False):
+                    ap.error('denoise: --%s needs --clean' % flag)
     return opt
 
 

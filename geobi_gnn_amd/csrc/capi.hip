@@ -720,6 +720,38 @@ int geobi_submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t 
   return submesh(fv, sel, n_sel, V, v_idx, f_sub, count, ws, ws_bytes, S(stream));
 }
 
+size_t geobi_clean_weld_ws_bytes(int64_t V) { return V < 0 || V > GEOBI_MAX_NODES ? 0 : clean_weld_ws_bytes(V); }
+
+int geobi_clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
+                     size_t ws_bytes, void* stream) {
+  SIZES(V, 0);
+  NOTNULL(points); NOTNULL(canon); NOTNULL(counts);
+  return clean_weld(points, V, mode, weld_tol, canon, counts, ws, ws_bytes, S(stream));
+}
+
+size_t geobi_clean_faces_ws_bytes(int64_t F) { return F < 0 || F > GEOBI_MAX_NODES ? 0 : clean_faces_ws_bytes(F); }
+
+int geobi_clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
+                      int32_t* faces_canon, int32_t* state, int32_t* rounds, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  NOTNULL(faces); NOTNULL(canon); NOTNULL(faces_canon); NOTNULL(state); NOTNULL(rounds);
+  return clean_faces(faces, canon, F, V, manifold, max_rounds, faces_canon, state, rounds, ws, ws_bytes, S(stream));
+}
+
+size_t geobi_clean_compact_ws_bytes(int64_t V, int64_t F) {
+  return V < 0 || F < 0 || V > GEOBI_MAX_NODES || F > GEOBI_MAX_NODES ? 0 : clean_compact_ws_bytes(V, F);
+}
+
+int geobi_clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon,
+                        int64_t V, int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map,
+                        int32_t* vertex_src, int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  NOTNULL(points); NOTNULL(faces_canon); NOTNULL(state); NOTNULL(canon); NOTNULL(points_out); NOTNULL(faces_out);
+  NOTNULL(vertex_map); NOTNULL(vertex_src); NOTNULL(face_map); NOTNULL(counts);
+  return clean_compact(points, faces_canon, state, canon, V, F, points_out, faces_out, vertex_map, vertex_src, face_map,
+                       counts, ws, ws_bytes, S(stream));
+}
+
 int geobi_patch_accumulate(const float* vert_p, const float* norm_p, const int32_t* v_idx, const int32_t* f_idx,
                            int64_t nv, int64_t nf, float* Vp, float* Np, int32_t* sum_v, void* stream) {
   SIZES(nv > nf ? nv : nf, 0);

@@ -383,6 +383,17 @@ size_t gnf_filter_ws_bytes(int64_t F, int64_t E);
 int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
                int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out, void* ws,
                size_t ws_bytes, hipStream_t s);
+// clean.hip (mesh repair: weld, degenerate faces, one owner per directed half-edge, compaction)
+size_t clean_weld_ws_bytes(int64_t V);
+int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
+               size_t ws_bytes, hipStream_t s);
+size_t clean_faces_ws_bytes(int64_t F);
+int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
+                int32_t* faces_canon, int32_t* state, int32_t* rounds, void* ws, size_t ws_bytes, hipStream_t s);
+size_t clean_compact_ws_bytes(int64_t V, int64_t F);
+int clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon, int64_t V,
+                  int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map, int32_t* vertex_src,
+                  int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

@@ -1,0 +1,149 @@
+"""Mesh repair on the MI355X: weld vertices, drop bad faces, compact -- the step in front of
+``meshprep`` for files that are not clean triangle meshes (scanner output, STL-derived triangle soups, CAD exports).
+
+The reference reads OBJ through openmesh, whose ``read_trimesh`` refuses a face that is degenerate, duplicated or would
+give a directed edge a second owner (code/test_dual.py:30, code/dataset.py:197); ``meshio.read_obj``
+keeps every face.  ``clean_mesh`` applies that rule, after a weld openmesh does not have:
+
+* **weld**: ``canon[v]`` = the lowest index among the vertices with v's key.  ``weld_tol=0.0``: the three float32 bit
+  patterns (-0.0 as +0.0); ``weld_tol > 0``: the int32 triple ``floorf(x / weld_tol)``, i.e. cells of side weld_tol --
+  this SNAPS TO A GRID, it is no epsilon-merge: two points closer than weld_tol can lie in two cells and stay apart;
+  ``weld_tol=None``: no welding
+* **degenerate faces** (two equal corners after welding) are dropped
+* **half-edge rule** (``manifold=True``): walking the faces in ascending index, a face is kept iff none of its directed
+  half-edges a->b, b->c, c->a is owned by a kept earlier face.  A second copy of a face is dropped, the same triangle
+  with the opposite orientation is kept, a dropped face owns nothing.  openmesh's complex-VERTEX ("bow-tie") rule is not
+  replicated
+* **compaction**: kept faces and used vertices keep their relative order; a welded group keeps the coordinates of its
+  lowest-index member (not a mean)
+
+Everything is integer-exact (geobi_clean_* in csrc/clean.hip).  No CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+
+class CleanResult(object):
+    """points [V', 3] float32, faces [F', 3] int32 (cleaned numbering), vertex_map [V] (new index of canon[v], or -1),
+    vertex_src [V'] (input index of every cleaned vertex), face_map [F'] (input index of every kept face), canon [V];
+    counts: welded, degenerate, nonmanifold, unreferenced, rounds."""
+
+    def __init__(self, points, faces, vertex_map, vertex_src, face_map, canon, counts):
+        self.points, self.faces = points, faces
+        self.vertex_map, self.vertex_src, self.face_map, self.canon = vertex_map, vertex_src, face_map, canon
+        self.counts = counts
+
+
+def _index(a, like):
+    """the index array ``a`` in the form that indexes ``like``: an int64 tensor on its device, or an int64 numpy array"""
+    if torch.is_tensor(like):
+        return torch.as_tensor(a).to(like.device).long()
+    return (a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.int64)
+
+
+def apply(result, points_in):
+    """Another position array of the INPUT's numbering [V, 3] (the paired noisy or ground-truth points) -> the cleaned
+    numbering [V', 3]: the row of every cleaned vertex's canonical input vertex.  Tensors or numpy arrays."""
+    if points_in.shape[0] != result.vertex_map.shape[0]:
+        raise ValueError('apply: %d rows for a cleaning of %d vertices' % (points_in.shape[0], result.vertex_map.shape[0]))
+    return points_in[_index(result.vertex_src, points_in)]
+
+
+def scatter_back(result, points_clean, points_in):
+    """Positions of the cleaned numbering [V', 3] -> the input's numbering [V, 3]: a row with vertex_map >= 0 takes
+    points_clean[vertex_map] (all members of a weld group share it), the rest keep points_in bit for bit."""
+    vm = _index(result.vertex_map, points_in)
+    if points_in.shape[0] != vm.shape[0] or points_clean.shape[0] != result.vertex_src.shape[0]:
+        raise ValueError('scatter_back: %d clean and %d input rows for a cleaning of %d -> %d vertices'
+                         % (points_clean.shape[0], points_in.shape[0], vm.shape[0], result.vertex_src.shape[0]))
+    out = points_in.clone() if torch.is_tensor(points_in) else np.array(points_in, copy=True)
+    hit = vm >= 0
+    out[hit] = points_clean[vm[hit]]
+    return out
+
+
+def _empty(n, width, dtype, dev):
+    shape = (max(n, 1),) if width == 0 else (max(n, 1), width)
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
+def weld(pts, weld_tol):
+    """Stage 1 on validated device points [V, 3]: -> (canon [max(V, 1)] int32, device counts [2] = groups, overflow flag);
+    enqueued, nothing is read back."""
+    dev, V = pts.device, pts.shape[0]
+    canon = _empty(V, 0, torch.int32, dev)
+    wcounts = torch.zeros(2, dtype=torch.int32, device=dev)
+    mode = 0 if weld_tol is None else (1 if float(weld_tol) == 0.0 else 2)
+    ws = L.workspace(L.size_query('geobi_clean_weld_ws_bytes', V), dev)
+    L.call('geobi_clean_weld', L.ptr(pts if V else _empty(0, 3, torch.float32, dev)), V, mode, float(weld_tol or 0.0),
+           L.ptr(canon), L.ptr(wcounts), L.ptr(ws), ws.numel(), L.stream())
+    return canon, wcounts
+
+
+def resolve_faces(fv, canon, V, manifold=True, max_rounds=1024):
+    """Stage 2 on range-checked device faces [F, 3] int32 of a mesh of V vertices: -> (faces through canon [max(F, 1), 3], state [max(F, 1)]: 1 kept,
+    2 dropped by the half-edge rule, 3 degenerate; rounds).  Waits for the device once per batch of rounds."""
+    dev, F = fv.device, fv.shape[0]
+    fc = _empty(F, 3, torch.int32, dev)
+    state = _empty(F, 0, torch.int32, dev)
+    rounds = (ctypes.c_int32 * 1)()
+    ws = L.workspace(L.size_query('geobi_clean_faces_ws_bytes', F), dev)
+    L.call('geobi_clean_faces', L.ptr(fv if F else fc), L.ptr(canon), F, int(V), 1 if manifold else 0, int(max_rounds),
+           L.ptr(fc), L.ptr(state), rounds, L.ptr(ws), ws.numel(), L.stream())
+    return fc, state, int(rounds[0])
+
+
+def compact(pts, fc, state, canon, F):
+    """Stage 3 (F: the number of faces, fc / state have at least one row): -> (points, faces, vertex_map, vertex_src, face_map) with room for V / F rows and the device counts [5] =
+    V', F', degenerate, nonmanifold, unreferenced; enqueued, nothing is read back."""
+    dev, V, F = pts.device, pts.shape[0], int(F)
+    p_out, f_out = _empty(V, 3, torch.float32, dev), _empty(F, 3, torch.int32, dev)
+    vmap, vsrc, fmap = _empty(V, 0, torch.int32, dev), _empty(V, 0, torch.int32, dev), _empty(F, 0, torch.int32, dev)
+    counts = torch.zeros(5, dtype=torch.int32, device=dev)
+    ws = L.workspace(L.size_query('geobi_clean_compact_ws_bytes', V, F), dev)
+    L.call('geobi_clean_compact', L.ptr(pts if V else p_out), L.ptr(fc), L.ptr(state), L.ptr(canon), V, F, L.ptr(p_out),
+           L.ptr(f_out), L.ptr(vmap), L.ptr(vsrc), L.ptr(fmap), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
+    return p_out, f_out, vmap, vsrc, fmap, counts
+
+
+def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, device=None):
+    """(points [V, 3], faces [F, 3]) -> CleanResult, on the device.  ValueError: non-finite points, a face index outside
+    [0, V), weld_tol < 0, max_rounds < 1.  GeobiError: the library's errors -- a grid quotient outside int32, more than
+    ``max_rounds`` rounds of the half-edge rule (a chain of faces that each share a directed edge with the next takes one
+    round per face)."""
+    if not torch.cuda.is_available():
+        raise L.GeobiError('meshclean.clean_mesh runs on the MI355X only (no CPU fallback)')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if weld_tol is not None and not float(weld_tol) >= 0.0:
+        raise ValueError('clean_mesh: weld_tol = %r (None, 0 or a positive cell size)' % (weld_tol,))
+    if weld_tol is not None and not np.isfinite(np.float32(weld_tol)):
+        raise ValueError('clean_mesh: weld_tol = %r is not a finite float32' % (weld_tol,))
+    if int(max_rounds) < 1:
+        raise ValueError('clean_mesh: max_rounds = %r (at least 1)' % (max_rounds,))
+    pts = torch.as_tensor(np.asarray(points) if not torch.is_tensor(points) else points)
+    pts = pts.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    fv = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces).reshape(-1, 3)
+    V, F = pts.shape[0], fv.shape[0]
+    # range-checked in the dtype it came in (an int64 id must not wrap into range), BEFORE any kernel walks it
+    if F > 0:
+        lo, hi = (int(t) for t in torch.aminmax(fv))
+        if lo < 0 or hi >= V:
+            raise ValueError('clean_mesh: faces index vertices outside [0, %d)' % V)
+    fv = fv.to(device=dev, dtype=torch.int32).contiguous()
+    if V > 0 and not bool(torch.isfinite(pts).all()):
+        raise ValueError('clean_mesh: non-finite point coordinates')
+    with torch.cuda.device(dev):
+        canon, wcounts = weld(pts, weld_tol)
+        groups, bad = L.read_i32(wcounts)
+        if bad:
+            raise L.GeobiError('clean_mesh: a coordinate divided by weld_tol = %g is outside the int32 range' % weld_tol)
+        fc, state, rounds = resolve_faces(fv, canon, V, manifold, max_rounds)
+        p_out, f_out, vmap, vsrc, fmap, counts = compact(pts, fc, state, canon, F)
+        v_new, f_new, degenerate, nonmanifold, unreferenced = L.read_i32(counts)
+    return CleanResult(p_out[:v_new], f_out[:f_new], vmap[:V], vsrc[:v_new], fmap[:f_new], canon[:V],
+                       {'welded': V - groups, 'degenerate': degenerate, 'nonmanifold': nonmanifold,
+                        'unreferenced': unreferenced, 'rounds': rounds})

@@ -4,7 +4,8 @@ with openmesh (om.read_trimesh / om.write_mesh, code/test_dual.py:30,73, code/da
 Vertex order and face order are the file's: the network's outputs are indexed by them.
 
 Known difference: openmesh's read_trimesh drops a face that would make an edge non-manifold (and a degenerate or
-duplicate one); this reader keeps every face the file lists.
+duplicate one); this reader keeps every face the file lists.  meshclean.clean_mesh applies that rule (and welds vertices)
+on the device: the `clean` command, `denoise --clean`.
 """
 import math
 

@@ -10,7 +10,8 @@
  *   - every pointer is a BORROWED device pointer (HBM) unless marked `host`; the library never
  *     allocates, frees or synchronises: scratch comes in through `ws` / `ws_bytes` (query the size
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
- *     Two documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), the whole-network
+ *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
+ *     (reads its undecided counts through it), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -528,6 +529,44 @@ int geobi_patch_accumulate(const float* vert_p, const float* norm_p, const int32
                            int64_t nv, int64_t nf, float* Vp, float* Np, int32_t* sum_v, void* stream);
 int geobi_patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, int64_t F, float scale, float cx,
                          float cy, float cz, void* stream);
+
+/* ---------------------------------------------------------------- mesh repair (weld, bad faces, compaction) ----
+ * What openmesh's read_trimesh does to a file while it reads it (code/test_dual.py:30, code/dataset.py:197) and this
+ * project's reader does not: a degenerate face, a second face on a directed edge ("complex edge") is refused.  Plus what
+ * a triangle soup needs first: vertices with equal keys become one.  Integer-exact; nothing depends on launch geometry.
+ * V, F <= GEOBI_MAX_NODES; points finite; faces index [0, V) (range-check them first: a corner outside it only makes its
+ * face degenerate here, it is not reported).
+ *   geobi_clean_weld     canon[v] = the LOWEST index among the vertices with v's key.  mode 0: no welding, canon[v] = v;
+ *                        1: key = the three float32 bit patterns, -0.0 as +0.0; 2: key = the int32 triple
+ *                        floorf(x / weld_tol) -- cells of side weld_tol, a SNAP TO A GRID and no epsilon-merge (two points
+ *                        closer than weld_tol may fall into two cells), plain correctly rounded division.
+ *                        counts (device int32 [2]): [0] = number of groups, [1] != 0: a quotient left the int32 range
+ *                        (canon is then not to be used).  Three stable 32-bit radix passes over (key, index).
+ *   geobi_clean_faces    faces_canon [F, 3] = the corners through canon; state [F]: 1 kept, 2 dropped by the half-edge
+ *                        rule, 3 degenerate (two equal corners after welding).  Half-edge rule (manifold != 0), stated
+ *                        sequentially: walk the faces in ascending index; a non-degenerate face (a, b, c) is kept iff none
+ *                        of a->b, b->c, c->a is owned by a kept earlier face; a kept face then owns its three.  Computed
+ *                        in Jacobi rounds over the stably sorted half-edges (48-bit keys a << 24 | b): the result IS the
+ *                        sequential one and *rounds (HOST int32) the same number for the same input, 0 when no face
+ *                        needed a decision (manifold == 0, F == 0, degenerate faces only).  A face that shares a directed
+ *                        edge with k earlier faces reads k states per round.  WAITS for `stream` (geobi_read_i32 on the
+ *                        undecided counts, once per batch of rounds: 4, then 32 at a time); more than max_rounds (>= 1)
+ *                        rounds is an error, never a spin.
+ *   geobi_clean_compact  kept faces in their order with face_map [F'] = their input index; a vertex is used when a kept
+ *                        face lists it (through canon); used vertices in their order with their OWN coordinates
+ *                        (points_out [V', 3]) and vertex_src [V'] = their input index; vertex_map [V] = new index of
+ *                        canon[v] or -1.  Outputs have room for V / F rows.  counts (device int32 [5]) = V', F',
+ *                        degenerate faces, faces dropped by the half-edge rule, vertices with vertex_map == -1.       */
+size_t geobi_clean_weld_ws_bytes(int64_t V);
+int geobi_clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
+                     size_t ws_bytes, void* stream);
+size_t geobi_clean_faces_ws_bytes(int64_t F);
+int geobi_clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
+                      int32_t* faces_canon, int32_t* state, int32_t* rounds, void* ws, size_t ws_bytes, void* stream);
+size_t geobi_clean_compact_ws_bytes(int64_t V, int64_t F);
+int geobi_clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon,
+                        int64_t V, int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map,
+                        int32_t* vertex_src, int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
