@@ -156,6 +156,30 @@ __global__ void ring_graph_kernel(const int* __restrict__ fv, const int* __restr
   if (PASS == 0) cnt[node] = pos;
 }
 
+// |p_i - p_j|^2 and n_i . n_j of an edge, each as ONE fixed sequence of roundings.  Left to the compiler's contraction, "a * b +
+// c * d" fuses whichever product it likes: the single-mesh and the per-part weight kernels came out with different ones for the
+// normal product, and a part's weights were an ulp off the bits the part alone gets.  The sequence is the one the single-mesh
+// kernels always had.
+__device__ __forceinline__ float edge_sq_len(const float* __restrict__ pos, int i, int j) {
+#pragma clang fp contract(off)
+  const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
+  return __builtin_fmaf(dy, dy, dx * dx) + dz * dz;
+}
+
+__device__ __forceinline__ float edge_normal_dot(const float* __restrict__ nrm, int i, int j) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(nrm[3 * i], nrm[3 * j], nrm[3 * i + 1] * nrm[3 * j + 1]) + nrm[3 * i + 2] * nrm[3 * j + 2];
+}
+
+// clamp(n_i . n_j, 1e-3) * exp(|dp|^2 / (-2 mean + 1e-12)): the one statement of a bilateral weight, for both weight kernels
+__device__ __forceinline__ float bilateral_weight(const float* __restrict__ pos, const float* __restrict__ nrm, int i, int j,
+                                                  float mean) {
+  const float den = __builtin_fmaf(-2.0f, mean, 1e-12f);
+  float dn = edge_normal_dot(nrm, i, j);
+  dn = dn > 0.001f ? dn : 0.001f;
+  return dn * expf(edge_sq_len(pos, i, j) / den);
+}
+
 // sum of edge lengths, fixed blocking -> deterministic; double accumulation (block_sum_fp64 / fold_ascending, common.h)
 __global__ __launch_bounds__(256) void edge_length_partial_kernel(const float* __restrict__ pos,
                                                                   const int* __restrict__ row,
@@ -164,8 +188,7 @@ __global__ __launch_bounds__(256) void edge_length_partial_kernel(const float* _
   double s = 0.0;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < E; e += (int64_t)gridDim.x * 256) {
     const int i = row[e], j = col[e];
-    const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
-    s += (double)sqrtf((dx * dx + dy * dy) + dz * dz);
+    s += (double)sqrtf(edge_sq_len(pos, i, j));
   }
   const double sum = block_sum_fp64<256>(s);
   if (threadIdx.x == 0) partial[blockIdx.x] = sum;
@@ -184,15 +207,9 @@ __global__ void calc_weight_kernel(const float* __restrict__ pos, const float* _
                                    const int* __restrict__ row, const int* __restrict__ col, int64_t E,
                                    const double* __restrict__ partial, int64_t denom, float* __restrict__ w) {
   const float mean = mean_from_partials(partial, denom);
-  const float den = -2.0f * mean + 1e-12f;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
-  const int i = row[e], j = col[e];
-  const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
-  const float len2 = (dx * dx + dy * dy) + dz * dz;
-  float dn = (nrm[3 * i] * nrm[3 * j] + nrm[3 * i + 1] * nrm[3 * j + 1]) + nrm[3 * i + 2] * nrm[3 * j + 2];
-  dn = dn > 0.001f ? dn : 0.001f;
-  w[e] = dn * expf(len2 / den);
+  w[e] = bilateral_weight(pos, nrm, row[e], col[e], mean);
 }
 
 // The same two kernels over a disjoint union of meshes ("parts": node ranges node_ptr[p] .. node_ptr[p+1], whose edges are
@@ -210,8 +227,7 @@ __global__ __launch_bounds__(256) void edge_length_partial_parts_kernel(const fl
   for (int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x; el < E; el += (int64_t)gridDim.x * 256) {
     const int64_t e = e0 + el;
     const int i = row[e], j = col[e];
-    const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
-    s += (double)sqrtf((dx * dx + dy * dy) + dz * dz);
+    s += (double)sqrtf(edge_sq_len(pos, i, j));
   }
   const double sum = block_sum_fp64<256>(s);
   if (threadIdx.x == 0) partial[(size_t)part * kPartials + blockIdx.x] = sum;
@@ -229,12 +245,7 @@ __global__ void calc_weight_parts_kernel(const float* __restrict__ pos, const fl
   const int a = node_ptr[part], b = node_ptr[part + 1];
   const int64_t denom = ((int64_t)rowptr[b] - rowptr[a]) + (b - a);        // the part's edges + one zero-length loop per node
   const float mean = mean_from_partials(partial + (size_t)part * kPartials, denom);
-  const float den = -2.0f * mean + 1e-12f;
-  const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
-  const float len2 = (dx * dx + dy * dy) + dz * dz;
-  float dn = (nrm[3 * i] * nrm[3 * j] + nrm[3 * i + 1] * nrm[3 * j + 1]) + nrm[3 * i + 2] * nrm[3 * j + 2];
-  dn = dn > 0.001f ? dn : 0.001f;
-  w[e] = dn * expf(len2 / den);
+  w[e] = bilateral_weight(pos, nrm, i, j, mean);
 }
 
 }  // namespace
