@@ -4,12 +4,14 @@
 * ``face_centroids``        the centroids the reference's driver would hand to ``loss_n(..., 'sided', fc_p, fc)``
 * ``update_position2``      /root/reference/code/data_util.py:529-556 (called at test_dual.py:63-72 right
   after the network; the reference moves the prediction to the CPU for it -- here it stays on the GPU)
+* ``denoise_tail``          what follows every denoise, the network's or a filter's (test_dual.py:63-87): that vertex
+  update and the two angular errors, with ``depth_direction``, the rule for the Kinect data types
 Same names and argument meaning; tensors must live on the MI355X.
 """
 import torch
 
 from . import _lib as L
-from . import ops
+from . import meshin, network, ops
 
 
 def computer_face_normal(points, fv_indices):
@@ -34,11 +36,8 @@ def face_centroids(points, fv_indices):
     if cache is not None and cache[2] == points.shape[0]:
         fv32 = cache[0]
     else:
+        meshin.check_faces(fv_indices, points.shape[0], 'fv_indices')     # the kernel gathers through it
         fv32 = fv_indices.to(torch.int32).contiguous()
-        if fv32.numel():                                  # the kernel gathers through it: range-checked first
-            lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(fv32)]))
-            if lo < 0 or hi >= points.shape[0]:
-                raise L.GeobiError('fv_indices index vertices outside [0, %d)' % points.shape[0])
     xf = torch.zeros((fv32.shape[0], 6), dtype=torch.float32, device=points.device)
     out = torch.empty((fv32.shape[0], 12), dtype=torch.float32, device=points.device)
     L.call('geobi_face_geom_fwd', L.ptr(points.detach().float().contiguous()), L.ptr(fv32), L.ptr(xf), 6, fv32.shape[0],
@@ -62,3 +61,37 @@ def update_position2(points, fv_indices, vf_indices, face_normals, n_iter=20, de
     L.call('geobi_update_position2', L.ptr(pts), L.ptr(fv32), L.ptr(vf32), vf32.shape[1], L.ptr(nrm), L.ptr(dd), V, F,
            int(n_iter), L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
     return out
+
+
+def depth_direction(points, data_type):
+    """The Kinect data types move a vertex along its viewing ray only (code/test_dual.py:69-71): -> normalize(points) for
+    them, None for every other type.  points: [N,3], or a list of such (the meshes of a union; joined only when needed)."""
+    if data_type not in ('Kinect_v1', 'Kinect_v2'):
+        return None
+    if not torch.is_tensor(points):
+        points = points[0] if len(points) == 1 else torch.cat(list(points))
+    return torch.nn.functional.normalize(points, dim=1)
+
+
+def angular_errors(normals, points_updated, fv_indices, gt_points=None, gt_normals=None):
+    """-> (angle1, angle2), device scalars in degrees: network.error_n of `normals`, and of the normals of the updated
+    mesh, against the ground truth's face normals -- `gt_normals`, else those of `gt_points` (arrays or tensors) on these
+    faces.  (None, None) without ground truth."""
+    if gt_normals is None:
+        if gt_points is None:
+            return None, None
+        gt = meshin.to_device(gt_points, points_updated.device, torch.float32)
+        if gt.shape != points_updated.shape:
+            raise ValueError('gt_points %s for points %s' % (tuple(gt.shape), tuple(points_updated.shape)))
+        gt_normals = computer_face_normal(gt, fv_indices)
+    return (network.error_n(normals, gt_normals),
+            network.error_n(computer_face_normal(points_updated, fv_indices), gt_normals))
+
+
+def denoise_tail(points, fv_indices, vf_indices, normals, n_iter, data_type, gt_points=None, ray_points=None):
+    """What follows every denoise: `n_iter` sweeps of update_position2 moving `points` towards `normals` -- for the Kinect
+    data types along depth_direction(ray_points; default: points) only -- then angular_errors of the result.
+    -> (V_updated, angle1, angle2); the angles stay on the device (a caller reads them when it wants them)."""
+    dd = depth_direction(points if ray_points is None else ray_points, data_type)
+    Vu = update_position2(points, fv_indices, vf_indices, normals, n_iter=n_iter, depth_direction=dd)
+    return (Vu,) + angular_errors(normals, Vu, fv_indices, gt_points)

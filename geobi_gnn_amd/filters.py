@@ -31,11 +31,11 @@ different faces that share at least 2 distinct vertex ids, every sweep makes fro
 The patch search costs sum_k |P_k|^2 normal comparisons per sweep; a call whose sum x sweeps exceeds GNF_COST_BUDGET is
 refused before the first kernel of the filter runs.
 """
-import numpy as np
 import torch
 
 from . import _lib as L
-from . import meshprep
+from . import meshin, meshprep
+from .data_util import denoise_tail
 
 
 # Normal comparisons (sum_k |P_k|^2 x sweeps) one guided call may ask for: about one second of gnf_measure_kernel at the
@@ -52,25 +52,11 @@ def _check_params(normal_iters, sigma_r, sigma_s):
             raise ValueError('%s = %r: positive and finite' % (name, v))
 
 
-def _device_mesh(points, faces, device):
-    """-> (points fp32 [V,3], faces int32 [F,3]) on the device, the face table range-checked before any kernel walks it."""
-    if not torch.cuda.is_available():
-        raise L.GeobiError('filters: the bilateral normal filter runs on the MI355X only (no CPU fallback)')
-    if device is None:
-        device = points.device if torch.is_tensor(points) and points.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    dev = torch.device(device)
-    pts = torch.as_tensor(np.asarray(points) if not torch.is_tensor(points) else points)
-    pts = pts.to(device=dev, dtype=torch.float32).contiguous()
-    fv = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces).to(device=dev, dtype=torch.int32)
-    fv = fv.contiguous()
-    if pts.dim() != 2 or pts.shape[1] != 3 or fv.dim() != 2 or fv.shape[1] != 3:
-        raise ValueError('points [V,3] and faces [F,3] expected, got %s and %s' % (tuple(pts.shape), tuple(fv.shape)))
-    V, F = pts.shape[0], fv.shape[0]
-    if F == 0:
+def _nonempty_mesh(points, faces, device):
+    """meshin.device_mesh; the filters refuse a mesh without faces."""
+    pts, fv = meshin.device_mesh(points, faces, device)
+    if fv.shape[0] == 0:
         raise ValueError('the mesh has no faces')
-    lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(fv)]))
-    if lo < 0 or hi >= V:
-        raise L.GeobiError('faces index vertices outside [0, %d)' % V)
     return pts, fv
 
 
@@ -89,12 +75,7 @@ def spatial_scale(points, fv, graph, sigma_s):
     edges; 0 when there is no edge (or no distance).  No host read."""
     if graph.E == 0:
         return torch.zeros(1, dtype=torch.float32, device=points.device)
-    F = fv.shape[0]
-    fn = torch.empty((F, 3), dtype=torch.float32, device=points.device)
-    cen = torch.empty((F, 3), dtype=torch.float32, device=points.device)
-    L.call('geobi_mesh_normals', L.ptr(points), L.ptr(fv), F, points.shape[0], None, None, L.ptr(fn), L.ptr(cen), None,
-           L.stream())
-    s = meshprep.mean_edge_length(cen, graph) * float(sigma_s)
+    s = meshprep.mean_edge_length(meshprep.face_normals_centroids(points, fv)[1], graph) * float(sigma_s)
     return torch.where(s > 0, 0.5 / (s * s), torch.zeros_like(s))
 
 
@@ -122,7 +103,7 @@ def bilateral_normals(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0,
     incidence: (rowptr, list) of meshprep.vertex_faces for these faces, if the caller has it already.
     normal_iters = 0 returns the start normals."""
     _check_params(normal_iters, sigma_r, sigma_s)
-    pts, fv = _device_mesh(points, faces, None)
+    pts, fv = _nonempty_mesh(points, faces, None)
     with torch.cuda.device(pts.device):
         return _bilateral_normals(pts, fv, normal_iters, sigma_r, sigma_s, incidence)
 
@@ -138,28 +119,18 @@ def bilateral_denoise(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0,
 
 
 def _denoise(normals_fn, points, faces, normal_iters, sigma_r, sigma_s, n_iter, data_type, gt_points, device):
-    from . import network
-    from .data_util import computer_face_normal, update_position2
     _check_params(normal_iters, sigma_r, sigma_s)
     if int(n_iter) != n_iter or n_iter < 0:
         raise ValueError('n_iter = %r: a whole number of sweeps, not negative' % (n_iter,))
-    pts, fv = _device_mesh(points, faces, device)
+    pts, fv = _nonempty_mesh(points, faces, device)
     with torch.cuda.device(pts.device):
         V = pts.shape[0]
         rowptr, lst = meshprep.vertex_faces(fv, V)
         Np = normals_fn(pts, fv, normal_iters, sigma_r, sigma_s, (rowptr, lst))
-        dd = torch.nn.functional.normalize(pts, dim=1) if data_type in ('Kinect_v1', 'Kinect_v2') else None
         vf = meshprep.vf_padded32(rowptr, lst, V)
-        Vu = update_position2(pts, fv, vf, Np, n_iter=int(n_iter), depth_direction=dd)
-        out = {'Np': Np, 'V_updated': Vu, 'angle1': None, 'angle2': None}
-        if gt_points is not None:
-            gt = torch.as_tensor(np.asarray(gt_points) if not torch.is_tensor(gt_points) else gt_points)
-            gt = gt.to(device=pts.device, dtype=torch.float32).contiguous()
-            if gt.shape != pts.shape:
-                raise ValueError('gt_points %s for points %s' % (tuple(gt.shape), tuple(pts.shape)))
-            Nt = computer_face_normal(gt, fv)
-            out['angle1'] = float(network.error_n(Np, Nt))
-            out['angle2'] = float(network.error_n(computer_face_normal(Vu, fv), Nt))
+        Vu, angle1, angle2 = denoise_tail(pts, fv, vf, Np, int(n_iter), data_type, gt_points)
+        out = {'Np': Np, 'V_updated': Vu, 'angle1': None if angle1 is None else float(angle1),
+               'angle2': None if angle2 is None else float(angle2)}
     return out
 
 
@@ -228,7 +199,7 @@ def guided_normals(points, faces, normal_iters=20, sigma_r=0.35, sigma_s=1.0, in
     normal_iters = 0 returns the start normals.  return_selection: -> (normals, int32 [normal_iters, F]: the patch every
     face took its guidance from, per sweep)."""
     _check_params(normal_iters, sigma_r, sigma_s)
-    pts, fv = _device_mesh(points, faces, None)
+    pts, fv = _nonempty_mesh(points, faces, None)
     with torch.cuda.device(pts.device):
         return _guided_normals(pts, fv, normal_iters, sigma_r, sigma_s, incidence, return_selection)
 

@@ -3,8 +3,7 @@ without the OBJ file IO: network forward under no_grad, de-normalisation, 60-swe
 device, and the two angular errors the reference prints."""
 import torch
 
-from . import network
-from .data_util import computer_face_normal, update_position2
+from .data_util import angular_errors, update_position2
 
 
 def predict_one_submesh(net, dual_data):
@@ -24,8 +23,6 @@ def predict_one(net, data_v, data_f, centroid, scale, vf_indices, n_iter=60, gt_
     Vp = Vp / scale + centroid.to(Vp.device)
     dd = getattr(data_v, 'depth_direction', None) if net.force_depth else None
     Vu = update_position2(Vp, data_f.fv_indices, vf_indices.to(Vp.device), Np, n_iter=n_iter, depth_direction=dd)
-    out = {'Vp': Vp, 'Np': Np, 'V_updated': Vu, 'angle1': None, 'angle2': None}
-    if gt_normals is not None:
-        out['angle1'] = float(network.error_n(Np, gt_normals))
-        out['angle2'] = float(network.error_n(computer_face_normal(Vu, data_f.fv_indices), gt_normals))
-    return out
+    angle1, angle2 = angular_errors(Np, Vu, data_f.fv_indices, gt_normals=gt_normals)
+    return {'Vp': Vp, 'Np': Np, 'V_updated': Vu, 'angle1': None if angle1 is None else float(angle1),
+            'angle2': None if angle2 is None else float(angle2)}

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import meshin
 
 
 class CleanResult(object):
@@ -115,25 +116,17 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
     [0, V), weld_tol < 0, max_rounds < 1.  GeobiError: the library's errors -- a grid quotient outside int32, more than
     ``max_rounds`` rounds of the half-edge rule (a chain of faces that each share a directed edge with the next takes one
     round per face)."""
-    if not torch.cuda.is_available():
-        raise L.GeobiError('meshclean.clean_mesh runs on the MI355X only (no CPU fallback)')
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = meshin.default_device(device)
     if weld_tol is not None and not float(weld_tol) >= 0.0:
         raise ValueError('clean_mesh: weld_tol = %r (None, 0 or a positive cell size)' % (weld_tol,))
     if weld_tol is not None and not np.isfinite(np.float32(weld_tol)):
         raise ValueError('clean_mesh: weld_tol = %r is not a finite float32' % (weld_tol,))
     if int(max_rounds) < 1:
         raise ValueError('clean_mesh: max_rounds = %r (at least 1)' % (max_rounds,))
-    pts = torch.as_tensor(np.asarray(points) if not torch.is_tensor(points) else points)
-    pts = pts.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    fv = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces).reshape(-1, 3)
+    # the face table is range-checked as it came in (an int64 id must not wrap into range), BEFORE any kernel walks it
+    pts, fv = meshin.device_mesh(meshin.as_tensor(points).reshape(-1, 3), meshin.as_tensor(faces).reshape(-1, 3), dev,
+                                 what='clean_mesh: faces', error=ValueError)
     V, F = pts.shape[0], fv.shape[0]
-    # range-checked in the dtype it came in (an int64 id must not wrap into range), BEFORE any kernel walks it
-    if F > 0:
-        lo, hi = (int(t) for t in torch.aminmax(fv))
-        if lo < 0 or hi >= V:
-            raise ValueError('clean_mesh: faces index vertices outside [0, %d)' % V)
-    fv = fv.to(device=dev, dtype=torch.int32).contiguous()
     if V > 0 and not bool(torch.isfinite(pts).all()):
         raise ValueError('clean_mesh: non-finite point coordinates')
     with torch.cuda.device(dev):

@@ -9,11 +9,10 @@ reduced in fp64 on the device (geobi_dist_summary), and one read brings a pair's
 import glob
 import os
 
-import numpy as np
 import torch
 
 from . import _lib as L
-from . import meshio, meshprep, network
+from . import meshin, meshio, meshprep, network
 from .data_util import computer_face_normal
 
 
@@ -48,13 +47,11 @@ def point_to_mesh(points, verts, faces):
     closest triangle, interior, edge or corner -> (dist float32 [Q], face int32 [Q])."""
     p, v = _points(points, 'query points'), _points(verts, 'mesh vertices')
     L.require_device(faces, 'faces')
+    Q, V, F = p.shape[0], v.shape[0], faces.shape[0]
+    if Q == 0 or V == 0 or F == 0 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise L.GeobiError('point_to_mesh: empty query set or mesh (Q = %d, V = %d, faces %s)' % (Q, V, tuple(faces.shape)))
+    meshin.check_faces(faces, V)                             # range-checked before a kernel walks it
     fv = faces.to(torch.int32).contiguous()
-    Q, V, F = p.shape[0], v.shape[0], fv.shape[0]
-    if Q == 0 or V == 0 or F == 0 or fv.dim() != 2 or fv.shape[1] != 3:
-        raise L.GeobiError('point_to_mesh: empty query set or mesh (Q = %d, V = %d, faces %s)' % (Q, V, tuple(fv.shape)))
-    lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(fv)]))    # range-checked before a kernel walks it
-    if lo < 0 or hi >= V:
-        raise L.GeobiError('faces index vertices outside [0, %d)' % V)
     dist = torch.empty(Q, dtype=torch.float32, device=p.device)
     face = torch.empty(Q, dtype=torch.int32, device=p.device)
     ws = _nearest_ws(Q, F, p.device)
@@ -75,11 +72,6 @@ def dist_summary(dist):
     return out
 
 
-def _to_dev(a, dev, dtype):
-    t = torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)
-    return t.to(device=dev, dtype=dtype).contiguous()
-
-
 def mean_edge_length(points, faces):
     """Mean length of the mesh edges, each undirected edge once (code/data_util.py:595-597) -> device float [1].
     The vertex graph lists every edge in both directions, so its mean is the same number."""
@@ -90,7 +82,7 @@ def mean_edge_length(points, faces):
 
 def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None):
     """The numbers of one (result, ground truth) pair, code/data_util.py:584-616.  Arrays or tensors; the work runs on
-    `device` (default: the tensors' device, else cuda:0).  gt_faces defaults to `faces` (a denoised mesh keeps its
+    `device` (default: the tensors' device, else the current one).  gt_faces defaults to `faces` (a denoised mesh keeps its
     connectivity).  Returns a dict:
 
       num_f, err_face (mean |n_r - n_o|^2), angle (mean angle in degrees, network.error_n), num_v,
@@ -98,22 +90,17 @@ def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None):
       mean edge length)                                                   -- the reference's six
       surf, surf_norm (mean distance to the ground-truth SURFACE, raw and over `scale`),
       hausdorff (the larger of the two directed maxima of nearest-vertex distance), scale."""
-    if device is None:
-        device = result_points.device if torch.is_tensor(result_points) and result_points.is_cuda else torch.device('cuda:0')
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise L.GeobiError('eval_pair runs on the MI355X only (no CPU fallback), got device %s' % dev)
-    pr, po = _to_dev(result_points, dev, torch.float32), _to_dev(gt_points, dev, torch.float32)
-    fr = _to_dev(faces, dev, torch.int32)
-    fo = fr if gt_faces is None else _to_dev(gt_faces, dev, torch.int32)
+    dev = meshin.default_device(device, result_points)
+    pr, po = meshin.to_device(result_points, dev, torch.float32), meshin.to_device(gt_points, dev, torch.float32)
+    fr = meshin.as_tensor(faces)
+    fo = fr if gt_faces is None or gt_faces is faces else meshin.as_tensor(gt_faces)
     if pr.shape != po.shape or fr.shape != fo.shape:
         raise ValueError('result (V = %d, F = %d) and ground truth (V = %d, F = %d) differ in size'
                          % (pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]))
+    same = fo is fr                                          # one table, also when handed in twice: one check
+    fr = meshin.device_mesh(pr, fr, dev)[1]
+    fo = fr if same else meshin.device_mesh(po, fo, dev)[1]
     V, F = pr.shape[0], fr.shape[0]
-    for f in ((fr,) if fo is fr else (fr, fo)):
-        lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(f)]))
-        if lo < 0 or hi >= V:
-            raise L.GeobiError('faces index vertices outside [0, %d)' % V)
     nr, no = computer_face_normal(pr, fr), computer_face_normal(po, fo)
     err_face = network.loss_n(nr, no, 'L2')
     angle = network.error_n(nr, no)

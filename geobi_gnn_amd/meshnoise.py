@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import meshprep
+from . import meshin, meshprep
 
 KINDS = ('gaussian', 'impulsive')
 DIRECTIONS = ('normal', 'random')
@@ -86,19 +86,8 @@ class MeshGeometry(object):
     vertex -> face incidence, the vertex normals and the mean edge length ``L`` (device scalar and host float)."""
 
     def __init__(self, points, faces, device=None):
-        if not torch.cuda.is_available():
-            raise L.GeobiError('meshnoise draws on the MI355X only (no CPU fallback)')
-        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        pts = torch.as_tensor(np.asarray(points) if not torch.is_tensor(points) else points)
-        self.points = pts.to(device=dev, dtype=torch.float32).contiguous()
-        if self.points.dim() != 2 or self.points.shape[1] != 3:
-            raise ValueError('points must be [V, 3]')
-        self.faces = meshprep._dev_i32(faces, dev)
-        V, F = self.points.shape[0], self.faces.shape[0]
-        if F > 0:         # as build_dual_data: checked BEFORE any kernel walks the table
-            lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(self.faces)]))
-            if lo < 0 or hi >= V:
-                raise L.GeobiError('faces index vertices outside [0, %d)' % V)
+        self.points, self.faces = meshin.device_mesh(points, faces, meshin.default_device(device))
+        V = self.points.shape[0]
         self.incidence = meshprep.vertex_faces(self.faces, V)
         self.graph_v = meshprep.ring_graph(0, self.faces, self.incidence[0], self.incidence[1], V)
         self.vnormal = meshprep.mesh_normals(self.points, self.faces, self.incidence[0], self.incidence[1])[2]

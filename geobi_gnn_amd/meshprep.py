@@ -15,17 +15,13 @@ The graphs are emitted directly as the (row, col)-sorted, loop-free CSR the conv
 ``reference_layout=True`` to get the reference's exact tensors instead (vertex graph: sorted pairs then
 V appended self loops; facet graph: self loops inline; loop weights as calc_weight gives them).
 """
-import numpy as np
 import torch
 
 from . import _lib as L
+from . import meshin
 from .data import Data
+from .data_util import depth_direction
 from .graph import Graph, attach
-
-
-def _dev_i32(a, device):
-    t = torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)
-    return t.to(device=device, dtype=torch.int32).contiguous()
 
 
 def vertex_faces(faces, num_vertices):
@@ -40,15 +36,24 @@ def vertex_faces(faces, num_vertices):
     return rowptr, lst[:3 * F]
 
 
-def vf_padded32(rowptr, lst, num_vertices):
-    """openmesh ``vf_indices`` as int32: [V, max_valence], -1 padded (what the device ring growth walks)."""
-    dev = rowptr.device
-    m = torch.zeros(1, dtype=torch.int32, device=dev)
+def max_valence(rowptr, num_vertices):
+    """The largest valence as a device word [1] (enqueued): the width of the padded vf table, once it is read."""
+    m = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
     L.call('geobi_max_degree', L.ptr(rowptr), int(num_vertices), L.ptr(m), L.stream())
-    maxval = max(L.read_i32(m, 1)[0], 1)
-    vf = torch.empty((int(num_vertices), maxval), dtype=torch.int32, device=dev)
+    return m
+
+
+def vf_padded32_fill(rowptr, lst, num_vertices, maxval):
+    """The padded table for the width read from max_valence (at least one column)."""
+    maxval = max(maxval, 1)
+    vf = torch.empty((int(num_vertices), maxval), dtype=torch.int32, device=rowptr.device)
     L.call('geobi_vf_padded', L.ptr(rowptr), L.ptr(lst), int(num_vertices), maxval, L.ptr(vf), L.stream())
     return vf
+
+
+def vf_padded32(rowptr, lst, num_vertices):
+    """openmesh ``vf_indices`` as int32: [V, max_valence], -1 padded (what the device ring growth walks)."""
+    return vf_padded32_fill(rowptr, lst, num_vertices, L.read_i32(max_valence(rowptr, num_vertices), 1)[0])
 
 
 def vf_padded(rowptr, lst, num_vertices):
@@ -68,15 +73,29 @@ def mesh_normals(points, faces, rowptr, lst):
     return fn, cen, vn
 
 
-def ring_graph(kind, faces, rowptr, lst, num_nodes):
-    """kind 0: vertex graph, 1: facet graph -> loop-free symmetric ``Graph`` ((row, col)-sorted CSR)."""
-    dev = faces.device
+def face_normals_centroids(points, faces):
+    """mesh_normals without the incidence (so without vertex normals) -> (face normals [F,3], face centroids [F,3])."""
+    F = faces.shape[0]
+    fn = torch.empty((F, 3), dtype=torch.float32, device=points.device)
+    cen = torch.empty((F, 3), dtype=torch.float32, device=points.device)
+    L.call('geobi_mesh_normals', L.ptr(points), L.ptr(faces), F, points.shape[0], None, None, L.ptr(fn), L.ptr(cen), None,
+           L.stream())
+    return fn, cen
+
+
+def ring_graph_count(kind, faces, rowptr, lst, num_nodes):
+    """ring_graph's first step, enqueued: the graph's row pointer [n+1]; its last word is the edge count."""
     n = int(num_nodes)
-    rp = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    ws = L.workspace(L.size_query('geobi_ring_graph_ws_bytes', n), dev)
+    rp = torch.empty(n + 1, dtype=torch.int32, device=faces.device)
+    ws = L.workspace(L.size_query('geobi_ring_graph_ws_bytes', n), faces.device)
     L.call('geobi_ring_graph_count', kind, L.ptr(faces), L.ptr(rowptr), L.ptr(lst), n, L.ptr(rp), L.ptr(ws),
            ws.numel(), L.stream())
-    E = L.read_i32(rp[n:n + 1], 1)[0]                       # one host read per graph (sizes the column array)
+    return rp
+
+
+def ring_graph_fill(kind, faces, rowptr, lst, rp, E):
+    """ring_graph's second step: the columns of the E edges counted in ``rp`` -> ``Graph``."""
+    dev, n = faces.device, rp.numel() - 1
     col = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
     if E > 0:         # a graph without edges (the facet graph of a one-face patch: found by tools/fuzz_mesh.py) has nothing to fill
         L.call('geobi_ring_graph_fill', kind, L.ptr(faces), L.ptr(rowptr), L.ptr(lst), n, L.ptr(rp), L.ptr(col),
@@ -85,6 +104,13 @@ def ring_graph(kind, faces, rowptr, lst, num_nodes):
     g.rowptr_out, g.col_out, g.E = rp, col, E
     g.symmetric = True                                      # sharing a face / a vertex is a symmetric relation
     return g
+
+
+def ring_graph(kind, faces, rowptr, lst, num_nodes):
+    """kind 0: vertex graph, 1: facet graph -> loop-free symmetric ``Graph`` ((row, col)-sorted CSR)."""
+    rp = ring_graph_count(kind, faces, rowptr, lst, num_nodes)
+    E = L.read_i32(rp[-1:], 1)[0]                           # one host read per graph (sizes the column array)
+    return ring_graph_fill(kind, faces, rowptr, lst, rp, E)
 
 
 def calc_weight(pos, normal, graph, extra_zero_edges=None, want_mean=False):
@@ -139,6 +165,27 @@ def calc_weight_parts(pos, normal, graph, node_ptr):
     return w
 
 
+def _normalisation(pts, g_v, centroid, scale, points_gt, host_scale):
+    """center_and_scale, s_type 0, as build_dual_data and refresh_dual_data share it: centroid = mean vertex [1,3] and
+    scale = 1 / mean mesh-edge length, unless given; host_scale: the computed scale as a host float (one read), else it
+    stays a device [1] tensor.  -> (centroid, scale, ground-truth points on the device, those normalised); None, None
+    without points_gt."""
+    if centroid is None:
+        cen = pts.mean(0, keepdim=True)
+    else:
+        cen = torch.as_tensor(centroid, dtype=torch.float32).reshape(1, 3).to(pts.device)
+    if scale is not None:
+        sc = float(scale)
+    else:
+        sc = 1.0 / mean_edge_length(pts, g_v)
+        if host_scale:
+            sc = float(sc.item())
+    if points_gt is None:
+        return cen, sc, None, None
+    pg = meshin.to_device(points_gt, pts.device, torch.float32)
+    return cen, sc, pg, (pg - cen) * sc
+
+
 def build_dual_data(points_noisy, faces, points_gt=None, name='mesh', data_type='Synthetic', device=None,
                     reference_layout=False, centroid=None, scale=None, trusted_faces=False, want_vf=True, parts=None):
     """(points [V,3], faces [F,3]) -> (data_v, data_f) as process_one_submesh + post_processing emit them,
@@ -150,56 +197,21 @@ def build_dual_data(points_noisy, faces, points_gt=None, name='mesh', data_type=
     parts: (vertex_ptr, face_ptr) host int lists when the input is a DISJOINT UNION of meshes (the patches of one network
     pass, vertices / faces of part k in [ptr[k], ptr[k+1])): one preprocessing for all of them -- every step is local to a
     connected component except the bilateral weights' mean edge length, which is taken per part; ``mesh_ptr`` is set."""
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    if not torch.cuda.is_available():
-        raise L.GeobiError('meshprep.build_dual_data runs on the MI355X only (no CPU fallback); '
-                           'meshgen.build_dual_data is the host-side generator')
-    pts = torch.as_tensor(np.asarray(points_noisy) if not torch.is_tensor(points_noisy) else points_noisy)
-    pts = pts.to(device=dev, dtype=torch.float32).contiguous()
-    fv = _dev_i32(faces, dev)
-    V, F = pts.shape[0], fv.shape[0]
-
     # A face table from outside is range-checked BEFORE any kernel walks it (a bad vertex id is a faulting gather); one
     # produced by this library (a patch of geobi_submesh) is not.
-    if not trusted_faces and F > 0:
-        lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(fv)]))
-        if lo < 0 or hi >= V:
-            raise L.GeobiError('faces index vertices outside [0, %d)' % V)
+    pts, fv = meshin.device_mesh(points_noisy, faces, meshin.default_device(device), check=not trusted_faces)
+    dev, V, F = pts.device, pts.shape[0], fv.shape[0]
     # Everything else whose size the host must know before it can allocate comes back in ONE read: both graphs' edge
     # counts and the largest valence (width of the padded vf table).  Until round 4 these were separate reads.
     rowptr_vf, lst = vertex_faces(fv, V)
-    rp_v = torch.empty(V + 1, dtype=torch.int32, device=dev)
-    rp_f = torch.empty(F + 1, dtype=torch.int32, device=dev)
-    for kind, n, rp in ((0, V, rp_v), (1, F, rp_f)):
-        ws = L.workspace(L.size_query('geobi_ring_graph_ws_bytes', n), dev)
-        L.call('geobi_ring_graph_count', kind, L.ptr(fv), L.ptr(rowptr_vf), L.ptr(lst), n, L.ptr(rp), L.ptr(ws), ws.numel(),
-               L.stream())
-    size_words = [rp_v[V:V + 1], rp_f[F:F + 1]]
-    if want_vf:
-        m = torch.zeros(1, dtype=torch.int32, device=dev)
-        L.call('geobi_max_degree', L.ptr(rowptr_vf), V, L.ptr(m), L.stream())
-        size_words.append(m)
+    rp_v = ring_graph_count(0, fv, rowptr_vf, lst, V)
+    rp_f = ring_graph_count(1, fv, rowptr_vf, lst, F)
+    size_words = [rp_v[-1:], rp_f[-1:]] + ([max_valence(rowptr_vf, V)] if want_vf else [])
     sizes = L.read_i32(torch.cat(size_words))
-    E_v, E_f = sizes[0], sizes[1]
-
-    def finish_graph(kind, n, rp, E):
-        col = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        if E > 0:     # (a one-face patch has a facet graph without edges)
-            L.call('geobi_ring_graph_fill', kind, L.ptr(fv), L.ptr(rowptr_vf), L.ptr(lst), n, L.ptr(rp), L.ptr(col), L.stream())
-        g = Graph(n, dev)
-        g.rowptr_out, g.col_out, g.E = rp, col, E
-        g.symmetric = True                                  # sharing a face / a vertex is a symmetric relation
-        return g
     fn, pos_f, vn = mesh_normals(pts, fv, rowptr_vf, lst)
-    g_v = finish_graph(0, V, rp_v, E_v)
-    g_f = finish_graph(1, F, rp_f, E_f)
-
-    # center_and_scale, s_type 0: centroid = mean vertex, scale = 1 / mean mesh-edge length
-    if centroid is None:
-        cen = pts.mean(0, keepdim=True)
-    else:
-        cen = torch.as_tensor(centroid, dtype=torch.float32).reshape(1, 3).to(dev)
-    sc = float((1.0 / mean_edge_length(pts, g_v)).item()) if scale is None else float(scale)
+    g_v = ring_graph_fill(0, fv, rowptr_vf, lst, rp_v, sizes[0])
+    g_f = ring_graph_fill(1, fv, rowptr_vf, lst, rp_f, sizes[1])
+    cen, sc, pg, y = _normalisation(pts, g_v, centroid, scale, points_gt, host_scale=True)
 
     if parts is None:
         ew_v = calc_weight(pts, vn, g_v)
@@ -222,23 +234,10 @@ def build_dual_data(points_noisy, faces, points_gt=None, name='mesh', data_type=
     else:
         data_v.set_graph(g_v); data_v.edge_weight = ew_v
         data_f.set_graph(g_f); data_f.edge_weight = ew_f
-    data_v.depth_direction = None
-    if data_type in ('Kinect_v1', 'Kinect_v2'):
-        data_v.depth_direction = torch.nn.functional.normalize(pts, dim=1)
-    if points_gt is not None:
-        pg = torch.as_tensor(np.asarray(points_gt) if not torch.is_tensor(points_gt) else points_gt)
-        pg = pg.to(device=dev, dtype=torch.float32).contiguous()
-        data_v.y = (pg - cen) * sc
-        gt_fn = torch.empty((F, 3), dtype=torch.float32, device=dev)
-        gt_c = torch.empty((F, 3), dtype=torch.float32, device=dev)
-        L.call('geobi_mesh_normals', L.ptr(pg), L.ptr(fv), F, V, None, None, L.ptr(gt_fn), L.ptr(gt_c), None, L.stream())
-        data_f.y = gt_fn
-    vf = None
-    if want_vf:
-        maxval = max(sizes[2], 1)
-        vf = torch.empty((V, maxval), dtype=torch.int32, device=dev)
-        L.call('geobi_vf_padded', L.ptr(rowptr_vf), L.ptr(lst), V, maxval, L.ptr(vf), L.stream())
-        vf = vf.long()
+    data_v.depth_direction = depth_direction(pts, data_type)
+    if pg is not None:
+        data_v.y, data_f.y = y, face_normals_centroids(pg, fv)[0]
+    vf = vf_padded32_fill(rowptr_vf, lst, V, sizes[2]).long() if want_vf else None
     data_v.meta = {'centroid': cen, 'scale': sc, 'vf_indices': vf, 'incidence': (rowptr_vf, lst)}
     if parts is not None:
         data_v.mesh_ptr = torch.tensor(list(parts[0]), dtype=torch.long)
@@ -259,9 +258,7 @@ def refresh_dual_data(data_v, data_f, points_noisy, points_gt, data_type='Synthe
     g_v, g_f = data_v.graph(), data_f.graph()
     if g_v.eid_out is not None or g_f.eid_out is not None:
         raise L.GeobiError('refresh_dual_data: a pair in the reference layout (COO with self loops) is rebuilt, not refreshed')
-    dev = g_v.device
-    pts = torch.as_tensor(np.asarray(points_noisy) if not torch.is_tensor(points_noisy) else points_noisy)
-    pts = pts.to(device=dev, dtype=torch.float32).contiguous()
+    pts = meshin.to_device(points_noisy, g_v.device, torch.float32)
     cache = getattr(data_f.fv_indices, '_geobi_fv', None)
     V = g_v.N
     if cache is None or cache[2] != V:
@@ -274,28 +271,15 @@ def refresh_dual_data(data_v, data_f, points_noisy, points_gt, data_type='Synthe
         incidence = meta['incidence'] if isinstance(meta, dict) and meta.get('incidence') is not None else vertex_faces(fv, V)
     rowptr_vf, lst = incidence
     fn, pos_f, vn = mesh_normals(pts, fv, rowptr_vf, lst)
-    if centroid is None:
-        cen = pts.mean(0, keepdim=True)
-    else:
-        cen = torch.as_tensor(centroid, dtype=torch.float32).reshape(1, 3).to(dev)
-    if scale is not None:
-        sc = float(scale)
-    else:
-        sc = 1.0 / mean_edge_length(pts, g_v)           # float32 [1]: the value build_dual_data reads back, used in place
-        if isinstance(meta, dict):
-            sc = float(sc.item())
+    cen, sc, _, y = _normalisation(pts, g_v, centroid, scale, points_gt, host_scale=isinstance(meta, dict))
     ew_v = calc_weight(pts, vn, g_v)
     ew_f = calc_weight(pos_f, fn, g_f)
     data_v.x = torch.cat(((pts - cen) * sc, vn), 1)
     data_f.x = torch.cat(((pos_f - cen) * sc, fn), 1)
     data_v.edge_weight, data_f.edge_weight = ew_v, ew_f
-    data_v.depth_direction = None
-    if data_type in ('Kinect_v1', 'Kinect_v2'):
-        data_v.depth_direction = torch.nn.functional.normalize(pts, dim=1)
-    if points_gt is not None:
-        pg = torch.as_tensor(np.asarray(points_gt) if not torch.is_tensor(points_gt) else points_gt)
-        pg = pg.to(device=dev, dtype=torch.float32).contiguous()
-        data_v.y = (pg - cen) * sc
+    data_v.depth_direction = depth_direction(pts, data_type)
+    if y is not None:
+        data_v.y = y
     if isinstance(meta, dict):
         meta['centroid'], meta['scale'] = cen, sc
     return data_v, data_f

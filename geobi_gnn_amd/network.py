@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from . import executor, ops
+from . import executor, meshin, ops
 from .feast_conv import FeaStConv
 from .net_util import PoolingLayer
 
@@ -83,11 +83,8 @@ def _fv_index(data_f, num_vertices):
     fv = data_f.fv_indices
     cache = getattr(fv, '_geobi_fv', None)
     if cache is None or cache[2] != num_vertices:
+        meshin.check_faces(fv, num_vertices, 'fv_indices')      # once per mesh (cached): a bad id would be a faulting gather
         fv32 = fv.to(torch.int32).contiguous()
-        if fv32.numel():        # once per mesh (cached): a bad vertex id would be a faulting gather later
-            lo, hi = torch.aminmax(fv32)
-            if int(lo) < 0 or int(hi) >= num_vertices:
-                raise L.GeobiError('fv_indices index vertices outside [0, %d)' % num_vertices)
         mark_face_table(fv, fv32, num_vertices)
         cache = fv._geobi_fv
     return cache[0], cache[1]

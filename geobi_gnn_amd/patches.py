@@ -14,12 +14,11 @@ openmesh run (whole rings do not depend on the order).
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib as L
-from . import meshprep, network
-from .data_util import computer_face_normal, update_position2
+from . import meshin, meshprep
+from .data_util import angular_errors, denoise_tail
 from .infer import predict_one_submesh
 
 
@@ -219,17 +218,9 @@ def predict_mesh(net, points, faces, sub_size=20000, n_iter=60, data_type='Synth
     from . import parallel
     rank, world = parallel.rank_world() if distributed is None or distributed else (0, 1)
     dev = next(net.parameters()).device
-    pts = torch.as_tensor(np.asarray(points) if not torch.is_tensor(points) else points)
-    pts = pts.to(device=dev, dtype=torch.float32).contiguous()
-    fv = torch.as_tensor(np.asarray(faces) if not torch.is_tensor(faces) else faces).to(device=dev, dtype=torch.int32)
-    fv = fv.contiguous()
+    pts, fv = meshin.device_mesh(points, faces, dev)       # the caller's face table: range-checked before any kernel walks it
     V, F = pts.shape[0], fv.shape[0]
     ph = _Phases(stats)
-    if F > 0:                          # the caller's face table: range-checked before any kernel walks it
-        lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(fv)]))
-        if lo < 0 or hi >= V:
-            raise L.GeobiError('faces index vertices outside [0, %d)' % V)
-    vf = None
     if F <= sub_size:
         n_patches = 1
         if rank != 0:                  # one patch: nothing to share out
@@ -287,17 +278,9 @@ def predict_mesh(net, points, faces, sub_size=20000, n_iter=60, data_type='Synth
                         'angle2': None}
         L.call('geobi_patch_finalize', L.ptr(Vp), L.ptr(Np), L.ptr(sum_v), V, F, scale, c[0], c[1], c[2], L.stream())
 
-    dd = torch.nn.functional.normalize(pts, dim=1) if data_type in ('Kinect_v1', 'Kinect_v2') else None
-    if vf is None:
-        vf = meshprep.vf_padded(rowptr, lst, V)
-    Vu = update_position2(Vp, fv, vf, Np, n_iter=n_iter, depth_direction=dd)
-    out = {'Vp': Vp, 'Np': Np, 'V_updated': Vu, 'n_patches': n_patches, 'angle1': None, 'angle2': None}
-    if gt_points is not None:
-        gt = torch.as_tensor(np.asarray(gt_points) if not torch.is_tensor(gt_points) else gt_points)
-        gt = gt.to(device=dev, dtype=torch.float32).contiguous()
-        Nt = computer_face_normal(gt, fv)
-        out['angle1'] = float(network.error_n(Np, Nt))
-        out['angle2'] = float(network.error_n(computer_face_normal(Vu, fv), Nt))
+    Vu, angle1, angle2 = denoise_tail(Vp, fv, vf, Np, n_iter, data_type, gt_points, ray_points=pts)
+    out = {'Vp': Vp, 'Np': Np, 'V_updated': Vu, 'n_patches': n_patches,
+           'angle1': None if angle1 is None else float(angle1), 'angle2': None if angle2 is None else float(angle2)}
     ph.tick('merge+update')
     return out
 
@@ -444,17 +427,11 @@ def _predict_split_group(net, jobs, results, sub_size, n_iter, data_type, patch_
             for j, v0, f0 in zip(live, vptr, fptr):
                 w = int(j.vf32.shape[1])
                 vf_u[v0:v0 + j.V, :w] = torch.where(j.vf32 >= 0, j.vf32 + f0, j.vf32)
-        dd = None
-        if data_type in ('Kinect_v1', 'Kinect_v2'):
-            dd = torch.nn.functional.normalize(torch.cat([j.pts for j in live]), dim=1)
-        Vu = update_position2(Vp_u, fv_u, vf_u, Np_u, n_iter=n_iter, depth_direction=dd)
+        Vu = denoise_tail(Vp_u, fv_u, vf_u, Np_u, n_iter, data_type, ray_points=[j.pts for j in live])[0]
         for j, v0, f0 in zip(live, vptr, fptr):
-            out = {'Vp': j.Vp, 'Np': j.Np, 'V_updated': Vu[v0:v0 + j.V], 'n_patches': j.n_patches, 'angle1': None, 'angle2': None}
-            if j.gt is not None:
-                g_ = torch.as_tensor(np.asarray(j.gt) if not torch.is_tensor(j.gt) else j.gt).to(device=dev, dtype=torch.float32).contiguous()
-                Nt = computer_face_normal(g_, j.fv)
-                out['angle1'] = network.error_n(j.Np, Nt)                 # device scalars: predict_batch reads them all at once
-                out['angle2'] = network.error_n(computer_face_normal(out['V_updated'], j.fv), Nt)
+            out = {'Vp': j.Vp, 'Np': j.Np, 'V_updated': Vu[v0:v0 + j.V], 'n_patches': j.n_patches}
+            # device scalars: predict_batch reads them all at once
+            out['angle1'], out['angle2'] = angular_errors(j.Np, out['V_updated'], j.fv, j.gt)
             results[j.index] = out
     finally:
         for j in jobs:                        # nothing of a chain may still be running when its buffers and the mailbox go back
@@ -499,7 +476,7 @@ def predict_batch(net, meshes, max_faces=100000, sub_size=20000, n_iter=60, data
             meta = d[0].meta
             Vp[v0:v1] = Vp[v0:v1] / meta['scale'] + meta['centroid']
         if len(group) == 1:
-            fv_u, vf_u, pts_u = group[0][2], group[0][3][0].meta['vf_indices'], group[0][1]
+            fv_u, vf_u = group[0][2], group[0][3][0].meta['vf_indices']
         else:
             from .data import _Concat
             cc = _Concat(dev)
@@ -507,35 +484,25 @@ def predict_batch(net, meshes, max_faces=100000, sub_size=20000, n_iter=60, data
             cc.run()
             rowptr, lst = meshprep.vertex_faces(fv_u, Vp.shape[0])
             vf_u = meshprep.vf_padded32(rowptr, lst, Vp.shape[0])
-            pts_u = None
-        dd = None
-        if data_type in ('Kinect_v1', 'Kinect_v2'):
-            dd = torch.nn.functional.normalize(torch.cat([g[1] for g in group]) if pts_u is None else pts_u, dim=1)
-        Vu = update_position2(Vp, fv_u, vf_u, Np, n_iter=n_iter, depth_direction=dd)
+        Vu = denoise_tail(Vp, fv_u, vf_u, Np, n_iter, data_type, ray_points=[g[1] for g in group])[0]
         for (i, pts, fv, d, gt), (v0, v1), (f0, f1) in zip(group, vr, fr):
-            out = {'Vp': Vp[v0:v1], 'Np': Np[f0:f1], 'V_updated': Vu[v0:v1], 'n_patches': 1, 'angle1': None, 'angle2': None}
-            if gt is not None:
-                g_ = torch.as_tensor(np.asarray(gt) if not torch.is_tensor(gt) else gt).to(device=dev, dtype=torch.float32).contiguous()
-                Nt = computer_face_normal(g_, fv)
-                out['angle1'] = network.error_n(out['Np'], Nt)            # device scalars, read all at once at the end
-                out['angle2'] = network.error_n(computer_face_normal(out['V_updated'], fv), Nt)
+            out = {'Vp': Vp[v0:v1], 'Np': Np[f0:f1], 'V_updated': Vu[v0:v1], 'n_patches': 1}
+            # device scalars, read all at once at the end
+            out['angle1'], out['angle2'] = angular_errors(out['Np'], out['V_updated'], fv, gt)
             results[i] = out
         del group[:]
 
     for i, m in enumerate(meshes):
         gt = m[2] if len(m) > 2 else None
-        pts = torch.as_tensor(np.asarray(m[0]) if not torch.is_tensor(m[0]) else m[0]).to(device=dev, dtype=torch.float32).contiguous()
-        fv = torch.as_tensor(np.asarray(m[1]) if not torch.is_tensor(m[1]) else m[1]).to(device=dev, dtype=torch.int32).contiguous()
-        F = fv.shape[0]
-        if F > sub_size or F == 0:              # the group of small meshes stays open: results are placed by index
-            if F == 0 or int(split_group) <= 1:
-                kw = {} if gt is None else {'gt_points': gt}
-                results[i] = predict_mesh(net, pts, fv, sub_size=sub_size, n_iter=n_iter, data_type=data_type,
-                                          patch_batch=patch_batch, distributed=False, **kw)
-                continue
-            lo, hi = L.read_i32(torch.cat([t.reshape(1) for t in torch.aminmax(fv)]))     # range-checked before any kernel
-            if lo < 0 or hi >= pts.shape[0]:
-                raise L.GeobiError('faces index vertices outside [0, %d)' % pts.shape[0])
+        faces = meshin.as_tensor(m[1])
+        F = faces.shape[0]
+        if F == 0 or (F > sub_size and int(split_group) <= 1):        # the group of small meshes stays open: results are
+            kw = {} if gt is None else {'gt_points': gt}              # placed by index
+            results[i] = predict_mesh(net, m[0], faces, sub_size=sub_size, n_iter=n_iter, data_type=data_type,
+                                      patch_batch=patch_batch, distributed=False, **kw)
+            continue
+        pts, fv = meshin.device_mesh(m[0], faces, dev)     # the caller's face table: range-checked before any kernel
+        if F > sub_size:
             big.append(_SplitJob(i, pts, fv, gt))
             if len(big) >= int(split_group):
                 flush_big()
@@ -543,8 +510,7 @@ def predict_batch(net, meshes, max_faces=100000, sub_size=20000, n_iter=60, data
         if group and faces_in_group + F > max_faces:
             flush()
             faces_in_group = 0
-        # the caller's face table is range-checked inside build_dual_data before any kernel walks it
-        dual = meshprep.build_dual_data(pts, fv, name='mesh', data_type=data_type, device=dev)
+        dual = meshprep.build_dual_data(pts, fv, name='mesh', data_type=data_type, device=dev, trusted_faces=True)
         group.append((i, pts, fv, dual, gt))
         faces_in_group += F
     flush()

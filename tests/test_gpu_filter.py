@@ -18,13 +18,11 @@ import torch
 
 import bnf_model as M
 import geom_model as G
+from filter_cases import (FAN_VALENCES, FANS, SWEEPS, U, _all_degenerate, _angle, _bar, _DeviceMesh, _icosahedron, _one_face,
+                          _opposite, _shifted, _sphere8_with_truth)
 from train_cases import _run
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-SWEEPS = (0, 1, 2, 5)
-FAN_VALENCES = (3, 4, 5, 8, 9, 16, 17, 33, 64, 65, 200)
 
 
 @pytest.fixture(scope='module')
@@ -34,36 +32,10 @@ def dev():
 
 
 # ------------------------------------------------------------------------------------------------ meshes and references
-def _one_face():
-    return G._f32_values([[0.1, 0.2, 0.3], [1.3, 0.1, 0.2], [0.4, 1.1, 0.9]]), torch.tensor([[0, 1, 2]])
-
-
-def _icosahedron():
-    from geobi_gnn_amd import meshgen
-    pts, faces = meshgen.icosphere(1)
-    return G._f32_values(pts), torch.from_numpy(np.asarray(faces, dtype=np.int64))
-
-
-def _all_degenerate():
-    """Collinear points: every face has exactly zero area, the centroids differ."""
-    pts = G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [2.0, 0.0, 0.0], [4.0, 0.0, 0.0]])
-    return pts, torch.tensor([[0, 1, 2], [1, 2, 3], [0, 0, 3]])
-
-
-def _opposite():
-    """One triangle with both orientations: equal areas, one centroid, exactly opposite normals."""
-    return G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), torch.tensor([[0, 1, 2], [0, 2, 1]])
-
-
-def _shifted():
-    pts, faces = G.sphere(8, 0.3, 1)
-    return G._f32_values((pts + torch.tensor([1000.0, -2000.0, 500.0], dtype=torch.float64)).numpy()), faces
-
-
 MESHES = {'one_face': _one_face, 'icosahedron': _icosahedron, 'sphere16': lambda: G.sphere(16, 0.2, 0),
           'sphere8': lambda: G.sphere(8, 0.3, 1), 'degenerate': lambda: G.degenerate_sphere()[:2],
           'all_degenerate': _all_degenerate, 'opposite': _opposite, 'shifted': _shifted}
-MESHES.update({'fan%d' % v: (lambda v_=v: G.fan(v_)) for v in FAN_VALENCES})
+MESHES.update(FANS)
 _CACHE = {}
 
 
@@ -79,22 +51,8 @@ def _case(name, sigma_r=0.35):
     return _CACHE[key]
 
 
-def _bar(d32):
-    return 8 * max(d32, 4 * U)
-
-
-class _Device(object):
+class _Device(_DeviceMesh):
     """The filter's device inputs for one mesh: records, facet graph, the spatial scale."""
-
-    def __init__(self, pts, faces, dev, sigma_s=1.0):
-        from geobi_gnn_amd import filters, meshprep
-        self.filters = filters
-        self.pts = pts.float().to(dev).contiguous()
-        self.fv = faces.to(device=dev, dtype=torch.int32).contiguous()
-        rowptr, lst = meshprep.vertex_faces(self.fv, self.pts.shape[0])
-        self.graph = meshprep.ring_graph(1, self.fv, rowptr, lst, self.fv.shape[0])
-        self.rec_c, self.rec_n = filters.face_records(self.pts, self.fv)
-        self.inv2ss = filters.spatial_scale(self.pts, self.fv, self.graph, sigma_s)
 
     def run(self, n_sweeps, start=None, sigma_r=0.35):
         out = self.filters.filter_records(self.rec_c, self.rec_n if start is None else start, self.graph, self.inv2ss,
@@ -207,16 +165,6 @@ def test_start_normals_and_records(dev):
 
 
 # ------------------------------------------------------------------------------------------------ bilateral_denoise
-def _sphere8_with_truth():
-    from geobi_gnn_amd import meshgen
-    noisy, clean, faces = meshgen.noisy_icosphere(8, 0.3, seed=1)
-    return noisy, clean, np.asarray(faces, dtype=np.int64)
-
-
-def _angle(a, b):
-    return float(G.row_terms(a, b, 3).mean())
-
-
 def test_bilateral_denoise_against_the_model(dev):
     """n = 8, sigma 0.3, defaults: angle1 and angle2 within 0.01 degrees of the model's normals pushed through the fp64
     vertex update; and the filter denoises (below a quarter of the input's angle, the condition checked on the host)."""
@@ -282,6 +230,12 @@ def test_errors(dev):
             fn(noisy, faces, normal_iters=-1)
     with pytest.raises(ValueError, match='n_iter'):
         filters.bilateral_denoise(noisy, faces, n_iter=-1)
+    # an int64 id that the conversion to int32 would wrap into range (2^32 + 1 -> 1) is refused as it arrives
+    p4 = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+    wrap = np.array([[0, 1, 2], [1, 2, 2 ** 32 + 1]], dtype=np.int64)
+    for fn in (filters.bilateral_normals, filters.bilateral_denoise):
+        with pytest.raises(L.GeobiError, match='outside'):
+            fn(p4, wrap)
     # the C entry points enforce the size limits and their own arguments
     d = _Device(*_case('icosahedron')[:2], dev)
     out = torch.empty_like(d.rec_n)

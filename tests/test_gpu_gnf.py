@@ -27,13 +27,11 @@ import torch
 import bnf_model as B
 import geom_model as G
 import gnf_model as M
+from filter_cases import (FAN_VALENCES, FANS, SWEEPS, U, _all_degenerate, _angle, _bar, _DeviceMesh, _icosahedron, _one_face,
+                          _opposite, _shifted, _sphere8_with_truth)
 from train_cases import _run
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-SWEEPS = (0, 1, 2, 5)
-FAN_VALENCES = (3, 4, 5, 8, 9, 16, 17, 33, 64, 65, 200)
 
 
 @pytest.fixture(scope='module')
@@ -43,10 +41,6 @@ def dev():
 
 
 # ------------------------------------------------------------------------------------------------ meshes and references
-def _one_face():
-    return G._f32_values([[0.1, 0.2, 0.3], [1.3, 0.1, 0.2], [0.4, 1.1, 0.9]]), torch.tensor([[0, 1, 2]])
-
-
 def _two_faces():
     return (G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 2.0, 0.0], [0.5, -1.0, 1.0]]),
             torch.tensor([[0, 1, 2], [1, 0, 3]]))
@@ -55,26 +49,6 @@ def _two_faces():
 def _tetrahedron():
     return (G._f32_values([[0.0, 0.0, 0.0], [1.1, 0.1, 0.0], [0.2, 0.9, 0.1], [0.3, 0.2, 1.2]]),
             torch.tensor([[0, 2, 1], [0, 1, 3], [1, 2, 3], [2, 0, 3]]))
-
-
-def _icosahedron():
-    from geobi_gnn_amd import meshgen
-    pts, faces = meshgen.icosphere(1)
-    return G._f32_values(pts), torch.from_numpy(np.asarray(faces, dtype=np.int64))
-
-
-def _all_degenerate():
-    pts = G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [2.0, 0.0, 0.0], [4.0, 0.0, 0.0]])
-    return pts, torch.tensor([[0, 1, 2], [1, 2, 3], [0, 0, 3]])
-
-
-def _opposite():
-    return G._f32_values([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), torch.tensor([[0, 1, 2], [0, 2, 1]])
-
-
-def _shifted():
-    pts, faces = G.sphere(8, 0.3, 1)
-    return G._f32_values((pts + torch.tensor([1000.0, -2000.0, 500.0], dtype=torch.float64)).numpy()), faces
 
 
 def _three_on_an_edge():
@@ -87,7 +61,7 @@ MESHES = {'one_face': _one_face, 'two_faces': _two_faces, 'tetrahedron': _tetrah
           'sphere4': lambda: G.sphere(4, 0.3, 1), 'sphere8': lambda: G.sphere(8, 0.3, 1),
           'degenerate': lambda: G.degenerate_sphere()[:2], 'all_degenerate': _all_degenerate, 'opposite': _opposite,
           'three_on_an_edge': _three_on_an_edge, 'shifted': _shifted}
-MESHES.update({'fan%d' % v: (lambda v_=v: G.fan(v_)) for v in FAN_VALENCES})
+MESHES.update(FANS)
 _CACHE = {}
 
 
@@ -99,23 +73,12 @@ def _case(name):
     return _CACHE[name]
 
 
-def _bar(d32):
-    return 8 * max(d32, 4 * U)
-
-
-class _Device(object):
+class _Device(_DeviceMesh):
     """The filter's device inputs for one mesh: records, facet graph, the spatial scale, the edge-pair flags."""
 
     def __init__(self, pts, faces, dev, sigma_s=1.0):
-        from geobi_gnn_amd import filters, meshprep
-        self.filters = filters
-        self.pts = pts.float().to(dev).contiguous()
-        self.fv = faces.to(device=dev, dtype=torch.int32).contiguous()
-        rowptr, lst = meshprep.vertex_faces(self.fv, self.pts.shape[0])
-        self.graph = meshprep.ring_graph(1, self.fv, rowptr, lst, self.fv.shape[0])
-        self.rec_c, self.rec_n = filters.face_records(self.pts, self.fv)
-        self.inv2ss = filters.spatial_scale(self.pts, self.fv, self.graph, sigma_s)
-        self.flags = filters.edge_flags(self.fv, self.graph)
+        super().__init__(pts, faces, dev, sigma_s)
+        self.flags = self.filters.edge_flags(self.fv, self.graph)
 
     def run(self, n_sweeps, start=None, sigma_r=0.35):
         out, sel = self.filters.guided_records(self.rec_c, self.rec_n if start is None else start, self.fv, self.graph,
@@ -301,16 +264,6 @@ def test_bilateral_filter_is_untouched(dev):
 
 
 # ------------------------------------------------------------------------------------------------ guided_denoise
-def _sphere8_with_truth():
-    from geobi_gnn_amd import meshgen
-    noisy, clean, faces = meshgen.noisy_icosphere(8, 0.3, seed=1)
-    return noisy, clean, np.asarray(faces, dtype=np.int64)
-
-
-def _angle(a, b):
-    return float(G.row_terms(a, b, 3).mean())
-
-
 def test_guided_denoise_against_the_model(dev):
     """n = 8, sigma 0.3, defaults: angle1 and angle2 within 0.01 degrees of the model's normals (replaying the device's
     selections, 20 sweeps) pushed through the fp64 vertex update."""
@@ -375,6 +328,12 @@ def test_errors(dev, monkeypatch):
             fn(noisy, faces, normal_iters=-1)
     with pytest.raises(ValueError, match='n_iter'):
         filters.guided_denoise(noisy, faces, n_iter=-1)
+    # an int64 id that the conversion to int32 would wrap into range (2^32 + 1 -> 1) is refused as it arrives
+    p4 = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+    wrap = np.array([[0, 1, 2], [1, 2, 2 ** 32 + 1]], dtype=np.int64)
+    for fn in (filters.guided_normals, filters.guided_denoise):
+        with pytest.raises(L.GeobiError, match='outside'):
+            fn(p4, wrap)
     # the cost guard: sum of squared patch sizes x sweeps against the module's budget, both named in the refusal
     d = _Device(*_case('fan200')[:2], dev)
     assert filters.patch_cost(d.graph, 200) == 200 ** 3

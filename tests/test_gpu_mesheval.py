@@ -507,3 +507,12 @@ def test_bad_arguments_raise(dev):
     bad[3, 1] = -1
     with pytest.raises(GeobiError, match='outside'):
         mesheval.point_to_mesh(qd, td, bad)
+    # an int64 id that the conversion to int32 would wrap into range (2^32 + 1 -> 1) is refused as it arrives
+    p4 = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+    wrap = np.array([[0, 1, 2], [1, 2, 2 ** 32 + 1]], dtype=np.int64)
+    with pytest.raises(GeobiError, match='outside'):
+        mesheval.point_to_mesh(qd, _t(p4, dev), torch.from_numpy(wrap).to(dev))
+    with pytest.raises(GeobiError, match='outside'):
+        mesheval.eval_pair(p4, wrap, p4, device=dev)
+    with pytest.raises(GeobiError, match='outside'):
+        mesheval.eval_pair(p4, [[0, 1, 2], [1, 2, 3]], p4, gt_faces=wrap, device=dev)

@@ -139,3 +139,31 @@ def test_rejects_bad_input(dev):
     pts = np.zeros((4, 3), dtype=np.float32)
     with pytest.raises(GeobiError):
         meshprep.build_dual_data(pts, np.array([[0, 1, 7]]), device=dev)
+
+
+def test_the_intake_takes_every_form_of_a_mesh(dev):
+    """The icosahedron (V = 12, F = 20) as lists, np.int64, np.int32, CPU int64 tensors and fitting device tensors: the
+    filter's normals and both Data objects of build_dual_data come out with the same bits whatever the form, and tensors that
+    already fit are handed on as they are (same memory)."""
+    from geobi_gnn_amd import filters, meshgen, meshin, meshprep
+    pts, faces = meshgen.icosphere(1)
+    pts, f64 = np.asarray(pts, dtype=np.float32), np.asarray(faces, dtype=np.int64)
+    assert pts.shape == (12, 3) and f64.shape == (20, 3)
+    pd, fd = torch.from_numpy(pts).to(dev), torch.from_numpy(f64).to(device=dev, dtype=torch.int32)
+    forms = {'list': (pts.tolist(), f64.tolist()), 'int64': (pts, f64), 'int32': (pts, f64.astype(np.int32)),
+             'cpu tensor': (torch.from_numpy(pts), torch.from_numpy(f64)), 'device tensor': (pd, fd)}
+
+    def results(p, f):
+        dv, df = meshprep.build_dual_data(p, f, device=dev)
+        out = [filters.bilateral_normals(p, f), dv.x, df.x, dv.edge_weight, df.edge_weight, df.fv_indices]
+        for g in (dv.graph(), df.graph()):
+            out += [g.rowptr_out, g.col_out]
+        return out
+    want = results(pts, f64)
+    assert want[6].numel() == 13 and want[8].numel() == 21 and want[7].numel() == 60
+    for name, (p, f) in forms.items():
+        for k, (a, b) in enumerate(zip(results(p, f), want)):
+            assert a.dtype == b.dtype and torch.equal(a, b), (name, k)
+    a, b = meshin.device_mesh(pd, fd)
+    assert a.data_ptr() == pd.data_ptr() and b.data_ptr() == fd.data_ptr()
+    assert meshin.to_device(pd, dev, torch.float32) is pd and meshin.to_device(fd, dev, torch.int32) is fd

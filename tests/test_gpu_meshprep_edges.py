@@ -267,6 +267,12 @@ def test_loud_errors(dev):
     for p, f in ((pts, none), (pts[:0], [[0, 1, 2]]), (pts[:0], none), (pts, [[0, 1, 3]]), (pts, [[0, -1, 2]])):
         with pytest.raises(GeobiError):
             P.build_dual_data(p, np.asarray(f, dtype=np.int64).reshape(-1, 3), device=dev)
+    # an int64 id that the conversion to int32 would wrap into range (2^32 + 1 -> 1) is refused as it arrives
+    p4 = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+    wrap = np.array([[0, 1, 2], [1, 2, 2 ** 32 + 1]], dtype=np.int64)
+    for f in (wrap, torch.from_numpy(wrap), torch.from_numpy(wrap).to(dev)):
+        with pytest.raises(GeobiError, match='outside'):
+            P.build_dual_data(p4, f, device=dev)
     torch.cuda.synchronize()
     dv, df = P.build_dual_data(pts, np.asarray([[0, 1, 2]]), device=dev)           # and the device is as it was
     assert dv.graph().E == 6 and df.graph().E == 0

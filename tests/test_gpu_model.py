@@ -575,6 +575,18 @@ def test_bad_face_table_is_rejected(dev):
     with pytest.raises(GeobiError, match='fv_indices'):
         with torch.no_grad():
             net((dv, df))
+    # an int64 id that the conversion to int32 would wrap into range (2^32 + 1 -> 1) is refused as it arrives
+    from geobi_gnn_amd import data_util
+    p4 = torch.tensor([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], device=dev)
+    wrap = torch.tensor([[0, 1, 2], [1, 2, 2 ** 32 + 1]], device=dev)
+    with pytest.raises(GeobiError, match='fv_indices index vertices outside'):
+        data_util.face_centroids(p4, wrap)
+    dv, df = (d.to(dev) for d in meshgen.synthetic_dual_data(3, 0.2, seed=1))
+    df.fv_indices = df.fv_indices.clone()
+    df.fv_indices[0, 0] = 2 ** 32 + 1
+    with pytest.raises(GeobiError, match='fv_indices index vertices outside'):
+        with torch.no_grad():
+            net((dv, df))
 
 
 def test_malformed_bags_raise_instead_of_reaching_the_device(dev):

@@ -226,6 +226,11 @@ def test_add_noise(dev):
     bad[0, 0] = V
     with pytest.raises(L.GeobiError):
         meshnoise.add_noise(pts, bad, 0.1, seed=1)
+    # an int64 id that the conversion to int32 would wrap into range (2^32 + 1 -> 1) is refused as it arrives
+    p4 = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+    wrap = np.array([[0, 1, 2], [1, 2, 2 ** 32 + 1]], dtype=np.int64)
+    with pytest.raises(L.GeobiError, match='outside'):
+        meshnoise.add_noise(p4, wrap, 0.1, seed=1)
 
 
 # ------------------------------------------------------------------------------------------------ command

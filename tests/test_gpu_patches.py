@@ -476,6 +476,24 @@ def test_predict_batch_edge_cases(dev):
         patches.predict_batch(net, [bad], sub_size=3000, n_iter=5)
 
 
+def test_face_ids_are_checked_as_they_arrive(dev):
+    """predict_mesh and predict_batch refuse a face table with an id outside [0, V) before the network is used: V, -1, and
+    the int64 id 2^32 + 1, which the conversion to int32 would wrap to 1."""
+    from geobi_gnn_amd import network, patches
+    from geobi_gnn_amd._lib import GeobiError
+    net = network.DualGNN().to(dev).eval()
+    p4 = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+    for bad in (4, -1, 2 ** 32 + 1):
+        faces = np.array([[0, 1, 2], [1, 2, bad]], dtype=np.int64)
+        for f in (faces, torch.from_numpy(faces).to(dev)):
+            with pytest.raises(GeobiError, match='outside'):
+                patches.predict_mesh(net, p4, f)
+            with pytest.raises(GeobiError, match='outside'):
+                patches.predict_batch(net, [(p4, f)])
+            with pytest.raises(GeobiError, match='outside'):
+                patches.predict_batch(net, [(p4, f)], sub_size=1)
+
+
 def test_one_face_patch(dev):
     """A connected component of ONE face becomes a patch of its own (the growth stops when a component is exhausted): its
     facet graph has no edges.  The graph fill used to be called with an empty column array and refused it
