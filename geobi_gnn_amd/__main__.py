@@ -7,7 +7,9 @@
   python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
   python -m geobi_gnn_amd clean --data_dir DIR [--out_dir DIR/clean] [--weld_tol 0] [--no_weld] [--no_manifold]
-  python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold]
+  python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold] [--orient] [--min_component N]
+  python -m geobi_gnn_amd clean ... [--orient] [--min_component N]
+  python -m geobi_gnn_amd info --data_dir DIR [--weld_tol 0] [--no_weld] [--gpu -1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -22,8 +24,11 @@ repairs files that are no clean triangle meshes -- welds vertices, drops degener
 directed edge a second owner, drops unused vertices -- which openmesh does for the reference while it reads a file; with
 DIR/original present the cleaning is computed from original/NAME.obj and the SAME maps are applied to every
 noisy/NAME_n*.obj of equal size (welding noisy coordinates would be wrong: duplicates carry independent noise).  `denoise
---clean` cleans every file before it is denoised and writes the result in the file's own numbering.  All device work runs
-in this one process.
+--clean` cleans every file before it is denoised and writes the result in the file's own numbering.  `--orient` (meshtopo.py)
+winds the faces of every connected part consistently before the half-edge rule, which otherwise drops one of every two
+neighbours wound in opposite senses; `--min_component N` drops the edge-connected parts of fewer than N faces (scan debris).
+`info` prints what a file is before any of that is chosen: edges, boundary, complex and inconsistent edges, parts, whether
+it is closed and orientable.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -127,7 +132,8 @@ def denoise(opt):
             if clean:
                 # the cleaning comes from the file itself; the ground truth follows its maps, the result goes back to the
                 # file's numbering and faces (welded duplicates share one position, unused vertices keep theirs)
-                cleaned = meshclean.clean_mesh(points, faces, weld_tol=_weld_tol(opt), manifold=not opt.no_manifold, device=dev)
+                cleaned = meshclean.clean_mesh(points, faces, weld_tol=_weld_tol(opt), manifold=not opt.no_manifold, device=dev,
+                                               **_topo_args(opt))
                 n_faces = cleaned.faces.shape[0]
                 if n_faces == 0:
                     raise ValueError('%s: no faces left after cleaning' % noisy_file)
@@ -222,11 +228,20 @@ def _weld_tol(opt):
     return None if opt.no_weld else opt.weld_tol
 
 
+def _topo_args(opt):
+    """--orient / --min_component as clean_mesh takes them (neither is in the options without its flag)"""
+    return {'orient': getattr(opt, 'orient', False), 'min_component': getattr(opt, 'min_component', 0)}
+
+
 def _clean_line(cleaned, V, F, out_file):
-    c = cleaned.counts
-    return ("V: %7d -> %7d,  F: %7d -> %7d,  welded: %d,  degenerate: %d,  nonmanifold: %d,  unreferenced: %d,  rounds: %d,  '%s'"
+    c, t = cleaned.counts, cleaned.topology
+    line = ("V: %7d -> %7d,  F: %7d -> %7d,  welded: %d,  degenerate: %d,  nonmanifold: %d,  unreferenced: %d,  rounds: %d,  '%s'"
             % (V, cleaned.points.shape[0], F, cleaned.faces.shape[0], c['welded'], c['degenerate'], c['nonmanifold'],
                c['unreferenced'], c['rounds'], os.path.basename(out_file)))
+    if t is not None:          # '-': the stage that counts it was not asked for
+        line += ',  ' + ',  '.join('%s: %s' % (label, t.get(key, '-')) for label, key in (
+            ('flipped', 'flipped'), ('nonorientable', 'nonorientable'), ('components', 'components'), ('small', 'faces_dropped')))
+    return line
 
 
 def clean(opt):
@@ -252,7 +267,8 @@ def clean(opt):
         name = os.path.basename(path)[:-4]
         try:
             points, faces = meshio.read_obj(path)
-            cleaned = meshclean.clean_mesh(points, faces, weld_tol=weld_tol, manifold=not opt.no_manifold, device=dev)
+            cleaned = meshclean.clean_mesh(points, faces, weld_tol=weld_tol, manifold=not opt.no_manifold, device=dev,
+                                           **_topo_args(opt))
             if cleaned.faces.shape[0] == 0:
                 raise ValueError('%s: no faces left after cleaning' % path)
             faces_out = cleaned.faces.cpu().numpy()
@@ -282,6 +298,37 @@ def clean(opt):
     return 1 if failed or not files else 0
 
 
+INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 'complex_edges', 'inconsistent_edges',
+             'components', 'orient_components', 'nonorientable', 'would_flip', 'euler')
+
+
+def info(opt):
+    """One meshtopo.mesh_report line per DIR/original/*.obj if that folder exists, else per DIR/*.obj."""
+    from . import meshio, meshtopo
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    original_dir = os.path.join(opt.data_dir, 'original')
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if os.path.isdir(original_dir) else opt.data_dir), '*.obj')))
+    weld_tol = _weld_tol(opt)
+    print('\nInfo, weld %s, %d files ...\n'
+          % ('off' if weld_tol is None else ('exact' if weld_tol == 0 else 'grid %g' % weld_tol), len(files)), flush=True)
+    failed = 0
+    for path in files:
+        try:
+            points, faces = meshio.read_obj(path)
+            r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev)
+            print("V: %7d,  F: %7d,  %s,  closed: %s,  '%s'"
+                  % (points.shape[0], faces.shape[0], ',  '.join('%s: %d' % (k, r[k]) for k in INFO_KEYS),
+                     'yes' if r['closed'] else 'no', os.path.basename(path)), flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d of %d files skipped' % (failed, len(files)), file=sys.stderr)
+    return 1 if failed or not files else 0
+
+
 def train(opt):
     from . import trainer
     trainer.require_single_process()              # before the device is touched
@@ -296,11 +343,18 @@ def _weld_tol_arg(text):
     return v
 
 
+def _min_component_arg(text):
+    v = int(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError('--min_component is 0 (keep every part) or a number of faces, not %r' % text)
+    return v
+
+
 class _TrueGiven(argparse.Action):
     """store_true, and note in <dest>_given that the flag was on the command line"""
 
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+    def __init__(self, option_strings, dest, default=False, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=default, **kw)
 
     def __call__(self, parser, namespace, values, option_string=None):
         setattr(namespace, self.dest, True)
@@ -313,6 +367,12 @@ def _add_clean_flags(p, given=False):
                         'side (a snap to a grid, not an epsilon-merge)')
     p.add_argument('--no_weld', action=_TrueGiven, help='keep every vertex apart')
     p.add_argument('--no_manifold', action=_TrueGiven, help='keep faces that give a directed edge a second owner')
+    # the two topology flags leave no entry in the options unless they are given: what `denoise` hands on stays as it was
+    p.add_argument('--orient', action=_TrueGiven, default=argparse.SUPPRESS,
+                   help='wind the faces of every connected part consistently (its lowest face decides) before the half-edge '
+                        'rule')
+    p.add_argument('--min_component', type=_min_component_arg, default=argparse.SUPPRESS, action=_StoreGiven, metavar='N',
+                   help='drop the edge-connected parts of fewer than N faces')
 
 
 def build_parser():
@@ -365,6 +425,12 @@ def build_parser():
     _add_clean_flags(c)
     c.add_argument('--gpu', type=int, default=-1)
     c.set_defaults(fn=clean)
+    i = sub.add_parser('info', help='edges, boundary / complex / inconsistent edges, parts, closed, orientable: one line per mesh')
+    i.add_argument('--data_dir', type=str, required=True, help='holds original/, or the OBJ files themselves')
+    i.add_argument('--weld_tol', type=_weld_tol_arg, default=0.0, help='as for clean: the report is computed after the weld')
+    i.add_argument('--no_weld', action='store_true', help='keep every vertex apart')
+    i.add_argument('--gpu', type=int, default=-1)
+    i.set_defaults(fn=info)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)
@@ -381,7 +447,7 @@ def parse_args(argv=None):
         if opt.method in ('bnf', 'gnf') and (opt.normal_iters < 0 or not opt.sigma_r > 0 or not opt.sigma_s > 0 or opt.n_iter < 0):
             ap.error('denoise: --normal_iters and --n_iter are not negative, --sigma_r and --sigma_s positive')
         if not opt.clean:
-            for flag in ('weld_tol', 'no_weld', 'no_manifold'):
+            for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component'):
                 if getattr(opt, flag + '_given', False):
                     ap.error('denoise: --%s needs --clean' % flag)
     return opt

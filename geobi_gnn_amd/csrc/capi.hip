@@ -752,6 +752,35 @@ int geobi_clean_compact(const float* points, const int32_t* faces_canon, const i
                        counts, ws, ws_bytes, S(stream));
 }
 
+size_t geobi_topo_ws_bytes(int64_t F, int64_t V) {
+  return V < 0 || F < 0 || V > GEOBI_MAX_NODES || F > GEOBI_MAX_NODES ? 0 : topo_ws_bytes(F, V);
+}
+
+int geobi_topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds,
+                      int32_t* faces_out, int32_t* flip, int32_t* label, int32_t* counts, int32_t* rounds,
+                      float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  NOTNULL(faces); NOTNULL(faces_out); NOTNULL(flip); NOTNULL(label); NOTNULL(counts); NOTNULL(rounds);
+  return topo_orient(faces, state, F, V, max_rounds, faces_out, flip, label, counts, rounds, stage_ms, ws, ws_bytes,
+                     S(stream));
+}
+
+int geobi_topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int min_component,
+                          int max_rounds, int32_t* comp, int32_t* state_out, int32_t* counts, int32_t* rounds,
+                          float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  NOTNULL(faces); NOTNULL(comp); NOTNULL(state_out); NOTNULL(counts); NOTNULL(rounds);
+  return topo_components(faces, state, F, V, min_component, max_rounds, comp, state_out, counts, rounds, stage_ms, ws,
+                         ws_bytes, S(stream));
+}
+
+int geobi_topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
+                      int32_t* rounds, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  NOTNULL(faces); NOTNULL(counts); NOTNULL(rounds);
+  return topo_report(faces, state, F, V, max_rounds, counts, rounds, ws, ws_bytes, S(stream));
+}
+
 int geobi_patch_accumulate(const float* vert_p, const float* norm_p, const int32_t* v_idx, const int32_t* f_idx,
                            int64_t nv, int64_t nf, float* Vp, float* Np, int32_t* sum_v, void* stream) {
   SIZES(nv > nf ? nv : nf, 0);

@@ -394,6 +394,16 @@ size_t clean_compact_ws_bytes(int64_t V, int64_t F);
 int clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon, int64_t V,
                   int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map, int32_t* vertex_src,
                   int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s);
+// topo.hip (mesh topology: consistent winding, connected components, the edge report)
+size_t topo_ws_bytes(int64_t F, int64_t V);
+int topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* faces_out,
+                int32_t* flip, int32_t* label, int32_t* counts, int32_t* rounds, float* stage_ms, void* ws, size_t ws_bytes,
+                hipStream_t s);
+int topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int min_component, int max_rounds,
+                    int32_t* comp, int32_t* state_out, int32_t* counts, int32_t* rounds, float* stage_ms, void* ws,
+                    size_t ws_bytes, hipStream_t s);
+int topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
+                int32_t* rounds, void* ws, size_t ws_bytes, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

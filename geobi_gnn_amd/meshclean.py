@@ -17,6 +17,11 @@ keeps every face.  ``clean_mesh`` applies that rule, after a weld openmesh does 
 * **compaction**: kept faces and used vertices keep their relative order; a welded group keeps the coordinates of its
   lowest-index member (not a mean)
 
+* **topology** (``orient=True``, ``min_component=m``; ``meshtopo``): after the weld and before the
+  half-edge rule the faces are wound consistently per component -- two neighbours wound in opposite senses walk their
+  common edge in the same direction, and the half-edge rule alone would drop one of them; after the rule, the faces of
+  every edge-connected part of fewer than m kept faces are dropped too (state 4, not counted as nonmanifold)
+
 Everything is integer-exact (geobi_clean_* in csrc/clean.hip).  No CPU fallback.
 """
 import ctypes
@@ -31,12 +36,15 @@ from . import meshin
 class CleanResult(object):
     """points [V', 3] float32, faces [F', 3] int32 (cleaned numbering), vertex_map [V] (new index of canon[v], or -1),
     vertex_src [V'] (input index of every cleaned vertex), face_map [F'] (input index of every kept face), canon [V];
-    counts: welded, degenerate, nonmanifold, unreferenced, rounds."""
+    counts: welded, degenerate, nonmanifold, unreferenced, rounds.  With ``orient`` / ``min_component``: topology, a dict of
+    flipped, nonorientable, orient_components, orient_rounds (orient) and components, components_dropped, faces_dropped,
+    component_rounds (min_component), else None; face_flip [F] (input numbering: 1 where the winding was reversed)."""
 
-    def __init__(self, points, faces, vertex_map, vertex_src, face_map, canon, counts):
+    def __init__(self, points, faces, vertex_map, vertex_src, face_map, canon, counts, topology=None, face_flip=None):
         self.points, self.faces = points, faces
         self.vertex_map, self.vertex_src, self.face_map, self.canon = vertex_map, vertex_src, face_map, canon
         self.counts = counts
+        self.topology, self.face_flip = topology, face_flip
 
 
 def _index(a, like):
@@ -111,18 +119,28 @@ def compact(pts, fc, state, canon, F):
     return p_out, f_out, vmap, vsrc, fmap, counts
 
 
-def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, device=None):
-    """(points [V, 3], faces [F, 3]) -> CleanResult, on the device.  ValueError: non-finite points, a face index outside
-    [0, V), weld_tol < 0, max_rounds < 1.  GeobiError: the library's errors -- a grid quotient outside int32, more than
-    ``max_rounds`` rounds of the half-edge rule (a chain of faces that each share a directed edge with the next takes one
-    round per face)."""
-    dev = meshin.default_device(device)
+def check_weld_tol(what, weld_tol):
     if weld_tol is not None and not float(weld_tol) >= 0.0:
-        raise ValueError('clean_mesh: weld_tol = %r (None, 0 or a positive cell size)' % (weld_tol,))
+        raise ValueError('%s: weld_tol = %r (None, 0 or a positive cell size)' % (what, weld_tol))
     if weld_tol is not None and not np.isfinite(np.float32(weld_tol)):
-        raise ValueError('clean_mesh: weld_tol = %r is not a finite float32' % (weld_tol,))
+        raise ValueError('%s: weld_tol = %r is not a finite float32' % (what, weld_tol))
+
+
+def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, device=None, orient=False, min_component=0):
+    """(points [V, 3], faces [F, 3]) -> CleanResult, on the device.  ValueError: non-finite points, a face index outside
+    [0, V), weld_tol < 0, max_rounds < 1, min_component < 0.  GeobiError: the library's errors -- a grid quotient outside
+    int32, more than ``max_rounds`` rounds of the half-edge rule (a chain of faces that each share a directed edge with the
+    next takes one round per face), more than 256 rounds of the component search (``meshtopo``).
+
+    ``orient``: weld, corners through canon, consistent winding per component (meshtopo.orient_device), then the
+    half-edge rule on the oriented table.  ``min_component = m > 0``: after the rule, the kept faces of every
+    edge-connected part of fewer than m faces are dropped (a face they displaced under the rule does not come back)."""
+    dev = meshin.default_device(device)
+    check_weld_tol('clean_mesh', weld_tol)
     if int(max_rounds) < 1:
         raise ValueError('clean_mesh: max_rounds = %r (at least 1)' % (max_rounds,))
+    if int(min_component) < 0:
+        raise ValueError('clean_mesh: min_component = %r (0 or more)' % (min_component,))
     # the face table is range-checked as it came in (an int64 id must not wrap into range), BEFORE any kernel walks it
     pts, fv = meshin.device_mesh(meshin.as_tensor(points).reshape(-1, 3), meshin.as_tensor(faces).reshape(-1, 3), dev,
                                  what='clean_mesh: faces', error=ValueError)
@@ -134,9 +152,30 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
         groups, bad = L.read_i32(wcounts)
         if bad:
             raise L.GeobiError('clean_mesh: a coordinate divided by weld_tol = %g is outside the int32 range' % weld_tol)
+        topology, face_flip, tcounts = None, None, []
+        if orient or min_component > 0:
+            from . import meshtopo
+            topology = {}
+        # the stages hand on tables padded to one row for F == 0: only their F rows [:F] are a mesh
+        if orient:
+            fc, _, _ = resolve_faces(fv, canon, V, False, max_rounds)           # the corners through canon
+            oriented, face_flip, _, ocounts, orient_rounds = meshtopo.orient_device(fc[:F], V)
+            fv = oriented[:F]
+            tcounts.append(ocounts)
+            topology['orient_rounds'] = orient_rounds
+        # canon is idempotent: on an oriented table it leaves every corner as it is
         fc, state, rounds = resolve_faces(fv, canon, V, manifold, max_rounds)
+        if min_component > 0:
+            _, state, ccounts, topology['component_rounds'] = meshtopo.components_device(fc[:F], V, state[:F], min_component)
+            tcounts.append(ccounts)
         p_out, f_out, vmap, vsrc, fmap, counts = compact(pts, fc, state, canon, F)
-        v_new, f_new, degenerate, nonmanifold, unreferenced = L.read_i32(counts)
+        host = L.read_i32(torch.cat([counts] + tcounts) if tcounts else counts)      # one read for all counts
+        v_new, f_new, degenerate, nonmanifold, unreferenced = host[:5]
+        if orient:
+            topology['orient_components'], topology['nonorientable'], topology['flipped'] = host[5:8]
+            face_flip = face_flip[:F]
+        if min_component > 0:
+            topology['components'], topology['components_dropped'], topology['faces_dropped'] = host[-3:]
     return CleanResult(p_out[:v_new], f_out[:f_new], vmap[:V], vsrc[:v_new], fmap[:f_new], canon[:V],
                        {'welded': V - groups, 'degenerate': degenerate, 'nonmanifold': nonmanifold,
-                        'unreferenced': unreferenced, 'rounds': rounds})
+                        'unreferenced': unreferenced, 'rounds': rounds}, topology, face_flip)

@@ -11,7 +11,8 @@
  *     allocates, frees or synchronises: scratch comes in through `ws` / `ws_bytes` (query the size
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
  *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
- *     (reads its undecided counts through it), the whole-network
+ *     (reads its undecided counts through it), geobi_topo_orient / _components / _report (read the changed flags of
+ *     their rounds through it), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -543,7 +544,8 @@ int geobi_patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, 
  *                        counts (device int32 [2]): [0] = number of groups, [1] != 0: a quotient left the int32 range
  *                        (canon is then not to be used).  Three stable 32-bit radix passes over (key, index).
  *   geobi_clean_faces    faces_canon [F, 3] = the corners through canon; state [F]: 1 kept, 2 dropped by the half-edge
- *                        rule, 3 degenerate (two equal corners after welding).  Half-edge rule (manifold != 0), stated
+ *                        rule, 3 degenerate (two equal corners after welding); 4, "small part", is written by
+ *                        geobi_topo_components only.  Half-edge rule (manifold != 0), stated
  *                        sequentially: walk the faces in ascending index; a non-degenerate face (a, b, c) is kept iff none
  *                        of a->b, b->c, c->a is owned by a kept earlier face; a kept face then owns its three.  Computed
  *                        in Jacobi rounds over the stably sorted half-edges (48-bit keys a << 24 | b): the result IS the
@@ -553,7 +555,8 @@ int geobi_patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, 
  *                        undecided counts, once per batch of rounds: 4, then 32 at a time); more than max_rounds (>= 1)
  *                        rounds is an error, never a spin.
  *   geobi_clean_compact  kept faces in their order with face_map [F'] = their input index; a vertex is used when a kept
- *                        face lists it (through canon); used vertices in their order with their OWN coordinates
+ *                        face (state 1; every other state is dropped, 2 and 3 are counted) lists it (through canon);
+ *                        used vertices in their order with their OWN coordinates
  *                        (points_out [V', 3]) and vertex_src [V'] = their input index; vertex_map [V] = new index of
  *                        canon[v] or -1.  Outputs have room for V / F rows.  counts (device int32 [5]) = V', F',
  *                        degenerate faces, faces dropped by the half-edge rule, vertices with vertex_map == -1.       */
@@ -567,6 +570,53 @@ size_t geobi_clean_compact_ws_bytes(int64_t V, int64_t F);
 int geobi_clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon,
                         int64_t V, int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map,
                         int32_t* vertex_src, int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- mesh topology (winding, parts, edge report) ----
+ * The stage between geobi_clean_faces and the graphs: make the winding consistent, find the connected
+ * parts, report the edges.  No counterpart in the reference (openmesh refuses the faces instead).  Integer-exact; nothing
+ * depends on launch geometry.  faces [F, 3] int32 are corners already taken through canon, V, F <= GEOBI_MAX_NODES; state
+ * [F] may be NULL (every face 1).  A face is INCLUDED when its state is 1 and its three corners differ (and lie in [0, V));
+ * the others have no links and label -1.
+ *   edge table           every included face lists its undirected edges {lo, hi} (key lo << 24 | hi) in the slots 3f + k
+ *                        for the corner pair (k, k + 1 mod 3); direction bit 0 when the face walks lo -> hi; opposite
+ *                        corner k + 2 mod 3.  One stable 48-bit sort of (key, slot): a run lists the claimants of an edge
+ *                        in ascending slot order.
+ *   geobi_topo_orient    ORIENTATION LINK: a run of exactly two claimants with different opposite corners (two copies of
+ *                        one triangle stay unlinked); ODD when the direction bits are equal.  label [F] = the lowest face
+ *                        of the face's component over these links (-1: not included); flip [F] = the parity of odd links
+ *                        on a path from that face, 0 throughout a NON-ORIENTABLE component (one with a link that
+ *                        contradicts the parities); faces_out [F, 3] = the table with every flipped (a, b, c) as (a, c, b):
+ *                        the lowest face of a component keeps its winding and decides for the rest.  counts (device
+ *                        int32 [3]) = components, non-orientable components, flipped faces.
+ *   geobi_topo_components  COMPONENT LINK: consecutive claimants of every run of two or more, whatever the direction --
+ *                        faces that share an EDGE; two fans that meet in one vertex are two components.  comp [F] = the
+ *                        lowest included face reachable (-1: not included); state_out [F] = the input state (1 without
+ *                        one; 3 for a state-1 face with equal corners), and 4 ("small part") for every face of a component
+ *                        of fewer than min_component (>= 0) faces.  counts (device int32 [3]) = components, components
+ *                        below min_component, their faces.
+ *   geobi_topo_report    counts (device int32 [16]) from one pass over the run heads: [0] edges, [1] boundary edges (run of
+ *                        1), [2] complex edges (3 and more), [3] inconsistent edges (2 with equal direction bits); [4]
+ *                        vertices an included face lists, [5] included faces, [6] the other faces; [7] components; [8]
+ *                        orientation components, [9] non-orientable ones, [10] faces geobi_topo_orient would flip.
+ *                        rounds: HOST int32 [2] (orientation, components).
+ * The components are found in synchronous rounds over key[x] = 2 * label + parity (start 2x): a round reads `key` only and
+ * lowers a copy `next` with integer atomic min -- for every link u -> w: next[parent(u)] and next[u] towards w's grandparent
+ * with the parities composed, then next[x] towards x's own grandparent.  No thread reads `next` during a round and min
+ * commutes: the result and *rounds (HOST int32: the rounds that changed a key, 0 without links) are functions of the input
+ * alone.  A sphere of 150 k faces takes 10 rounds; WAITS for `stream` (geobi_read_i32 on the changed flags, 8 rounds at a
+ * time).  More than max_rounds (>= 1) changed rounds is an error, never a spin.  One workspace size serves all three
+ * (V = 0 is enough for orient and components).  F == 0 is valid.  stage_ms (HOST float [3], normally NULL) is for
+ * measurement: when given, device events at the stage borders give the milliseconds of the edge table, of the rounds with
+ * their waits, and of the rest, and the call waits for its own end.                                                  */
+size_t geobi_topo_ws_bytes(int64_t F, int64_t V);
+int geobi_topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds,
+                      int32_t* faces_out, int32_t* flip, int32_t* label, int32_t* counts, int32_t* rounds,
+                      float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int min_component,
+                          int max_rounds, int32_t* comp, int32_t* state_out, int32_t* counts, int32_t* rounds,
+                          float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
+                      int32_t* rounds, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
