@@ -326,6 +326,8 @@ int geobi_match_heavy_edge(const int32_t* rowptr, const int32_t* col, const floa
 }
 
 int geobi_set_match_round_cap(int cap) { set_match_round_cap(cap); return 0; }
+int geobi_set_match_scanfree(int on) { set_match_scanfree(on); return 0; }
+int geobi_set_scan_lookback(int on) { set_scan_lookback(on); return 0; }
 int geobi_set_tile_rows(int rows) { return set_tile_rows(rows); }
 int geobi_set_head_precision(int mode) { return set_head_precision(mode); }
 int geobi_set_rowpass_form(int staged, int chunked64) { return set_rowpass_form(staged, chunked64); }
@@ -340,6 +342,29 @@ int geobi_match_coarsen(const int32_t* rowptr, const int32_t* col, const float* 
   NOTNULL(members); NOTNULL(counters); NOTNULL(ws);
   return match_coarsen(rowptr, col, w, N, rounds, init, state, cluster_final, cnew, segptr, members, counters, ws,
                        ws_bytes, S(stream));
+}
+
+int geobi_debug_match_coarsen_rowinfo(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, int rounds,
+                                      int init, int32_t* state, int32_t* cluster_final, int32_t* cnew, int32_t* segptr,
+                                      int32_t* members, int32_t* counters, int32_t* rowinfo, int32_t* rowinfo_made,
+                                      void* ws, size_t ws_bytes, void* stream) {
+  SIZES(N, 0);
+  NOTNULL(rowptr); NOTNULL(state); NOTNULL(cluster_final); NOTNULL(cnew); NOTNULL(segptr);
+  NOTNULL(members); NOTNULL(counters); NOTNULL(rowinfo); NOTNULL(rowinfo_made); NOTNULL(ws);
+  bool made = false;
+  GEOBI_TRY(match_coarsen(rowptr, col, w, N, rounds, init, state, cluster_final, cnew, segptr, members, counters, ws,
+                          ws_bytes, S(stream), rowinfo, &made));
+  *rowinfo_made = made ? 1 : 0;
+  return 0;
+}
+
+size_t geobi_debug_scan_ws_bytes(int64_t n) { return scan_ws_bytes(n); }
+int geobi_debug_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(0, n);
+  if (n <= 0) return 0;
+  NOTNULL(in); NOTNULL(out); NOTNULL(ws);
+  GEOBI_REQUIRE(ws_bytes >= scan_ws_bytes(n), "%s: workspace too small (%zu < %zu)", __func__, ws_bytes, scan_ws_bytes(n));
+  return scan_exclusive_i32(ws, ws_bytes, in, out, n, S(stream));
 }
 
 size_t geobi_relabel_ws_bytes(int64_t N) { return relabel_ws_bytes(N); }
@@ -382,6 +407,29 @@ int geobi_segment_max_bwd(const float* gout, const int32_t* arg, const int32_t* 
   SIZES(n_fine, 0);
   return segment_max_bwd(gout, arg, seg, C, nseg, n_fine, gx, S(stream));
 }
+int geobi_debug_segment_max2_fwd(const float* x, int C, const int32_t* segptr1, const int32_t* members1,
+                                 const int32_t* segptr2, const int32_t* members2, int64_t nseg2, float* out,
+                                 int32_t* arg12, void* stream) {
+  SIZES(nseg2, 0);
+  GEOBI_REQUIRE(C > 0, "%s: C = %d", __func__, C);
+  if (nseg2 > 0) { NOTNULL(x); NOTNULL(segptr1); NOTNULL(members1); NOTNULL(segptr2); NOTNULL(members2); NOTNULL(out); NOTNULL(arg12); }
+  return segment_max2_fwd(x, C, segptr1, members1, segptr2, members2, nseg2, out, arg12, S(stream));
+}
+int geobi_debug_segment_max2_bwd(const float* gout, const int32_t* arg12, const int32_t* seg12, int C, int64_t nseg2,
+                                 int64_t n_fine, float* gx, int add, void* stream) {
+  SIZES(n_fine, 0);
+  SIZES(nseg2, 0);
+  GEOBI_REQUIRE(C > 0, "%s: C = %d", __func__, C);
+  if (n_fine > 0) { NOTNULL(gout); NOTNULL(arg12); NOTNULL(seg12); NOTNULL(gx); }
+  return segment_max2_bwd(gout, arg12, seg12, C, nseg2, n_fine, gx, add, S(stream));
+}
+int geobi_debug_segment_sum2(const float* x, int C, const int32_t* segptr1, const int32_t* members1,
+                             const int32_t* segptr2, const int32_t* members2, int64_t nseg2, float* out, void* stream) {
+  SIZES(nseg2, 0);
+  GEOBI_REQUIRE(C > 0, "%s: C = %d", __func__, C);
+  if (nseg2 > 0) { NOTNULL(x); NOTNULL(segptr1); NOTNULL(members1); NOTNULL(segptr2); NOTNULL(members2); NOTNULL(out); }
+  return segment_sum2(x, C, segptr1, members1, segptr2, members2, nseg2, out, S(stream));
+}
 int geobi_segment_sum(const float* x, int C, const int32_t* segptr, const int32_t* members, int64_t nseg, int mean,
                       float* out, void* stream) {
   SIZES(nseg, 0);
@@ -406,6 +454,22 @@ int geobi_pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32
   NOTNULL(row_c); NOTNULL(col_c); NOTNULL(count); NOTNULL(overflow);
   return pool_edge_rows(cnew, segptr, members, rowptr, col, w, ncount, nbound, rowptr_c, row_c, col_c, w_c, count,
                         overflow, ws, ws_bytes, S(stream));
+}
+size_t geobi_debug_pool_edge_rows_onepass_ws_bytes(int64_t nbound, int64_t E) {
+  return pool_edge_rows_ws_bytes_onepass(nbound, E);
+}
+int geobi_debug_pool_edge_rows_onepass(const int32_t* cnew, const int32_t* segptr, const int32_t* members,
+                                       const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* ncount,
+                                       int64_t nbound, int64_t E_fine, const int32_t* rowinfo_in, int32_t* rowptr_c,
+                                       int32_t* row_c, int32_t* col_c, float* w_c, int32_t* count, int32_t* overflow,
+                                       void* ws, size_t ws_bytes, void* stream) {
+  SIZES(nbound, E_fine);
+  GEOBI_REQUIRE(E_fine > 0, "%s: the one-pass form needs the fine edge count (E_fine = %lld)", __func__, (long long)E_fine);
+  NOTNULL(cnew); NOTNULL(segptr); NOTNULL(members); NOTNULL(rowptr); NOTNULL(col); NOTNULL(ncount); NOTNULL(rowptr_c);
+  NOTNULL(row_c); NOTNULL(col_c); NOTNULL(count); NOTNULL(overflow); NOTNULL(ws);
+  if (w != nullptr) NOTNULL(w_c);
+  return pool_edge_rows(cnew, segptr, members, rowptr, col, w, ncount, nbound, rowptr_c, row_c, col_c, w_c, count,
+                        overflow, ws, ws_bytes, S(stream), E_fine, rowinfo_in);
 }
 size_t geobi_pool_edge_ws_bytes(int64_t E) { return pool_edge_ws_bytes(E); }
 int geobi_pool_edge(const int32_t* cnew, const int32_t* row, const int32_t* col, const float* w, int64_t E,

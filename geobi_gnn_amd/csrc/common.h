@@ -108,7 +108,12 @@ __device__ __forceinline__ double fold_ascending(const double* __restrict__ part
 }
 
 // ---- optional per-kernel timing for bench.py's roofline object (events on the launch stream)
-enum ProfKernel { PROF_NONE = 0, PROF_AGG_FWD = 1, PROF_AGG_BWD = 2, PROF_ROWPASS = 3, PROF_GEMM = 4 };
+enum ProfKernel { PROF_NONE = 0, PROF_AGG_FWD = 1, PROF_AGG_BWD = 2, PROF_ROWPASS = 3, PROF_GEMM = 4, PROF_POOL_FORM = 5 };
+// tags of PROF_POOL_FORM (pool.hip): which form of a scan / of match_coarsen's tail a call took
+enum PoolForm {
+  POOL_FORM_SCAN_ONE_BLOCK = 1, POOL_FORM_SCAN_LOOKBACK = 2, POOL_FORM_SCAN_ROCPRIM = 3,
+  POOL_FORM_MATCH_SCANFREE = 4, POOL_FORM_MATCH_TWOPASS_DUAL = 5
+};
 void prof_begin(int kernel, hipStream_t s, double alg_bytes, int tag);
 void prof_end(int kernel, hipStream_t s);
 // The same bracket for ONE kernel launched through hipExtLaunchKernelGGL: the two events are bound to the kernel's own
@@ -267,6 +272,8 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
 int match_heavy_edge(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, int rounds, int init,
                      int32_t* cluster, int32_t* cluster_final, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
 void set_match_round_cap(int cap);
+void set_match_scanfree(int on);      // test hooks: 1 / 0 force the form, < 0 = as the environment says
+void set_scan_lookback(int on);
 size_t relabel_ws_bytes(int64_t N);
 int relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t* cnew, int32_t* count, void* ws,
                     size_t ws_bytes,

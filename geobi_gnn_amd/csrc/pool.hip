@@ -16,6 +16,7 @@
 // sequential statement of the same rule.
 #include "common.h"
 
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -26,6 +27,11 @@ namespace geobi {
 namespace {
 
 constexpr uint64_t kSentinel = ~0ull;
+
+// A/B knobs with a test hook: the environment decides (unset or non-zero = on) until geobi_set_* forces a form
+static bool env_on(const char* name) { const char* f = getenv(name); return !f || atoi(f) != 0; }
+static std::atomic<bool>& scan_lookback_knob() { static std::atomic<bool> v{env_on("GEOBI_SCAN_LOOKBACK")}; return v; }
+static std::atomic<bool>& match_scanfree_knob() { static std::atomic<bool> v{env_on("GEOBI_MATCH_SCANFREE")}; return v; }
 
 static inline int key_bits(int64_t N) {   // (1 << bits) > N: see graph.hip
   int b = 1;
@@ -1118,12 +1124,22 @@ static hipError_t lookback_scan(const int* in, int* out, int64_t n, hipStream_t 
 static hipError_t exclusive_scan_int(void* temp, size_t& tb, const int* in, int* out, int64_t n, hipStream_t s) {
   if (n <= kSmallScan) {
     if (temp == nullptr) { tb = 16; return hipSuccess; }
-    static const bool lookback = [] { const char* f = getenv("GEOBI_SCAN_LOOKBACK"); return !f || atoi(f) != 0; }();   // A/B knob
-    if (lookback && n > kOneBlockScan) return lookback_scan(in, out, n, s);
+    const bool lookback = scan_lookback_knob().load(std::memory_order_relaxed);
+    if (lookback && n > kOneBlockScan) {
+      prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_LOOKBACK);
+      const hipError_t e = lookback_scan(in, out, n, s);
+      prof_end(PROF_POOL_FORM, s);
+      return e;
+    }
+    prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_ONE_BLOCK);
     small_exclusive_scan_kernel<<<1, 1024, 0, s>>>(in, out, n);
+    prof_end(PROF_POOL_FORM, s);
     return hipGetLastError();
   }
-  return rocprim::exclusive_scan(temp, tb, in, out, 0, (size_t)n, rocprim::plus<int>(), s, false);
+  prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_ROCPRIM);
+  const hipError_t e = rocprim::exclusive_scan(temp, tb, in, out, 0, (size_t)n, rocprim::plus<int>(), s, false);
+  prof_end(PROF_POOL_FORM, s);
+  return e;
 }
 
 template <typename T>
@@ -1202,6 +1218,11 @@ int expand_rowptr(const int32_t* rowptr, int64_t N, int32_t* row, hipStream_t s)
 static int g_round_cap = 0;
 void set_match_round_cap(int cap) { g_round_cap = cap > 0 ? cap : 0; }
 
+// Test hooks (geobi_set_match_scanfree / geobi_set_scan_lookback): 1 / 0 force the form, a negative value goes back to
+// what the environment says.  Without a call nothing changes.
+void set_match_scanfree(int on) { match_scanfree_knob().store(on < 0 ? env_on("GEOBI_MATCH_SCANFREE") : on != 0); }
+void set_scan_lookback(int on) { scan_lookback_knob().store(on < 0 ? env_on("GEOBI_SCAN_LOOKBACK") : on != 0); }
+
 static void launch_match_rounds(const int32_t* rowptr, const int32_t* col, const float* w, int N, int rounds, int init,
                                 int32_t* cluster, int32_t* status, int*& pp, int*& pn, hipStream_t s) {
   const int blocks = cdiv(N, 256);
@@ -1269,15 +1290,17 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
   int* pp = prop0;
   int* pn = prop1;
   launch_match_rounds(rowptr, col, w, (int)N, rounds, init, state, counters, pp, pn, s);
-  static const bool scan_free = [] { const char* f = getenv("GEOBI_MATCH_SCANFREE"); return !f || atoi(f) != 0; }();   // A/B knob
+  const bool scan_free = match_scanfree_knob().load(std::memory_order_relaxed);
   if (scan_free && blocks <= kMaxScanBlocks) {
     // scan-free pair: block-local prefixes in the commit kernel, block totals folded by the list kernel
     int* bt_rank = rank;                 // rank / offs are free in this variant: reuse them for the block totals
     int* bt_offs = offs;
+    prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_MATCH_SCANFREE);
     match_commit_scan_kernel<<<blocks, 256, 0, s>>>(pp, (int)N, state, counters, cluster_final, flag, sz, bt_rank, bt_offs);
     GEOBI_LAUNCH_OK();
     match_lists_scan_kernel<<<blocks, 256, 0, s>>>(state, cluster_final, flag, sz, bt_rank, bt_offs, blocks, (int)N, cnew,
                                                    counters + 1, segptr, members, rowptr, (int4*)rowinfo_out);
+    prof_end(PROF_POOL_FORM, s);
     GEOBI_LAUNCH_OK();
     if (rowinfo_made) *rowinfo_made = rowinfo_out != nullptr;
     return 0;
@@ -1286,7 +1309,9 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
   match_commit_kernel<<<blocks, 256, 0, s>>>(pp, (int)N, state, counters, cluster_final, flag, sz);
   GEOBI_LAUNCH_OK();
   if (N + 1 <= kSmallScan) {
+    prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_MATCH_TWOPASS_DUAL);
     small_exclusive_scan2_kernel<<<1, 1024, 0, s>>>(flag, sz, rank, offs, N + 1);
+    prof_end(PROF_POOL_FORM, s);
     GEOBI_LAUNCH_OK();
   } else {
     GEOBI_TRY(scan_exclusive_i32(temp_a, tb, flag, rank, N + 1, s));

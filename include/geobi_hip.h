@@ -187,6 +187,14 @@ int geobi_match_heavy_edge(const int32_t* rowptr, const int32_t* col, const floa
  * become 1 and every resume of a caller's repair loop (rounds doubled each time) 2, 4, ...: the resume paths of
  * PoolingLayer.forward / geobi_net_forward run on graphs that otherwise converge at once. */
 int geobi_set_match_round_cap(int cap);
+/* test hooks for the forms of the pooling front end (1 / 0 force a form, a negative value goes back to what the
+ * environment variable of the same knob says; results do not depend on the form):
+ *   geobi_set_match_scanfree: geobi_match_coarsen's tail -- the scan-free kernel pair (default up to 2^20 nodes,
+ *                             GEOBI_MATCH_SCANFREE) or commit + exclusive scans + lists
+ *   geobi_set_scan_lookback : the exclusive int scan of 2^14 < n <= 2^18 entries -- the several-block look-back kernel
+ *                             (default, GEOBI_SCAN_LOOKBACK) or the one-block walk                                  */
+int geobi_set_match_scanfree(int on);
+int geobi_set_scan_lookback(int on);
 /* geobi_match_coarsen: the integer front end of one pooling step (code/net_util.py:127-128 plus the inverse
  * lists the feature pooling needs) in one call: the rounds of geobi_match_heavy_edge, then dense ids and
  * segment lists of the matching -- the results of geobi_relabel_compact and geobi_segment_csr_pairs, with
@@ -766,7 +774,9 @@ int geobi_side_join(void* stream);
 /* ---------------------------------------------------------------- measurement --------------
  * When enabled, the selected kernel family is bracketed with HIP events on its launch stream
  * (kernel: 1 = FeaSt aggregation forward, 2 = transposed aggregation backward, 3 = backward row
- * pass, 4 = the dense GEMMs).  geobi_prof_collect synchronises the recorded events and returns the
+ * pass, 4 = the dense GEMMs, 5 = the forms of the pooling front end: one record per scan or per geobi_match_coarsen tail,
+ * tag 1 one-block scan, 2 look-back scan, 3 rocPRIM scan, 4 scan-free matching tail, 5 two-pass tail with the dual
+ * one-block scan).  geobi_prof_collect synchronises the recorded events and returns the
  * launch count, the summed device time (ms) and the summed ALGORITHMIC bytes
  * of launches whose channel count equals `tag` (tag = 0: all).  For kernel 4 the third figure is the
  * flop count 2*M*N*K instead and the tag is 1 for gemm_nn (+ its split-K reduce), 2 for gemm_tn
@@ -776,6 +786,39 @@ int geobi_prof_enable(int kernel);
  * differences to the row maximum, i.e. FINITE and <= 0: <= 2 ulp against exp, results below 2^-126 flush to 0; a
  * non-finite argument is outside its contract).  Exposed so that a test can check it in isolation.              */
 int geobi_debug_exp_le0(const float* x, float* y, int64_t n, void* stream);
+/* diagnostic entries of the pooling front end (csrc/pool.hip), for tests: forms that otherwise only the executor calls.
+ *   geobi_debug_scan_exclusive_i32     : the library's exclusive int scan (out[i] = in[0] + ... + in[i-1]); workspace of
+ *                                        geobi_debug_scan_ws_bytes(n) bytes
+ *   geobi_debug_segment_max2_fwd / _bwd: max over the composition of two clusterings in one pass (segptr1 / members1:
+ *                                        fine -> mid lists, segptr2 / members2: mid -> coarse, every mid segment
+ *                                        non-empty); arg12 [nseg2, C] = fine row of the maximum (-1: empty); the
+ *                                        backward routes gout to that row (seg12 [n_fine] = composed index), add != 0:
+ *                                        on top of what gx holds
+ *   geobi_debug_segment_sum2           : sum over the same composition, C a multiple of 4
+ *   geobi_debug_match_coarsen_rowinfo  : geobi_match_coarsen plus rowinfo [N, 4] = (r0, d0, r1, d1), start and length of
+ *                                        the fine rows of each coarse node's members; rowinfo_made[0] (HOST int32) = 1 if
+ *                                        the form that ran wrote it
+ *   geobi_debug_pool_edge_rows_onepass : geobi_pool_edge_rows in its one-pass form (merge once, park, compact);
+ *                                        E_fine = fine edge count (> 0), rowinfo_in = the array above or NULL           */
+size_t geobi_debug_scan_ws_bytes(int64_t n);
+int geobi_debug_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, void* ws, size_t ws_bytes, void* stream);
+int geobi_debug_segment_max2_fwd(const float* x, int C, const int32_t* segptr1, const int32_t* members1,
+                                 const int32_t* segptr2, const int32_t* members2, int64_t nseg2, float* out,
+                                 int32_t* arg12, void* stream);
+int geobi_debug_segment_max2_bwd(const float* gout, const int32_t* arg12, const int32_t* seg12, int C, int64_t nseg2,
+                                 int64_t n_fine, float* gx, int add, void* stream);
+int geobi_debug_segment_sum2(const float* x, int C, const int32_t* segptr1, const int32_t* members1,
+                             const int32_t* segptr2, const int32_t* members2, int64_t nseg2, float* out, void* stream);
+int geobi_debug_match_coarsen_rowinfo(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, int rounds,
+                                      int init, int32_t* state, int32_t* cluster_final, int32_t* cnew, int32_t* segptr,
+                                      int32_t* members, int32_t* counters, int32_t* rowinfo, int32_t* rowinfo_made,
+                                      void* ws, size_t ws_bytes, void* stream);
+size_t geobi_debug_pool_edge_rows_onepass_ws_bytes(int64_t nbound, int64_t E);
+int geobi_debug_pool_edge_rows_onepass(const int32_t* cnew, const int32_t* segptr, const int32_t* members,
+                                       const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* ncount,
+                                       int64_t nbound, int64_t E_fine, const int32_t* rowinfo_in, int32_t* rowptr_c,
+                                       int32_t* row_c, int32_t* col_c, float* w_c, int32_t* count, int32_t* overflow,
+                                       void* ws, size_t ws_bytes, void* stream);
 int geobi_prof_collect(int tag, int64_t* launches, double* total_ms, double* total_bytes);
 
 #ifdef __cplusplus

@@ -635,7 +635,8 @@ def test_feast_split_input_equals_concatenated_at_scale(dev):
 @pytest.mark.parametrize('n,m', [(700, 2500), (12000, 40000), (300000, 900000)])
 def test_match_coarsen_equals_separate_calls(dev, n, m):
     """geobi_match_coarsen = geobi_match_heavy_edge + geobi_relabel_compact + geobi_segment_csr_pairs
-    (the last size runs the two-pass scans instead of the single-launch dual scan)."""
+    (every size here takes the scan-free kernel pair: it serves up to 256 * 4096 nodes; the commit + scans + lists form
+    is held by tests/test_gpu_pool.py)."""
     from geobi_gnn_amd.graph import Graph
     from geobi_gnn_amd import net_util, ops
     ei = _sym_graph(n, m, seed=n + 1, loops=False)
