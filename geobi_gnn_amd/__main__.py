@@ -4,7 +4,8 @@
   python -m geobi_gnn_amd denoise --model net.pt --data_dir DIR [--out_dir DIR/result] [--sub_size 20000]
   python -m geobi_gnn_amd denoise --method bnf --data_dir DIR [--normal_iters 20] [--sigma_r 0.35] [--sigma_s 1.0] [--n_iter 20]
   python -m geobi_gnn_amd denoise --method gnf --data_dir DIR [the same flags]
-  python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original
+  python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original [--align [--scale]] [--free]
+  python -m geobi_gnn_amd align --data_dir DIR --target_dir DIR2 [--out_dir DIR/aligned] [--scale] [--reflect] [--max_iter 100]
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
   python -m geobi_gnn_amd clean --data_dir DIR [--out_dir DIR/clean] [--weld_tol 0] [--no_weld] [--no_manifold]
   python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold] [--orient] [--min_component N]
@@ -28,7 +29,10 @@ noisy/NAME_n*.obj of equal size (welding noisy coordinates would be wrong: dupli
 winds the faces of every connected part consistently before the half-edge rule, which otherwise drops one of every two
 neighbours wound in opposite senses; `--min_component N` drops the edge-connected parts of fewer than N faces (scan debris).
 `info` prints what a file is before any of that is chosen: edges, boundary, complex and inconsistent edges, parts, whether
-it is closed and orientable.  All device work runs in this one process.
+it is closed and orientable.  `align` (ops.icp) brings every DIR/NAME_*.obj -- or DIR/NAME.obj where a stem has none -- into
+the frame of DIR2/NAME.obj by rigid point-to-point ICP and writes it with its own faces; the two meshes may differ in size.
+`eval --align` does the same before it scores (AlignInfo.txt beside ErrorInfo_h.txt), `eval --free` scores pairs whose
+vertex counts or face tables differ (ErrorInfo_free.txt).  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -175,13 +179,65 @@ def evaluate(opt):
     stats = {}
     t0 = time.time()
     try:
-        rows, _ = mesheval.eval_dirs(opt.result_dir, opt.original_dir, device=dev, stats=stats)
+        rows, _ = mesheval.eval_dirs(opt.result_dir, opt.original_dir, device=dev, stats=stats, align=opt.align, free=opt.free,
+                                     estimate_scale=opt.scale)
     except (ValueError, OSError, GeobiError) as e:
         print('eval failed: %s' % e, file=sys.stderr)
         return 1
     print('%d pairs in %.3f s (reading OBJ %.3f s, device work %.3f s)'
           % (len(rows), time.time() - t0, stats.get('parse', 0.0), stats.get('device', 0.0)))
     return 0 if rows else 1
+
+
+def align_list(data_dir, target_dir):
+    """[(source file, target file)] in sorted order: mesheval.pair_files' pairing, every target_dir/NAME.obj with every
+    data_dir/NAME_*.obj, and with data_dir/NAME.obj where the stem has no NAME_*.obj."""
+    jobs = []
+    for target in sorted(glob.glob(os.path.join(glob.escape(target_dir), '*.obj'))):
+        stem = os.path.basename(target)[:-4]
+        found = sorted(glob.glob(os.path.join(glob.escape(data_dir), glob.escape(stem) + '_*.obj')))
+        same = os.path.join(data_dir, stem + '.obj')
+        if not found and os.path.isfile(same):
+            found = [same]
+        jobs.extend((f, target) for f in found)
+    return jobs
+
+
+def align(opt):
+    """Every source mesh of --data_dir aligned to its target of --target_dir by rigid ICP on the device (mesheval.align),
+    written to --out_dir with aligned vertices and its own faces."""
+    from . import mesheval, meshio
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    jobs = align_list(opt.data_dir, opt.target_dir)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'aligned')
+    os.makedirs(out_dir, exist_ok=True)
+    print('\nAlign, scale %s, reflections %s, max_iter %d, rmse_thr %g, %d files ...\n'
+          % ('on' if opt.scale else 'off', 'on' if opt.reflect else 'off', opt.max_iter, opt.rmse_thr, len(jobs)), flush=True)
+    failed = 0
+    for source, target in jobs:
+        t0 = time.time()
+        try:
+            points, faces = meshio.read_obj(source)
+            t_points, _ = meshio.read_obj(target)
+            if points.shape[0] == 0 or t_points.shape[0] == 0:
+                raise ValueError('%s or its target %s has no vertices' % (source, target))
+            res = mesheval.align(points, t_points, device=dev, estimate_scale=opt.scale, allow_reflection=opt.reflect,
+                                 max_iterations=opt.max_iter, relative_rmse_thr=opt.rmse_thr)
+            out_file = os.path.join(out_dir, os.path.basename(source))
+            meshio.write_obj(out_file, res.xt.cpu().numpy(), faces)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+            continue
+        info = mesheval.align_info(res)
+        print("iterations: %3d,  converged: %s,  rmse: %.6e,  scale: %.6f,  angle: %10.6f,  shift: %.6f,  time: %7.4f s,  '%s'"
+              % (info['icp_iterations'], 'yes' if info['icp_converged'] else 'no', info['icp_rmse'], info['icp_scale'],
+                 info['icp_angle'], info['icp_shift'], time.time() - t0, os.path.basename(out_file)), flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d of %d files skipped' % (failed, len(jobs)), file=sys.stderr)
+    return 1 if failed or not jobs else 0
 
 
 def noise(opt):
@@ -405,7 +461,23 @@ def build_parser():
     e.add_argument('--result_dir', type=str, required=True)
     e.add_argument('--original_dir', type=str, required=True)
     e.add_argument('--gpu', type=int, default=-1)
+    e.add_argument('--align', action='store_true',
+                   help='bring every result into the frame of its ground truth by rigid ICP first; writes AlignInfo.txt')
+    e.add_argument('--scale', action='store_true', help='with --align: estimate a scale as well')
+    e.add_argument('--free', action='store_true',
+                   help='score pairs whose vertex counts or face tables differ (surface distances both ways, normals by the '
+                        'nearest ground-truth triangle); writes ErrorInfo_free.txt')
     e.set_defaults(fn=evaluate)
+    a = sub.add_parser('align', help='align every mesh of a folder to its target by rigid ICP and write it with its own faces')
+    a.add_argument('--data_dir', type=str, required=True, help='the meshes to move: NAME_*.obj, or NAME.obj')
+    a.add_argument('--target_dir', type=str, required=True, help='holds the targets NAME.obj')
+    a.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/aligned')
+    a.add_argument('--scale', action='store_true', help='estimate a scale as well (a similarity instead of a rigid motion)')
+    a.add_argument('--reflect', action='store_true', help='allow reflections (det R = -1)')
+    a.add_argument('--max_iter', type=int, default=100, help='iterations at most; a pair that hits it is written and reported')
+    a.add_argument('--rmse_thr', type=float, default=1e-6, help='stop once the relative change of the rmse is at most this')
+    a.add_argument('--gpu', type=int, default=-1)
+    a.set_defaults(fn=align)
     n = sub.add_parser('noise', help='write noisy/NAME_n<k>.obj for every original/NAME.obj, drawn on the device')
     from .meshnoise import DIRECTIONS, KINDS
     from .trainer import noise_levels_arg
@@ -450,6 +522,13 @@ def parse_args(argv=None):
             for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component'):
                 if getattr(opt, flag + '_given', False):
                     ap.error('denoise: --%s needs --clean' % flag)
+    if opt.command == 'eval' and opt.scale and not opt.align:
+        ap.error('eval: --scale needs --align')
+    if opt.command == 'align':
+        if opt.max_iter < 1:
+            ap.error('align: --max_iter is at least 1, not %d' % opt.max_iter)
+        if not opt.rmse_thr >= 0:
+            ap.error('align: --rmse_thr is not negative, got %r' % opt.rmse_thr)
     return opt
 
 

@@ -563,6 +563,26 @@ int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, cons
   NOTNULL(p); NOTNULL(t); NOTNULL(idx_a); NOTNULL(segptr); NOTNULL(members); NOTNULL(gout); NOTNULL(gp);
   return chamfer_bwd(p, t, idx_a, segptr, members, qptr, tptr, P, gout, gp, S(stream));
 }
+size_t geobi_icp_ws_bytes(const int64_t* xptr, int P) { (void)xptr; return icp_ws_bytes(P); }
+int geobi_icp_init(void* state, int P, const double* init, void* stream) {
+  GEOBI_REQUIRE(P >= 1, "%s: P = %d parts (at least one)", __func__, P);
+  NOTNULL(state);
+  return icp_init((double*)state, P, init, S(stream));
+}
+int geobi_icp_apply(const float* x, const int64_t* xptr, int P, const void* state, int mode, float* out, void* stream) {
+  GEOBI_TRY(parts_check(__func__, xptr, xptr, P));
+  GEOBI_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0: s x R + T, 1: s x R^T)", __func__, mode);
+  NOTNULL(x); NOTNULL(state); NOTNULL(out);
+  return icp_apply(x, xptr, P, (const double*)state, mode, out, S(stream));
+}
+int geobi_icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P,
+                   int flags, double relative_rmse_thr, void* state, float* xt, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_TRY(parts_check(__func__, xptr, yptr, P));
+  GEOBI_REQUIRE((flags & ~3) == 0, "%s: flags %d (bit 0 estimate_scale, bit 1 allow_reflection)", __func__, flags);
+  GEOBI_REQUIRE(relative_rmse_thr >= 0.0, "%s: relative_rmse_thr %g is negative", __func__, relative_rmse_thr);
+  NOTNULL(x); NOTNULL(y); NOTNULL(idx); NOTNULL(state); NOTNULL(xt); NOTNULL(ws);
+  return icp_step(x, y, idx, xptr, yptr, P, flags, relative_rmse_thr, (double*)state, xt, ws, ws_bytes, S(stream));
+}
 size_t geobi_dist_summary_ws_bytes(int64_t n) { return dist_summary_ws_bytes(n); }
 int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t ws_bytes, void* stream) {
   SIZES(n, 0);

@@ -371,6 +371,12 @@ int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const i
                 size_t ws_bytes, hipStream_t s);
 int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
                 const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, hipStream_t s);
+// icp.hip (rigid point-to-point ICP of a union batch on top of nearest_parts)
+size_t icp_ws_bytes(int P);
+int icp_init(double* state, int P, const double* init, hipStream_t s);
+int icp_apply(const float* x, const int64_t* xptr, int P, const double* state, int mode, float* out, hipStream_t s);
+int icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P, int flags,
+             double relative_rmse_thr, double* state, float* xt, void* ws, size_t ws_bytes, hipStream_t s);
 // noise.hip (synthetic mesh noise: counter-based Philox4x32-10, one counter per vertex)
 int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
                uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s);

@@ -12,8 +12,8 @@ import os
 import torch
 
 from . import _lib as L
-from . import meshin, meshio, meshprep, network
-from .data_util import computer_face_normal
+from . import meshin, meshio, meshprep, network, ops
+from .data_util import computer_face_normal, face_centroids
 
 
 def _points(t, what):
@@ -80,10 +80,34 @@ def mean_edge_length(points, faces):
     return meshprep.mean_edge_length(points, meshprep.ring_graph(0, faces, rowptr, lst, V))
 
 
-def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None):
+def align(points, target_points, device=None, estimate_scale=False, allow_reflection=False, max_iterations=100,
+          relative_rmse_thr=1e-6):
+    """Rigid ICP of one point set onto another (ops.icp; arrays or tensors, sizes may differ) -> ops.IcpResult: xt the
+    aligned points on the device, R [1,3,3], T [1,3], s, rmse, iterations, converged [1] on the host."""
+    dev = meshin.default_device(device, points)
+    p, t = meshin.to_device(points, dev, torch.float32), meshin.to_device(target_points, dev, torch.float32)
+    return ops.icp(_points(p, 'points'), _points(t, 'target points'), estimate_scale=estimate_scale,
+                   allow_reflection=allow_reflection, max_iterations=max_iterations, relative_rmse_thr=relative_rmse_thr)
+
+
+def align_info(res):
+    """The AlignInfo.txt fields of a single-pair IcpResult: iterations, converged, rmse, scale, the rotation angle in
+    degrees and |T|."""
+    import math
+    cos = max(-1.0, min(1.0, (float(res.R[0].diagonal().sum()) - 1.0) / 2.0))
+    return {'icp_iterations': int(res.iterations[0]), 'icp_converged': bool(res.converged[0]), 'icp_rmse': float(res.rmse[0]),
+            'icp_scale': float(res.s[0]), 'icp_angle': math.degrees(math.acos(cos)), 'icp_shift': float(res.T[0].norm())}
+
+
+_ALIGN_KEYS = ('icp_rmse', 'icp_iterations', 'icp_converged')
+_align_points = align          # the scoring functions below take a flag of the same name
+
+
+def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None, align=False, estimate_scale=False):
     """The numbers of one (result, ground truth) pair, code/data_util.py:584-616.  Arrays or tensors; the work runs on
     `device` (default: the tensors' device, else the current one).  gt_faces defaults to `faces` (a denoised mesh keeps its
-    connectivity).  Returns a dict:
+    connectivity).  align: the result points are first brought into the ground truth's frame by rigid ICP (align();
+    estimate_scale: with a scale), and the dict gains icp_rmse, icp_iterations, icp_converged.  Returns a dict:
 
       num_f, err_face (mean |n_r - n_o|^2), angle (mean angle in degrees, network.error_n), num_v,
       err_v (mean distance to the nearest ground-truth vertex), err_v_norm (the same over `scale`, the ground truth's
@@ -99,6 +123,10 @@ def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None):
                          % (pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]))
     same = fo is fr                                          # one table, also when handed in twice: one check
     fr = meshin.device_mesh(pr, fr, dev)[1]
+    icp = None
+    if align:
+        icp = _align_points(pr, po, dev, estimate_scale=estimate_scale)
+        pr = icp.xt
     fo = fr if same else meshin.device_mesh(po, fo, dev)[1]
     V, F = pr.shape[0], fr.shape[0]
     nr, no = computer_face_normal(pr, fr), computer_face_normal(po, fo)
@@ -112,8 +140,53 @@ def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None):
     host = torch.cat([err_face.reshape(1).double(), angle.reshape(1).double(), scale.double(), s_ro, s_or, s_surf]).tolist()
     err_face, angle, scale = host[0], host[1], host[2]
     err_v, surf = host[3] / V, host[7] / V
-    return {'num_f': F, 'err_face': err_face, 'angle': angle, 'num_v': V, 'err_v': err_v, 'err_v_norm': err_v / scale,
-            'surf': surf, 'surf_norm': surf / scale, 'hausdorff': max(host[4], host[6]), 'scale': scale}
+    row = {'num_f': F, 'err_face': err_face, 'angle': angle, 'num_v': V, 'err_v': err_v, 'err_v_norm': err_v / scale,
+           'surf': surf, 'surf_norm': surf / scale, 'hausdorff': max(host[4], host[6]), 'scale': scale}
+    if icp is not None:
+        info = align_info(icp)
+        row.update((k, info[k]) for k in _ALIGN_KEYS)
+    return row
+
+
+def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, align=False, estimate_scale=False):
+    """The numbers of a pair whose vertex counts, face tables or numbering DIFFER (another tool's output, a scan against
+    its CAD model): nothing here pairs row i with row i.  align / estimate_scale as in eval_pair.  Returns a dict:
+
+      num_f, num_v, num_f_gt, num_v_gt,
+      angle (mean over the result's faces of the angle, in degrees, between the face normal and the normal of the
+      ground-truth triangle nearest to the face's centroid: point_to_mesh's face index, a gather, network.error_n),
+      surf (mean distance from the result's vertices to the ground-truth SURFACE), surf_back (from the ground truth's
+      vertices to the result's surface), hausdorff (the larger of the two directed maxima of those distances),
+      scale (the ground truth's mean edge length), surf_norm, surf_back_norm (over scale),
+      and with align: icp_rmse, icp_iterations, icp_converged."""
+    dev = meshin.default_device(device, result_points)
+    pr, fr = meshin.device_mesh(result_points, result_faces, dev)
+    po, fo = meshin.device_mesh(gt_points, gt_faces, dev)
+    if min(pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]) == 0:
+        raise ValueError('eval_free: empty mesh (result V = %d, F = %d, ground truth V = %d, F = %d)'
+                         % (pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]))
+    icp = None
+    if align:
+        icp = _align_points(pr, po, dev, estimate_scale=estimate_scale)
+        pr = icp.xt
+    nr, no = computer_face_normal(pr, fr).contiguous(), computer_face_normal(po, fo).contiguous()
+    _, near = point_to_mesh(face_centroids(pr, fr), po, fo)
+    ng = torch.empty_like(nr)
+    L.call('geobi_gather_rows', L.ptr(no), L.ptr(near), 3, near.shape[0], L.ptr(ng), L.stream())
+    angle = network.error_n(nr, ng)
+    scale = mean_edge_length(po, fo)
+    d_ro, _ = point_to_mesh(pr, po, fo)
+    d_or, _ = point_to_mesh(po, pr, fr)
+    host = torch.cat([angle.reshape(1).double(), scale.double(), dist_summary(d_ro), dist_summary(d_or)]).tolist()
+    scale = host[1]
+    surf, back = host[2] / pr.shape[0], host[4] / po.shape[0]
+    row = {'num_f': fr.shape[0], 'num_v': pr.shape[0], 'num_f_gt': fo.shape[0], 'num_v_gt': po.shape[0], 'angle': host[0],
+           'surf': surf, 'surf_back': back, 'hausdorff': max(host[3], host[5]), 'scale': scale, 'surf_norm': surf / scale,
+           'surf_back_norm': back / scale}
+    if icp is not None:
+        info = align_info(icp)
+        row.update((k, info[k]) for k in _ALIGN_KEYS)
+    return row
 
 
 def pair_files(dir_result, dir_original):
@@ -148,35 +221,93 @@ def totals(rows):
 _COLUMNS = ('num_f', 'err_face', 'angle', 'num_v', 'err_v', 'err_v_norm', 'surf', 'surf_norm', 'hausdorff')
 
 
-def eval_dirs(dir_result, dir_original, device=None, stats=None):
+_FREE_COLUMNS = ('num_f', 'num_v', 'num_f_gt', 'num_v_gt', 'angle', 'surf', 'surf_norm', 'surf_back', 'surf_back_norm',
+                 'hausdorff')
+_FREE_FMT = '{0:<{1}}  {2:>7}  {3:>7}  {4:>7}  {5:>7}  {6:9.6f}  {7:.6f}  {8:9.6f}  {9:.6f}  {10:9.6f}  {11:.6f}\n'
+_ALIGN_FMT = '{0:<{1}}  {2:>4}  {3:>3}  {4:.6e}  {5:.6f}  {6:10.6f}  {7:.6f}\n'
+
+
+def free_totals(rows):
+    """Face- / vertex-count weighted means of eval_free's columns (the back distances over the ground truth's vertices);
+    hausdorff is the maximum over the files."""
+    n = {k: sum(r[k] for r in rows) for k in ('num_f', 'num_v', 'num_f_gt', 'num_v_gt')}
+
+    def mean(key, weight):
+        return sum(r[key] * r[weight] for r in rows) / n[weight]
+    n.update(angle=mean('angle', 'num_f'), surf=mean('surf', 'num_v'), surf_norm=mean('surf_norm', 'num_v'),
+             surf_back=mean('surf_back', 'num_v_gt'), surf_back_norm=mean('surf_back_norm', 'num_v_gt'),
+             hausdorff=max(r['hausdorff'] for r in rows))
+    return n
+
+
+def align_line(name, width, info):
+    return _ALIGN_FMT.format(name, width, info['icp_iterations'], 'yes' if info['icp_converged'] else 'no', info['icp_rmse'],
+                             info['icp_scale'], info['icp_angle'], info['icp_shift'])
+
+
+def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, free=False, estimate_scale=False):
     """eval_denoising_result(dir_result, dir_original): every pair of pair_files scored with eval_pair, the per-file
     and totals lines printed and written to dir_result/ErrorInfo_h.txt in the reference's format with three columns
     appended (surf, surf_norm, hausdorff).  A result whose V or F differs from its ground truth is a ValueError naming
     both files.  stats (optional dict): seconds spent in 'parse' (reading the OBJ files) and 'device' are added.
-    Returns (rows, totals) -- rows carry 'file'."""
+    align: every result is first aligned to its ground truth by rigid ICP (estimate_scale: with a scale) and
+    dir_result/AlignInfo.txt lists per file: iterations, converged, rmse, scale, rotation angle in degrees, |T|.
+    free: every pair is scored with eval_free instead (sizes may differ) and dir_result/ErrorInfo_free.txt is written;
+    ErrorInfo_h.txt is not.  Returns (rows, totals) -- rows carry 'file'."""
     import time
     pairs = pair_files(dir_result, dir_original)
     if not pairs:
         print('--- empty data ---')
         return [], None
+    dev = meshin.default_device(device)
     width = max(len(os.path.basename(r)) for r, _ in pairs)
-    rows = []
+    rows, infos = [], []
     for file_r, file_o in pairs:
         t0 = time.time()
         pr, fr = meshio.read_obj(file_r)
         po, fo = meshio.read_obj(file_o)
         t1 = time.time()
-        if pr.shape != po.shape or fr.shape != fo.shape:
+        if not free and (pr.shape != po.shape or fr.shape != fo.shape):
             raise ValueError('%s (V = %d, F = %d) and its ground truth %s (V = %d, F = %d) differ in size'
                              % (file_r, pr.shape[0], fr.shape[0], file_o, po.shape[0], fo.shape[0]))
-        row = eval_pair(pr, fr, po, gt_faces=fo, device=device)
+        if align:
+            res = _align_points(pr, po, dev, estimate_scale=estimate_scale)
+            infos.append(align_info(res))
+            pr = res.xt
+        row = eval_free(pr, fr, po, fo, device=dev) if free else eval_pair(pr, fr, po, gt_faces=fo, device=dev)
+        if align:
+            row.update((k, infos[-1][k]) for k in _ALIGN_KEYS)
         row['file'] = os.path.basename(file_r)
         rows.append(row)
         if stats is not None:
             stats['parse'] = stats.get('parse', 0.0) + (t1 - t0)
             stats['device'] = stats.get('device', 0.0) + (time.time() - t1)
-        print('{0:<{1}}  {2:>7}  {3:.4f}  {4:7.4f}  {5:>7}  {6:7.4f}  {7:.4f}  {8:7.4f}  {9:.4f}  {10:7.4f}'.format(
-            row['file'], width, *[row[k] for k in _COLUMNS]))
+        if free:
+            print('{0:<{1}}  {2:>7}  {3:>7}  {4:>7}  {5:>7}  {6:7.4f}  {7:.4f}  {8:7.4f}  {9:.4f}  {10:7.4f}  {11:.4f}'.format(
+                row['file'], width, *[row[k] for k in _FREE_COLUMNS]))
+        else:
+            print('{0:<{1}}  {2:>7}  {3:.4f}  {4:7.4f}  {5:>7}  {6:7.4f}  {7:.4f}  {8:7.4f}  {9:.4f}  {10:7.4f}'.format(
+                row['file'], width, *[row[k] for k in _COLUMNS]))
+    if align:
+        file_txt = os.path.join(dir_result, 'AlignInfo.txt')
+        with open(file_txt, 'w') as f:
+            f.write('Align:  iterations  converged  rmse  scale  angle_deg  shift \n')
+            for row, info in zip(rows, infos):
+                f.write(align_line(row['file'], width, info))
+        print('%s saved.' % file_txt)
+    if free:
+        tot = free_totals(rows)
+        print('{0:>7}  {1:>7}  {2:>7}  {3:>7}  {4:7.4f}  {5:.4f}  {6:7.4f}  {7:.4f}  {8:7.4f}  {9:.4f} \n'.format(
+            *[tot[k] for k in _FREE_COLUMNS]))
+        file_txt = os.path.join(dir_result, 'ErrorInfo_free.txt')
+        with open(file_txt, 'w') as f:
+            f.write('Error_free:  num_f  num_v  num_f_gt  num_v_gt  angle_mean  surf  surf_norm  surf_back  surf_back_norm  hausdorff \n')
+            f.write(_FREE_FMT.format('', width, *[tot[k] for k in _FREE_COLUMNS]))
+            f.write('\n')
+            for row in rows:
+                f.write(_FREE_FMT.format(row['file'], width, *[row[k] for k in _FREE_COLUMNS]))
+        print('%s saved.' % file_txt)
+        return rows, tot
     tot = totals(rows)
     print('{0:>8}  {1:.4f}  {2:7.4f}  {3:>8}  {4:7.4f}  {5:.4f}  {6:7.4f}  {7:.4f}  {8:7.4f} \n'.format(
         *[tot[k] for k in _COLUMNS]))

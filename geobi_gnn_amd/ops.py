@@ -592,3 +592,132 @@ def sided_loss(np_, n, fc_p, fc, fptr=None, weights=None):
     ng = torch.empty((idx.shape[0], 3), dtype=torch.float32, device=n.device)
     L.call('geobi_gather_rows', L.ptr(n), L.ptr(idx), 3, idx.shape[0], L.ptr(ng), L.stream())
     return row_loss(np_, ng, 0, weights, 1.0 if weights is not None else None)
+
+
+# ------------------------------------------------------- rigid ICP alignment (apply_icp's step)
+ICP_STATE = 24   # GEOBI_ICP_STATE
+
+
+class IcpResult(object):
+    """What ops.icp returns.  xt float32 [Q, 3] on the device: the aligned points s x R + T; `state` the raw device
+    float64 [P, GEOBI_ICP_STATE] (include/geobi_hip.h).  The rest is the final host read of that state, per part, as CPU
+    tensors: R float64 [P, 3, 3], T float64 [P, 3], s, rmse float64 [P], iterations int64 [P], converged bool [P]."""
+    __slots__ = ('xt', 'R', 'T', 's', 'rmse', 'iterations', 'converged', 'state', 'xptr')
+
+    def __init__(self, xt, state, xptr):
+        host = state.cpu()
+        self.xt, self.state, self.xptr = xt, state, xptr
+        self.R, self.T, self.s = host[:, :9].reshape(-1, 3, 3).clone(), host[:, 9:12].clone(), host[:, 12].clone()
+        self.rmse, self.iterations, self.converged = host[:, 13].clone(), host[:, 15].long(), host[:, 16] != 0
+
+
+def _icp_state(state, P):
+    L.require_device(state, 'ICP state')
+    if state.dtype != torch.float64 or tuple(state.shape) != (P, ICP_STATE) or not state.is_contiguous():
+        raise L.GeobiError('ICP state must be a contiguous float64 [%d, %d] tensor, got %s %s'
+                           % (P, ICP_STATE, state.dtype, tuple(state.shape)))
+    return state
+
+
+def icp_init(P, device, init=None):
+    """A fresh state for P parts: the identity, or `init` [P, 13] = (R row-major, T, s) per part (array or tensor)."""
+    state = torch.empty((int(P), ICP_STATE), dtype=torch.float64, device=device)
+    L.require_device(state, 'ICP state')
+    if init is not None:
+        init = torch.as_tensor(init).to(device=device, dtype=torch.float64).contiguous()
+        if tuple(init.shape) != (int(P), 13):
+            raise L.GeobiError('icp: init must be [%d, 13] (R row-major, T, s per part), got %s' % (P, tuple(init.shape)))
+    L.call('geobi_icp_init', L.ptr(state), int(P), L.ptr(init), L.stream())
+    return state
+
+
+def icp_apply(x, state, xptr=None, mode=0):
+    """geobi_icp_apply: mode 0 -> s x R + T, mode 1 -> s x R^T (the gradient of mode 0 to x for a constant transform),
+    per part of `xptr`, computed in fp64 and rounded once -> float32 [Q, 3]."""
+    x = _points3(x, 'points')
+    xp = _part_ptr(xptr, x.shape[0], 'xptr')
+    P = len(xp) - 1
+    _icp_state(state, P)
+    if mode not in (0, 1):
+        raise L.GeobiError('icp_apply: mode %r (0: s x R + T, 1: s x R^T)' % (mode,))
+    (xa, xc) = _c_ptr(xp)
+    out = torch.empty_like(x)
+    L.call('geobi_icp_apply', L.ptr(x), xc, P, L.ptr(state), int(mode), L.ptr(out), L.stream())
+    return out
+
+
+def icp_step(x, y, idx, state, xt, xptr=None, yptr=None, relative_rmse_thr=1e-6, estimate_scale=False,
+             allow_reflection=False):
+    """geobi_icp_step: for every part that has not converged, the Umeyama alignment of the ORIGINAL x to y[idx], the new
+    xt (written in place) and the new state (updated in place).  idx int32 [Q]: rows of y, as ops.nearest_parts(xt, y)
+    returns them.  Nothing is read back: no sync."""
+    x, y = _points3(x, 'points'), _points3(y, 'target points')
+    Q = x.shape[0]
+    xp, yp = _part_ptr(xptr, Q, 'xptr'), _part_ptr(yptr, y.shape[0], 'yptr')
+    if len(xp) != len(yp):
+        raise L.GeobiError('icp_step: %d point parts but %d target parts' % (len(xp) - 1, len(yp) - 1))
+    P = len(xp) - 1
+    _icp_state(state, P)
+    L.require_device(idx, 'idx')
+    L.require_device(xt, 'xt')
+    if idx.dtype != torch.int32 or tuple(idx.shape) != (Q,) or not idx.is_contiguous():
+        raise L.GeobiError('icp_step: idx must be a contiguous int32 [%d] tensor, got %s %s' % (Q, idx.dtype, tuple(idx.shape)))
+    if xt.dtype != torch.float32 or xt.shape != x.shape or not xt.is_contiguous():
+        raise L.GeobiError('icp_step: xt must be a contiguous float32 %s tensor, got %s %s'
+                           % (tuple(x.shape), xt.dtype, tuple(xt.shape)))
+    if xt.data_ptr() == x.data_ptr():
+        raise L.GeobiError('icp_step: xt is x itself (every step aligns the ORIGINAL points; give xt its own storage)')
+    if not relative_rmse_thr >= 0:
+        raise L.GeobiError('icp_step: relative_rmse_thr %r is negative' % (relative_rmse_thr,))
+    (xa, xc), (ya, yc) = _c_ptr(xp), _c_ptr(yp)
+    ws = L.workspace(L.lib().geobi_icp_ws_bytes(xc, P), x.device)
+    flags = (1 if estimate_scale else 0) | (2 if allow_reflection else 0)
+    L.call('geobi_icp_step', L.ptr(x), L.ptr(y), L.ptr(idx), xc, yc, P, flags, float(relative_rmse_thr), L.ptr(state),
+           L.ptr(xt), L.ptr(ws), ws.numel(), L.stream())
+
+
+def icp(x, y, xptr=None, yptr=None, init=None, max_iterations=100, relative_rmse_thr=1e-6, estimate_scale=False,
+        allow_reflection=False, check_every=4):
+    """Rigid point-to-point ICP of x [Q, 3] onto y [M, 3], per part of a union batch (host part pointers as in
+    nearest_parts): pytorch3d's iterative_closest_point as loss_v(..., apply_icp=True) calls it (code/network.py:364-367).
+    xt = s x R + T; every iteration is nearest_parts(xt, y) followed by icp_step.  A part stops at iteration k >= 2 once
+    (prev_rmse - rmse) / prev_rmse <= relative_rmse_thr, or when rmse == 0, and is frozen from then on; the loop ends when
+    every part has stopped or after max_iterations.  The host reads the converged flags once every `check_every` iterations
+    and once at the end; because converged parts are frozen the result does not depend on check_every.
+    init: [P, 13] (R row-major, T, s) per part, applied to form the first xt only.  -> IcpResult."""
+    x, y = _points3(x, 'points'), _points3(y, 'target points')
+    xp, yp = _part_ptr(xptr, x.shape[0], 'xptr'), _part_ptr(yptr, y.shape[0], 'yptr')
+    if len(xp) != len(yp):
+        raise L.GeobiError('icp: %d point parts but %d target parts' % (len(xp) - 1, len(yp) - 1))
+    if int(max_iterations) < 1 or int(check_every) < 1:
+        raise L.GeobiError('icp: max_iterations and check_every are at least 1, got %r and %r' % (max_iterations, check_every))
+    state = icp_init(len(xp) - 1, x.device, init)
+    xt = icp_apply(x, state, xp, 0)
+    for k in range(1, int(max_iterations) + 1):
+        _, idx = nearest_parts(xt, y, xp, yp)
+        icp_step(x, y, idx, state, xt, xp, yp, relative_rmse_thr, estimate_scale, allow_reflection)
+        if k % int(check_every) == 0 and k < int(max_iterations) and bool((state[:, 16] != 0).all()):
+            break
+    return IcpResult(xt, state, xp)
+
+
+class IcpAlignFn(Function):
+    """x -> the ICP-aligned x with the transform treated as a CONSTANT: forward icp(x.detach(), y).xt, backward
+    icp_apply(grad, mode=1) = s grad R^T.  pytorch3d differentiates through the SVD of the covariance; this does not
+    (DESIGN.md 4j): the gradient is that of a fixed similarity, which is what moves vertices inside the aligned frame."""
+
+    @staticmethod
+    def forward(ctx, x, y, xptr, yptr, kw):
+        res = icp(x.detach(), y, xptr, yptr, **kw)
+        ctx.state, ctx.xp = res.state, res.xptr
+        return res.xt
+
+    @staticmethod
+    def backward(ctx, gout):
+        return icp_apply(gout, ctx.state, ctx.xp, 1), None, None, None, None
+
+
+def icp_align(x, y, xptr=None, yptr=None, **kw):
+    """The points x aligned to y by ops.icp (same keywords), differentiable with respect to x for a constant transform
+    (IcpAlignFn).  network.loss_v(..., apply_icp=True) keeps raising; compose loss_v(ops.icp_align(vp, v), v, 'CD')."""
+    return IcpAlignFn.apply(x, y, xptr, yptr, kw)

@@ -348,6 +348,33 @@ int geobi_chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, c
 int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
                       const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, void* stream);
 
+/* ---------------------------------------------------------------- rigid ICP alignment ----
+ * Point-to-point ICP of x [Q, 3] onto y [M, 3] per part of a disjoint-union batch (host part pointers as above): what
+ * loss_v(..., apply_icp=True) asks of pytorch3d's iterative_closest_point (code/network.py:15,364-367).  The convention is
+ * xt = s x R + T with row vectors, det R = +1 unless reflections are allowed.  One iteration is geobi_nearest_parts(xt, y)
+ * followed by geobi_icp_step, which aligns the ORIGINAL x to y[idx] by Umeyama's closed form in fp64 (3x3 SVD by one-sided
+ * Jacobi: C^T C is never formed), writes xt = float32(s x R + T) rounded once, and takes rmse from the fp64 values.  A part
+ * converges at iteration k if k >= 2, prev_rmse > 0 and (prev_rmse - rmse) / prev_rmse <= relative_rmse_thr, or if rmse
+ * == 0; a converged part is FROZEN: neither its state nor its xt rows are written again, so extra steps change nothing.
+ * The sums are fp64 in a fixed order that depends on the part's own row count only (no atomics): a part gives the same
+ * bits alone and inside a union.  A rank-deficient covariance still yields an orthonormal R with the requested determinant.
+ * state is a DEVICE double [P][GEOBI_ICP_STATE]: 0-8 R row-major, 9-11 T, 12 s, 13 rmse, 14 last relative change,
+ * 15 iterations done, 16 converged (0 / 1), 17 smallest singular value of the last covariance over the largest, 18-23
+ * reserved (0).
+ *   geobi_icp_init    state <- init (DEVICE double [P][13]: R, T, s per part; NULL = identity), slots 13-23 = 0
+ *   geobi_icp_apply   mode 0: out = s x R + T; mode 1: out = s x R^T (the linear part transposed: the gradient of mode 0
+ *                     to x for a constant transform); fp64 inside, rounded once; every part, frozen or not
+ *   geobi_icp_step    the step above for every part whose slot 16 is 0.  flags: bit 0 = estimate_scale (s = tr(E S) /
+ *                     var(x), 1 for var(x) == 0), bit 1 = allow_reflection.  idx [Q] is clamped into the part's own rows
+ *                     of y before the gather: a foreign array never reads outside y.  xt [Q, 3] is updated in place.
+ *                     ws: geobi_icp_ws_bytes(xptr, P)                                                                     */
+#define GEOBI_ICP_STATE 24
+size_t geobi_icp_ws_bytes(const int64_t* xptr, int P);
+int geobi_icp_init(void* state, int P, const double* init, void* stream);
+int geobi_icp_apply(const float* x, const int64_t* xptr, int P, const void* state, int mode, float* out, void* stream);
+int geobi_icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P,
+                   int flags, double relative_rmse_thr, void* state, float* xt, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- synthetic mesh noise ----
  * The reference has NO call site for this: its dataset is an external download (README.md:7) and the generator of its
  * noisy meshes is not in its tree.  out[v] = points[v] + displacement(v), v in [0, V); out may alias points; V == 0 is a
