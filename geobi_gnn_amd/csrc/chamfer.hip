@@ -105,20 +105,21 @@ void fill_job(ChamferJob* job, const int64_t* qptr, const int64_t* tptr, int bas
   }
 }
 
+// the block sums of every launch (kMaxParts parts each)
+double* carve_partials(Arena& a, int P) {
+  const int launches = P < 1 ? 0 : (P + kMaxParts - 1) / kMaxParts;
+  return a.take<double>((size_t)launches * kMaxBlocks);
+}
+
 }  // namespace
 
-size_t chamfer_ws_bytes(int P) {
-  if (P < 1) return 256;
-  const size_t launches = (size_t)(P + kMaxParts - 1) / kMaxParts;
-  return align_up(launches * kMaxBlocks * sizeof(double)) + 256;
-}
+size_t chamfer_ws_bytes(int P) { return carve_bytes([&](Arena& a) { carve_partials(a, P); }); }
 
 int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out, void* ws,
                 size_t ws_bytes, hipStream_t s) {
   Arena ar(ws, ws_bytes);
-  const int launches = (P + kMaxParts - 1) / kMaxParts;
-  double* partial = ar.take<double>((size_t)launches * kMaxBlocks);
-  GEOBI_REQUIRE(ar.ok() && partial, "chamfer_fwd: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
+  double* partial = carve_partials(ar, P);
+  GEOBI_WS_CHECK("chamfer_fwd", ar, ws, ws_bytes);
   int used = 0;
   for (int base = 0; base < P; base += kMaxParts) {
     ChamferJob job;

@@ -16,9 +16,8 @@
 //   compact  used flags by plain stores of one value, two exclusive scans, gathers
 // The only floating-point operation is the division of the grid key.
 #include "common.h"
+#include "rocprim_temp.h"
 #include "../../include/geobi_hip.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace geobi {
 
@@ -27,15 +26,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kFirstBatch = 4;       // rounds enqueued before the first read of the undecided counts
 constexpr int kBatch = 32;           // and per read after that (geobi_read_i32 takes 64 words)
-constexpr uint64_t kNoEdge = (1ull << 48) - 1;     // key of a degenerate face's slots: a == b never is a half-edge
-
-enum FaceState { kUndecided = 0, kKept = 1, kDropped = 2, kDegenerate = 3 };
-
-// one atomic per wave for a count of lanes (integer adds: the total does not depend on their order)
-__device__ __forceinline__ void count_lanes(bool mine, int* __restrict__ counter) {
-  const unsigned long long m = __ballot(mine);
-  if (m != 0 && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(counter, __popcll(m));
-}
 
 // mode 1: the bit pattern with -0.0 folded into +0.0 (what x + 0.0f gives, without an fp operation);
 // mode 2: floorf(x / tol) as int32, plain correctly rounded division; a quotient outside int32 sets bad[0]
@@ -121,9 +111,9 @@ __global__ void face_remap_kernel(const int* __restrict__ fv, const int* __restr
     fc[3 * (size_t)f] = a; fc[3 * (size_t)f + 1] = b; fc[3 * (size_t)f + 2] = c;
     state[f] = deg ? kDegenerate : (manifold ? kUndecided : kKept);
     if (manifold) {
-      keys[3 * (size_t)f] = deg ? kNoEdge : ((uint64_t)a << 24 | (uint64_t)b);
-      keys[3 * (size_t)f + 1] = deg ? kNoEdge : ((uint64_t)b << 24 | (uint64_t)c);
-      keys[3 * (size_t)f + 2] = deg ? kNoEdge : ((uint64_t)c << 24 | (uint64_t)a);
+      keys[3 * (size_t)f] = deg ? kNoEdge : edge_key(a, b);
+      keys[3 * (size_t)f + 1] = deg ? kNoEdge : edge_key(b, c);
+      keys[3 * (size_t)f + 2] = deg ? kNoEdge : edge_key(c, a);
       slots[3 * f] = 3 * f; slots[3 * f + 1] = 3 * f + 1; slots[3 * f + 2] = 3 * f + 2;
     }
   }
@@ -219,69 +209,40 @@ __global__ void compact_faces_kernel(const int* __restrict__ fc, const int* __re
   }
 }
 
-template <typename K>
-size_t sort_temp_bytes(int64_t n) {
-  size_t tb = 0;
-  if (n > 0)
-    (void)rocprim::radix_sort_pairs(nullptr, tb, (K*)nullptr, (K*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n, 0u,
-                                    (unsigned)(8 * sizeof(K)), (hipStream_t)0, false);
-  return tb ? tb : 16;
-}
-
 struct WeldBuffers {
   uint32_t *kx, *ky, *kz, *ka, *kb;
   int *idx, *va, *vb, *flag, *rank, *head, *bad;
-  void *sort_temp, *scan_temp;
-  size_t sort_bytes, scan_bytes;
+  SubWs sort_temp, scan_temp;
 };
-void carve_weld(Arena& a, int64_t V, WeldBuffers& w) {
-  w.kx = a.take<uint32_t>(V); w.ky = a.take<uint32_t>(V); w.kz = a.take<uint32_t>(V);
-  w.ka = a.take<uint32_t>(V); w.kb = a.take<uint32_t>(V);
-  w.idx = a.take<int>(V); w.va = a.take<int>(V); w.vb = a.take<int>(V);
-  w.flag = a.take<int>(V + 1); w.rank = a.take<int>(V + 1); w.head = a.take<int>(V);
-  w.bad = a.take<int>(1);
-  w.sort_bytes = sort_temp_bytes<uint32_t>(V);
-  w.scan_bytes = scan_ws_bytes(V + 1);
-  w.sort_temp = a.take<char>(w.sort_bytes);
-  w.scan_temp = a.take<char>(w.scan_bytes);
+WeldBuffers carve_weld(Arena& a, int64_t V) {
+  return {a.take<uint32_t>(V), a.take<uint32_t>(V), a.take<uint32_t>(V), a.take<uint32_t>(V), a.take<uint32_t>(V),
+          a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V + 1), a.take<int>(V + 1), a.take<int>(V),
+          a.take<int>(1), a.take_ws(sort_pairs_temp_bytes<uint32_t, int>(V)), a.take_ws(scan_ws_bytes(V + 1))};
 }
 
 struct FaceBuffers {
   uint64_t *k_in, *k_out;
   int *v_in, *v_out, *pos, *state_b, *counters;
-  void* sort_temp;
-  size_t sort_bytes;
+  SubWs sort_temp;
 };
-void carve_faces(Arena& a, int64_t F, FaceBuffers& b) {
-  b.k_in = a.take<uint64_t>(3 * F); b.k_out = a.take<uint64_t>(3 * F);
-  b.v_in = a.take<int>(3 * F); b.v_out = a.take<int>(3 * F); b.pos = a.take<int>(3 * F);
-  b.state_b = a.take<int>(F);
-  b.counters = a.take<int>(1 + kBatch);
-  b.sort_bytes = sort_temp_bytes<uint64_t>(3 * F);
-  b.sort_temp = a.take<char>(b.sort_bytes);
+FaceBuffers carve_faces(Arena& a, int64_t F) {
+  return {a.take<uint64_t>(3 * F), a.take<uint64_t>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F),
+          a.take<int>(F), a.take<int>(1 + kBatch), a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(3 * F, kEdgeKeyBits))};
 }
 
 struct CompactBuffers {
   int *used, *vrank, *keep, *frank;
-  void *scan_v, *scan_f;
-  size_t scan_v_bytes, scan_f_bytes;
+  SubWs scan_v, scan_f;
 };
-void carve_compact(Arena& a, int64_t V, int64_t F, CompactBuffers& c) {
-  c.used = a.take<int>(V + 1); c.vrank = a.take<int>(V + 1);
-  c.keep = a.take<int>(F + 1); c.frank = a.take<int>(F + 1);
-  c.scan_v_bytes = scan_ws_bytes(V + 1);
-  c.scan_f_bytes = scan_ws_bytes(F + 1);
-  c.scan_v = a.take<char>(c.scan_v_bytes);
-  c.scan_f = a.take<char>(c.scan_f_bytes);
+CompactBuffers carve_compact(Arena& a, int64_t V, int64_t F) {
+  return {a.take<int>(V + 1), a.take<int>(V + 1), a.take<int>(F + 1), a.take<int>(F + 1),
+          a.take_ws(scan_ws_bytes(V + 1)), a.take_ws(scan_ws_bytes(F + 1))};
 }
 
 }  // namespace
 
 size_t clean_weld_ws_bytes(int64_t V) {
-  Arena a(nullptr, 0);
-  WeldBuffers w;
-  carve_weld(a, V, w);
-  return align_up(a.off) + 256;
+  return carve_bytes([&](Arena& a) { carve_weld(a, V); });
 }
 
 int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
@@ -295,26 +256,25 @@ int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t
     return 0;
   }
   Arena a(ws, ws_bytes);
-  WeldBuffers w;
-  carve_weld(a, V, w);
-  GEOBI_REQUIRE(a.ok() && ws != nullptr, "clean_weld: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const WeldBuffers w = carve_weld(a, V);
+  GEOBI_WS_CHECK("clean_weld", a, ws, ws_bytes);
   GEOBI_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), s));
   weld_keys_kernel<<<blocks, kT, 0, s>>>(points, n, mode, weld_tol, w.kx, w.ky, w.kz, w.idx, w.bad);
   GEOBI_LAUNCH_OK();
   // LSD: least significant word first; each pass is stable, so the order of the earlier passes survives among equal keys
-  size_t tb = w.sort_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp, tb, w.kz, w.kb, w.idx, w.vb, (size_t)V, 0u, 32u, s, false));
+  size_t tb = w.sort_temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp.p, tb, w.kz, w.kb, w.idx, w.vb, (size_t)V, 0u, 32u, s, false));
   gather_u32_kernel<<<blocks, kT, 0, s>>>(w.ky, w.vb, n, w.ka);
   GEOBI_LAUNCH_OK();
-  tb = w.sort_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp, tb, w.ka, w.kb, w.vb, w.va, (size_t)V, 0u, 32u, s, false));
+  tb = w.sort_temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp.p, tb, w.ka, w.kb, w.vb, w.va, (size_t)V, 0u, 32u, s, false));
   gather_u32_kernel<<<blocks, kT, 0, s>>>(w.kx, w.va, n, w.ka);
   GEOBI_LAUNCH_OK();
-  tb = w.sort_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp, tb, w.ka, w.kb, w.va, w.vb, (size_t)V, 0u, 32u, s, false));
+  tb = w.sort_temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp.p, tb, w.ka, w.kb, w.va, w.vb, (size_t)V, 0u, 32u, s, false));
   weld_heads_kernel<<<cdiv(V + 1, kT), kT, 0, s>>>(w.kx, w.ky, w.kz, w.vb, n, w.flag);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(w.scan_temp, w.scan_bytes, w.flag, w.rank, V + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(w.scan_temp.p, w.scan_temp.bytes, w.flag, w.rank, V + 1, s));
   weld_head_index_kernel<<<blocks, kT, 0, s>>>(w.vb, w.flag, w.rank, n, w.head);
   GEOBI_LAUNCH_OK();
   weld_canon_kernel<<<blocks, kT, 0, s>>>(w.vb, w.flag, w.rank, w.head, n, w.bad, canon, counts);
@@ -323,10 +283,7 @@ int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t
 }
 
 size_t clean_faces_ws_bytes(int64_t F) {
-  Arena a(nullptr, 0);
-  FaceBuffers b;
-  carve_faces(a, F, b);
-  return align_up(a.off) + 256;
+  return carve_bytes([&](Arena& a) { carve_faces(a, F); });
 }
 
 int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
@@ -335,16 +292,16 @@ int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V
   *rounds = 0;
   if (F == 0) return 0;
   Arena a(ws, ws_bytes);
-  FaceBuffers b;
-  carve_faces(a, F, b);
-  GEOBI_REQUIRE(a.ok() && ws != nullptr, "clean_faces: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const FaceBuffers b = carve_faces(a, F);
+  GEOBI_WS_CHECK("clean_faces", a, ws, ws_bytes);
   const int n = (int)F, blocks = cdiv(F, kT);
   GEOBI_HIP(hipMemsetAsync(b.counters, 0, sizeof(int), s));
   face_remap_kernel<<<blocks, kT, 0, s>>>(faces, canon, n, (int)V, manifold, faces_canon, state, b.k_in, b.v_in, b.counters);
   GEOBI_LAUNCH_OK();
   if (!manifold) return 0;
-  size_t tb = b.sort_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, 48u, s, false));
+  size_t tb = b.sort_temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
+                                      s, false));
   slot_position_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.v_out, 3 * n, b.pos);
   GEOBI_LAUNCH_OK();
   int* cur = state;
@@ -376,25 +333,21 @@ int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V
 }
 
 size_t clean_compact_ws_bytes(int64_t V, int64_t F) {
-  Arena a(nullptr, 0);
-  CompactBuffers c;
-  carve_compact(a, V, F, c);
-  return align_up(a.off) + 256;
+  return carve_bytes([&](Arena& a) { carve_compact(a, V, F); });
 }
 
 int clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon, int64_t V,
                   int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map, int32_t* vertex_src,
                   int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s) {
   Arena a(ws, ws_bytes);
-  CompactBuffers c;
-  carve_compact(a, V, F, c);
-  GEOBI_REQUIRE(a.ok() && ws != nullptr, "clean_compact: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const CompactBuffers c = carve_compact(a, V, F);
+  GEOBI_WS_CHECK("clean_compact", a, ws, ws_bytes);
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 5, s));
   GEOBI_HIP(hipMemsetAsync(c.used, 0, sizeof(int) * (size_t)(V + 1), s));
   compact_mark_kernel<<<cdiv(F + 1, kT), kT, 0, s>>>(faces_canon, state, (int)F, (int)V, c.keep, c.used, counts);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(c.scan_v, c.scan_v_bytes, c.used, c.vrank, V + 1, s));
-  GEOBI_TRY(scan_exclusive_i32(c.scan_f, c.scan_f_bytes, c.keep, c.frank, F + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(c.scan_v.p, c.scan_v.bytes, c.used, c.vrank, V + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(c.scan_f.p, c.scan_f.bytes, c.keep, c.frank, F + 1, s));
   if (V > 0) {
     compact_vertices_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, canon, c.used, c.vrank, (int)V, points_out, vertex_map,
                                                        vertex_src, counts);

@@ -34,11 +34,13 @@ int set_error(const char* fmt, ...);
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+struct SubWs { void* p; size_t bytes; };   // a workspace inside a workspace
 // bump allocator over a caller-provided workspace (no hipMalloc on the hot path)
 struct Arena {
   char* base;
   size_t off, cap;
-  bool dry;  // dry run: only measure
+  bool dry;             // dry run: only measure
+  bool failed = false;  // a nested size query failed
   Arena(void* p, size_t bytes) : base((char*)p), off(0), cap(bytes), dry(p == nullptr) {}
   template <typename T>
   T* take(size_t n) {
@@ -47,8 +49,39 @@ struct Arena {
     if (dry) return nullptr;
     return (off <= cap) ? (T*)(base + o) : nullptr;
   }
-  bool ok() const { return dry || off <= cap; }
+  // a nested workspace, sized by its own *_ws_bytes or temp-size query (0: that query failed, and so does this carve)
+  SubWs take_ws(size_t bytes) {
+    if (bytes == 0) failed = true;
+    return {take<char>(bytes), bytes};
+  }
+  bool ok() const { return !failed && (dry || off <= cap); }
 };
+
+// ---- the workspace rule: a launcher's takes live in ONE carve, a function that returns its buffers (a
+// braced list: the takes run in the order written); its *_ws_bytes is carve_bytes of that carve (a dry run), the launcher
+// runs the same carve over the caller's memory and checks it with GEOBI_WS_CHECK.
+constexpr size_t kWsSlack = 256;       // beyond the last take: the one slack constant of every workspace size
+template <typename Carve>
+static inline size_t carve_bytes(Carve&& carve) {
+  Arena a(nullptr, 0);
+  carve(a);
+  return a.ok() ? align_up(a.off) + kWsSlack : 0;
+}
+#define GEOBI_WS_CHECK(fn, a, ws, ws_bytes)                                                                        \
+  GEOBI_REQUIRE((a).ok() && (ws) != nullptr, "%s: workspace too small (%zu bytes given, %zu needed)", fn, \
+                (size_t)(ws_bytes), (a).off)
+
+// ---- mesh repair and topology (clean.hip, topo.hip): the state of a face, and the 48-bit key a << 24 | b of a
+// half-edge (clean.hip: directed a -> b; topo.hip: undirected, a < b) -- vertex indices stay below 2^24
+enum FaceState { kUndecided = 0, kKept = 1, kDropped = 2, kDegenerate = 3, kSmallPart = 4 };
+constexpr unsigned kEdgeKeyBits = 48;
+constexpr uint64_t kNoEdge = (1ull << kEdgeKeyBits) - 1;   // key of an excluded face's slots: a == b never is an edge
+__host__ __device__ __forceinline__ uint64_t edge_key(int a, int b) { return (uint64_t)a << 24 | (uint64_t)b; }
+// one atomic per wave for a count of lanes (integer adds: the total does not depend on their order)
+__device__ __forceinline__ void count_lanes(bool mine, int* __restrict__ counter) {
+  const unsigned long long m = __ballot(mine);
+  if (m != 0 && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(counter, __popcll(m));
+}
 
 // ---- part table of a disjoint-union batch, carried in the kernel arguments: no copy of the host arrays, nothing out
 // of stream order.  A launch takes kMaxParts parts; begin[k] .. begin[k + 1] are the rows of its part k.

@@ -363,9 +363,13 @@ int summary_blocks(int64_t n) {
   return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
 
-size_t partial_bytes(const Slicing& c, int64_t Q) {
-  return align_up((size_t)c.slices * Q * sizeof(float)) + align_up((size_t)c.slices * Q * sizeof(int)) + 256;
+// per slice and query row: the best squared distance and its target
+struct Partials { float* d2; int* idx; };
+Partials carve_partials(Arena& a, int slices, int64_t rows) {
+  return {a.take<float>((size_t)slices * rows), a.take<int>((size_t)slices * rows)};
 }
+size_t partials_bytes(int slices, int64_t rows) { return carve_bytes([&](Arena& a) { carve_partials(a, slices, rows); }); }
+double* carve_summary(Arena& a, int blocks) { return a.take<double>((size_t)2 * blocks); }
 
 }  // namespace
 
@@ -375,10 +379,10 @@ int nearest_slices(int64_t Q, int64_t T, int triangles) {
 }
 
 size_t nearest_ws_bytes(int64_t Q, int64_t T) {
-  if (Q <= 0 || T <= 0) return 256;
+  if (Q <= 0 || T <= 0) return partials_bytes(0, 0);
   // enough for either kernel
-  const Slicing a = choose_slices(Q, T, kPointQpl, kPointTile), b = choose_slices(Q, T, kTriQpl, kTriTile);
-  return partial_bytes(a.slices > b.slices ? a : b, Q);
+  return std::max(partials_bytes(choose_slices(Q, T, kPointQpl, kPointTile).slices, Q),
+                  partials_bytes(choose_slices(Q, T, kTriQpl, kTriTile).slices, Q));
 }
 
 int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
@@ -386,11 +390,10 @@ int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* d
   GEOBI_REQUIRE(Q > 0 && T > 0, "nearest_point: empty query or target set (Q = %lld, T = %lld)", (long long)Q, (long long)T);
   const Slicing c = choose_slices(Q, T, kPointQpl, kPointTile);
   Arena ar(ws, ws_bytes);
-  float* pd = ar.take<float>((size_t)c.slices * Q);
-  int* pi = ar.take<int>((size_t)c.slices * Q);
-  GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_point: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
-  nearest_point_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, t, (int)Q, (int)T, c.tiles_per_slice, pd, pi);
-  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, pd, pi, (int)Q, dist, idx);
+  const Partials p = carve_partials(ar, c.slices, Q);
+  GEOBI_WS_CHECK("nearest_point", ar, ws, ws_bytes);
+  nearest_point_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, t, (int)Q, (int)T, c.tiles_per_slice, p.d2, p.idx);
+  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, p.d2, p.idx, (int)Q, dist, idx);
   GEOBI_LAUNCH_OK();
   return 0;
 }
@@ -418,9 +421,8 @@ int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P) {
 }
 
 size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
-  const int smax = nearest_parts_slices(qptr, tptr, P);
-  if (smax == 0) return 256;
-  return align_up((size_t)smax * qptr[P] * sizeof(float)) + align_up((size_t)smax * qptr[P] * sizeof(int)) + 256;
+  const int smax = nearest_parts_slices(qptr, tptr, P);      // 0: the part pointers failed their check
+  return partials_bytes(smax, smax == 0 ? 0 : qptr[P]);
 }
 
 int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,
@@ -429,9 +431,8 @@ int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int
   const int smax = max_part_slices(qptr, tptr, P);
   const int ld = (int)qptr[P];
   Arena ar(ws, ws_bytes);
-  float* pd = ar.take<float>((size_t)smax * ld);
-  int* pi = ar.take<int>((size_t)smax * ld);
-  GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_parts: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
+  const Partials p = carve_partials(ar, smax, ld);
+  GEOBI_WS_CHECK("nearest_parts", ar, ws, ws_bytes);
   for (int base = 0; base < P; base += kMaxParts) {
     PartsJob job;
     fill_parts(&job.q, qptr, base, P);
@@ -444,9 +445,9 @@ int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int
       blocks += c.qblocks;
       if (k < job.q.n) sl_max = std::max(sl_max, c.slices);
     }
-    nearest_parts_kernel<<<dim3(blocks, sl_max), kThreads, 0, s>>>(job, q, t, ld, pd, pi);
+    nearest_parts_kernel<<<dim3(blocks, sl_max), kThreads, 0, s>>>(job, q, t, ld, p.d2, p.idx);
     const int rows = job.q.begin[job.q.n] - job.q.begin[0];
-    nearest_reduce_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(job, pd, pi, ld, d2, idx);
+    nearest_reduce_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(job, p.d2, p.idx, ld, d2, idx);
   }
   GEOBI_LAUNCH_OK();
   return 0;
@@ -458,24 +459,23 @@ int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int6
                 (long long)Q, (long long)V, (long long)F);
   const Slicing c = choose_slices(Q, F, kTriQpl, kTriTile);
   Arena ar(ws, ws_bytes);
-  float* pd = ar.take<float>((size_t)c.slices * Q);
-  int* pi = ar.take<int>((size_t)c.slices * Q);
-  GEOBI_REQUIRE(ar.ok() && pd && pi, "nearest_triangle: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
+  const Partials p = carve_partials(ar, c.slices, Q);
+  GEOBI_WS_CHECK("nearest_triangle", ar, ws, ws_bytes);
   nearest_triangle_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, verts, fv, (int)Q, (int)V, (int)F,
-                                                                         c.tiles_per_slice, pd, pi);
-  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, pd, pi, (int)Q, dist, face);
+                                                                         c.tiles_per_slice, p.d2, p.idx);
+  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, p.d2, p.idx, (int)Q, dist, face);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-size_t dist_summary_ws_bytes(int64_t n) { return align_up((size_t)summary_blocks(n) * 2 * sizeof(double)) + 256; }
+size_t dist_summary_ws_bytes(int64_t n) { return carve_bytes([&](Arena& a) { carve_summary(a, summary_blocks(n)); }); }
 
 int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(n > 0, "dist_summary: empty vector");
   Arena ar(ws, ws_bytes);
   const int blocks = summary_blocks(n);
-  double* partial = ar.take<double>((size_t)2 * blocks);
-  GEOBI_REQUIRE(ar.ok() && partial, "dist_summary: workspace too small");
+  double* partial = carve_summary(ar, blocks);
+  GEOBI_WS_CHECK("dist_summary", ar, ws, ws_bytes);
   dist_summary_partial_kernel<<<blocks, kThreads, 0, s>>>(dist, n, partial);
   dist_summary_final_kernel<<<1, 64, 0, s>>>(partial, blocks, out);
   GEOBI_LAUNCH_OK();

@@ -13,6 +13,7 @@
 //   dz = g W_packed^T;  row pass over targets: s_ijh = dz_i[h,:].x_j, softmax backward -> dl_ij;
 //   column pass over sources j: r_j[h,:] = sum_i q_ijh/deg_i g_i  (same gather kernel, transposed CSR);
 //   dx = [r | dp] [lin.weight ; u.weight];  dW = z^T g;  du = dp^T x;  dc, dbias column sums.
+#include <algorithm>
 #include <cstdlib>
 
 #include "common.h"
@@ -688,10 +689,22 @@ double feast_agg_bytes(int64_t N, int64_t E, int C, int ld_out) {
          4.0 * (double)N * ld_out;
 }
 
-size_t feast_fwd_ws_bytes(int64_t N, int Cin, int Cout) {
+namespace {
+// fused (z never reaches HBM): the fragment-ordered forward weights.  Unfused: the packed weights Wf and the split-K
+// slices of the node GEMM.  own_weights: the caller supplied no buffer for the weights, they live here
+struct FwdBuffers { float *bf, *wf; SubWs gemm; };
+FwdBuffers carve_fwd(Arena& a, int64_t N, int Cin, int Cout, bool fused, bool own_weights) {
   const int Kp = feast_ldz(Cin);
-  return align_up((size_t)Kp * Cout * sizeof(float)) + align_up(feast_fused_fwd_pack_floats(Cin, Cout) * sizeof(float)) +
-         gemm_nn_fixed_ws_bytes(N, Cout, feast_fwd_slices(Kp, Cout)) + 1024;
+  if (fused) return {own_weights ? a.take<float>(feast_fused_fwd_pack_floats(Cin, Cout)) : nullptr, nullptr, {nullptr, 0}};
+  return {nullptr, own_weights ? a.take<float>((size_t)Kp * Cout) : nullptr,
+          a.take_ws(gemm_nn_fixed_ws_bytes(N, Cout, feast_fwd_slices(Kp, Cout)))};
+}
+}  // namespace
+
+// either path, with the weights in the workspace (the caller does not say which)
+size_t feast_fwd_ws_bytes(int64_t N, int Cin, int Cout) {
+  return std::max(carve_bytes([&](Arena& a) { carve_fwd(a, N, Cin, Cout, false, true); }),
+                  carve_bytes([&](Arena& a) { carve_fwd(a, N, Cin, Cout, true, true); }));
 }
 
 int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64_t Ecap, const int32_t* rowptr_in,
@@ -704,16 +717,16 @@ int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   GEOBI_REQUIRE(N > 0 && N < (1ll << 31), "feast_fwd: bad node count");
   GEOBI_REQUIRE(Cb == 0 || Ca == Cb, "feast_fwd: a split input must have two equal halves");
   const int Kp = feast_ldz(Cin);
+  const bool fused = z == nullptr;
+  const bool own_weights = wf_out == nullptr && !(fused && bf_packed != nullptr);
   Arena a(ws, ws_bytes);
-  if (z == nullptr) {
+  const FwdBuffers fb = carve_fwd(a, N, Cin, Cout, fused, own_weights);
+  if (!fused || own_weights) GEOBI_WS_CHECK("feast_fwd", a, ws, ws_bytes);      // else nothing is taken
+  if (fused) {
     // Fused path: aggregation + node transform in one kernel, z never reaches HBM (feast_fused.hip).
     const size_t plain = feast_wpack_plain_floats(Cin, Cout);
     const float* bf = bf_packed;
-    if (bf == nullptr) {
-      float* bfw = wf_out ? wf_out + plain : a.take<float>(feast_fused_fwd_pack_floats(Cin, Cout));
-      GEOBI_REQUIRE(a.ok() && bfw, "feast_fwd: workspace too small (%zu < %zu)", ws_bytes, a.off);
-      bf = bfw;
-    }
+    if (bf == nullptr) bf = wf_out ? wf_out + plain : fb.bf;
     if (bf_packed != nullptr) {
       // packed by the caller
     } else if (wf_out != nullptr) {      // + the backward's packed forms (Wf for dz, the fused dx weights), one launch
@@ -731,11 +744,7 @@ int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
     prof_end(PROF_AGG_FWD, s);
     return rcf;
   }
-  float* wf = wf_out ? wf_out : a.take<float>((size_t)Kp * Cout);   // packed weights, kept for the backward
-  const int fwd_slices = feast_fwd_slices(Kp, Cout);
-  const size_t gws = gemm_nn_fixed_ws_bytes(N, Cout, fwd_slices);
-  void* gemm_ws = a.take<char>(gws);
-  GEOBI_REQUIRE(a.ok() && wf, "feast_fwd: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  float* wf = wf_out ? wf_out : fb.wf;   // packed weights, kept for the backward
   if (wf_out != nullptr) {     // kept for the backward: Wf and W' side by side
     const int ldr_ = feast_ldr(Cout);
     pack_weights_kernel<<<cdiv((int64_t)Kp * Cout + (int64_t)ldr_ * Cin, 256), 256, 0, s>>>(
@@ -754,15 +763,14 @@ int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   GemmEpilogue ep;
   ep.bias = bias;
   ep.slope = slope;
-  ep.ws = gemm_ws;
-  ep.ws_bytes = gws;
-  ep.fixed_slices = fwd_slices;      // shape-only split: batching-invariant forward results
+  ep.ws = fb.gemm.p;
+  ep.ws_bytes = fb.gemm.bytes;
+  ep.fixed_slices = feast_fwd_slices(Kp, Cout);      // shape-only split: batching-invariant forward results
   GEOBI_TRY(gemm_nn(z, Kp, wf, Cout, 0, out, Cout, (int)N, Cout, Kp, ep, s));
   return 0;
 }
 
 struct BwdPlan {
-  size_t total;
   float *g, *wf, *dz, *dl, *dpn, *rp, *wp, *z, *bdx, *dpd;
   void *tn_ws, *tn_ws2, *tn_ws3, *gemm_ws;
   size_t tn_bytes, tn_bytes2, tn_bytes3, gemm_bytes;
@@ -788,21 +796,20 @@ static void plan_bwd(Arena& a, int64_t N, int64_t Ecap, int Cin, int Cout, bool 
     const size_t t = gemm_tn_ws_bytes(rows, ldr, N);
     if (t > b.tn_bytes3) b.tn_bytes3 = t;
   }
-  b.tn_ws3 = a.take<char>(b.tn_bytes3);
+  b.tn_ws3 = a.take_ws(b.tn_bytes3).p;
   b.bdx = a.take<float>(feast_fused_dx_pack_floats(Cin, Cout));
   b.tn_bytes = gemm_tn_ws_bytes(Kp + 1, Cout, N);           // [z | 1]^T g   (side stream)
-  b.tn_ws = a.take<char>(b.tn_bytes);
+  b.tn_ws = a.take_ws(b.tn_bytes).p;
   b.tn_bytes2 = gemm_tn_ws_bytes_any_width(2 * HP, Cin + 1, N);   // [dp | dcs]^T [x | 1], per input half
   if (b.tn_bytes2 < (size_t)2048 * (128 + H) * sizeof(float) + 256) b.tn_bytes2 = (size_t)2048 * (128 + H) * sizeof(float) + 256;
   {                                                               // or the per-edge du / dc partials (level 0)
     const size_t du_bytes = align_up((size_t)cdiv(N, 64) * (H * Cin + H) * sizeof(float)) + 256;
     if ((Cin == 6 || Cin == 12) && du_bytes > b.tn_bytes2) b.tn_bytes2 = du_bytes;
   }
-  b.tn_ws2 = a.take<char>(b.tn_bytes2);
+  b.tn_ws2 = a.take_ws(b.tn_bytes2).p;
   size_t g1 = need_dz ? gemm_nn_ws_bytes(N, Kp) : 0, g2 = gemm_nn_ws_bytes(N, Cin);
   b.gemm_bytes = g1 > g2 ? g1 : g2;
-  b.gemm_ws = a.take<char>(b.gemm_bytes);
-  b.total = align_up(a.off) + 256;
+  b.gemm_ws = a.take_ws(b.gemm_bytes).p;
 }
 
 static bool rowpass_fused_enabled() {
@@ -818,20 +825,14 @@ static void bwd_needs(int Cin, int Cb, int Cout, bool fused, bool need_dx, bool&
 
 // any path (the C ABI's query: the caller does not say which)
 size_t feast_bwd_ws_bytes(int64_t N, int64_t Ecap, int Cin, int Cout) {
-  Arena a(nullptr, 0);
-  BwdPlan b;
-  plan_bwd(a, N, Ecap, Cin, Cout, true, true, b);
-  return b.total;
+  return carve_bytes([&](Arena& a) { BwdPlan b; plan_bwd(a, N, Ecap, Cin, Cout, true, true, b); });
 }
 
 // the fused path with this input split and this need for an input gradient (the executor's query)
 size_t feast_bwd_ws_bytes_for(int64_t N, int64_t Ecap, int Cin, int Cb, int Cout, bool need_dx) {
   bool need_dz, need_z;
   bwd_needs(Cin, Cb, Cout, true, need_dx, need_dz, need_z);
-  Arena a(nullptr, 0);
-  BwdPlan b;
-  plan_bwd(a, N, Ecap, Cin, Cout, need_dz, need_z, b);
-  return b.total;
+  return carve_bytes([&](Arena& a) { BwdPlan b; plan_bwd(a, N, Ecap, Cin, Cout, need_dz, need_z, b); });
 }
 
 int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64_t Ecap, const int32_t* rowptr_in,
@@ -848,7 +849,7 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   bool need_dz, need_z;
   bwd_needs(Cin, Cb, Cout, z == nullptr, dxa != nullptr, need_dz, need_z);
   plan_bwd(a, N, Ecap, Cin, Cout, need_dz, need_z, b);
-  GEOBI_REQUIRE(a.ok() && ws, "feast_bwd: workspace too small (%zu < %zu)", ws_bytes, b.total);
+  GEOBI_WS_CHECK("feast_bwd", a, ws, ws_bytes);
   const float* xb_ = xb ? xb : xa;
   const int Ca_ = Cb ? Ca : Cin;
 

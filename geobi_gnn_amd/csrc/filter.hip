@@ -140,10 +140,13 @@ int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t
   return 0;
 }
 
+namespace {
 // one buffer of normals (the sweeps alternate between it and `out`) and the per-edge spatial factors
-size_t bnf_filter_ws_bytes(int64_t F, int64_t E) {
-  return align_up((size_t)F * sizeof(float4)) + align_up((size_t)E * sizeof(float)) + 256;
-}
+struct BnfBuffers { float4* tmp; float* wsp; };
+BnfBuffers carve_bnf(Arena& a, int64_t F, int64_t E) { return {a.take<float4>(F), a.take<float>(E)}; }
+}  // namespace
+
+size_t bnf_filter_ws_bytes(int64_t F, int64_t E) { return carve_bytes([&](Arena& a) { carve_bnf(a, F, E); }); }
 
 int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
                const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
@@ -156,15 +159,14 @@ int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, co
     return 0;
   }
   Arena a(ws, ws_bytes);
-  float4* tmp = a.take<float4>(F);
-  float* wsp = a.take<float>(E > 0 ? E : 1);
-  GEOBI_REQUIRE(a.ok() && tmp && wsp, "bnf_filter: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const BnfBuffers b = carve_bnf(a, F, E);
+  GEOBI_WS_CHECK("bnf_filter", a, ws, ws_bytes);
   const int blocks = cdiv(F, kFacesPerBlock);
-  GEOBI_TRY(bnf_spatial_factors(rec_c, rowptr, col, F, E, inv2ss, wsp, s));
+  GEOBI_TRY(bnf_spatial_factors(rec_c, rowptr, col, F, E, inv2ss, b.wsp, s));
   const float4* src = (const float4*)rec_n;
   for (int k = 1; k <= n_sweeps; ++k) {
-    float4* dst = ((n_sweeps - k) & 1) ? tmp : (float4*)out;     // the last sweep lands in `out`
-    bnf_sweep_kernel<<<blocks, kThreads, 0, s>>>((const float4*)rec_c, src, rowptr, col, (int)F, inv2sr, wsp, dst);
+    float4* dst = ((n_sweeps - k) & 1) ? b.tmp : (float4*)out;     // the last sweep lands in `out`
+    bnf_sweep_kernel<<<blocks, kThreads, 0, s>>>((const float4*)rec_c, src, rowptr, col, (int)F, inv2sr, b.wsp, dst);
     GEOBI_LAUNCH_OK();
     src = dst;
   }

@@ -10,6 +10,8 @@
 //   colsum  : column sums (bias / c gradients), same two-stage scheme.
 #include "common.h"
 
+#include <algorithm>
+
 namespace geobi {
 
 namespace {
@@ -751,16 +753,18 @@ int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float*
   return 0;
 }
 
+// one [I, J] slab of partial sums per block row
+static float* carve_tn(Arena& a, const TnPlan& p, int I, int J) { return a.take<float>((size_t)p.blocks_y * I * J); }
+
 size_t gemm_tn_ws_bytes(int I, int J, int64_t M) {
   // the slab count depends on the tile shape, which depends on the alignment of A: take the larger
   TnPlan p0 = plan_tn(nullptr, 4, I, J, M, (I & 3) == 1 ? I - 1 : -1);
   TnPlan p1 = plan_tn(nullptr, 1, I, J, M, -1);
-  int by = p0.blocks_y > p1.blocks_y ? p0.blocks_y : p1.blocks_y;
-  // the caller may ask for the column sums of B as one more row (I + 1 rows per slab) + a [J] scratch for them
+  // the caller may ask for the column sums of B as row I - 1: the tiles then cover I - 1 rows
   TnPlan p2 = plan_tn(nullptr, 4, I > 1 ? I - 1 : I, J, M, -1), p3 = plan_tn(nullptr, 1, I > 1 ? I - 1 : I, J, M, -1);
-  if (p2.blocks_y > by) by = p2.blocks_y;
-  if (p3.blocks_y > by) by = p3.blocks_y;
-  return align_up((size_t)by * (I + 1) * J * sizeof(float)) + align_up((size_t)J * sizeof(float)) + 512;
+  size_t best = 0;
+  for (const TnPlan& p : {p0, p1, p2, p3}) best = std::max(best, carve_bytes([&](Arena& a) { carve_tn(a, p, I, J); }));
+  return best;
 }
 
 // Upper bound over every column width J' <= J the caller may pass for the same (I, M): the conv backward
@@ -786,8 +790,8 @@ int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, 
   const int I_mma = sum_row >= 0 ? I - 1 : I;
   TnPlan p = plan_tn(A, lda, I_mma, J, M > 0 ? M : 1, ones_row);
   Arena a(ws, ws_bytes);
-  float* slabs = a.take<float>((size_t)p.blocks_y * I * J);
-  GEOBI_REQUIRE(a.ok() && slabs, "gemm_tn: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  float* slabs = carve_tn(a, p, I, J);
+  GEOBI_WS_CHECK("gemm_tn", a, ws, ws_bytes);
   prof_begin(PROF_GEMM, s, 2.0 * (double)M * I_mma * J, 2);
   dim3 grid(p.tiles_i * p.tiles_j, p.blocks_y);
 #define GEOBI_TN(TI_, TJ_, U_, VA_)                                                                         \
@@ -818,14 +822,16 @@ static int colsum_blocks(int64_t M) {
   return (int)b;
 }
 
-size_t colsum_ws_bytes(int64_t M, int J) { return align_up((size_t)colsum_blocks(M) * J * sizeof(float)) + 256; }
+static float* carve_colsum(Arena& a, int64_t M, int J) { return a.take<float>((size_t)colsum_blocks(M) * J); }
+
+size_t colsum_ws_bytes(int64_t M, int J) { return carve_bytes([&](Arena& a) { carve_colsum(a, M, J); }); }
 
 int colsum(const float* A, int lda, int64_t M, int J, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
   if (J <= 0) return 0;
   int blocks = colsum_blocks(M);
   Arena a(ws, ws_bytes);
-  float* partial = a.take<float>((size_t)blocks * J);
-  GEOBI_REQUIRE(a.ok() && partial, "colsum: workspace too small");
+  float* partial = carve_colsum(a, M, J);
+  GEOBI_WS_CHECK("colsum", a, ws, ws_bytes);
   int64_t rpb = (M + blocks - 1) / blocks;
   if (rpb < 1) rpb = 1;
   colsum_partial_kernel<<<dim3(blocks, cdiv(J, 256)), 256, 0, s>>>(A, lda, M, J, rpb, partial);

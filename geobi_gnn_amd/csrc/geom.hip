@@ -8,6 +8,8 @@
 //               vertex head: (* depth_direction) + xyz;   face head: F.normalize(dim=1).
 #include "common.h"
 
+#include <algorithm>
+
 namespace geobi {
 
 namespace {
@@ -296,15 +298,17 @@ static int loss_blocks(int64_t n) {
   return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
 
-size_t row_loss_ws_bytes(int64_t n) { return align_up((size_t)loss_blocks(n) * sizeof(float)) + 256; }
+static float* carve_loss_partials(Arena& a, int64_t n) { return a.take<float>(loss_blocks(n)); }
+
+size_t row_loss_ws_bytes(int64_t n) { return carve_bytes([&](Arena& a) { carve_loss_partials(a, n); }); }
 
 int row_loss_fwd(const float* a, const float* b, const float* w, int64_t n, int kind, float scale, float* out,
                  void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(n > 0 && kind >= 0 && kind <= 3, "row_loss: bad arguments");
   Arena ar(ws, ws_bytes);
   int blocks = loss_blocks(n);
-  float* partial = ar.take<float>(blocks);
-  GEOBI_REQUIRE(ar.ok() && partial, "row_loss: workspace too small");
+  float* partial = carve_loss_partials(ar, n);
+  GEOBI_WS_CHECK("row_loss_fwd", ar, ws, ws_bytes);
   row_loss_partial_kernel<<<blocks, 256, 0, s>>>(a, b, w, n, kind, partial);
   row_loss_final_kernel<<<1, 64, 0, s>>>(partial, blocks, scale, out);
   GEOBI_LAUNCH_OK();
@@ -319,8 +323,12 @@ int row_loss_bwd(const float* a, const float* b, const float* w, const float* go
   return 0;
 }
 
+// the second buffer of the ping-pong over the positions
+static float* carve_positions(Arena& a, int64_t V) { return a.take<float>((size_t)V * 3); }
+
 size_t update_position_ws_bytes(int64_t V, int64_t F) {
-  return align_up((size_t)F * 3 * sizeof(float)) + align_up((size_t)V * 3 * sizeof(float)) + 512;
+  (void)F;
+  return carve_bytes([&](Arena& a) { carve_positions(a, V); });
 }
 
 int update_position2(const float* points, const int32_t* fv, const int32_t* vf, int maxval, const float* normals,
@@ -328,8 +336,8 @@ int update_position2(const float* points, const int32_t* fv, const int32_t* vf, 
                      hipStream_t s) {
   GEOBI_REQUIRE(V > 0 && F > 0 && n_iter >= 0, "update_position2: empty mesh");
   Arena a(ws, ws_bytes);
-  float* tmp = a.take<float>((size_t)V * 3);
-  GEOBI_REQUIRE(a.ok() && ws, "update_position2: workspace too small");
+  float* tmp = carve_positions(a, V);
+  GEOBI_WS_CHECK("update_position2", a, ws, ws_bytes);
   // ping-pong so that the LAST iteration lands in `out`
   const float* src = points;
   if (n_iter == 0) {
@@ -383,37 +391,37 @@ int head_fwd(const float* x, int Cin, int64_t N, const float* w1, const float* b
   return 0;
 }
 
+namespace {
+// graw [N, 3]; then the fused kernel's workspace, or dh [N, K] and the workspace of the two weight-gradient products
+struct HeadBwdBuffers { float *graw, *dh; SubWs nested; };
+HeadBwdBuffers carve_head_bwd(Arena& a, int64_t N, int Cin, int K, bool fused) {
+  if (fused) return {a.take<float>((size_t)N * 3), nullptr, a.take_ws(head_bwd_fused_ws_bytes(N))};
+  return {a.take<float>((size_t)N * 3), a.take<float>((size_t)N * K),
+          a.take_ws(std::max(gemm_tn_ws_bytes(K, Cin + 1, N), gemm_tn_ws_bytes(3, K + 1, N)))};
+}
+}  // namespace
+
+// either path (the caller does not say which)
 size_t head_bwd_ws_bytes(int64_t N, int Cin, int K) {
-  size_t t1 = gemm_tn_ws_bytes(K, Cin + 1, N), t2 = gemm_tn_ws_bytes(3, K + 1, N);
-  size_t c = colsum_ws_bytes(N, K);
-  size_t unfused = align_up((size_t)N * 3 * sizeof(float)) + align_up((size_t)N * K * sizeof(float)) +
-                   align_up(t1 > t2 ? t1 : t2) + align_up(c) + 1024;
-  size_t fused = align_up((size_t)N * 3 * sizeof(float)) + head_bwd_fused_ws_bytes(N) + 1024;
-  return unfused > fused ? unfused : fused;
+  return std::max(carve_bytes([&](Arena& a) { carve_head_bwd(a, N, Cin, K, false); }),
+                  carve_bytes([&](Arena& a) { carve_head_bwd(a, N, Cin, K, true); }));
 }
 
 int head_bwd(const float* x, int Cin, int64_t N, const float* w1, const float* b1, int K, const float* w2, int nout,
              float slope, int mode, const float* dd, const float* h, const float* raw, const float* gout, float* dx,
              float* dw1, float* db1, float* dw2, float* db2, int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
+  const bool fused = h == nullptr;   // the forward did not save the hidden activation: recompute it in-kernel
+  GEOBI_REQUIRE(!fused || (head_fused_supported(Cin, K, nout) && dx != nullptr && b1 != nullptr),
+                "head_bwd: fused path needs Cin=32, K=1024, b1 and dx");
   Arena a(ws, ws_bytes);
-  float* graw = a.take<float>((size_t)N * 3);
-  if (h == nullptr) {   // fused path (forward did not save the hidden activation): recompute it in-kernel
-    GEOBI_REQUIRE(head_fused_supported(Cin, K, nout) && dx != nullptr && b1 != nullptr,
-                  "head_bwd: fused path needs Cin=32, K=1024, b1 and dx");
-    size_t fb = head_bwd_fused_ws_bytes(N);
-    void* fws = a.take<char>(fb);
-    GEOBI_REQUIRE(a.ok() && ws, "head_bwd: workspace too small (%zu < %zu)", ws_bytes, a.off);
-    head_finish_bwd_kernel<<<cdiv(N, 256), 256, 0, s>>>(gout, raw, nout, mode, dd, (int)N, graw);
-    GEOBI_LAUNCH_OK();
-    return head_bwd_fused(x, N, w1, b1, w2, nout, slope, graw, dx, dw1, db1, dw2, db2, accumulate, fws, fb, s);
-  }
-  float* dh = a.take<float>((size_t)N * K);
-  size_t t1 = gemm_tn_ws_bytes(K, Cin + 1, N), t2 = gemm_tn_ws_bytes(3, K + 1, N);
-  size_t tnb = t1 > t2 ? t1 : t2;
-  void* tn_ws = a.take<char>(tnb);
-  GEOBI_REQUIRE(a.ok() && ws, "head_bwd: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const HeadBwdBuffers b = carve_head_bwd(a, N, Cin, K, fused);
+  GEOBI_WS_CHECK("head_bwd", a, ws, ws_bytes);
+  float *graw = b.graw, *dh = b.dh;
+  void* tn_ws = b.nested.p;
+  const size_t tnb = b.nested.bytes;
   head_finish_bwd_kernel<<<cdiv(N, 256), 256, 0, s>>>(gout, raw, nout, mode, dd, (int)N, graw);
   GEOBI_LAUNCH_OK();
+  if (fused) return head_bwd_fused(x, N, w1, b1, w2, nout, slope, graw, dx, dw1, db1, dw2, db2, accumulate, tn_ws, tnb, s);
   // dW2 = graw^T h and db2 = graw^T 1 in one pass (implicit ones column appended to h)
   TnOutput o2;
   o2.C = dw2; o2.ldc = K; o2.C2 = db2; o2.extra_col = 1; o2.accumulate = accumulate;

@@ -8,10 +8,9 @@
 // the conv kernels apply implicitly, and the pooling layer drops them first too
 // (/root/reference/code/net_util.py:163).
 #include "common.h"
+#include "rocprim_temp.h"
 
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace geobi {
 
@@ -112,37 +111,17 @@ __global__ void reverse_index_kernel(const int32_t* __restrict__ rowptr, const i
   }
 }
 
-struct SortBuffers {
-  uint64_t *k_in, *k_out;
-  int32_t *v_in, *v_out;
-  void* temp;
-  size_t temp_bytes;
-};
-
-int carve_sort(Arena& a, int64_t E, SortBuffers& sb) {
-  size_t tb = 0;
-  if (E > 0) {
-    hipError_t err = rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr,
-                                               (int32_t*)nullptr, (size_t)E, 0u, 64u, (hipStream_t)0, false);
-    if (err != hipSuccess) return set_error("rocprim radix_sort size query failed: %s", hipGetErrorString(err));
-  }
-  sb.temp_bytes = tb;
-  sb.k_in = a.take<uint64_t>(E);
-  sb.k_out = a.take<uint64_t>(E);
-  sb.v_in = a.take<int32_t>(E);
-  sb.v_out = a.take<int32_t>(E);
-  sb.temp = a.take<char>(tb ? tb : 1);
-  return 0;
+struct SortBuffers { uint64_t *k_in, *k_out; int32_t *v_in, *v_out; SubWs temp; };
+SortBuffers carve_sort(Arena& a, int64_t E) {
+  return {a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<int32_t>(E), a.take<int32_t>(E),
+          a.take_ws(sort_pairs_temp_bytes<uint64_t, int32_t>(E))};
 }
 
 }  // namespace
 
 size_t csr_ws_bytes(int64_t E, int64_t N) {
   (void)N;
-  Arena a(nullptr, 0);
-  SortBuffers sb;
-  if (carve_sort(a, E, sb) != 0) return 0;
-  return align_up(a.off) + 256;
+  return carve_bytes([&](Arena& a) { carve_sort(a, E); });
 }
 
 int csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, int drop_self, int32_t* rowptr,
@@ -154,15 +133,14 @@ int csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, i
     return 0;
   }
   Arena a(ws, ws_bytes);
-  SortBuffers sb;
-  GEOBI_TRY(carve_sort(a, E, sb));
-  GEOBI_REQUIRE(a.ok() && ws != nullptr, "csr_from_coo: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const SortBuffers sb = carve_sort(a, E);
+  GEOBI_WS_CHECK("csr_from_coo", a, ws, ws_bytes);
   const int T = 256;
   const int bits = key_bits(N);
   make_keys_kernel<<<cdiv(E, T), T, 0, s>>>(seg, nbr, E, N, drop_self, bits, sb.k_in, sb.v_in, bad);
   GEOBI_LAUNCH_OK();
-  size_t tb = sb.temp_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(sb.temp, tb, sb.k_in, sb.k_out, sb.v_in, eid, (size_t)E, 0u, (unsigned)(2 * bits), s,
+  size_t tb = sb.temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(sb.temp.p, tb, sb.k_in, sb.k_out, sb.v_in, eid, (size_t)E, 0u, (unsigned)(2 * bits), s,
                                       false));
   unpack_sorted_kernel<<<cdiv(E, T), T, 0, s>>>(sb.k_out, E, bits, col);
   GEOBI_LAUNCH_OK();
@@ -190,16 +168,15 @@ int csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t 
     return 0;
   }
   Arena a(ws, ws_bytes);
-  SortBuffers sb;
-  GEOBI_TRY(carve_sort(a, Ecap, sb));
-  GEOBI_REQUIRE(a.ok() && ws != nullptr, "csr_transpose: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const SortBuffers sb = carve_sort(a, Ecap);
+  GEOBI_WS_CHECK("csr_transpose", a, ws, ws_bytes);
   const int T = 256;
   int blocks = cdiv(N > 0 ? N : 1, T);
   const int bits = key_bits(N);
   expand_keys_kernel<<<blocks, T, 0, s>>>(rowptr, col, (int)N, Ecap, bits, sb.k_in, sb.v_in);
   GEOBI_LAUNCH_OK();
-  size_t tb = sb.temp_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(sb.temp, tb, sb.k_in, sb.k_out, sb.v_in, pos_t, (size_t)Ecap, 0u,
+  size_t tb = sb.temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(sb.temp.p, tb, sb.k_in, sb.k_out, sb.v_in, pos_t, (size_t)Ecap, 0u,
                                       (unsigned)(2 * bits), s, false));
   // low 32 bits of the transposed key hold the original row = the neighbour in the transposed view
   unpack_sorted_kernel<<<cdiv(Ecap, T), T, 0, s>>>(sb.k_out, Ecap, bits, col_t);

@@ -280,12 +280,16 @@ int gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* r
   return 0;
 }
 
+namespace {
 // one buffer of normals (the sweeps alternate between it and `out`), the per-edge spatial factors and edge-pair flags,
 // and per face H, the patch means and the guidance normals
-size_t gnf_filter_ws_bytes(int64_t F, int64_t E) {
-  return 3 * align_up((size_t)F * sizeof(float4)) + align_up((size_t)F * sizeof(float)) +
-         align_up((size_t)E * sizeof(float)) + align_up((size_t)E) + 6 * 256;
+struct GnfBuffers { float4 *tmp, *pmean, *g; float *H, *wsp; uint8_t* flags; };
+GnfBuffers carve_gnf(Arena& a, int64_t F, int64_t E) {
+  return {a.take<float4>(F), a.take<float4>(F), a.take<float4>(F), a.take<float>(F), a.take<float>(E), a.take<uint8_t>(E)};
 }
+}  // namespace
+
+size_t gnf_filter_ws_bytes(int64_t F, int64_t E) { return carve_bytes([&](Arena& a) { carve_gnf(a, F, E); }); }
 
 int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
                int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out, void* ws,
@@ -299,25 +303,19 @@ int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const 
     return 0;
   }
   Arena a(ws, ws_bytes);
-  float4* tmp = a.take<float4>(F);
-  float4* pmean = a.take<float4>(F);
-  float4* g = a.take<float4>(F);
-  float* H = a.take<float>(F);
-  float* wsp = a.take<float>(E > 0 ? E : 1);
-  uint8_t* flags = a.take<uint8_t>(E > 0 ? E : 1);
-  GEOBI_REQUIRE(a.ok() && tmp && pmean && g && H && wsp && flags, "gnf_filter: workspace too small (%zu < %zu)", ws_bytes,
-                a.off);
+  const GnfBuffers b = carve_gnf(a, F, E);
+  GEOBI_WS_CHECK("gnf_filter", a, ws, ws_bytes);
   const int blocks = cdiv(F, kFacesPerBlock);
-  GEOBI_TRY(bnf_spatial_factors(rec_c, rowptr, col, F, E, inv2ss, wsp, s));
-  GEOBI_TRY(gnf_edge_flags(fv, rowptr, col, F, E, flags, s));
+  GEOBI_TRY(bnf_spatial_factors(rec_c, rowptr, col, F, E, inv2ss, b.wsp, s));
+  GEOBI_TRY(gnf_edge_flags(fv, rowptr, col, F, E, b.flags, s));
   const float4* src = (const float4*)rec_n;
   for (int k = 1; k <= n_sweeps; ++k) {
-    float4* dst = ((n_sweeps - k) & 1) ? tmp : (float4*)out;     // the last sweep lands in `out`
-    GEOBI_TRY(gnf_patch_measure(rec_c, (const float*)src, rowptr, col, flags, F, H, (float*)pmean, s));
-    gnf_select_kernel<<<blocks, kThreads, 0, s>>>(src, rowptr, col, (int)F, H, pmean,
-                                                  sel_out ? sel_out + (size_t)(k - 1) * F : nullptr, g);
+    float4* dst = ((n_sweeps - k) & 1) ? b.tmp : (float4*)out;     // the last sweep lands in `out`
+    GEOBI_TRY(gnf_patch_measure(rec_c, (const float*)src, rowptr, col, b.flags, F, b.H, (float*)b.pmean, s));
+    gnf_select_kernel<<<blocks, kThreads, 0, s>>>(src, rowptr, col, (int)F, b.H, b.pmean,
+                                                  sel_out ? sel_out + (size_t)(k - 1) * F : nullptr, b.g);
     GEOBI_LAUNCH_OK();
-    gnf_sweep_kernel<<<blocks, kThreads, 0, s>>>((const float4*)rec_c, src, g, rowptr, col, (int)F, inv2sr, wsp, dst);
+    gnf_sweep_kernel<<<blocks, kThreads, 0, s>>>((const float4*)rec_c, src, b.g, rowptr, col, (int)F, inv2sr, b.wsp, dst);
     GEOBI_LAUNCH_OK();
     src = dst;
   }

@@ -582,11 +582,17 @@ int head_fwd_fused(const float* x, int64_t N, const float* w1, const float* b1, 
   return 0;
 }
 
-size_t head_bwd_fused_ws_bytes(int64_t N) {
-  size_t b = bwd_blocks(N);
-  return align_up(b * (size_t)NCHUNK * 16 * 64 * sizeof(float)) + align_up(b * 3 * HID * sizeof(float)) +
-         align_up(b * HID * sizeof(float)) + align_up(b * 4 * sizeof(float)) + 1024;
+namespace {
+// the per-block partial sums of the weight gradients
+struct HeadBwdPartials { float *dw1, *dw2, *db1, *db2; };
+HeadBwdPartials carve_head_bwd_fused(Arena& a, int64_t N) {
+  const size_t blocks = bwd_blocks(N);
+  return {a.take<float>(blocks * NCHUNK * 16 * 64), a.take<float>(blocks * 3 * HID), a.take<float>(blocks * HID),
+          a.take<float>(blocks * 4)};
 }
+}  // namespace
+
+size_t head_bwd_fused_ws_bytes(int64_t N) { return carve_bytes([&](Arena& a) { carve_head_bwd_fused(a, N); }); }
 
 // graw [N, nout] is the gradient w.r.t. the pre-finish head output (head_finish_bwd in geom.hip).
 int head_bwd_fused(const float* x, int64_t N, const float* w1, const float* b1, const float* w2, int nout,
@@ -594,11 +600,9 @@ int head_bwd_fused(const float* x, int64_t N, const float* w1, const float* b1, 
                    int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
   const int blocks = bwd_blocks(N);
   Arena a(ws, ws_bytes);
-  float* p_dw1 = a.take<float>((size_t)blocks * NCHUNK * 16 * 64);
-  float* p_dw2 = a.take<float>((size_t)blocks * 3 * HID);
-  float* p_db1 = a.take<float>((size_t)blocks * HID);
-  float* p_db2 = a.take<float>((size_t)blocks * 4);
-  GEOBI_REQUIRE(a.ok() && ws, "head_bwd_fused: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const HeadBwdPartials p = carve_head_bwd_fused(a, N);
+  GEOBI_WS_CHECK("head_bwd_fused", a, ws, ws_bytes);
+  float *p_dw1 = p.dw1, *p_dw2 = p.dw2, *p_db1 = p.db1, *p_db2 = p.db2;
   const int ntiles = cdiv(N, 32);
   constexpr size_t kLds = (size_t)(NCHUNK * 16 * 64 + 3 * HID + HID + HBW * 16 * 32) * sizeof(float);   // 160 KiB
   static_assert(kLds == 163840, "the backward head kernel uses the whole LDS of a CU");

@@ -181,12 +181,16 @@ __global__ void icp_finish_kernel(IcpJob job, double thr, double* __restrict__ s
   st[16] = ((compare && rel <= thr) || rmse == 0.0) ? 1.0 : 0.0;
 }
 
+// per part and block: the moment sums of the solve, the squared residual of the apply
+struct IcpBuffers { double *partial, *residual; };
+IcpBuffers carve_icp(Arena& a, int P) {
+  const size_t parts = P < 1 ? 0 : P;
+  return {a.take<double>(parts * kMaxBlocks * kIcpMoments), a.take<double>(parts * kMaxBlocks)};
+}
+
 }  // namespace
 
-size_t icp_ws_bytes(int P) {
-  if (P < 1) return 256;
-  return align_up((size_t)P * kMaxBlocks * kIcpMoments * sizeof(double)) + align_up((size_t)P * kMaxBlocks * sizeof(double)) + 256;
-}
+size_t icp_ws_bytes(int P) { return carve_bytes([&](Arena& a) { carve_icp(a, P); }); }
 
 int icp_init(double* state, int P, const double* init, hipStream_t s) {
   icp_init_kernel<<<cdiv(P, 64), 64, 0, s>>>(state, P, init);
@@ -208,9 +212,9 @@ int icp_apply(const float* x, const int64_t* xptr, int P, const double* state, i
 int icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P, int flags,
              double relative_rmse_thr, double* state, float* xt, void* ws, size_t ws_bytes, hipStream_t s) {
   Arena ar(ws, ws_bytes);
-  double* partial = ar.take<double>((size_t)P * kMaxBlocks * kIcpMoments);
-  double* residual = ar.take<double>((size_t)P * kMaxBlocks);
-  GEOBI_REQUIRE(ar.ok() && partial && residual, "icp_step: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ar.off);
+  const IcpBuffers b = carve_icp(ar, P);
+  GEOBI_WS_CHECK("icp_step", ar, ws, ws_bytes);
+  double *partial = b.partial, *residual = b.residual;
   for (int base = 0; base < P; base += kMaxParts) {
     IcpJob job;
     fill_parts(&job.x, xptr, base, P);

@@ -248,28 +248,35 @@ __global__ void calc_weight_parts_kernel(const float* __restrict__ pos, const fl
   w[e] = bilateral_weight(pos, nrm, i, j, mean);
 }
 
+// n + 1 counts, with_cursor: the fill cursors of vertex_faces (cursor[n] doubles as the bad-index counter), and the
+// temporary of the scan over the counts
+struct CountBuffers { int *cnt, *cursor; SubWs temp; };
+CountBuffers carve_counts(Arena& a, int64_t n, bool with_cursor) {
+  return {a.take<int>(n + 1), with_cursor ? a.take<int>(n + 1) : nullptr, a.take_ws(scan_ws_bytes(n + 1))};
+}
+double* carve_partials(Arena& a, size_t n_parts) { return a.take<double>(n_parts * kPartials); }
+
 }  // namespace
 
 size_t vertex_faces_ws_bytes(int64_t F, int64_t V) {
-  return align_up((size_t)(V + 1) * sizeof(int)) * 2 + scan_ws_bytes(V + 1) + 1024;
+  (void)F;
+  return carve_bytes([&](Arena& a) { carve_counts(a, V, true); });
 }
 
 int vertex_faces(const int32_t* fv, int64_t F, int64_t V, int32_t* rowptr, int32_t* list, void* ws, size_t ws_bytes,
                  hipStream_t s) {
   GEOBI_REQUIRE(F >= 0 && V > 0, "vertex_faces: empty mesh");
   Arena a(ws, ws_bytes);
-  int* cnt = a.take<int>(V + 1);
-  int* cursor = a.take<int>(V + 1);      // cursor[V] doubles as the bad-index counter
-  size_t tb = scan_ws_bytes(V + 1);
-  void* temp = a.take<char>(tb);
-  GEOBI_REQUIRE(a.ok() && cnt, "vertex_faces: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const CountBuffers c = carve_counts(a, V, true);
+  GEOBI_WS_CHECK("vertex_faces", a, ws, ws_bytes);
+  int *cnt = c.cnt, *cursor = c.cursor;
   GEOBI_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (V + 1), s));
   GEOBI_HIP(hipMemsetAsync(cursor, 0, sizeof(int) * (V + 1), s));
   const int64_t F3 = 3 * F;
   const int blocks = cdiv(F3 > 0 ? F3 : 1, 256);
   vf_count_kernel<<<blocks, 256, 0, s>>>(fv, F3, (int)V, cnt, cursor + V);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(temp, tb, cnt, rowptr, V + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, rowptr, V + 1, s));
   vf_fill_kernel<<<blocks, 256, 0, s>>>(fv, F3, (int)V, rowptr, cursor, list);
   GEOBI_LAUNCH_OK();
   vf_sort_kernel<<<cdiv(V, 128), 128, 0, s>>>(rowptr, (int)V, list);
@@ -305,24 +312,23 @@ int mesh_normals(const float* points, const int32_t* fv, int64_t F, int64_t V, c
   return 0;
 }
 
-size_t ring_graph_ws_bytes(int64_t n_nodes) { return align_up((size_t)(n_nodes + 1) * sizeof(int)) + scan_ws_bytes(n_nodes + 1) + 512; }
+size_t ring_graph_ws_bytes(int64_t n_nodes) { return carve_bytes([&](Arena& a) { carve_counts(a, n_nodes, false); }); }
 
 int ring_graph_count(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list, int64_t n_nodes,
                      int32_t* rowptr_g, void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(kind == 0 || kind == 1, "ring_graph: kind is 0 (vertex graph) or 1 (facet graph)");
   GEOBI_REQUIRE(n_nodes > 0, "ring_graph: empty");
   Arena a(ws, ws_bytes);
-  int* cnt = a.take<int>(n_nodes + 1);
-  size_t tb = scan_ws_bytes(n_nodes + 1);
-  void* temp = a.take<char>(tb);
-  GEOBI_REQUIRE(a.ok() && cnt, "ring_graph: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const CountBuffers c = carve_counts(a, n_nodes, false);
+  GEOBI_WS_CHECK("ring_graph_count", a, ws, ws_bytes);
+  int* cnt = c.cnt;
   const int blocks = cdiv(n_nodes, 128);
   if (kind == 0)
     ring_graph_kernel<0, 0><<<blocks, 128, 0, s>>>(fv, rowptr_vf, list, (int)n_nodes, cnt, nullptr, nullptr);
   else
     ring_graph_kernel<1, 0><<<blocks, 128, 0, s>>>(fv, rowptr_vf, list, (int)n_nodes, cnt, nullptr, nullptr);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(temp, tb, cnt, rowptr_g, n_nodes + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, rowptr_g, n_nodes + 1, s));
   return 0;
 }
 
@@ -339,13 +345,13 @@ int ring_graph_fill(int kind, const int32_t* fv, const int32_t* rowptr_vf, const
   return 0;
 }
 
-size_t calc_weight_ws_bytes() { return align_up(kPartials * sizeof(double)) + 256; }
+size_t calc_weight_ws_bytes() { return calc_weight_parts_ws_bytes(1); }
 
 int calc_weight(const float* pos, const float* normal, const int32_t* row, const int32_t* col, int64_t E,
                 int64_t extra_zero_edges, float* w, float* mean_len, void* ws, size_t ws_bytes, hipStream_t s) {
   Arena a(ws, ws_bytes);
-  double* partial = a.take<double>(kPartials);
-  GEOBI_REQUIRE(a.ok() && partial, "calc_weight: workspace too small");
+  double* partial = carve_partials(a, 1);
+  GEOBI_WS_CHECK("calc_weight", a, ws, ws_bytes);
   edge_length_partial_kernel<<<kPartials, 256, 0, s>>>(pos, row, col, E, partial);
   GEOBI_LAUNCH_OK();
   const int64_t denom = E + extra_zero_edges;
@@ -360,14 +366,16 @@ int calc_weight(const float* pos, const float* normal, const int32_t* row, const
   return 0;
 }
 
-size_t calc_weight_parts_ws_bytes(int n_parts) { return align_up((size_t)(n_parts > 0 ? n_parts : 1) * kPartials * sizeof(double)) + 256; }
+size_t calc_weight_parts_ws_bytes(int n_parts) {
+  return carve_bytes([&](Arena& a) { carve_partials(a, n_parts > 0 ? n_parts : 1); });
+}
 
 int calc_weight_parts(const float* pos, const float* normal, const int32_t* rowptr, const int32_t* row, const int32_t* col,
                       int64_t E, const int32_t* node_ptr, int n_parts, float* w, void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(n_parts > 0 && n_parts <= 4096, "calc_weight_parts: 1 .. 4096 parts (got %d)", n_parts);
   Arena a(ws, ws_bytes);
-  double* partial = a.take<double>((size_t)n_parts * kPartials);
-  GEOBI_REQUIRE(a.ok() && partial, "calc_weight_parts: workspace too small");
+  double* partial = carve_partials(a, n_parts);
+  GEOBI_WS_CHECK("calc_weight_parts", a, ws, ws_bytes);
   if (E <= 0) return 0;
   edge_length_partial_parts_kernel<<<dim3(kPartials, n_parts), 256, 0, s>>>(pos, rowptr, row, col, node_ptr, partial);
   GEOBI_LAUNCH_OK();

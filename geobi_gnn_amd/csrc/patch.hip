@@ -477,28 +477,31 @@ int patch_grow(const int32_t* fv, const int32_t* vf, int maxval, int64_t F, int6
   return 0;
 }
 
+namespace {
+struct SubmeshBuffers { int *first, *flag, *rank; SubWs temp; };
+SubmeshBuffers carve_submesh(Arena& a, int64_t n_sel, int64_t V) {
+  return {a.take<int>(V), a.take<int>(3 * n_sel + 1), a.take<int>(3 * n_sel + 1), a.take_ws(scan_ws_bytes(3 * n_sel + 1))};
+}
+}  // namespace
+
 size_t submesh_ws_bytes(int64_t n_sel, int64_t V) {
-  return align_up((size_t)V * sizeof(int)) + align_up((size_t)(3 * n_sel + 1) * sizeof(int)) * 2 +
-         scan_ws_bytes(3 * n_sel + 1) + 1024;
+  return carve_bytes([&](Arena& a) { carve_submesh(a, n_sel, V); });
 }
 
 int submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t V, int32_t* v_idx, int32_t* f_sub,
             int32_t* count, void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(n_sel > 0 && V > 0, "submesh: empty selection");
   Arena a(ws, ws_bytes);
-  int* first = a.take<int>(V);
-  int* flag = a.take<int>(3 * n_sel + 1);
-  int* rank = a.take<int>(3 * n_sel + 1);
-  size_t tb = scan_ws_bytes(3 * n_sel + 1);
-  void* temp = a.take<char>(tb);
-  GEOBI_REQUIRE(a.ok() && first, "submesh: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const SubmeshBuffers b = carve_submesh(a, n_sel, V);
+  GEOBI_WS_CHECK("submesh", a, ws, ws_bytes);
+  int *first = b.first, *flag = b.flag, *rank = b.rank;
   GEOBI_HIP(hipMemsetAsync(first, 0x7f, sizeof(int) * V, s));       // 0x7f7f7f7f: larger than any position
   const int blocks = cdiv(3 * n_sel, 256);
   submesh_first_use_kernel<<<blocks, 256, 0, s>>>(fv, sel, n_sel, first);
   GEOBI_LAUNCH_OK();
   submesh_flag_kernel<<<blocks, 256, 0, s>>>(fv, sel, n_sel, first, flag);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(temp, tb, flag, rank, 3 * n_sel + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(b.temp.p, b.temp.bytes, flag, rank, 3 * n_sel + 1, s));
   submesh_assign_kernel<<<blocks, 256, 0, s>>>(fv, sel, n_sel, first, rank, v_idx, f_sub, count);
   GEOBI_LAUNCH_OK();
   return 0;

@@ -15,12 +15,11 @@
 // order, computed by rounds of mutual proposals.  oracle/oracle_c.c:oracle_greedy_sorted is the
 // sequential statement of the same rule.
 #include "common.h"
+#include "rocprim_temp.h"
 
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace geobi {
 
@@ -1142,34 +1141,9 @@ static hipError_t exclusive_scan_int(void* temp, size_t& tb, const int* in, int*
   return e;
 }
 
-template <typename T>
-size_t scan_temp_bytes(int64_t n) {
-  size_t tb = 0;
-  (void)rocprim::exclusive_scan(nullptr, tb, (T*)nullptr, (T*)nullptr, (T)0, (size_t)n, rocprim::plus<T>(), (hipStream_t)0,
-                          false);
-  return tb;
-}
-
-size_t sort_keys_temp_bytes(int64_t n) {
-  size_t tb = 0;
-  (void)rocprim::radix_sort_keys(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)n, 0u, 64u, (hipStream_t)0,
-                           false);
-  return tb;
-}
-
-size_t sort_pairs_temp_bytes(int64_t n) {
-  size_t tb = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (int*)nullptr, (int*)nullptr,
-                            (size_t)n, 0u, 64u, (hipStream_t)0, false);
-  return tb;
-}
-
 }  // namespace
 
-size_t scan_ws_bytes(int64_t n) {
-  size_t tb = n <= kSmallScan ? 16 : scan_temp_bytes<int>(n);
-  return align_up(tb ? tb : 16);
-}
+size_t scan_ws_bytes(int64_t n) { return n <= kSmallScan ? 16 : scan_temp_bytes<int>(n); }
 
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s) {
   size_t tb = temp_bytes;
@@ -1241,7 +1215,20 @@ static void launch_match_rounds(const int32_t* rowptr, const int32_t* col, const
   }
 }
 
-size_t match_ws_bytes(int64_t N) { return 2 * align_up((size_t)N * sizeof(int)) + 1024; }
+namespace {
+struct MatchBuffers { int *prop0, *prop1; };            // the proposals, ping-pong
+struct CoarsenBuffers { MatchBuffers m; int *flag, *sz, *rank, *offs; SubWs temp_a, temp_b; };
+MatchBuffers carve_match(Arena& a, int64_t N) { return {a.take<int>(N), a.take<int>(N)}; }
+CoarsenBuffers carve_match_coarsen(Arena& a, int64_t N) {
+  return {carve_match(a, N), a.take<int>(N + 1), a.take<int>(N + 1), a.take<int>(N + 1), a.take<int>(N + 1),
+          a.take_ws(scan_ws_bytes(N + 1)), a.take_ws(scan_ws_bytes(N + 1))};
+}
+// n counts (or flags) and the temporary of the scan over them
+struct CountScan { int* cnt; SubWs temp; };
+CountScan carve_count_scan(Arena& a, int64_t n) { return {a.take<int>(n), a.take_ws(scan_ws_bytes(n))}; }
+}  // namespace
+
+size_t match_ws_bytes(int64_t N) { return carve_bytes([&](Arena& a) { carve_match(a, N); }); }
 
 // Runs `rounds` proposal rounds.  init != 0 starts from scratch, init == 0 continues from the state
 // in `cluster` (entries < 0 = undecided).  `status[0]` receives the number of nodes still undecided
@@ -1252,21 +1239,18 @@ int match_heavy_edge(const int32_t* rowptr, const int32_t* col, const float* w, 
                      hipStream_t s) {
   GEOBI_REQUIRE(N > 0 && rounds > 0, "match: empty graph or no rounds");
   Arena a(ws, ws_bytes);
-  int* prop0 = a.take<int>(N);
-  int* prop1 = a.take<int>(N);
-  GEOBI_REQUIRE(a.ok() && prop0, "match: workspace too small");
+  const MatchBuffers m = carve_match(a, N);
+  GEOBI_WS_CHECK("match_heavy_edge", a, ws, ws_bytes);
   int blocks = cdiv(N, 256);
-  int* pp = prop0;
-  int* pn = prop1;
+  int* pp = m.prop0;
+  int* pn = m.prop1;
   launch_match_rounds(rowptr, col, w, (int)N, rounds, init, cluster, status, pp, pn, s);
   match_commit_kernel<<<blocks, 256, 0, s>>>(pp, (int)N, cluster, status, cluster_final, nullptr, nullptr);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-size_t match_coarsen_ws_bytes(int64_t N) {
-  return match_ws_bytes(N) + 5 * align_up((size_t)(N + 1) * sizeof(int)) + 2 * scan_ws_bytes(N + 1) + 1024;
-}
+size_t match_coarsen_ws_bytes(int64_t N) { return carve_bytes([&](Arena& a) { carve_match_coarsen(a, N); }); }
 
 // One pooling step's integer front end in one call: matching rounds, commit, dense relabel and the inverse
 // lists of the matching (what geobi_match_heavy_edge + geobi_relabel_compact + geobi_segment_csr_pairs
@@ -1276,19 +1260,12 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
                   int32_t* counters, void* ws, size_t ws_bytes, hipStream_t s, void* rowinfo_out, bool* rowinfo_made) {
   GEOBI_REQUIRE(N > 0 && rounds > 0, "match_coarsen: empty graph or no rounds");
   Arena a(ws, ws_bytes);
-  int* prop0 = a.take<int>(N);
-  int* prop1 = a.take<int>(N);
-  int* flag = a.take<int>(N + 1);
-  int* sz = a.take<int>(N + 1);
-  int* rank = a.take<int>(N + 1);
-  int* offs = a.take<int>(N + 1);
-  size_t tb = scan_ws_bytes(N + 1);
-  void* temp_a = a.take<char>(tb);
-  void* temp_b = a.take<char>(tb);
-  GEOBI_REQUIRE(a.ok() && prop0, "match_coarsen: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const CoarsenBuffers b = carve_match_coarsen(a, N);
+  GEOBI_WS_CHECK("match_coarsen", a, ws, ws_bytes);
+  int *flag = b.flag, *sz = b.sz, *rank = b.rank, *offs = b.offs;
   const int blocks = cdiv(N, 256);
-  int* pp = prop0;
-  int* pn = prop1;
+  int* pp = b.m.prop0;
+  int* pn = b.m.prop1;
   launch_match_rounds(rowptr, col, w, (int)N, rounds, init, state, counters, pp, pn, s);
   const bool scan_free = match_scanfree_knob().load(std::memory_order_relaxed);
   if (scan_free && blocks <= kMaxScanBlocks) {
@@ -1314,8 +1291,8 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
     prof_end(PROF_POOL_FORM, s);
     GEOBI_LAUNCH_OK();
   } else {
-    GEOBI_TRY(scan_exclusive_i32(temp_a, tb, flag, rank, N + 1, s));
-    GEOBI_TRY(scan_exclusive_i32(temp_b, tb, sz, offs, N + 1, s));
+    GEOBI_TRY(scan_exclusive_i32(b.temp_a.p, b.temp_a.bytes, flag, rank, N + 1, s));
+    GEOBI_TRY(scan_exclusive_i32(b.temp_b.p, b.temp_b.bytes, sz, offs, N + 1, s));
   }
   match_lists_kernel<<<blocks, 256, 0, s>>>(state, cluster_final, rank, offs, (int)N, cnew, counters + 1, segptr,
                                             members);
@@ -1323,19 +1300,20 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
   return 0;
 }
 
-size_t relabel_ws_bytes(int64_t N) {
-  return align_up((size_t)N * sizeof(int)) * 2 + align_up(scan_temp_bytes<int>(N)) + 512;
-}
+namespace {
+struct RelabelBuffers { CountScan flag; int* rank; };
+RelabelBuffers carve_relabel(Arena& a, int64_t N) { return {carve_count_scan(a, N), a.take<int>(N)}; }
+}  // namespace
+
+size_t relabel_ws_bytes(int64_t N) { return carve_bytes([&](Arena& a) { carve_relabel(a, N); }); }
 
 int relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t* cnew, int32_t* count, void* ws,
                     size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(N > 0, "relabel: empty");
   Arena a(ws, ws_bytes);
-  int* flag = a.take<int>(N);
-  int* rank = a.take<int>(N);
-  size_t tb = scan_temp_bytes<int>(N);
-  void* temp = a.take<char>(tb ? tb : 1);
-  GEOBI_REQUIRE(a.ok() && flag, "relabel: workspace too small");
+  const RelabelBuffers b = carve_relabel(a, N);
+  GEOBI_WS_CHECK("relabel_compact", a, ws, ws_bytes);
+  int *flag = b.flag.cnt, *rank = b.rank;
   int blocks = cdiv(N, 256);
   if (rep_is_self) {
     rep_self_flag_kernel<<<blocks, 256, 0, s>>>(cluster, (int)N, flag);
@@ -1344,15 +1322,20 @@ int relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t*
     rep_flag_kernel<<<blocks, 256, 0, s>>>(cluster, (int)N, flag);
   }
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(exclusive_scan_int(temp, tb, flag, rank, N, s));
+  GEOBI_TRY(scan_exclusive_i32(b.flag.temp.p, b.flag.temp.bytes, flag, rank, N, s));
   relabel_apply_kernel<<<blocks, 256, 0, s>>>(cluster, flag, rank, (int)N, cnew, count);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-size_t segment_csr_ws_bytes(int64_t n) {
-  return align_up((size_t)n * sizeof(uint64_t)) * 2 + align_up(sort_keys_temp_bytes(n)) + 512;
+namespace {
+struct KeySortBuffers { uint64_t *k_in, *k_out; SubWs temp; };
+KeySortBuffers carve_key_sort(Arena& a, int64_t n) {
+  return {a.take<uint64_t>(n), a.take<uint64_t>(n), a.take_ws(sort_keys_temp_bytes<uint64_t>(n))};
 }
+}  // namespace
+
+size_t segment_csr_ws_bytes(int64_t n) { return carve_bytes([&](Arena& a) { carve_key_sort(a, n); }); }
 
 int segment_csr(const int32_t* seg, int64_t n, int64_t nseg, int32_t* segptr, int32_t* members, void* ws,
                 size_t ws_bytes, hipStream_t s) {
@@ -1361,38 +1344,34 @@ int segment_csr(const int32_t* seg, int64_t n, int64_t nseg, int32_t* segptr, in
     return 0;
   }
   Arena a(ws, ws_bytes);
-  uint64_t* k_in = a.take<uint64_t>(n);
-  uint64_t* k_out = a.take<uint64_t>(n);
-  size_t tb = sort_keys_temp_bytes(n);
-  void* temp = a.take<char>(tb ? tb : 1);
-  GEOBI_REQUIRE(a.ok() && k_in, "segment_csr: workspace too small");
+  const KeySortBuffers b = carve_key_sort(a, n);
+  GEOBI_WS_CHECK("segment_csr", a, ws, ws_bytes);
+  uint64_t *k_in = b.k_in, *k_out = b.k_out;
+  size_t tb = b.temp.bytes;
   const int bits = key_bits(n);                 // member index < n
   const int sbits = key_bits(nseg);
   seg_keys_kernel<<<cdiv(n, 256), 256, 0, s>>>(seg, n, bits, k_in);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(rocprim::radix_sort_keys(temp, tb, k_in, k_out, (size_t)n, 0u, (unsigned)(bits + sbits), s, false));
+  GEOBI_HIP(rocprim::radix_sort_keys(b.temp.p, tb, k_in, k_out, (size_t)n, 0u, (unsigned)(bits + sbits), s, false));
   seg_unpack_kernel<<<cdiv(n, 256), 256, 0, s>>>(k_out, n, bits, members);
   seg_ptr_kernel<<<cdiv(nseg + 1, 256), 256, 0, s>>>(k_out, n, (int)nseg, bits, segptr);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-size_t segment_pairs_ws_bytes(int64_t nseg) {
-  return align_up((size_t)nseg * sizeof(int)) + align_up(scan_temp_bytes<int>(nseg)) + 512;
-}
+size_t segment_pairs_ws_bytes(int64_t nseg) { return carve_bytes([&](Arena& a) { carve_count_scan(a, nseg); }); }
 
 int segment_csr_pairs(const int32_t* cnew, const int32_t* raw, int64_t N, int64_t nseg, int32_t* segptr,
                       int32_t* members, void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(N > 0 && nseg > 0, "segment_csr_pairs: empty");
   Arena a(ws, ws_bytes);
-  int* cnt = a.take<int>(nseg);
-  size_t tb = scan_temp_bytes<int>(nseg);
-  void* temp = a.take<char>(tb ? tb : 1);
-  GEOBI_REQUIRE(a.ok() && cnt, "segment_csr_pairs: workspace too small");
+  const CountScan c = carve_count_scan(a, nseg);
+  GEOBI_WS_CHECK("segment_csr_pairs", a, ws, ws_bytes);
+  int* cnt = c.cnt;
   pair_count_kernel<<<cdiv(nseg, 256), 256, 0, s>>>(cnew, raw, (int)N, (int)nseg, cnt);
   pair_mark_kernel<<<cdiv(N, 256), 256, 0, s>>>(cnew, raw, (int)N, cnt);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(exclusive_scan_int(temp, tb, cnt, segptr, nseg, s));
+  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, segptr, nseg, s));
   pair_fill_kernel<<<cdiv(N, 256), 256, 0, s>>>(cnew, raw, (int)N, (int)nseg, segptr, members);
   GEOBI_LAUNCH_OK();
   return 0;
@@ -1403,13 +1382,12 @@ int segment_csr_compose(const int32_t* segptr1, const int32_t* members1, const i
                         int32_t* members12, void* ws, size_t ws_bytes, hipStream_t s) {
   GEOBI_REQUIRE(nseg2 > 0, "segment_csr_compose: empty");
   Arena a(ws, ws_bytes);
-  int* cnt = a.take<int>(nseg2);
-  size_t tb = scan_temp_bytes<int>(nseg2);
-  void* temp = a.take<char>(tb ? tb : 1);
-  GEOBI_REQUIRE(a.ok() && cnt, "segment_csr_compose: workspace too small");
+  const CountScan c = carve_count_scan(a, nseg2);
+  GEOBI_WS_CHECK("segment_csr_compose", a, ws, ws_bytes);
+  int* cnt = c.cnt;
   compose_count_kernel<<<cdiv(nseg2, 256), 256, 0, s>>>(segptr1, segptr2, members2, (int)nseg2, cnt);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(exclusive_scan_int(temp, tb, cnt, segptr12, nseg2, s));
+  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, segptr12, nseg2, s));
   compose_fill_kernel<<<cdiv(nseg2, 256), 256, 0, s>>>(segptr1, members1, segptr2, members2, (int)nseg2,
                                                        (int)n_fine, segptr12, members12);
   GEOBI_LAUNCH_OK();
@@ -1481,15 +1459,19 @@ int gather_rows(const float* x, const int32_t* idx, int C, int64_t n_out, float*
   return 0;
 }
 
-// with E (the fine edge count) the workspace also holds the scratch pair of the one-pass form
-size_t pool_edge_rows_ws_bytes_onepass(int64_t nbound, int64_t E) {
-  return pool_edge_rows_ws_bytes(nbound) + 2 * align_up((size_t)E * sizeof(int)) + 256;
+namespace {
+struct EdgeRowsBuffers { CountScan cnt; int4* rowinfo; int* tcol; float* tw; };
+// with E_fine (the fine edge count) the workspace also holds the scratch pair tcol, tw of the one-pass form
+EdgeRowsBuffers carve_edge_rows(Arena& a, int64_t nbound, int64_t E_fine) {
+  return {carve_count_scan(a, nbound + 1), a.take<int4>(nbound), E_fine > 0 ? a.take<int>(E_fine) : nullptr,
+          E_fine > 0 ? a.take<float>(E_fine) : nullptr};
 }
+}  // namespace
 
-size_t pool_edge_rows_ws_bytes(int64_t nbound) {
-  return align_up((size_t)(nbound + 1) * sizeof(int)) + align_up(scan_temp_bytes<int>(nbound + 1)) +
-         align_up((size_t)nbound * sizeof(int4)) + 512;
+size_t pool_edge_rows_ws_bytes_onepass(int64_t nbound, int64_t E) {
+  return carve_bytes([&](Arena& a) { carve_edge_rows(a, nbound, E); });
 }
+size_t pool_edge_rows_ws_bytes(int64_t nbound) { return pool_edge_rows_ws_bytes_onepass(nbound, 0); }
 
 // cnew, (segptr, members) = pair lists built with the bound `nbound` (fine node count), ncount = device
 // count of coarse nodes.  rowptr_c has nbound + 1 entries; count[0] = coarse edges; overflow[0] |= 1 if
@@ -1501,23 +1483,21 @@ int pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32_t* me
                    int32_t* publish_host, int publish_seq) {
   GEOBI_REQUIRE(nbound > 0, "pool_edge_rows: empty");
   Arena a(ws, ws_bytes);
-  int* cnt = a.take<int>(nbound + 1);
-  size_t tb = scan_temp_bytes<int>(nbound + 1);
-  void* temp = a.take<char>(tb ? tb : 1);
-  int4* rowinfo = a.take<int4>(nbound);
-  GEOBI_REQUIRE(a.ok() && cnt && rowinfo, "pool_edge_rows: workspace too small");
+  const EdgeRowsBuffers b = carve_edge_rows(a, nbound, E_fine);
+  GEOBI_WS_CHECK("pool_edge_rows", a, ws, ws_bytes);
+  int* cnt = b.cnt.cnt;
+  int4* rowinfo = b.rowinfo;
   int blocks = cdiv(nbound, 4);
   if (E_fine > 0) {
     // one-pass form (callers that sized the workspace with pool_edge_rows_ws_bytes_onepass): gather + relabel + sort +
     // merge ONCE, entries parked in scratch, then a short copy pass instead of a second merge
-    int* tcol = a.take<int>(E_fine);
-    float* tw = a.take<float>(E_fine);
-    GEOBI_REQUIRE(a.ok() && tcol && tw, "pool_edge_rows: workspace too small for the one-pass form");
+    int* tcol = b.tcol;
+    float* tw = b.tw;
     pool_edge_rows_kernel<2><<<blocks, 256, 0, s>>>(cnew, segptr, members, rowptr, col, w, ncount, (int)nbound, cnt,
                                                      nullptr, nullptr, tcol, tw, overflow, nullptr, rowinfo,
                                                      (const int4*)rowinfo_in);
     GEOBI_LAUNCH_OK();
-    GEOBI_HIP(exclusive_scan_int(temp, tb, cnt, rowptr_c, nbound + 1, s));
+    GEOBI_TRY(scan_exclusive_i32(b.cnt.temp.p, b.cnt.temp.bytes, cnt, rowptr_c, nbound + 1, s));
     pool_edge_compact_kernel<<<cdiv(nbound * 16, 256), 256, 0, s>>>(ncount, (int)nbound, rowptr_c, rowinfo, tcol,
                                                                     w ? tw : nullptr, row_c, col_c, w_c, count,
                                                                     publish_src, publish_host, publish_seq);
@@ -1527,17 +1507,22 @@ int pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32_t* me
   pool_edge_rows_kernel<0><<<blocks, 256, 0, s>>>(cnew, segptr, members, rowptr, col, w, ncount, (int)nbound, cnt,
                                                    nullptr, nullptr, nullptr, nullptr, overflow, nullptr, rowinfo, nullptr);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(exclusive_scan_int(temp, tb, cnt, rowptr_c, nbound + 1, s));
+  GEOBI_TRY(scan_exclusive_i32(b.cnt.temp.p, b.cnt.temp.bytes, cnt, rowptr_c, nbound + 1, s));
   pool_edge_rows_kernel<1><<<blocks, 256, 0, s>>>(cnew, segptr, members, rowptr, col, w, ncount, (int)nbound, cnt,
                                                    rowptr_c, row_c, col_c, w_c, overflow, count, rowinfo, nullptr);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-size_t pool_edge_ws_bytes(int64_t E) {
-  return align_up((size_t)E * sizeof(uint64_t)) * 3 + align_up((size_t)E * sizeof(int)) * 4 +
-         align_up(sort_pairs_temp_bytes(E)) + align_up(scan_temp_bytes<int>(E)) + 1024;
+namespace {
+struct PoolEdgeBuffers { uint64_t *k_in, *k_out, *ukeys; int *v_in, *v_out, *rank; CountScan head; SubWs t_sort; };
+PoolEdgeBuffers carve_pool_edge(Arena& a, int64_t E) {
+  return {a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<int>(E), a.take<int>(E), a.take<int>(E),
+          carve_count_scan(a, E), a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(E))};
 }
+}  // namespace
+
+size_t pool_edge_ws_bytes(int64_t E) { return carve_bytes([&](Arena& a) { carve_pool_edge(a, E); }); }
 
 // Outputs are sized for the worst case (E entries, nmax + 1 row pointers); the true edge count is
 // written to count[0] on the device.
@@ -1550,26 +1535,20 @@ int pool_edge(const int32_t* cnew, const int32_t* row, const int32_t* col, const
     return 0;
   }
   Arena a(ws, ws_bytes);
-  uint64_t* k_in = a.take<uint64_t>(E);
-  uint64_t* k_out = a.take<uint64_t>(E);
-  uint64_t* ukeys = a.take<uint64_t>(E);
-  int* v_in = a.take<int>(E);
-  int* v_out = a.take<int>(E);
-  int* head = a.take<int>(E);
-  int* rank = a.take<int>(E);
-  size_t tb_sort = sort_pairs_temp_bytes(E), tb_scan = scan_temp_bytes<int>(E);
-  void* t_sort = a.take<char>(tb_sort ? tb_sort : 1);
-  void* t_scan = a.take<char>(tb_scan ? tb_scan : 1);
-  GEOBI_REQUIRE(a.ok() && k_in, "pool_edge: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const PoolEdgeBuffers b = carve_pool_edge(a, E);
+  GEOBI_WS_CHECK("pool_edge", a, ws, ws_bytes);
+  uint64_t *k_in = b.k_in, *k_out = b.k_out, *ukeys = b.ukeys;
+  int *v_in = b.v_in, *v_out = b.v_out, *head = b.head.cnt, *rank = b.rank;
+  size_t tb_sort = b.t_sort.bytes;
   int blocks = cdiv(E, 256);
   const int bits = key_bits(nmax);
   pool_edge_keys_kernel<<<blocks, 256, 0, s>>>(cnew, row, col, E, bits, k_in, v_in);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(rocprim::radix_sort_pairs(t_sort, tb_sort, k_in, k_out, v_in, v_out, (size_t)E, 0u, (unsigned)(2 * bits),
+  GEOBI_HIP(rocprim::radix_sort_pairs(b.t_sort.p, tb_sort, k_in, k_out, v_in, v_out, (size_t)E, 0u, (unsigned)(2 * bits),
                                       s, false));
   pool_edge_heads_kernel<<<blocks, 256, 0, s>>>(k_out, E, head);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(exclusive_scan_int(t_scan, tb_scan, head, rank, E, s));
+  GEOBI_TRY(scan_exclusive_i32(b.head.temp.p, b.head.temp.bytes, head, rank, E, s));
   pool_edge_emit_kernel<<<blocks, 256, 0, s>>>(k_out, v_out, head, rank, w, E, row_c, col_c, w_c, ukeys, count,
                                                bits);
   GEOBI_LAUNCH_OK();

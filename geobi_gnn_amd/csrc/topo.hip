@@ -16,9 +16,8 @@
 //            component sizes by integer adds, the lanes of a wave that share a label first summed in the wave
 // Every value used as an index is a face index below F: keys only ever hold 2 * face + bit, links hold slot / 3.
 #include "common.h"
+#include "rocprim_temp.h"
 #include "../../include/geobi_hip.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace geobi {
 
@@ -26,14 +25,6 @@ namespace {
 
 constexpr int kT = 256;
 constexpr int kBatch = 8;            // rounds enqueued per read of the changed flags
-constexpr uint64_t kNoEdge = (1ull << 48) - 1;     // key of an excluded face's slots
-constexpr int kKept = 1, kDegenerate = 3, kSmallPart = 4;
-
-// one atomic per wave for a count of lanes (integer adds: the total does not depend on their order)
-__device__ __forceinline__ void count_lanes(bool mine, int* __restrict__ counter) {
-  const unsigned long long m = __ballot(mine);
-  if (m != 0 && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(counter, __popcll(m));
-}
 
 __device__ __forceinline__ bool face_included(const int* __restrict__ fv, const int* __restrict__ state, int f, int V,
                                               int& a, int& b, int& c) {
@@ -53,7 +44,7 @@ __global__ void topo_edges_kernel(const int* __restrict__ fv, const int* __restr
   for (int k = 0; k < 3; ++k) {
     const int a = c[k], b = c[(k + 1) % 3];
     const int lo = a < b ? a : b, hi = a < b ? b : a;
-    keys[3 * (size_t)f + k] = inc ? ((uint64_t)lo << 24 | (uint64_t)hi) : kNoEdge;
+    keys[3 * (size_t)f + k] = inc ? edge_key(lo, hi) : kNoEdge;
     vals[3 * f + k] = (3 * f + k) << 1 | (a < b ? 0 : 1);
   }
 }
@@ -252,39 +243,25 @@ __global__ void topo_components_out_kernel(const int* __restrict__ fv, const int
   count_lanes(small, counts + 2);
 }
 
-size_t sort_temp_bytes(int64_t n) {
-  size_t tb = 0;
-  if (n > 0)
-    (void)rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (int*)nullptr, (int*)nullptr,
-                                    (size_t)n, 0u, 48u, (hipStream_t)0, false);
-  return tb ? tb : 16;
-}
-
 struct TopoBuffers {
   uint64_t *k_in, *k_out;
-  int *v_in, *v_out, *olink, *clink, *per_label, *used, *flags;
+  int *v_in, *v_out, *olink, *clink, *per_label, *used, *flags;    // per_label: bad marks, then component sizes
   uint32_t *key, *next;
-  void* sort_temp;
-  size_t sort_bytes;
+  SubWs sort_temp;
 };
-void carve_topo(Arena& a, int64_t F, int64_t V, TopoBuffers& b) {
-  b.k_in = a.take<uint64_t>(3 * F); b.k_out = a.take<uint64_t>(3 * F);
-  b.v_in = a.take<int>(3 * F); b.v_out = a.take<int>(3 * F);
-  b.olink = a.take<int>(3 * F); b.clink = a.take<int>(6 * F);
-  b.per_label = a.take<int>(F);        // bad marks, then component sizes
-  b.used = a.take<int>(V);
-  b.flags = a.take<int>(kBatch);
-  b.key = a.take<uint32_t>(F); b.next = a.take<uint32_t>(F);
-  b.sort_bytes = sort_temp_bytes(3 * F);
-  b.sort_temp = a.take<char>(b.sort_bytes);
+TopoBuffers carve_topo(Arena& a, int64_t F, int64_t V) {
+  return {a.take<uint64_t>(3 * F), a.take<uint64_t>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F),
+          a.take<int>(6 * F), a.take<int>(F), a.take<int>(V), a.take<int>(kBatch), a.take<uint32_t>(F), a.take<uint32_t>(F),
+          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(3 * F, kEdgeKeyBits))};
 }
 
 int build_table(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, const TopoBuffers& b, hipStream_t s) {
   const int n = (int)F;
   topo_edges_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, state, n, (int)V, b.k_in, b.v_in);
   GEOBI_LAUNCH_OK();
-  size_t tb = b.sort_bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, 48u, s, false));
+  size_t tb = b.sort_temp.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
+                                      s, false));
   topo_links_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.k_out, b.v_out, faces, 3 * n, b.olink, b.clink);
   GEOBI_LAUNCH_OK();
   return 0;
@@ -347,18 +324,15 @@ struct StageTimer {
 
 int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, TopoBuffers& b) {
   Arena a(ws, ws_bytes);
-  carve_topo(a, F, V, b);
-  GEOBI_REQUIRE(a.ok() && ws != nullptr, "%s: workspace too small (%zu < %zu)", what, ws_bytes, a.off);
+  b = carve_topo(a, F, V);
+  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
   return 0;
 }
 
 }  // namespace
 
 size_t topo_ws_bytes(int64_t F, int64_t V) {
-  Arena a(nullptr, 0);
-  TopoBuffers b;
-  carve_topo(a, F, V, b);
-  return align_up(a.off) + 256;
+  return carve_bytes([&](Arena& a) { carve_topo(a, F, V); });
 }
 
 int topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* faces_out,
