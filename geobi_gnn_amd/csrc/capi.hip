@@ -112,7 +112,7 @@ void prof_end(int kernel, hipStream_t s) {
 // Context = host thread.  Everything below the overlap switch is per host thread: a thread drives one stream at a time
 // (the caller's stream of a per-op call; the stream of ONE mesh group in geobi_net_train_groups), so every context has
 // its own side streams and fork / join events and two groups in flight never meet on a shared event.
-static std::atomic<int> g_overlap{[] { const char* e = getenv("GEOBI_OVERLAP"); return (e && atoi(e) == 0) ? 0 : 1; }()};
+static Knob g_overlap{"GEOBI_OVERLAP", 1};      // process-wide (geobi_set_overlap)
 static thread_local int g_overlap_here = -1;   // this context's override of g_overlap (-1: none); side_override()
 static thread_local int g_defer = 0;     // 1: backward calls fork but do not join; the caller joins once (geobi_side_join)
 // Two side streams: [0] at the default priority, [1] at the lowest.  On a big batch the weight-gradient products
@@ -126,8 +126,8 @@ static thread_local hipStream_t g_side = nullptr;           // the stream the cu
 static thread_local hipEvent_t g_fork_ev = nullptr, g_join_ev = nullptr;
 
 void side_select(int low_priority) {
-  static const bool allow = [] { const char* e = getenv("GEOBI_SIDE_PRIORITY"); return !e || atoi(e) != 0; }();
-  g_side_sel = (low_priority && allow) ? 1 : 0;
+  static Knob allow{"GEOBI_SIDE_PRIORITY", 1};
+  g_side_sel = (low_priority && allow.on()) ? 1 : 0;
 }
 
 void side_override(int mode) { g_overlap_here = mode; }
@@ -135,7 +135,7 @@ hipStream_t side_current() { return g_side; }
 
 Fork fork_side_stream(hipStream_t main) {
   Fork f;
-  if (g_overlap_here == 0 || (g_overlap_here < 0 && !g_overlap)) return f;
+  if (g_overlap_here == 0 || (g_overlap_here < 0 && !g_overlap.on())) return f;
   if (g_sides[g_side_sel] == nullptr) {
     int lo = 0, hi = 0;
     if (g_side_sel == 0 || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = 0;
@@ -146,7 +146,7 @@ Fork fork_side_stream(hipStream_t main) {
     }
     if (g_fork_ev == nullptr &&
         (hipEventCreateWithFlags(&g_fork_ev, hipEventDisableTiming) != hipSuccess ||
-         hipEventCreateWithFlags(&g_join_ev, hipEventDisableTiming) != hipSuccess)) { g_overlap = 0; return f; }
+         hipEventCreateWithFlags(&g_join_ev, hipEventDisableTiming) != hipSuccess)) { g_overlap.set(0); return f; }
   }
   g_side = g_sides[g_side_sel];
   if (hipEventRecord(g_fork_ev, main) != hipSuccess) return f;
@@ -932,7 +932,7 @@ int geobi_read_i32(const int32_t* dev, int n, int32_t* host, void* stream) {
 }
 
 int geobi_set_overlap(int enable) {
-  g_overlap = enable ? 1 : 0;
+  g_overlap.set(enable ? 1 : 0);
   return 0;
 }
 

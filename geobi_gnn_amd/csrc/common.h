@@ -5,7 +5,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <stdlib.h>
+
 #include <atomic>
+#include <type_traits>
 
 #define GEOBI_H 9    // FeaSt heads on the hot path (network.py:258-268 always passes 9)
 #define GEOBI_HP 12  // row stride (floats) of per-node / per-edge head vectors: 9 padded to 3 x float4
@@ -33,6 +36,50 @@ int set_error(const char* fmt, ...);
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- Knob: a switch the environment decides until a geobi_set_* hook sets it.  One relaxed atomic: it may be set while
+// other host threads launch.  A knob is a file-local object next to the code it switches (name NULL: no variable).
+struct Knob {
+  static constexpr long long kUnread = INT64_MIN;
+  const char* name;
+  long long unset;                                  // the value when the variable is not set
+  std::atomic<long long> v{kUnread};
+  constexpr Knob(const char* name_, long long unset_) : name(name_), unset(unset_) {}
+  long long env() const {
+    const char* e = name ? getenv(name) : nullptr;
+    return e ? atoll(e) : unset;
+  }
+  long long get() {
+    long long x = v.load(std::memory_order_relaxed);
+    if (x != kUnread) return x;
+    const long long e = env();                      // first use; a set() that lands meanwhile wins
+    return v.compare_exchange_strong(x, e, std::memory_order_relaxed) ? e : x;
+  }
+  bool on() { return get() != 0; }
+  void set(long long x) { v.store(x, std::memory_order_relaxed); }
+  void reset() { set(env()); }                      // back to what the environment says
+};
+
+// ---- a run-time int as a template argument: fn(std::integral_constant<int, V>) for the V of the list that equals v.
+// kNoCase: v is not in the list (or fn pruned the case with `if constexpr`); the caller reports it in its own words.
+constexpr int kNoCase = INT32_MIN;
+template <int... Vs, typename Fn>
+static inline int dispatch_int(int v, Fn&& fn) {
+  int rc = kNoCase;
+  (void)((v == Vs && (rc = fn(std::integral_constant<int, Vs>{}), true)) || ...);
+  return rc;
+}
+
+// ---- more dynamic LDS than the default limit: the opt-in of one kernel, once per process
+template <auto kKernel>
+static inline int allow_dynamic_lds(size_t bytes) {
+  static std::atomic<bool> done{false};   // several host threads may launch (one per mesh group)
+  if (!done.load(std::memory_order_relaxed)) {
+    GEOBI_HIP(hipFuncSetAttribute((const void*)kKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done.store(true, std::memory_order_relaxed);
+  }
+  return 0;
+}
 
 struct SubWs { void* p; size_t bytes; };   // a workspace inside a workspace
 // bump allocator over a caller-provided workspace (no hipMalloc on the hot path)
@@ -216,21 +263,55 @@ int feast_fused_pack_dx(const float* lin_w, const float* u_w, const float* c, in
 int feast_fused_pack_all(const float* lin_w, const float* u_w, const float* c, int Cin, int Cout, int Kp, float* wf,
                          float* bf, float* bdx, hipStream_t s);
 double feast_fused_bytes(int64_t N, int64_t E, int C, int nout);
-int feast_fused_fwd(const float* xa, const float* xb, int Ca, int Cin, const float* p, const float* cvec,
-                    const int* rowptr, const int* col, int N, int LC, const float* ul, const float* Bp, int Cout,
-                    const float* bias, float slope, float* out, hipStream_t s);
-int feast_fused_dx(const float* g, int Cout, const float* p, const float* cvec, const int* rowptr_out,
-                   const int* col_out, const int* rowptr_in, const int* pos, const float* dl, const float* dpn, int N,
-                   int LC, const float* xl, const float* ul, const float* dpd, const float* Bp, int Cin, float* dxa,
-                   int Ca, float* dxb, int Cb, float* tile_out, hipStream_t s);
+// ---- launch records: host-side only, filled by field name, passed by const reference down to the one
+// place that spells a kernel's argument list.
+// the layer input as every FeaSt kernel sees it; a second one describes the transposed graph the dx side walks
+struct FeastIn {
+  const float *xa = nullptr, *xb = nullptr;   // the two parts of a row; xb is never NULL (= xa when the input is unsplit)
+  int Ca = 0;                                 // width of the first part (= the whole row when unsplit)
+  const float *p = nullptr, *cvec = nullptr;
+  const int *rowptr = nullptr, *col = nullptr;
+  int N = 0, LC = 0;                          // LC: per-edge logit channels (0 / 6 / 12)
+  const float* ul = nullptr;
+};
+// what feast_fused_kernel takes beyond the input
+struct FusedLaunch {
+  const int* deg_rowptr = nullptr;
+  const float *xl = nullptr, *dpd = nullptr, *dl = nullptr;
+  const int* pos = nullptr;
+  const float *dpn = nullptr, *Bp = nullptr;
+  int NOUT = 0;
+  const float* bias = nullptr;
+  float slope = 1.0f;
+  float* out = nullptr;
+  int ldo = 0;
+  float* out1 = nullptr;
+  int split = 0, ldo1 = 0;
+  float* tile_out = nullptr;
+};
+// the backward row pass, fused (gout .. g_out: dz stays in LDS) or standalone (dz, ldz: dz from the plain GEMM)
+struct RowpassLaunch {
+  const float *gout = nullptr, *out_act = nullptr;
+  float slope = 1.0f;
+  const float* Wf = nullptr;
+  int Kp = 0;
+  float* g_out = nullptr;
+  const float* dz = nullptr;
+  int ldz = 0;
+  float *dl = nullptr, *dpn = nullptr, *dcs = nullptr;
+  int ld_dcs = 0;
+};
+int feast_fused_fwd(const FeastIn& in, int Cin, const float* Bp, int Cout, const float* bias, float slope, float* out,
+                    hipStream_t s);
+// gin: the rows of g [N, Cout] over the transposed CSR
+int feast_fused_dx(const FeastIn& gin, const int* rowptr_in, const int* pos, const float* dl, const float* dpn,
+                   const float* xl, const float* dpd, const float* Bp, int Cin, float* dxa, int Ca, float* dxb, int Cb,
+                   float* tile_out, hipStream_t s);
 bool feast_rowpass_fused_supported(int Cin, int Cb, int Cout);
 int set_tile_rows(int rows);
 int set_rowpass_form(int staged, int chunked64);
 int set_column_parts(int parts);
-int feast_rowpass_fused(const float* xa, const float* xb, int Ca, int Cin, const float* p, const float* cvec,
-                        const int* rowptr, const int* col, int N, int LC, const float* ul, const float* gout,
-                        const float* out_act, float slope, int Cout, const float* Wf, int Kp, float* g_out, float* dl,
-                        float* dpn, float* dcs, int ld_dcs, hipStream_t s);
+int feast_rowpass_fused(const FeastIn& in, int Cin, int Cout, const RowpassLaunch& r, hipStream_t s);
 // packed-weight buffer layout: [Wf | W' | Bf (fused forward) | Bdx (fused dx)]
 static inline size_t feast_wpack_plain_floats(int Cin, int Cout) {
   return (size_t)((GEOBI_H * Cin + 3) / 4 * 4) * Cout + (size_t)(GEOBI_H * Cout + 2 * GEOBI_HP) * Cin;

@@ -745,7 +745,8 @@ int run_group(const geobi_net_params_t* prm, geobi_train_group_t* g, int kind_v,
   // With several groups in flight the other groups ARE the concurrent work: a side stream per group on top of that measured
   // slower (same box, alternating, bench batch as 2 groups: 4.13-4.25 ms per step without, 4.29-4.56 with side streams at
   // the default priority, 5.6-5.9 at the lowest -- the join at the end of a backward then waits for starved products).
-  static const int side_in_groups = [] { const char* e = getenv("GEOBI_GROUP_SIDE"); return e ? atoi(e) : 0; }();
+  static Knob side_in_groups_knob{"GEOBI_GROUP_SIDE", 0};
+  const bool side_in_groups = side_in_groups_knob.on();
   SideOverride scoped(n_groups > 1 && !side_in_groups ? 0 : -1);
   hipStream_t s = (hipStream_t)g->stream;
   if (start) GEOBI_HIP(hipStreamWaitEvent(s, start, 0));
@@ -874,7 +875,8 @@ extern "C" int geobi_net_train_groups(const geobi_net_params_t* prm, geobi_train
   // the groups read what `main_stream` has produced so far (parameters of the last optimiser step) and must not zero
   // their buckets before the previous step's sum has read them
   GEOBI_HIP(hipEventRecord(g_group_start, ms));
-  static const int skew_us = [] { const char* e = getenv("GEOBI_GROUP_SKEW_US"); return e ? atoi(e) : 0; }();
+  static Knob skew_knob{"GEOBI_GROUP_SKEW_US", 0};
+  const int skew_us = (int)skew_knob.get();
   const auto call_t0 = std::chrono::steady_clock::now();
   auto body = [&](int k) {
     geobi_train_group_t& g = groups[k];

@@ -554,33 +554,20 @@ __global__ void lrelu_bwd_kernel(const float* __restrict__ gout, const float* __
 __host__ inline int edge_logit_channels(int Cin, int Cb) { return (Cb == 0 && (Cin == 6 || Cin == 12)) ? Cin : 0; }
 
 template <int MODE>
-int launch_aggregate(int C, const float* xa, const float* xb, int Ca, const float* p, const float* cvec,
-                     const int* rowptr, const int* col, const int* deg_rowptr, int N, float* out, int ldo,
-                     int LC, const float* xl, const float* ul, hipStream_t s) {
-#define GEOBI_AGG(C_, V_, L_)                                                                                    \
-  do {                                                                                                            \
-    constexpr int NPW_ = 64 / (C_ / V_);                                                                          \
-    feast_aggregate_kernel<C_, V_, MODE, L_><<<xcd_grid(cdiv(N, 4 * NPW_)), 256, 0, s>>>(                           \
-        xa, xb, Ca, p, cvec, rowptr, col, deg_rowptr, N, out, ldo, xl, ul);                                       \
-  } while (0)
-#define GEOBI_AGG_L(C_, V_)                                                                                       \
-  do {                                                                                                            \
-    if (LC == 0) GEOBI_AGG(C_, V_, 0);                                                                            \
-    else if (LC == 6) GEOBI_AGG(C_, V_, 6);                                                                       \
-    else GEOBI_AGG(C_, V_, 12);                                                                                   \
-  } while (0)
+int launch_aggregate(int C, const FeastIn& in, const int* deg_rowptr, float* out, int ldo, const float* xl, hipStream_t s) {
+  const int LC = in.LC;
   if (LC != 0 && LC != 6 && LC != 12) return set_error("feast: per-edge logits take 6 or 12 channels, got %d", LC);
   if (MODE == 0 && LC != 0 && LC != C) return set_error("feast: forward per-edge logits read the layer input");
-  switch (C) {
-    case 6: if (MODE == 0) { if (LC) GEOBI_AGG(6, 3, 6); else GEOBI_AGG(6, 3, 0); } else GEOBI_AGG_L(6, 3); break;
-    case 12: if (MODE == 0) { if (LC) GEOBI_AGG(12, 3, 12); else GEOBI_AGG(12, 3, 0); } else GEOBI_AGG_L(12, 3); break;
-    case 32: if (MODE == 0) GEOBI_AGG(32, 4, 0); else GEOBI_AGG_L(32, 4); break;
-    case 64: if (MODE == 0) GEOBI_AGG(64, 4, 0); else GEOBI_AGG_L(64, 4); break;
-    case 128: if (MODE == 0) GEOBI_AGG(128, 4, 0); else GEOBI_AGG_L(128, 4); break;
-    default: return set_error("feast: unsupported channel count %d (supported: 6, 12, 32, 64, 128)", C);
-  }
-#undef GEOBI_AGG_L
-#undef GEOBI_AGG
+  // every (C, LC) pair is built for both modes, as it always was: the forward ones with LC != C are behind the check above
+  const int rc = dispatch_int<6, 12, 32, 64, 128>(C, [&](auto c) {
+    return dispatch_int<0, 6, 12>(LC, [&](auto lc) {
+      constexpr int kC = decltype(c)::value, kLC = decltype(lc)::value, kV = kC < 32 ? 3 : 4, kNPW = 64 / (kC / kV);
+      feast_aggregate_kernel<kC, kV, MODE, kLC><<<xcd_grid(cdiv(in.N, 4 * kNPW)), 256, 0, s>>>(
+          in.xa, in.xb, in.Ca, in.p, in.cvec, in.rowptr, in.col, deg_rowptr, in.N, out, ldo, xl, in.ul);
+      return 0;
+    });
+  });
+  if (rc == kNoCase) return set_error("feast: unsupported channel count %d (supported: 6, 12, 32, 64, 128)", C);
   GEOBI_LAUNCH_OK();
   return 0;
 }
@@ -605,68 +592,51 @@ __global__ __launch_bounds__(256, 4) void feast_rowpass_edge_kernel(
                                              lane % 16, dl, dpn, dcs, ld_dcs);
 }
 
-int launch_rowpass(int C, const float* xa, const float* xb, int Ca, const float* p, const float* cvec,
-                   const int* rowptr, const int* col, const float* dz, int ldz, int N, float* dl, float* dpn,
-                   float* dcs, int ld_dcs, int LC, const float* ul, hipStream_t s) {
-#define GEOBI_ROW(C_, V_, L_)                                                                                 \
-  do {                                                                                                        \
-    constexpr int NPW_ = 64 / (C_ / V_);                                                                      \
-    feast_rowpass_kernel<C_, V_, L_><<<xcd_grid(cdiv(N, 4 * NPW_)), 256, 0, s>>>(                               \
-        xa, xb, Ca, p, cvec, rowptr, col, dz, ldz, N, dl, dpn, dcs, ld_dcs, ul);                              \
-  } while (0)
+static Knob g_rowpass_edge{"GEOBI_ROWPASS_EDGE", 1};   // A/B knob
+
+int launch_rowpass(int C, const FeastIn& in, const RowpassLaunch& r, hipStream_t s) {
   // lane = edge form unless the first input part of a split row ends off a 16-channel batch boundary; the per-edge
   // logit layers (LC > 0: level 0, normally inside the fused kernel) keep the older form here
-  static const bool edge_form = [] { const char* f = getenv("GEOBI_ROWPASS_EDGE"); return !f || atoi(f) != 0; }();   // A/B knob
-  if (edge_form && LC == 0 && (Ca >= C || (C >= 32 && Ca % 16 == 0))) {
-#define GEOBI_ROWE(C_, L_)                                                                                    \
-  feast_rowpass_edge_kernel<C_, L_><<<xcd_grid(cdiv(N, 16)), 256, 0, s>>>(xa, xb, Ca, p, cvec, rowptr, col, dz, ldz, \
-                                                                        N, dl, dpn, dcs, ld_dcs, ul)
-    switch (C) {
-      case 6: GEOBI_ROWE(6, 0); break;
-      case 12: GEOBI_ROWE(12, 0); break;
-      case 32: GEOBI_ROWE(32, 0); break;
-      case 64: GEOBI_ROWE(64, 0); break;
-      case 128: GEOBI_ROWE(128, 0); break;
-      default: return set_error("feast: unsupported channel count %d", C);
+  const bool edge = g_rowpass_edge.on() && in.LC == 0 && (in.Ca >= C || (C >= 32 && in.Ca % 16 == 0));
+  const int rc = dispatch_int<6, 12, 32, 64, 128>(C, [&](auto c) {
+    constexpr int kC = decltype(c)::value, kV = kC < 32 ? 3 : 4, kNPW = 64 / (kC / kV);
+    auto with_args = [&](auto&& go) {
+      go(in.xa, in.xb, in.Ca, in.p, in.cvec, in.rowptr, in.col, r.dz, r.ldz, in.N, r.dl, r.dpn, r.dcs, r.ld_dcs, in.ul);
+    };
+    const int blocks = xcd_grid(cdiv(in.N, 4 * kNPW));
+    if (edge) {
+      with_args([&](auto... a) { feast_rowpass_edge_kernel<kC, 0><<<xcd_grid(cdiv(in.N, 16)), 256, 0, s>>>(a...); });
+      return 0;
     }
-#undef GEOBI_ROWE
-    GEOBI_LAUNCH_OK();
+    if constexpr (kC <= 12) {      // per-edge logits: from the layer's own 6 / 12-channel input
+      if (in.LC) {
+        with_args([&](auto... a) { feast_rowpass_kernel<kC, kV, kC><<<blocks, 256, 0, s>>>(a...); });
+        return 0;
+      }
+    }
+    with_args([&](auto... a) { feast_rowpass_kernel<kC, kV, 0><<<blocks, 256, 0, s>>>(a...); });
     return 0;
-  }
-  switch (C) {
-    case 6: if (LC) GEOBI_ROW(6, 3, 6); else GEOBI_ROW(6, 3, 0); break;
-    case 12: if (LC) GEOBI_ROW(12, 3, 12); else GEOBI_ROW(12, 3, 0); break;
-    case 32: GEOBI_ROW(32, 4, 0); break;
-    case 64: GEOBI_ROW(64, 4, 0); break;
-    case 128: GEOBI_ROW(128, 4, 0); break;
-    default: return set_error("feast: unsupported channel count %d", C);
-  }
-#undef GEOBI_ROW
+  });
+  if (rc == kNoCase) return set_error("feast: unsupported channel count %d", C);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-int launch_logits(int C, const float* xa, const float* xb, int Ca, const float* u, int N, float* p, hipStream_t s) {
-  if (C >= 32 && Ca % (C / 16) == 0) {            // a lane's channels never straddle the two input parts
-    const int gb = cdiv(N, 16);
-    switch (C) {
-      case 32: feast_logits_group_kernel<32><<<gb, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-      case 64: feast_logits_group_kernel<64><<<gb, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-      case 128: feast_logits_group_kernel<128><<<gb, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-      default: return set_error("feast: unsupported channel count %d", C);
-    }
-    GEOBI_LAUNCH_OK();
-    return 0;
+// p = the node-level logits of the layer input
+int launch_logits(int C, const FeastIn& in, float* p, hipStream_t s) {
+  int rc;
+  if (C >= 32 && in.Ca % (C / 16) == 0) {            // a lane's channels never straddle the two input parts
+    rc = dispatch_int<32, 64, 128>(C, [&](auto c) {
+      feast_logits_group_kernel<decltype(c)::value><<<cdiv(in.N, 16), 256, 0, s>>>(in.xa, in.xb, in.Ca, in.ul, in.N, p);
+      return 0;
+    });
+  } else {
+    rc = dispatch_int<6, 12, 32, 64, 128>(C, [&](auto c) {
+      feast_logits_kernel<decltype(c)::value><<<cdiv(in.N, 256), 256, 0, s>>>(in.xa, in.xb, in.Ca, in.ul, in.N, p);
+      return 0;
+    });
   }
-  int blocks = cdiv(N, 256);
-  switch (C) {
-    case 6: feast_logits_kernel<6><<<blocks, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-    case 12: feast_logits_kernel<12><<<blocks, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-    case 32: feast_logits_kernel<32><<<blocks, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-    case 64: feast_logits_kernel<64><<<blocks, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-    case 128: feast_logits_kernel<128><<<blocks, 256, 0, s>>>(xa, xb, Ca, u, N, p); break;
-    default: return set_error("feast: unsupported channel count %d", C);
-  }
+  if (rc == kNoCase) return set_error("feast: unsupported channel count %d", C);
   GEOBI_LAUNCH_OK();
   return 0;
 }
@@ -721,6 +691,17 @@ int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   const bool own_weights = wf_out == nullptr && !(fused && bf_packed != nullptr);
   Arena a(ws, ws_bytes);
   const FwdBuffers fb = carve_fwd(a, N, Cin, Cout, fused, own_weights);
+  FeastIn in;
+  in.xa = xa;
+  in.xb = xb ? xb : xa;
+  in.Ca = Cb ? Ca : Cin;
+  in.p = p;
+  in.cvec = cvec;
+  in.rowptr = rowptr_in;
+  in.col = col_in;
+  in.N = (int)N;
+  in.LC = edge_logit_channels(Cin, Cb);      // level-0 layers: logits per edge from the raw rows, no p
+  in.ul = u_w;
   if (!fused || own_weights) GEOBI_WS_CHECK("feast_fwd", a, ws, ws_bytes);      // else nothing is taken
   if (fused) {
     // Fused path: aggregation + node transform in one kernel, z never reaches HBM (feast_fused.hip).
@@ -736,11 +717,9 @@ int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
     } else {
       GEOBI_TRY(feast_fused_pack_fwd(lin_w, cvec, Cin, Cout, const_cast<float*>(bf), s));
     }
-    const int LCf = edge_logit_channels(Cin, Cb);
-    if (LCf == 0) GEOBI_TRY(launch_logits(Cin, xa, xb ? xb : xa, Cb ? Ca : Cin, u_w, (int)N, p, s));
+    if (in.LC == 0) GEOBI_TRY(launch_logits(Cin, in, p, s));
     prof_begin_launch(PROF_AGG_FWD, s, feast_fused_bytes(N, Ecap, Cin, Cout), Cin * 1000 + Cout);   // ONE launch: feast_fused_kernel
-    int rcf = feast_fused_fwd(xa, xb ? xb : xa, Cb ? Ca : Cin, Cin, p, cvec, rowptr_in, col_in, (int)N, LCf, u_w, bf,
-                              Cout, bias, slope, out, s);
+    int rcf = feast_fused_fwd(in, Cin, bf, Cout, bias, slope, out, s);
     prof_end(PROF_AGG_FWD, s);
     return rcf;
   }
@@ -753,11 +732,9 @@ int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
     pack_wf_kernel<<<cdiv((int64_t)Kp * Cout, 256), 256, 0, s>>>(lin_w, Cin, Cout, Kp, wf);
   }
   GEOBI_LAUNCH_OK();
-  const int LC = edge_logit_channels(Cin, Cb);      // level-0 layers: logits per edge from the raw rows, no p
-  if (LC == 0) GEOBI_TRY(launch_logits(Cin, xa, xb ? xb : xa, Cb ? Ca : Cin, u_w, (int)N, p, s));
+  if (in.LC == 0) GEOBI_TRY(launch_logits(Cin, in, p, s));
   prof_begin(PROF_AGG_FWD, s, feast_agg_bytes(N, Ecap, Cin, Kp), Cin);
-  int rc = launch_aggregate<0>(Cin, xa, xb ? xb : xa, Cb ? Ca : Cin, p, cvec, rowptr_in, col_in, nullptr, (int)N, z,
-                               Kp, LC, xa, u_w, s);
+  int rc = launch_aggregate<0>(Cin, in, nullptr, z, Kp, xa, s);
   prof_end(PROF_AGG_FWD, s);
   GEOBI_TRY(rc);
   GemmEpilogue ep;
@@ -812,14 +789,11 @@ static void plan_bwd(Arena& a, int64_t N, int64_t Ecap, int Cin, int Cout, bool 
   b.gemm_ws = a.take_ws(b.gemm_bytes).p;
 }
 
-static bool rowpass_fused_enabled() {
-  static const bool on = [] { const char* f = getenv("GEOBI_ROWPASS_FUSED"); return !f || atoi(f) != 0; }();
-  return on;
-}
+static Knob g_rowpass_fused{"GEOBI_ROWPASS_FUSED", 1};
 
 // what feast_bwd will take from its workspace, from the same facts it decides its path with
 static void bwd_needs(int Cin, int Cb, int Cout, bool fused, bool need_dx, bool& need_dz, bool& need_z) {
-  need_dz = !(fused && rowpass_fused_enabled() && feast_rowpass_fused_supported(Cin, Cb, Cout));
+  need_dz = !(fused && g_rowpass_fused.on() && feast_rowpass_fused_supported(Cin, Cb, Cout));
   need_z = fused && !need_dx;
 }
 
@@ -850,10 +824,19 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   bwd_needs(Cin, Cb, Cout, z == nullptr, dxa != nullptr, need_dz, need_z);
   plan_bwd(a, N, Ecap, Cin, Cout, need_dz, need_z, b);
   GEOBI_WS_CHECK("feast_bwd", a, ws, ws_bytes);
-  const float* xb_ = xb ? xb : xa;
-  const int Ca_ = Cb ? Ca : Cin;
-
   const int LC = edge_logit_channels(Cin, Cb);
+  FeastIn in;                    // the layer input over the in-CSR
+  in.xa = xa;
+  in.xb = xb ? xb : xa;
+  in.Ca = Cb ? Ca : Cin;
+  in.p = p;
+  in.cvec = cvec;
+  in.rowptr = rowptr_in;
+  in.col = col_in;
+  in.N = (int)N;
+  in.LC = LC;
+  in.ul = u_w;
+  const int Ca_ = in.Ca;
   // Fused forward (z == NULL): the aggregated rows were never written
   const bool fused = z == nullptr;
   // [dp | dcs]: the tail columns of r' (unfused dx GEMM) or a compact [N, 24] array (fused dx kernel)
@@ -871,10 +854,22 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   const bool rp_fused = !need_dz;
   const float* g = gout;
   if (slope != 1.0f) g = b.g;
+  RowpassLaunch row;
+  row.gout = gout;
+  row.out_act = slope != 1.0f ? out : nullptr;
+  row.slope = slope;
+  row.Wf = wf;
+  row.Kp = Kp;
+  row.g_out = b.g;
+  row.dz = b.dz;
+  row.ldz = Kp;
+  row.dl = b.dl;
+  row.dpn = b.dpn;
+  row.dcs = dpd + HP;
+  row.ld_dcs = ld_dpd;
   if (rp_fused) {
     prof_begin(PROF_ROWPASS, s, 0.0, Cin);
-    int rcf = feast_rowpass_fused(xa, xb_, Ca_, Cin, p, cvec, rowptr_in, col_in, (int)N, LC, u_w, gout,
-                                  slope != 1.0f ? out : nullptr, slope, Cout, wf, Kp, b.g, b.dl, b.dpn, dpd + HP, ld_dpd, s);
+    int rcf = feast_rowpass_fused(in, Cin, Cout, row, s);
     prof_end(PROF_ROWPASS, s);
     GEOBI_TRY(rcf);
   } else if (slope != 1.0f) {
@@ -886,8 +881,13 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
   // kernel forms anyway (dW[h,k,o] = sum_j x_j[k] r_j[h,o]): no z needed.  Without dx (first layer of the vertex
   // branch) z is recomputed by the aggregation kernel for dW = z^T g.
   const bool rform = fused && dxa != nullptr;
+  FeastIn gin = in;              // what the dx side walks: the unsplit rows of g [N, Cout] over the transposed graph
+  gin.xa = gin.xb = g;
+  gin.Ca = Cout;
+  gin.rowptr = rowptr_out;
+  gin.col = col_out;
   if (fused && !rform) {
-    GEOBI_TRY(launch_aggregate<0>(Cin, xa, xb_, Ca_, p, cvec, rowptr_in, col_in, nullptr, (int)N, b.z, Kp, LC, xa, u_w, s));
+    GEOBI_TRY(launch_aggregate<0>(Cin, in, nullptr, b.z, Kp, xa, s));
     z = b.z;
   }
   // 2'. weight + bias gradient [z | 1]^T g: needs only z and g, nothing downstream needs it -> side stream
@@ -906,8 +906,7 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
     GEOBI_TRY(gemm_nn(g, Cout, wf, Cout, 1, b.dz, Kp, (int)N, Kp, Cout, ep0, s));
     // 3. row pass: per-edge softmax backward
     prof_begin(PROF_ROWPASS, s, 0.0, Cin);
-    rc = launch_rowpass(Cin, xa, xb_, Ca_, p, cvec, rowptr_in, col_in, b.dz, Kp, (int)N, b.dl, b.dpn, dpd + HP, ld_dpd, LC,
-                        u_w, s);
+    rc = launch_rowpass(Cin, in, row, s);
     prof_end(PROF_ROWPASS, s);
     GEOBI_TRY(rc);
   }
@@ -954,8 +953,7 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
       GEOBI_TRY(feast_fused_pack_dx(lin_w, u_w, cvec, Cin, Cout, b.bdx, s));
     }
     prof_begin(PROF_AGG_BWD, s, feast_fused_bytes(N, Ecap, Cout, Cin), Cout);
-    rc = feast_fused_dx(g, Cout, p, cvec, rowptr_out, col_out, rowptr_in, pos_in, b.dl, b.dpn, (int)N, LC, xa, u_w, dpd,
-                        bdx, Cin, dxa, Cb ? Ca : Cin, dxb, Cb, b.rp, s);
+    rc = feast_fused_dx(gin, rowptr_in, pos_in, b.dl, b.dpn, xa, dpd, bdx, Cin, dxa, Ca_, dxb, Cb, b.rp, s);
     prof_end(PROF_AGG_BWD, s);
     GEOBI_TRY(rc);
     // every weight gradient of the layer: [x | 1]^T r' (side stream; du / dc of the per-edge-logit layers come from
@@ -975,8 +973,7 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
     }
   } else if (dxa != nullptr) {
     prof_begin(PROF_AGG_BWD, s, feast_agg_bytes(N, Ecap, Cout, H * Cout), Cout);
-    rc = launch_aggregate<1>(Cout, g, g, Cout, p, cvec, rowptr_out, col_out, rowptr_in, (int)N, b.rp, ldr, LC, xa, u_w,
-                             s);
+    rc = launch_aggregate<1>(Cout, gin, rowptr_in, b.rp, ldr, xa, s);
     prof_end(PROF_AGG_BWD, s);
     GEOBI_TRY(rc);
     const float* wp = wf_saved ? wf_saved + (size_t)Kp * Cout : b.wp;

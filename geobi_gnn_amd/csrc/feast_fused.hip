@@ -1127,27 +1127,19 @@ __global__ void pack_fused_batch_kernel(PackBatch pb) {
   }
 }
 
-// Tile geometry of the fused kernels: GEOBI_TILE16 (read once): 1 = 16-row tiles / four workgroups per CU (default),
-// 0 = 32-row tiles / two workgroups per CU.  Same-box A/B knob; both forms stay under the parity tests.
-int g_tile_rows = 0;          // 0: not set yet -> GEOBI_TILE16 decides; 16 / 32 once geobi_set_tile_rows was called
-// Forms of the fused backward row pass at 64 input channels (-1: environment / built-in default; set_rowpass_form):
+// Tile geometry of the fused kernels: GEOBI_TILE16: 1 = 16-row tiles / four workgroups per CU (default),
+// 0 = 32-row tiles / two workgroups per CU.  Same-box A/B knob (set_tile_rows); both forms stay under the parity tests.
+Knob g_tile16{"GEOBI_TILE16", 1};
+// Forms of the fused backward row pass at 64 input channels (set_rowpass_form; -1 there: back to the environment):
 //   staged   1 (default; GEOBI_ROWPASS_STAGED): neighbour rows staged through LDS, 0: lane-private row reads
 //   chunked  1: the channel-chunked kernel (32-node tiles, two chunks of 32 channels) for every 64-channel layer,
 //            0: for none; default (GEOBI_ROWPASS_CHUNKED64 unset): for Cout = 128 only -- measured 31 against 36 us
 //            there, 102 against 86 us at Cout = 32
-int g_rp_staged = -1, g_rp_chunked = -1;
-bool rp_staged() {
-  static const bool env_on = [] { const char* f = getenv("GEOBI_ROWPASS_STAGED"); return !f || atoi(f) != 0; }();
-  return g_rp_staged < 0 ? env_on : g_rp_staged != 0;
-}
+constexpr long long kChunkedAuto = -(1ll << 40);      // "unset": no number anybody writes into the variable
+Knob g_rp_staged{"GEOBI_ROWPASS_STAGED", 1}, g_rp_chunked{"GEOBI_ROWPASS_CHUNKED64", kChunkedAuto};
 bool rp_chunked64(int Cout) {
-  static const int env = [] { const char* f = getenv("GEOBI_ROWPASS_CHUNKED64"); return f ? (atoi(f) != 0 ? 1 : 0) : -1; }();
-  const int v = g_rp_chunked < 0 ? env : g_rp_chunked;
-  return v < 0 ? Cout == 128 : v != 0;
-}
-bool tile16() {
-  static const bool env_on = [] { const char* f = getenv("GEOBI_TILE16"); return !f || atoi(f) != 0; }();
-  return g_tile_rows ? g_tile_rows == 16 : env_on;
+  const long long v = g_rp_chunked.get();
+  return v == kChunkedAuto ? Cout == 128 : v != 0;
 }
 
 // Column parts of a launch (feast_fused_kernel's CS): 2 when the layer reads 128 channels and the 16-row tiles alone would
@@ -1155,90 +1147,88 @@ bool tile16() {
 // tile's matrix phase (one wave per SIMD, 0.3-0.6 MB of weights streamed per tile) is what the kernel's time follows:
 // 128 -> 128 dx 43.7 -> 33.0 us at 264 tiles, 65.2 -> 54.2 at 424.  Measured slower for 64-channel layers and from 768 tiles
 // up (profiles/r04_weight_ring.txt).  Same bits either way, so the choice may depend on N.
-std::atomic<int> g_col_parts{-1};          // -1: from the environment on first use; 0: per launch; 1 / 2: forced
-int g_col_parts_max_tiles = 512;
+Knob g_col_parts{"GEOBI_COLUMN_PARTS", 0};          // 0 (or anything outside 0..2): per launch; 1 / 2: forced
+Knob g_col_parts_max_tiles{"GEOBI_COLUMN_PARTS_MAX_TILES", 512};
 int column_parts(int tiles) {
-  int v = g_col_parts.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* f = getenv("GEOBI_COLUMN_PARTS");
-    v = f ? atoi(f) : 0;
-    if (v < 0 || v > 2) v = 0;
-    if (const char* t = getenv("GEOBI_COLUMN_PARTS_MAX_TILES")) g_col_parts_max_tiles = atoi(t);
-    g_col_parts.store(v, std::memory_order_relaxed);
-  }
-  if (v != 0) return v;
-  return tiles <= g_col_parts_max_tiles ? 2 : 1;
+  const long long v = g_col_parts.get();
+  if (v == 1 || v == 2) return (int)v;
+  return tiles <= g_col_parts_max_tiles.get() ? 2 : 1;
 }
 
 // GEOBI_WARM_L2=0: without the up-front request of the packed weights (feast_dev.h: warm_l2) -- same-box A/B
-bool warm_l2_enabled() {
-  static const bool on = [] { const char* f = getenv("GEOBI_WARM_L2"); return !f || atoi(f) != 0; }();
-  return on;
-}
+Knob g_warm_l2{"GEOBI_WARM_L2", 1};
+
+// ---- which instantiations exist: the dispatch below prunes its cases with these, so the kernels built are these alone
+// forward and row pass read per-edge logits from the layer's own unsplit 6 / 12-channel input: LC == C
+template <int C, int LC>
+constexpr bool kOwnLogits = LC == 0 || LC == C;
+// dx (MODE 1) gathers g [N, Cout] under any of the layer's logit forms
+template <int C, int MODE, int LC>
+constexpr bool kFusedLeaf = MODE == 1 || kOwnLogits<C, LC>;
+// dx with per-edge logits writes a 6- or 12-channel input gradient: one column tile
+template <int MODE, int LC, int NT>
+constexpr bool kFusedWidth = NT == 1 || !(MODE == 1 && LC > 0);
+// two column parts: 128 channels read, node-level logits (0.3-0.6 MB of weights per tile); 16-row tiles only
+template <int C, int LC>
+constexpr bool kTwoParts = C >= 128 && LC == 0;
+// the staged row reads of the fused row pass: 64 channels, node-level logits; 16-row tiles only
+template <int C, int LC>
+constexpr bool kRowpassStaged = C == 64 && LC == 0;
 
 template <int C, int MODE, int LC, int NT, int ROWS, int CS = 1>
-int launch_one(const float* xa, const float* xb, int Ca, const float* p, const float* cvec, const int* rowptr,
-               const int* col, const int* deg_rowptr, int N, const float* xl, const float* ul, const float* dpd,
-               const float* dl, const int* pos, const float* dpn, const float* Bp, int NOUT, const float* bias, float slope, float* out, int ldo, float* out1, int split,
-               int ldo1, float* tile_out, hipStream_t s) {
+int launch_one(const FeastIn& in, const FusedLaunch& f, hipStream_t s) {
   constexpr size_t lds = (size_t)fused_lds_floats<C, MODE, LC, ROWS>() * sizeof(float);
   static_assert(lds <= 163840, "tile exceeds the LDS of a CU");
   static_assert(ROWS == 32 || lds <= 40960, "16-row tiles: four workgroups per CU");
-  static std::atomic<bool> attr_set{false};   // several host threads may launch (one per mesh group)
-  if (!attr_set) {
-    GEOBI_HIP(hipFuncSetAttribute((const void*)feast_fused_kernel<C, MODE, LC, NT, ROWS, CS>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  GEOBI_TRY((allow_dynamic_lds<feast_fused_kernel<C, MODE, LC, NT, ROWS, CS>>(lds)));
+  const dim3 grid(xcd_grid(cdiv(in.N, ROWS)), CS), block(16 * ROWS);
+  // the kernel's argument list, spelled once for both ways to launch
+  auto with_args = [&](auto&& go) {
+    go(in.xa, in.xb, in.Ca, in.p, in.cvec, in.rowptr, in.col, f.deg_rowptr, in.N, f.xl, in.ul, f.dpd, f.dl, f.pos, f.dpn,
+       f.Bp, f.NOUT, f.bias, f.slope, f.out, f.ldo, f.out1, f.split, f.ldo1, f.tile_out, g_warm_l2.on() ? 1 : 0);
+  };
   hipEvent_t ev_a, ev_b;
   if (MODE == 0 && prof_take_launch_events(&ev_a, &ev_b)) {
     // profiling pass of the bench (geobi_prof_enable): the two events are bound to THIS dispatch
-    hipExtLaunchKernelGGL((feast_fused_kernel<C, MODE, LC, NT, ROWS, CS>), dim3(xcd_grid(cdiv(N, ROWS)), CS), dim3(16 * ROWS),
-                          lds, s, ev_a, ev_b, 0, xa, xb, Ca, p, cvec, rowptr, col, deg_rowptr, N, xl, ul, dpd, dl, pos, dpn,
-                          Bp, NOUT, bias, slope, out, ldo, out1, split, ldo1, tile_out, warm_l2_enabled() ? 1 : 0);
-    GEOBI_LAUNCH_OK();
-    return 0;
+    with_args([&](auto... a) {
+      hipExtLaunchKernelGGL((feast_fused_kernel<C, MODE, LC, NT, ROWS, CS>), grid, block, lds, s, ev_a, ev_b, 0, a...);
+    });
+  } else {
+    with_args([&](auto... a) { feast_fused_kernel<C, MODE, LC, NT, ROWS, CS><<<grid, block, lds, s>>>(a...); });
   }
-  feast_fused_kernel<C, MODE, LC, NT, ROWS, CS><<<dim3(xcd_grid(cdiv(N, ROWS)), CS), 16 * ROWS, lds, s>>>(
-      xa, xb, Ca, p, cvec, rowptr, col, deg_rowptr, N, xl, ul, dpd, dl, pos, dpn, Bp, NOUT, bias, slope, out, ldo, out1,
-      split, ldo1, tile_out, warm_l2_enabled() ? 1 : 0);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-#define GEOBI_FUSED_ARGS                                                                                            \
-  xa, xb, Ca, p, cvec, rowptr, col, deg_rowptr, N, xl, ul, dpd, dl, pos, dpn, Bp, NOUT, bias, slope, out, ldo, out1, \
-      split, ldo1, tile_out, s
-
+// tile rows, column parts and output width of one (C, MODE, LC) leaf
 template <int C, int MODE, int LC>
-int launch_nt(int NT, const float* xa, const float* xb, int Ca, const float* p, const float* cvec, const int* rowptr,
-              const int* col, const int* deg_rowptr, int N, const float* xl, const float* ul, const float* dpd,
-              const float* dl, const int* pos, const float* dpn, const float* Bp, int NOUT, const float* bias, float slope, float* out, int ldo, float* out1, int split,
-              int ldo1, float* tile_out, hipStream_t s) {
-  // dx with per-edge logits writes a 6- or 12-channel input gradient: one column tile
-  constexpr bool kNarrowOnly = MODE == 1 && LC > 0;
-  if (tile16()) {
-    // two column parts: 128 channels read, node-level logits (0.3-0.6 MB of weights per tile)
-    if constexpr (C >= 128 && LC == 0) {
-      if (column_parts(cdiv(N, 16)) == 2) {
-        if (NT == 1) return launch_one<C, MODE, LC, 1, 16, 2>(GEOBI_FUSED_ARGS);
-        if (NT == 2) return launch_one<C, MODE, LC, 2, 16, 2>(GEOBI_FUSED_ARGS);
-        if (NT == 4) return launch_one<C, MODE, LC, 4, 16, 2>(GEOBI_FUSED_ARGS);
+int launch_tiles(const FeastIn& in, const FusedLaunch& f, hipStream_t s) {
+  const int rc = dispatch_int<1, 2, 4>(feast_fused_nt(f.NOUT), [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    if constexpr (kFusedWidth<MODE, LC, NT>) {
+      if (!g_tile16.on()) return launch_one<C, MODE, LC, NT, 32>(in, f, s);
+      if constexpr (kTwoParts<C, LC>) {
+        if (column_parts(cdiv(in.N, 16)) == 2) return launch_one<C, MODE, LC, NT, 16, 2>(in, f, s);
       }
+      return launch_one<C, MODE, LC, NT, 16>(in, f, s);
+    } else {
+      return kNoCase;
     }
-    if (NT == 1) return launch_one<C, MODE, LC, 1, 16>(GEOBI_FUSED_ARGS);
-    if constexpr (!kNarrowOnly) {
-      if (NT == 2) return launch_one<C, MODE, LC, 2, 16>(GEOBI_FUSED_ARGS);
-      if (NT == 4) return launch_one<C, MODE, LC, 4, 16>(GEOBI_FUSED_ARGS);
-    }
-  } else {
-    if (NT == 1) return launch_one<C, MODE, LC, 1, 32>(GEOBI_FUSED_ARGS);
-    if constexpr (!kNarrowOnly) {
-      if (NT == 2) return launch_one<C, MODE, LC, 2, 32>(GEOBI_FUSED_ARGS);
-      if (NT == 4) return launch_one<C, MODE, LC, 4, 32>(GEOBI_FUSED_ARGS);
-    }
-  }
-  return set_error("feast fused: unsupported output width %d", NOUT);
+  });
+  return rc == kNoCase ? set_error("feast fused: unsupported output width %d", f.NOUT) : rc;
+}
+
+// the one dispatch of feast_fused_kernel: C channels gathered (forward: Cin of 6 .. 128, dx: Cout of 32 .. 128)
+template <int MODE, int... Cs>
+int launch_fused(int C, const FeastIn& in, const FusedLaunch& f, hipStream_t s) {
+  return dispatch_int<Cs...>(C, [&](auto c) {
+    return dispatch_int<0, 6, 12>(in.LC, [&](auto lc) {
+      if constexpr (kFusedLeaf<decltype(c)::value, MODE, decltype(lc)::value>)
+        return launch_tiles<decltype(c)::value, MODE, decltype(lc)::value>(in, f, s);
+      else
+        return kNoCase;
+    });
+  });
 }
 
 }  // namespace
@@ -1254,62 +1244,38 @@ extern "C" int geobi_debug_stamps_bwd(void* host_dst, size_t bytes) {
 
 namespace {
 template <int C, int LC, int COUT, int RT, int RP = 0>
-int launch_rowpass_fused_rt(const float* xa, const float* xb, int Ca, const float* p, const float* cvec, const int* rowptr,
-                         const int* col, int N, const float* ul, const float* gout, const float* out_act, float slope,
-                         const float* Wf, int Kp, float* g_out, float* dl, float* dpn, float* dcs, int ld_dcs,
-                         hipStream_t s) {
+int launch_rowpass_fused_rt(const FeastIn& in, const RowpassLaunch& r, hipStream_t s) {
   constexpr int NCT = (H * C + 31) / 32;
   constexpr int LDZ = NCT * 32 + 4;
   constexpr size_t lds = ((size_t)RT * (COUT + 4) + (size_t)RT * LDZ + (LC > 0 ? LC * HP : 0)) * sizeof(float);
   static_assert(lds <= 163840, "tiles exceed the LDS of a CU");
-  static std::atomic<bool> attr_set{false};   // several host threads may launch (one per mesh group)
-  if (!attr_set) {
-    GEOBI_HIP(hipFuncSetAttribute((const void*)feast_rowpass_fused_kernel<C, LC, COUT, RT, RP>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  feast_rowpass_fused_kernel<C, LC, COUT, RT, RP><<<xcd_grid(cdiv(N, RT)), 16 * RT, lds, s>>>(
-      xa, xb, Ca, p, cvec, rowptr, col, N, ul, gout, out_act, slope, Wf, Kp, g_out, dl, dpn, dcs, ld_dcs);
+  GEOBI_TRY((allow_dynamic_lds<feast_rowpass_fused_kernel<C, LC, COUT, RT, RP>>(lds)));
+  feast_rowpass_fused_kernel<C, LC, COUT, RT, RP><<<xcd_grid(cdiv(in.N, RT)), 16 * RT, lds, s>>>(
+      in.xa, in.xb, in.Ca, in.p, in.cvec, in.rowptr, in.col, in.N, in.ul, r.gout, r.out_act, r.slope, r.Wf, r.Kp, r.g_out,
+      r.dl, r.dpn, r.dcs, r.ld_dcs);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
 template <int C, int LC, int COUT>
-int launch_rowpass_fused(const float* xa, const float* xb, int Ca, const float* p, const float* cvec, const int* rowptr,
-                         const int* col, int N, const float* ul, const float* gout, const float* out_act, float slope,
-                         const float* Wf, int Kp, float* g_out, float* dl, float* dpn, float* dcs, int ld_dcs,
-                         hipStream_t s) {
-  if (tile16()) {
-    if constexpr (C == 64 && LC == 0) {
-      // GEOBI_ROWPASS_STAGED=0 / set_rowpass_form: the lane-private row reads (same-box A/B; results are bit-identical)
-      if (rp_staged() && Ca % 32 == 0)
-        return launch_rowpass_fused_rt<C, LC, COUT, 16, 1>(xa, xb, Ca, p, cvec, rowptr, col, N, ul, gout, out_act, slope, Wf,
-                                                           Kp, g_out, dl, dpn, dcs, ld_dcs, s);
-    }
-    return launch_rowpass_fused_rt<C, LC, COUT, 16>(xa, xb, Ca, p, cvec, rowptr, col, N, ul, gout, out_act, slope, Wf, Kp,
-                                                    g_out, dl, dpn, dcs, ld_dcs, s);
+int launch_rowpass_fused(const FeastIn& in, const RowpassLaunch& r, hipStream_t s) {
+  if (!g_tile16.on()) return launch_rowpass_fused_rt<C, LC, COUT, 32>(in, r, s);
+  if constexpr (kRowpassStaged<C, LC>) {
+    // GEOBI_ROWPASS_STAGED=0 / set_rowpass_form: the lane-private row reads (same-box A/B; results are bit-identical)
+    if (g_rp_staged.on() && in.Ca % 32 == 0) return launch_rowpass_fused_rt<C, LC, COUT, 16, 1>(in, r, s);
   }
-  return launch_rowpass_fused_rt<C, LC, COUT, 32>(xa, xb, Ca, p, cvec, rowptr, col, N, ul, gout, out_act, slope, Wf, Kp,
-                                                  g_out, dl, dpn, dcs, ld_dcs, s);
+  return launch_rowpass_fused_rt<C, LC, COUT, 16>(in, r, s);
 }
-}  // namespace
 
-namespace {
+// the channel-chunked row pass: 128 input channels, or 64 (see rp_chunked64)
 template <int COUT, int C = 128>
-int launch_rowpass_fused128(const float* xa, const float* xb, int Ca, const float* p, const float* cvec,
-                            const int* rowptr, const int* col, int N, const float* gout, const float* out_act,
-                            float slope, const float* Wf, float* g_out, float* dl, float* dpn, float* dcs, int ld_dcs,
-                            hipStream_t s) {
+int launch_rowpass_fused128(const FeastIn& in, const RowpassLaunch& r, hipStream_t s) {
   constexpr size_t lds = ((size_t)TN * (COUT + 4) + (size_t)TN * (H * 32 + 4)) * sizeof(float);
   static_assert(lds <= 81920, "two workgroups per CU");
-  static std::atomic<bool> attr_set{false};   // several host threads may launch (one per mesh group)
-  if (!attr_set) {
-    GEOBI_HIP(hipFuncSetAttribute((const void*)feast_rowpass_fused128_kernel<COUT, C>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  feast_rowpass_fused128_kernel<COUT, C><<<xcd_grid(cdiv(N, TN)), KT9, lds, s>>>(
-      xa, xb, Ca, p, cvec, rowptr, col, N, gout, out_act, slope, Wf, g_out, dl, dpn, dcs, ld_dcs);
+  GEOBI_TRY((allow_dynamic_lds<feast_rowpass_fused128_kernel<COUT, C>>(lds)));
+  feast_rowpass_fused128_kernel<COUT, C><<<xcd_grid(cdiv(in.N, TN)), KT9, lds, s>>>(
+      in.xa, in.xb, in.Ca, in.p, in.cvec, in.rowptr, in.col, in.N, r.gout, r.out_act, r.slope, r.Wf, r.g_out, r.dl, r.dpn,
+      r.dcs, r.ld_dcs);
   GEOBI_LAUNCH_OK();
   return 0;
 }
@@ -1318,8 +1284,7 @@ int launch_rowpass_fused128(const float* xa, const float* xb, int Ca, const floa
 // column parts of the fused kernel from one process (parity tests, A/B timing): 1 / 2, 0 = chosen per launch
 int set_column_parts(int parts) {
   if (parts < 0 || parts > 2) return set_error("fused kernel column parts: 1, 2 or 0 (per launch), got %d", parts);
-  column_parts(1);                           // the environment's tile limit is read once
-  g_col_parts.store(parts, std::memory_order_relaxed);
+  g_col_parts.set(parts);
   return 0;
 }
 
@@ -1327,76 +1292,50 @@ int set_column_parts(int parts) {
 int set_rowpass_form(int staged, int chunked64) {
   if (staged < -1 || staged > 1 || chunked64 < -1 || chunked64 > 1)
     return set_error("row-pass form: staged and chunked64 are 1, 0 or -1 (default), got %d, %d", staged, chunked64);
-  g_rp_staged = staged;
-  g_rp_chunked = chunked64;
+  if (staged < 0) g_rp_staged.reset(); else g_rp_staged.set(staged);
+  if (chunked64 < 0) g_rp_chunked.reset(); else g_rp_chunked.set(chunked64);
   return 0;
 }
 
 // both tile geometries from one process (parity tests, A/B timing): rows = 16 / 32, 0 = back to GEOBI_TILE16
 int set_tile_rows(int rows) {
   if (rows != 0 && rows != 16 && rows != 32) return set_error("tile rows: 16, 32 or 0 (environment default), got %d", rows);
-  g_tile_rows = rows;
+  if (rows == 0) g_tile16.reset(); else g_tile16.set(rows == 16);
   return 0;
 }
 
 // split inputs: the row is read in batches of 16 channels (32 at 128 channels), so the first part must end on such a
 // boundary; 128 channels: Cout 64 or 128 (GEOBI_ROWPASS_FUSED128=0: the GEMM + standalone row pass)
+static Knob g_rowpass_fused128{"GEOBI_ROWPASS_FUSED128", 1};   // A/B knob
 bool feast_rowpass_fused_supported(int Cin, int Cb, int Cout) {
-  if (Cin == 128) {
-    static const bool on = [] { const char* f = getenv("GEOBI_ROWPASS_FUSED128"); return !f || atoi(f) != 0; }();   // A/B knob
-    return on && (Cout == 64 || Cout == 128) && (Cb == 0 || (Cin - Cb) % 32 == 0);
-  }
+  if (Cin == 128) return g_rowpass_fused128.on() && (Cout == 64 || Cout == 128) && (Cb == 0 || (Cin - Cb) % 32 == 0);
   return Cin <= 64 && (Cb == 0 || (Cin >= 32 && (Cin - Cb) % 16 == 0));
 }
 
-// g (written to g_out when slope != 1), dl, dpn, dcs of one layer in one launch; LC: per-edge logit channels (0 / 6 / 12)
-int feast_rowpass_fused(const float* xa, const float* xb, int Ca, int Cin, const float* p, const float* cvec,
-                        const int* rowptr, const int* col, int N, int LC, const float* ul, const float* gout,
-                        const float* out_act, float slope, int Cout, const float* Wf, int Kp, float* g_out, float* dl,
-                        float* dpn, float* dcs, int ld_dcs, hipStream_t s) {
-#define GEOBI_RP_ARGS xa, xb, Ca, p, cvec, rowptr, col, N, ul, gout, out_act, slope, Wf, Kp, g_out, dl, dpn, dcs, ld_dcs, s
-#define GEOBI_RP_COUT(C_, L_)                                                            \
-  switch (Cout) {                                                                        \
-    case 32: return launch_rowpass_fused<C_, L_, 32>(GEOBI_RP_ARGS);                     \
-    case 64: return launch_rowpass_fused<C_, L_, 64>(GEOBI_RP_ARGS);                     \
-    case 128: return launch_rowpass_fused<C_, L_, 128>(GEOBI_RP_ARGS);                   \
-    default: return set_error("feast fused row pass: unsupported Cout=%d", Cout);        \
-  }
+// g (written to g_out when slope != 1), dl, dpn, dcs of one layer in one launch
+int feast_rowpass_fused(const FeastIn& in, int Cin, int Cout, const RowpassLaunch& r, hipStream_t s) {
   if (Cin == 128) {
-    GEOBI_REQUIRE(LC == 0, "feast fused row pass: per-edge logits at 128 channels");
-    if (Cout == 64)
-      return launch_rowpass_fused128<64>(xa, xb, Ca, p, cvec, rowptr, col, N, gout, out_act, slope, Wf, g_out, dl, dpn,
-                                         dcs, ld_dcs, s);
-    if (Cout == 128)
-      return launch_rowpass_fused128<128>(xa, xb, Ca, p, cvec, rowptr, col, N, gout, out_act, slope, Wf, g_out, dl, dpn,
-                                          dcs, ld_dcs, s);
-    return set_error("feast fused row pass: unsupported Cout=%d at 128 input channels", Cout);
+    GEOBI_REQUIRE(in.LC == 0, "feast fused row pass: per-edge logits at 128 channels");
+    const int rc = dispatch_int<64, 128>(Cout, [&](auto co) { return launch_rowpass_fused128<decltype(co)::value>(in, r, s); });
+    return rc == kNoCase ? set_error("feast fused row pass: unsupported Cout=%d at 128 input channels", Cout) : rc;
   }
-  {
-    // the channel-chunked kernel (32-node tiles, half the weight bytes per node) at 64 input channels: see rp_chunked64
-    if (Cin == 64 && LC == 0 && (Ca == Cin || Ca % 32 == 0) && rp_chunked64(Cout)) {
-      if (Cout == 32)
-        return launch_rowpass_fused128<32, 64>(xa, xb, Ca, p, cvec, rowptr, col, N, gout, out_act, slope, Wf, g_out, dl,
-                                               dpn, dcs, ld_dcs, s);
-      if (Cout == 64)
-        return launch_rowpass_fused128<64, 64>(xa, xb, Ca, p, cvec, rowptr, col, N, gout, out_act, slope, Wf, g_out, dl,
-                                               dpn, dcs, ld_dcs, s);
-      if (Cout == 128)
-        return launch_rowpass_fused128<128, 64>(xa, xb, Ca, p, cvec, rowptr, col, N, gout, out_act, slope, Wf, g_out, dl,
-                                                dpn, dcs, ld_dcs, s);
-    }
+  // the channel-chunked kernel (32-node tiles, half the weight bytes per node) at 64 input channels: see rp_chunked64
+  if (Cin == 64 && in.LC == 0 && (in.Ca == Cin || in.Ca % 32 == 0) && rp_chunked64(Cout)) {
+    const int rc = dispatch_int<32, 64, 128>(Cout, [&](auto co) { return launch_rowpass_fused128<decltype(co)::value, 64>(in, r, s); });
+    if (rc != kNoCase) return rc;
   }
-  switch (Cin * 100 + LC) {
-    case 600: GEOBI_RP_COUT(6, 0)
-    case 606: GEOBI_RP_COUT(6, 6)
-    case 1200: GEOBI_RP_COUT(12, 0)
-    case 1212: GEOBI_RP_COUT(12, 12)
-    case 3200: GEOBI_RP_COUT(32, 0)
-    case 6400: GEOBI_RP_COUT(64, 0)
-    default: return set_error("feast fused row pass: unsupported Cin=%d (per-edge logit channels %d)", Cin, LC);
-  }
-#undef GEOBI_RP_COUT
-#undef GEOBI_RP_ARGS
+  const int rc = dispatch_int<6, 12, 32, 64>(Cin, [&](auto c) {
+    return dispatch_int<0, 6, 12>(in.LC, [&](auto lc) {
+      constexpr int C = decltype(c)::value, LC = decltype(lc)::value;
+      if constexpr (kOwnLogits<C, LC>) {
+        const int rco = dispatch_int<32, 64, 128>(Cout, [&](auto co) { return launch_rowpass_fused<C, LC, decltype(co)::value>(in, r, s); });
+        return rco == kNoCase ? set_error("feast fused row pass: unsupported Cout=%d", Cout) : rco;
+      } else {
+        return kNoCase;
+      }
+    });
+  });
+  return rc == kNoCase ? set_error("feast fused row pass: unsupported Cin=%d (per-edge logit channels %d)", Cin, in.LC) : rc;
 }
 
 int feast_fused_nt(int nout) { return nout <= 32 ? 1 : (nout <= 64 ? 2 : 4); }
@@ -1454,61 +1393,44 @@ double feast_fused_bytes(int64_t N, int64_t E, int C, int nout) {
   return (double)E * (4.0 + 4.0 * C + 4.0 * H) + 4.0 * (double)N * H + 4.0 * (double)(N + 1) + 4.0 * (double)N * nout;
 }
 
-// forward: out = lrelu(aggregate(x) Wf + bias); LC > 0: per-edge logits from the unsplit 6 / 12-channel input
-int feast_fused_fwd(const float* xa, const float* xb, int Ca, int Cin, const float* p, const float* cvec,
-                    const int* rowptr, const int* col, int N, int LC, const float* ul, const float* Bp, int Cout,
-                    const float* bias, float slope, float* out, hipStream_t s) {
-  const int* deg_rowptr = nullptr;
-  const float* xl = xa;
-  const float *dpd = nullptr, *dl = nullptr, *dpn = nullptr;
-  const int* pos = nullptr;
-  const int NOUT = Cout, ldo = Cout, split = 0, ldo1 = 0;
-  float* out1 = nullptr;
-  float* tile_out = nullptr;
-  const int NT = feast_fused_nt(Cout);
-  switch (Cin * 100 + LC) {
-    case 600: return launch_nt<6, 0, 0>(NT, GEOBI_FUSED_ARGS);
-    case 606: return launch_nt<6, 0, 6>(NT, GEOBI_FUSED_ARGS);
-    case 1200: return launch_nt<12, 0, 0>(NT, GEOBI_FUSED_ARGS);
-    case 1212: return launch_nt<12, 0, 12>(NT, GEOBI_FUSED_ARGS);
-    case 3200: return launch_nt<32, 0, 0>(NT, GEOBI_FUSED_ARGS);
-    case 6400: return launch_nt<64, 0, 0>(NT, GEOBI_FUSED_ARGS);
-    case 12800: return launch_nt<128, 0, 0>(NT, GEOBI_FUSED_ARGS);
-    default: return set_error("feast fused forward: unsupported Cin=%d (per-edge logit channels %d)", Cin, LC);
-  }
+// forward: out = lrelu(aggregate(x) Wf + bias); in.LC > 0: per-edge logits from the unsplit 6 / 12-channel input
+int feast_fused_fwd(const FeastIn& in, int Cin, const float* Bp, int Cout, const float* bias, float slope, float* out,
+                    hipStream_t s) {
+  FusedLaunch f;
+  f.xl = in.xa;                  // the logit-source rows are the layer input
+  f.Bp = Bp;
+  f.NOUT = Cout;
+  f.bias = bias;
+  f.slope = slope;
+  f.out = out;
+  f.ldo = Cout;
+  const int rc = launch_fused<0, 6, 12, 32, 64, 128>(Cin, in, f, s);
+  return rc == kNoCase ? set_error("feast fused forward: unsupported Cin=%d (per-edge logit channels %d)", Cin, in.LC) : rc;
 }
 
-// backward: (dxa | dxb) = [r | dp | dcs] W', r aggregated over the transposed CSR from g [N, Cout]; dp is formed in
-// the kernel from the row pass's dl [E, 12] (in-CSR order, reached through pos_in) and dpn [N, 12], dcs is the second
-// half of dpd's rows (the first half is not read)
-int feast_fused_dx(const float* g, int Cout, const float* p, const float* cvec, const int* rowptr_out,
-                   const int* col_out, const int* rowptr_in, const int* pos, const float* dl, const float* dpn, int N,
-                   int LC, const float* xl, const float* ul, const float* dpd, const float* Bp, int Cin, float* dxa, int Ca, float* dxb, int Cb, float* tile_out,
-                   hipStream_t s) {
-  const float *xa = g, *xb = g;
-  const int* rowptr = rowptr_out;
-  const int* col = col_out;
-  const int* deg_rowptr = rowptr_in;
-  const float* bias = nullptr;
-  const float slope = 1.0f;
-  const int NOUT = Cin;
-  float* out = dxa;
-  float* out1 = Cb ? dxb : nullptr;
-  const int ldo = Cb ? Ca : Cin, split = Cb ? Ca : Cin, ldo1 = Cb;
-  const int NT = feast_fused_nt(Cin);
-  Ca = Cout;                      // the gathered rows are the unsplit g
-  switch (Cout * 100 + LC) {
-    case 3200: return launch_nt<32, 1, 0>(NT, GEOBI_FUSED_ARGS);
-    case 3206: return launch_nt<32, 1, 6>(NT, GEOBI_FUSED_ARGS);
-    case 3212: return launch_nt<32, 1, 12>(NT, GEOBI_FUSED_ARGS);
-    case 6400: return launch_nt<64, 1, 0>(NT, GEOBI_FUSED_ARGS);
-    case 6406: return launch_nt<64, 1, 6>(NT, GEOBI_FUSED_ARGS);
-    case 6412: return launch_nt<64, 1, 12>(NT, GEOBI_FUSED_ARGS);
-    case 12800: return launch_nt<128, 1, 0>(NT, GEOBI_FUSED_ARGS);
-    case 12806: return launch_nt<128, 1, 6>(NT, GEOBI_FUSED_ARGS);
-    case 12812: return launch_nt<128, 1, 12>(NT, GEOBI_FUSED_ARGS);
-    default: return set_error("feast fused dx: unsupported Cout=%d (per-edge logit channels %d)", Cout, LC);
-  }
+// backward: (dxa | dxb) = [r | dp | dcs] W', r aggregated over the transposed CSR from g [N, Cout] (gin: xa = xb = g, the
+// gathered rows are the unsplit g, Ca = Cout); dp is formed in the kernel from the row pass's dl [E, 12] (in-CSR order,
+// reached through pos_in) and dpn [N, 12], dcs is the second half of dpd's rows (the first half is not read)
+int feast_fused_dx(const FeastIn& gin, const int* rowptr_in, const int* pos, const float* dl, const float* dpn,
+                   const float* xl, const float* dpd, const float* Bp, int Cin, float* dxa, int Ca, float* dxb, int Cb,
+                   float* tile_out, hipStream_t s) {
+  FusedLaunch f;
+  f.deg_rowptr = rowptr_in;
+  f.xl = xl;
+  f.dpd = dpd;
+  f.dl = dl;
+  f.pos = pos;
+  f.dpn = dpn;
+  f.Bp = Bp;
+  f.NOUT = Cin;
+  f.out = dxa;
+  f.ldo = f.split = Cb ? Ca : Cin;
+  f.out1 = Cb ? dxb : nullptr;
+  f.ldo1 = Cb;
+  f.tile_out = tile_out;
+  const int Cout = gin.Ca;
+  const int rc = launch_fused<1, 32, 64, 128>(Cout, gin, f, s);
+  return rc == kNoCase ? set_error("feast fused dx: unsupported Cout=%d (per-edge logit channels %d)", Cout, gin.LC) : rc;
 }
 
 }  // namespace geobi

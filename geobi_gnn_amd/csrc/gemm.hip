@@ -638,7 +638,8 @@ TnPlan plan_tn(const float* A, int lda, int I, int J, int64_t M, int ones_row) {
   int tiles = p.tiles_i * p.tiles_j;
   // One to two blocks per CU in ONE resident round (a second, partial round would idle most CUs for a
   // whole block time; more, shorter slices only add slab traffic), each wave taking >= 64 nodes.
-  static const int64_t cap_env = [] { const char* f = getenv("GEOBI_TN_CAP"); return f ? atoll(f) : 0ll; }();
+  static Knob cap_knob{"GEOBI_TN_CAP", 0};
+  const int64_t cap_env = cap_knob.get();
   // GEOBI_TN_CAP: tuning knob (tools/tn_cap_sweep.py).  Few output tiles (du/dc, narrow dWf): the slab
   // reduction is a chain of dependent loads per output, so half the slabs measured ~15 % faster overall.
   const int64_t capacity = cap_env > 0 ? cap_env : (tiles <= 3 ? 256 : 512);
@@ -721,7 +722,8 @@ int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float*
   //                     reductions -- dz = g Wf^T -- are bound by writing the output)
   // 64-deep k-tiles from K >= 512 (half the barriers per MFMA); the k order is the same for every shape,
   // so results do not depend on the choice.
-  static const int forced = [] { const char* f = getenv("GEOBI_NN_CFG"); return f ? atoi(f) : 0; }();
+  static Knob forced_knob{"GEOBI_NN_CFG", 0};
+  const int forced = (int)forced_knob.get();
   if (forced) {                 // tuning knob for tools/nn_cfg_sweep.py: force one tile shape for every call
     switch (forced) {
       case 1: GEOBI_GEMM_LAUNCH(2, 2, 1, 1, 32); break;

@@ -546,10 +546,10 @@ extern "C" int geobi_debug_head_stamps(void* host_dst, size_t bytes) {
 bool head_fused_supported(int Cin, int K, int nout) { return Cin == CIN && K == HID && (nout == 1 || nout == 3); }
 
 // 0: exact fp32 MFMA (default); 1: the first GEMM of the heads as six bf16 products (head_fwd_fused_bf16x3_kernel)
-static std::atomic<int> g_head_precision{[] { const char* e = getenv("GEOBI_HEAD_BF16X3"); return (e && atoi(e) != 0) ? 1 : 0; }()};
+static Knob g_head_precision{"GEOBI_HEAD_BF16X3", 0};
 int set_head_precision(int mode) {
   GEOBI_REQUIRE(mode == 0 || mode == 1, "head precision: 0 (fp32) or 1 (3 x bf16 split, six products)");
-  g_head_precision = mode;
+  g_head_precision.set(mode);
   return 0;
 }
 
@@ -557,7 +557,7 @@ int head_fwd_fused(const float* x, int64_t N, const float* w1, const float* b1, 
                    int nout, float slope, int mode, const float* dd, const float* resid, int ld_resid, float* raw,
                    float* out, hipStream_t s) {
   int blocks = cdiv(N, 32);
-  if (g_head_precision.load(std::memory_order_relaxed) == 1) {
+  if (g_head_precision.on()) {
     // the pieces of W1 (192 KB) live in a per-context buffer the library owns (the one allocation of this mode); they are
     // re-formed on every call, on the call's stream: the weights move with every optimiser step
     static thread_local __bf16* pack = nullptr;
@@ -606,14 +606,8 @@ int head_bwd_fused(const float* x, int64_t N, const float* w1, const float* b1, 
   const int ntiles = cdiv(N, 32);
   constexpr size_t kLds = (size_t)(NCHUNK * 16 * 64 + 3 * HID + HID + HBW * 16 * 32) * sizeof(float);   // 160 KiB
   static_assert(kLds == 163840, "the backward head kernel uses the whole LDS of a CU");
-  static std::atomic<bool> attr_set{false};   // several host threads may launch (one per mesh group)
-  if (!attr_set) {
-    GEOBI_HIP(hipFuncSetAttribute((const void*)head_bwd_fused_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kLds));
-    GEOBI_HIP(hipFuncSetAttribute((const void*)head_bwd_fused_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kLds));
-    attr_set = true;
-  }
+  GEOBI_TRY(allow_dynamic_lds<head_bwd_fused_kernel<3>>(kLds));
+  GEOBI_TRY(allow_dynamic_lds<head_bwd_fused_kernel<1>>(kLds));
   if (nout == 3)
     head_bwd_fused_kernel<3><<<blocks, 64 * HBW, kLds, s>>>(x, (int)N, ntiles, w1, b1, w2, slope, graw, dx, p_dw1, p_dw2,
                                                        p_db1, p_db2);

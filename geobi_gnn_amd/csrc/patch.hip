@@ -461,12 +461,7 @@ int patch_grow(const int32_t* fv, const int32_t* vf, int maxval, int64_t F, int6
   const bool bits = F <= kGrowFaceBits && V <= kGrowVertBits;
 #define GEOBI_GROW(B)                                                                                                  \
   do {                                                                                                                 \
-    static std::atomic<bool> attr_set{false};                                                                          \
-    if (!attr_set) {                                                                                                   \
-      GEOBI_HIP(hipFuncSetAttribute((const void*)patch_grow_kernel<B>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                    (int)lds));                                                                        \
-      attr_set = true;                                                                                                 \
-    }                                                                                                                  \
+    GEOBI_TRY(allow_dynamic_lds<patch_grow_kernel<B>>(lds));                                                           \
     patch_grow_kernel<B><<<1, kGrowThreads, lds, s>>>(fv, vf, maxval, (int)F, (int)V, d2, (int)seed, nc, rc, patch_id,  \
                                                       state, state + 2 * F, state + F, scalars, sel_out, n_out,        \
                                                       mailbox, pick_next);                                             \

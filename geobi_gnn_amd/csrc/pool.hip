@@ -28,9 +28,7 @@ namespace {
 constexpr uint64_t kSentinel = ~0ull;
 
 // A/B knobs with a test hook: the environment decides (unset or non-zero = on) until geobi_set_* forces a form
-static bool env_on(const char* name) { const char* f = getenv(name); return !f || atoi(f) != 0; }
-static std::atomic<bool>& scan_lookback_knob() { static std::atomic<bool> v{env_on("GEOBI_SCAN_LOOKBACK")}; return v; }
-static std::atomic<bool>& match_scanfree_knob() { static std::atomic<bool> v{env_on("GEOBI_MATCH_SCANFREE")}; return v; }
+Knob g_scan_lookback{"GEOBI_SCAN_LOOKBACK", 1}, g_match_scanfree{"GEOBI_MATCH_SCANFREE", 1};
 
 static inline int key_bits(int64_t N) {   // (1 << bits) > N: see graph.hip
   int b = 1;
@@ -1123,7 +1121,7 @@ static hipError_t lookback_scan(const int* in, int* out, int64_t n, hipStream_t 
 static hipError_t exclusive_scan_int(void* temp, size_t& tb, const int* in, int* out, int64_t n, hipStream_t s) {
   if (n <= kSmallScan) {
     if (temp == nullptr) { tb = 16; return hipSuccess; }
-    const bool lookback = scan_lookback_knob().load(std::memory_order_relaxed);
+    const bool lookback = g_scan_lookback.on();
     if (lookback && n > kOneBlockScan) {
       prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_LOOKBACK);
       const hipError_t e = lookback_scan(in, out, n, s);
@@ -1189,19 +1187,19 @@ int expand_rowptr(const int32_t* rowptr, int64_t N, int32_t* row, hipStream_t s)
 // Test hook (geobi_set_match_round_cap): at most cap x (rounds / 8) rounds per call.  The callers ask for 8 rounds and
 // double the number on every resume of their repair loops; a cap of 1 makes those 1, 2, 4, ... -- every pooling step then
 // comes back with undecided nodes and is resumed, which an uncapped mesh graph almost never needs.
-static int g_round_cap = 0;
-void set_match_round_cap(int cap) { g_round_cap = cap > 0 ? cap : 0; }
+static Knob g_round_cap{nullptr, 0};
+void set_match_round_cap(int cap) { g_round_cap.set(cap > 0 ? cap : 0); }
 
 // Test hooks (geobi_set_match_scanfree / geobi_set_scan_lookback): 1 / 0 force the form, a negative value goes back to
 // what the environment says.  Without a call nothing changes.
-void set_match_scanfree(int on) { match_scanfree_knob().store(on < 0 ? env_on("GEOBI_MATCH_SCANFREE") : on != 0); }
-void set_scan_lookback(int on) { scan_lookback_knob().store(on < 0 ? env_on("GEOBI_SCAN_LOOKBACK") : on != 0); }
+void set_match_scanfree(int on) { if (on < 0) g_match_scanfree.reset(); else g_match_scanfree.set(on != 0); }
+void set_scan_lookback(int on) { if (on < 0) g_scan_lookback.reset(); else g_scan_lookback.set(on != 0); }
 
 static void launch_match_rounds(const int32_t* rowptr, const int32_t* col, const float* w, int N, int rounds, int init,
                                 int32_t* cluster, int32_t* status, int*& pp, int*& pn, hipStream_t s) {
   const int blocks = cdiv(N, 256);
-  if (g_round_cap > 0) {
-    const int64_t capped = (int64_t)g_round_cap * (rounds > 8 ? rounds / 8 : 1);
+  if (const int64_t cap = g_round_cap.get(); cap > 0) {
+    const int64_t capped = cap * (rounds > 8 ? rounds / 8 : 1);
     if (capped < rounds) rounds = (int)capped;
   }
   for (int r = 0; r < rounds; ++r) {
@@ -1267,7 +1265,7 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
   int* pp = b.m.prop0;
   int* pn = b.m.prop1;
   launch_match_rounds(rowptr, col, w, (int)N, rounds, init, state, counters, pp, pn, s);
-  const bool scan_free = match_scanfree_knob().load(std::memory_order_relaxed);
+  const bool scan_free = g_match_scanfree.on();
   if (scan_free && blocks <= kMaxScanBlocks) {
     // scan-free pair: block-local prefixes in the commit kernel, block totals folded by the list kernel
     int* bt_rank = rank;                 // rank / offs are free in this variant: reuse them for the block totals

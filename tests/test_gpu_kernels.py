@@ -153,13 +153,22 @@ def _run_feast_impl(dev, Cin, Cout, ei, n, slope, split, seed, xscale, x):
     return errs
 
 
+_FEAST_SHAPES = [(6, 32, 0.2, False), (12, 32, 0.2, False), (32, 64, 0.2, False),
+                 (64, 128, 0.2, False), (128, 128, 0.2, False),
+                 (128, 64, 1.0, False), (128, 64, 0.2, True),
+                 (64, 32, 1.0, False), (64, 32, 0.2, True),
+                 (6, 64, 0.2, True), (12, 128, 1.0, False), (32, 32, 0.2, False),
+                 (12, 32, 0.2, True), (12, 128, 1.0, True)]     # 6 | 6: parts that cut a 16-B piece
+# ... and the rest of the product the C ABI accepts, slopes alternating: with the three values of `fused` this reaches
+# every leaf of the launchers' dispatch (forward, dx at one / two / four column tiles, every fused row pass, and the
+# standalone row pass in both forms: Cin = 128 with Cout = 32, the 3 | 3 and 6 | 6 splits)
+_FEAST_SHAPES += [(ci, co, (0.2, 1.0)[i % 2], sp) for i, (ci, co, sp) in enumerate(
+    (ci, co, sp) for ci in (6, 12, 32, 64, 128) for co in (32, 64, 128) for sp in (False, True)
+    if (ci, co, sp) not in {(a, b, d) for a, b, _, d in _FEAST_SHAPES})]
+
+
 @pytest.mark.parametrize('fused', [True, 32, False])
-@pytest.mark.parametrize('Cin,Cout,slope,split', [(6, 32, 0.2, False), (12, 32, 0.2, False), (32, 64, 0.2, False),
-                                                  (64, 128, 0.2, False), (128, 128, 0.2, False),
-                                                  (128, 64, 1.0, False), (128, 64, 0.2, True),
-                                                  (64, 32, 1.0, False), (64, 32, 0.2, True),
-                                                  (6, 64, 0.2, True), (12, 128, 1.0, False), (32, 32, 0.2, False),
-                                                  (12, 32, 0.2, True), (12, 128, 1.0, True)])     # 6 | 6: parts that cut a 16-B piece
+@pytest.mark.parametrize('Cin,Cout,slope,split', _FEAST_SHAPES)
 def test_feast_conv_random_graph(dev, Cin, Cout, slope, split, fused):
     n = 700          # 21 full tiles of 32 nodes + a ragged one
     ei = _sym_graph(n, 2500, seed=Cin + Cout)
