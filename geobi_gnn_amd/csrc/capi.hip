@@ -563,6 +563,28 @@ int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, cons
   NOTNULL(p); NOTNULL(t); NOTNULL(idx_a); NOTNULL(segptr); NOTNULL(members); NOTNULL(gout); NOTNULL(gp);
   return chamfer_bwd(p, t, idx_a, segptr, members, qptr, tptr, P, gout, gp, S(stream));
 }
+size_t geobi_mesh_reg_ws_bytes(int64_t V) { return V < 0 || V > GEOBI_MAX_NODES ? 0 : mesh_reg_ws_bytes(V); }
+int geobi_mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int32_t* rowptr, const int32_t* col,
+                       int64_t V, int64_t E, const float* w_lap, const float* w_edge, int terms, float* out, float* u,
+                       void* ws, size_t ws_bytes, void* stream) {
+  SIZES(V, E);
+  GEOBI_REQUIRE(V >= 1, "%s: V = %lld vertices (at least one)", __func__, (long long)V);
+  GEOBI_REQUIRE(terms >= 1 && terms <= 3, "%s: terms %d (bit 0 Laplacian, bit 1 edge length, at least one)", __func__, terms);
+  NOTNULL(vp); NOTNULL(v); NOTNULL(rowptr); NOTNULL(out); NOTNULL(ws);
+  if (E > 0) NOTNULL(col);
+  if (terms & 1) NOTNULL(u);
+  return mesh_reg_fwd(vp, v, normal, rowptr, col, V, E, w_lap, w_edge, terms, out, u, ws, ws_bytes, S(stream));
+}
+int geobi_mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const int32_t* col, int64_t V, int64_t E,
+                       const float* u, const float* w_edge, const float* gout, int terms, float* gvp, void* stream) {
+  SIZES(V, E);
+  GEOBI_REQUIRE(V >= 1, "%s: V = %lld vertices (at least one)", __func__, (long long)V);
+  GEOBI_REQUIRE(terms >= 1 && terms <= 3, "%s: terms %d (bit 0 Laplacian, bit 1 edge length, at least one)", __func__, terms);
+  NOTNULL(vp); NOTNULL(v); NOTNULL(rowptr); NOTNULL(gout); NOTNULL(gvp);
+  if (E > 0) NOTNULL(col);
+  if (terms & 1) NOTNULL(u);
+  return mesh_reg_bwd(vp, v, rowptr, col, V, E, u, w_edge, gout, terms, gvp, S(stream));
+}
 size_t geobi_icp_ws_bytes(const int64_t* xptr, int P) { (void)xptr; return icp_ws_bytes(P); }
 int geobi_icp_init(void* state, int P, const double* init, void* stream) {
   GEOBI_REQUIRE(P >= 1, "%s: P = %d parts (at least one)", __func__, P);

@@ -485,6 +485,13 @@ int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const i
                 size_t ws_bytes, hipStream_t s);
 int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
                 const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, hipStream_t s);
+// reg.hip (mesh regularisers over the symmetric vertex CSR: Laplacian and edge-length terms)
+size_t mesh_reg_ws_bytes(int64_t V);
+int mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int32_t* rowptr, const int32_t* col, int64_t V,
+                 int64_t E, const float* w_lap, const float* w_edge, int terms, float* out, float* u, void* ws,
+                 size_t ws_bytes, hipStream_t s);
+int mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const int32_t* col, int64_t V, int64_t E,
+                 const float* u, const float* w_edge, const float* gout, int terms, float* gvp, hipStream_t s);
 // icp.hip (rigid point-to-point ICP of a union batch on top of nearest_parts)
 size_t icp_ws_bytes(int P);
 int icp_init(double* state, int P, const double* init, hipStream_t s);

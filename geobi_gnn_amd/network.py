@@ -242,7 +242,9 @@ def error_n(np, n):
     return ops.row_loss(np.detach(), n, 3)
 
 
-def laplacian_loss(vp, v, edge_idx_v, normal=None):
+def laplacian_loss_torch(vp, v, edge_idx_v, normal=None):
+    """laplacian_loss by torch ops (gathers and an index_add_): the CPU path, and on the device the baseline that
+    tools/bench_reg.py times the kernel against (float atomics there: not reproducible bit for bit)."""
     keep = edge_idx_v[0] != edge_idx_v[1]
     row, col = edge_idx_v[0][keep], edge_idx_v[1][keep]
     n = vp.shape[0]
@@ -252,3 +254,28 @@ def laplacian_loss(vp, v, edge_idx_v, normal=None):
         out = torch.zeros_like(p).index_add_(0, row, p[row] - p[col]) / cnt
         return out if normal is None else normal * (out * normal).sum(1, keepdim=True)
     return (lap(vp) - lap(v)).abs().sum(1).mean()
+
+
+def laplacian_loss(vp, v, edge_idx_v, normal=None):
+    """network.py:347-361: mean_i sum_c |lap(vp)_i - lap(v)_i|, lap(p)_i = mean_{j in N(i)} (p_i - p_j) over the loop-free
+    edge_idx_v (self loops are dropped), projected on ``normal`` [V, 3] when one is given; gradient to vp.  Device tensors:
+    the fused kernel over the cached CSR (ops.mesh_reg), which needs a symmetric edge set as a mesh has; CPU tensors:
+    torch ops."""
+    if vp.is_cuda:
+        from .graph import graph_of
+        return ops.mesh_reg(vp, v, graph_of(edge_idx_v, vp.shape[0]), normal, terms=ops.TERM_LAP)[0]
+    return laplacian_loss_torch(vp, v, edge_idx_v, normal)
+
+
+def edge_length_loss(vp, v, edge_idx_v):
+    """The companion of laplacian_loss: mean over the loop-free entries (i, j) of edge_idx_v of
+    (|vp_i - vp_j| - |v_i - v_j|)^2 (both directions of an edge are entries: the mean over undirected edges); 0 without
+    edges; gradient to vp, none from an entry whose predicted ends coincide.  Device tensors: ops.mesh_reg; CPU: torch ops."""
+    if vp.is_cuda:
+        from .graph import graph_of
+        return ops.mesh_reg(vp, v, graph_of(edge_idx_v, vp.shape[0]), terms=ops.TERM_EDGE)[1]
+    keep = edge_idx_v[0] != edge_idx_v[1]
+    row, col = edge_idx_v[0][keep], edge_idx_v[1][keep]
+    if row.numel() == 0:
+        return vp.sum() * 0
+    return ((vp[row] - vp[col]).norm(dim=1) - (v[row] - v[col]).norm(dim=1)).pow(2).mean()

@@ -594,6 +594,69 @@ def sided_loss(np_, n, fc_p, fc, fptr=None, weights=None):
     return row_loss(np_, ng, 0, weights, 1.0 if weights is not None else None)
 
 
+# ------------------------------------------------------- mesh regularisers (Laplacian / edge length)
+TERM_LAP, TERM_EDGE = 1, 2   # bits of `terms` (include/geobi_hip.h)
+
+
+class MeshRegFn(Function):
+    """(L_lap, L_edge) of include/geobi_hip.h, "mesh regularisers": the reference's laplacian_loss (code/network.py:347-361)
+    and the edge-length term over the loop-free symmetric vertex CSR, both from one forward and one backward launch.  The
+    gradient goes to the prediction only; a term that `terms` leaves out is 0 and takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, vp, v, graph, normal, w_lap, w_edge, terms):
+        L.require_device(vp, 'prediction')
+        vp, v = _f32c(vp), _f32c(v.detach())
+        if vp.dim() != 2 or vp.shape[1] != 3 or v.shape != vp.shape:
+            raise L.GeobiError('mesh_reg expects two [V, 3] tensors, got %s and %s' % (tuple(vp.shape), tuple(v.shape)))
+        V = vp.shape[0]
+        terms = int(terms)
+        if terms not in (TERM_LAP, TERM_EDGE, TERM_LAP | TERM_EDGE):
+            raise L.GeobiError('mesh_reg: terms %r (TERM_LAP = 1, TERM_EDGE = 2 or both)' % (terms,))
+        if graph.symmetric is not True:
+            raise L.GeobiError('mesh_reg needs a graph known to be symmetric (its backward gathers over the rows that the '
+                               'forward walked); this one has symmetric = %r' % (graph.symmetric,))
+        if graph.N != V:
+            raise L.GeobiError('mesh_reg: a graph of %d nodes for %d vertices' % (graph.N, V))
+        rows = [('normal', normal), ('w_lap', w_lap), ('w_edge', w_edge)]
+        for k, (what, t) in enumerate(rows):
+            if t is None:
+                continue
+            L.require_device(t, what)
+            t = _f32c(t.detach())
+            if tuple(t.shape) != ((V, 3) if what == 'normal' else (V,)):
+                raise L.GeobiError('mesh_reg: %s is %s for %d vertices' % (what, tuple(t.shape), V))
+            rows[k] = (what, t)
+        normal, w_lap, w_edge = (t for _, t in rows)
+        dev = vp.device
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        u = torch.empty((V, 3), dtype=torch.float32, device=dev) if terms & TERM_LAP else None
+        ws = L.workspace(L.size_query('geobi_mesh_reg_ws_bytes', V), dev)
+        L.call('geobi_mesh_reg_fwd', L.ptr(vp), L.ptr(v), L.ptr(normal), L.ptr(graph.rowptr_out), L.ptr(graph.col_out), V,
+               graph.E, L.ptr(w_lap), L.ptr(w_edge), terms, L.ptr(out), L.ptr(u), L.ptr(ws), ws.numel(), L.stream())
+        ctx.graph, ctx.terms, ctx.has_u, ctx.has_w = graph, terms, u is not None, w_edge is not None
+        ctx.save_for_backward(vp, v, u if u is not None else vp, w_edge if w_edge is not None else vp)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_lap, g_edge):
+        vp, v, u, w_edge = ctx.saved_tensors
+        g = ctx.graph
+        gout = torch.stack([g_lap.reshape(()), g_edge.reshape(())]).float()
+        gvp = torch.empty_like(vp)
+        L.call('geobi_mesh_reg_bwd', L.ptr(vp), L.ptr(v), L.ptr(g.rowptr_out), L.ptr(g.col_out), vp.shape[0], g.E,
+               L.ptr(u) if ctx.has_u else None, L.ptr(w_edge) if ctx.has_w else None, L.ptr(gout), ctx.terms, L.ptr(gvp),
+               L.stream())
+        return gvp, None, None, None, None, None, None
+
+
+def mesh_reg(vp, v, graph, normal=None, w_lap=None, w_edge=None, terms=TERM_LAP | TERM_EDGE):
+    """-> (L_lap, L_edge), two device scalars from one autograd node.  graph: graph.Graph of the vertices (loop-free,
+    symmetric = True); normal [V, 3]: project the Laplacians on it (None: no projection); w_lap / w_edge [V]: per-row
+    weights of a union batch, 1 / (B n_mesh) and 1 / (B E_mesh) (None: the plain means over vertices / CSR entries)."""
+    return MeshRegFn.apply(vp, v, graph, normal, w_lap, w_edge, terms)
+
+
 # ------------------------------------------------------- rigid ICP alignment (apply_icp's step)
 ICP_STATE = 24   # GEOBI_ICP_STATE
 

@@ -290,3 +290,63 @@ def batched_losses(vp, npred, data_v, data_f, loss_v='L1', loss_n='L1'):
     else:
         ln = reduce(per_node(npred, data_f.y, loss_n), ptr_f)
     return lv, ln
+
+
+def _edge_weights(data, graph):
+    """Per-row weights 1 / (B * E_mesh) of the CSR entries of a union batch, E_mesh = the entries of the row's own mesh:
+    rowptr_out read at the mesh_ptr rows, on the device, nothing comes back to the host (cached on the Data bag)."""
+    ptr = getattr(data, 'mesh_ptr', None)
+    if ptr is None or ptr.numel() <= 2:
+        return None
+    w = getattr(data, '_edge_weights', None)
+    if w is None or w.device != graph.rowptr_out.device:
+        dev = graph.rowptr_out.device
+        ptr_d = ptr.to(dev)
+        ends = graph.rowptr_out[ptr_d]
+        counts = (ends[1:] - ends[:-1]).float()
+        per_mesh = torch.where(counts > 0, 1.0 / (counts * counts.numel()), torch.zeros_like(counts))
+        seg = torch.bucketize(torch.arange(int(ptr[-1]), device=dev), ptr_d[1:], right=True)
+        w = data._edge_weights = per_mesh[seg]
+    return w
+
+
+def batched_regularisers(vp, data_v, lap=True, edge=True):
+    """The mesh regularisers of a prediction vp against data_v.y over data_v's vertex graph, as batched_losses forms the
+    other losses: per-mesh means averaged over the meshes of a disjoint-union batch (mesh_ptr), the plain means without
+    one.  -> (Laplacian term, edge-length term); a term that is switched off is None.  On the MI355X both come from ONE
+    ops.mesh_reg call (geobi_mesh_reg_*); CPU tensors (gloo tests) use torch ops over data_v.edge_index."""
+    if not (lap or edge):
+        return None, None
+    if vp.is_cuda:
+        from . import ops
+        g = data_v.graph()
+        terms = (ops.TERM_LAP if lap else 0) | (ops.TERM_EDGE if edge else 0)
+        l_lap, l_edge = ops.mesh_reg(vp, data_v.y, g, None, _mesh_weights(data_v) if lap else None,
+                                     _edge_weights(data_v, g) if edge else None, terms)
+        return (l_lap if lap else None), (l_edge if edge else None)
+    from . import network
+    ptr = getattr(data_v, 'mesh_ptr', None)
+    cut = [0, vp.shape[0]] if ptr is None else [int(x) for x in ptr.tolist()]
+    ei = data_v.edge_index
+    terms = [[], []]
+    for a, b in zip(cut[:-1], cut[1:]):
+        inside = (ei[0] >= a) & (ei[0] < b)
+        sub = ei[:, inside] - a
+        if lap:
+            terms[0].append(network.laplacian_loss(vp[a:b], data_v.y[a:b], sub))
+        if edge:
+            terms[1].append(network.edge_length_loss(vp[a:b], data_v.y[a:b], sub))
+    return tuple(sum(t) / len(t) if t else None for t in terms)
+
+
+def add_regularisers(loss, vp, data_v, lap_scale=0, edge_scale=0):
+    """loss + lap_scale * L_lap + edge_scale * L_edge for the scales that are not 0 (batched_regularisers; with both 0 no
+    call is made and `loss` comes back as it is).  -> (loss, the unscaled terms that are on, detached, in that order)"""
+    if lap_scale == 0 and edge_scale == 0:
+        return loss, []
+    on = []
+    for term, scale in zip(batched_regularisers(vp, data_v, lap_scale != 0, edge_scale != 0), (lap_scale, edge_scale)):
+        if term is not None:
+            loss = loss + scale * term
+            on.append(term.detach())
+    return loss, on

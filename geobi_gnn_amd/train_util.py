@@ -5,6 +5,7 @@ learning-rate schedules, :233-263 evaluation means, :270-276 best-on-eval checkp
 The loop itself (data loading, TensorBoard, progress bars) is the reference's Python harness and stays out of
 scope; tools/train_synthetic.py drives these helpers on synthetic meshes.
 """
+import argparse
 import math
 
 import torch
@@ -14,6 +15,14 @@ from . import network
 from .parallel import reduce_sums
 
 LR_SCHEDULES = ('step', 'multi_step', 'exp', 'auto', 'lmd')
+
+
+def non_negative_float(text):
+    """argparse type of a loss scale: a float that is not negative (and not NaN)."""
+    value = float(text)
+    if not value >= 0:
+        raise argparse.ArgumentTypeError('%r is negative' % text)
+    return value
 
 
 def add_training_flags(parser):
@@ -26,6 +35,12 @@ def add_training_flags(parser):
                              'whose centroid is nearest to the predicted face)')
     parser.add_argument('--loss_v_scale', type=float, default=1)
     parser.add_argument('--loss_n_scale', type=float, default=1)
+    parser.add_argument('--loss_lap_scale', type=non_negative_float, default=0,
+                        help='> 0: add this times the Laplacian term (the mean L1 difference between the uniform '
+                             'Laplacians of the predicted and the ground-truth vertices over the mesh edges) to the loss')
+    parser.add_argument('--loss_edge_scale', type=non_negative_float, default=0,
+                        help='> 0: add this times the edge-length term (the mean squared difference between predicted and '
+                             'ground-truth edge lengths) to the loss')
     parser.add_argument('--wei_param', type=int, default=2)
     parser.add_argument('--max_epoch', type=int, default=1000)
     parser.add_argument('--batch_size', type=int, default=1)

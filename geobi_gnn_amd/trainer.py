@@ -25,10 +25,11 @@ import torch
 from . import meshnoise, network, train_util
 from .data import RandomRotate, rotate_union, union_batch_graphs
 from .dataset import DualDataset
-from .parallel import FlatParameters, batched_losses, shard_indices
+from .parallel import FlatParameters, add_regularisers, batched_losses, shard_indices
 
 DATA_TYPES = ('Synthetic', 'Kinect_v1', 'Kinect_v2', 'Kinect_Fusion')
 TRAIN_TAGS = ('loss_v', 'loss_f', 'dual_loss', 'error_v', 'error_f')
+REG_TAGS = (('loss_lap', 'loss_lap_scale'), ('loss_edge', 'loss_edge_scale'))       # a tag of train/ per regulariser that is on
 TEST_TAGS = (('loss_v', 'eval_loss_v'), ('loss_f', 'eval_loss_f'), ('error_v', 'eval_error_v'), ('error_f', 'eval_error_f'))
 
 
@@ -76,13 +77,26 @@ def make_rotation(mode, seed):
     return RandomRotate(z_rotated=mode == 'z', rng=np.random.default_rng(seed))
 
 
+def reg_scales(opt):
+    """(--loss_lap_scale, --loss_edge_scale); options from before the flags existed have neither: 0."""
+    return tuple(float(getattr(opt, flag, 0) or 0) for _, flag in REG_TAGS)
+
+
+def train_tags(opt):
+    """The scalars train_epoch hands out per step: TRAIN_TAGS, then the tag of every regulariser whose scale is not 0."""
+    return TRAIN_TAGS + tuple(tag for (tag, _), scale in zip(REG_TAGS, reg_scales(opt)) if scale != 0)
+
+
 def train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=None, scalars=None, iteration=0):
     """One pass over ``samples`` (a DualDataset or a list of resident pairs) in parallel.shard_indices order (seed,
     epoch), ``opt.batch_size`` samples per step; the last, short batch still steps.  scalars: optional list that takes
-    (iteration, device tensor of the five TRAIN_TAGS values) per step -- nothing is read back here.
+    (iteration, device tensor of the train_tags(opt) values: the five TRAIN_TAGS, then the unscaled term of every
+    regulariser that is on) per step -- nothing is read back here.  A regulariser (``opt.loss_lap_scale``,
+    ``opt.loss_edge_scale``) whose scale is 0 is not computed.
     -> (iteration, loss of the last step as a device scalar)"""
     net.train()
     order = shard_indices(len(samples), 0, 1, seed=opt.seed, epoch=epoch)
+    lap_scale, edge_scale = reg_scales(opt)
     loss = None
     for s in range(0, len(order), opt.batch_size):
         batch = order[s:s + opt.batch_size]
@@ -93,6 +107,7 @@ def train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=None, scalars=
         vp, npred, _ = net((dv.shallow_copy(), df.shallow_copy()))
         lv, ln = batched_losses(vp, npred, dv, df, opt.loss_v, opt.loss_n)
         loss = network.dual_loss(lv, ln, opt.loss_v_scale, opt.loss_n_scale)
+        loss, regs = add_regularisers(loss, vp, dv, lap_scale, edge_scale)
         loss.backward()
         optimizer.step()
         iteration += len(batch)
@@ -100,7 +115,7 @@ def train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=None, scalars=
             with torch.no_grad():
                 scalars.append((iteration, torch.stack([lv.detach(), ln.detach(), loss.detach(),
                                                         network.error_v(vp.detach(), dv.y),
-                                                        network.error_n(npred.detach(), df.y)])))
+                                                        network.error_n(npred.detach(), df.y)] + regs)))
     return iteration, loss
 
 
@@ -224,7 +239,7 @@ def _train(opt, dev, name, model_file, predict):
         iteration, loss = train_epoch(net, flat, optimizer, train_set, opt, epoch, rotate, scalars, iteration)
         # the reference reads five scalars back per iteration (.item()); here they stay on the device until the epoch ends
         for (it, _), vals in zip(scalars, torch.stack([v for _, v in scalars]).tolist() if scalars else []):
-            for tag, v in zip(TRAIN_TAGS, vals):
+            for tag, v in zip(train_tags(opt), vals):
                 train_writer.add_scalar(tag, v, it)
         train_writer.flush()
         res = evaluate(net, test_set, opt)

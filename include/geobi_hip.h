@@ -348,6 +348,38 @@ int geobi_chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, c
 int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
                       const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, void* stream);
 
+/* ---------------------------------------------------------------- mesh regularisers ----
+ * Two differential terms on the mesh itself, for training without correspondence (Chamfer / sided losses see no
+ * connectivity): the reference's laplacian_loss(vp, v, edge_idx_v, normal) (code/network.py:347-361) and an edge-length
+ * term.  Both live on the loop-free SYMMETRIC vertex CSR (rowptr [V + 1], col [E], int32, columns ascending in a row) that
+ * the prediction vp [V,3] and the ground truth v [V,3] share.  N(i) = row i, deg_i its length, m_i = max(deg_i, 1).
+ *   lap(p)_i = (1 / m_i) sum_{j in N(i)} (p_i - p_j);  with normal [V,3] (may be NULL): lap(p)_i <- n_i (n_i . lap(p)_i)
+ *   d_i      = lap(vp)_i - lap(v)_i
+ *   L_lap    = sum_i w_lap[i] sum_c |d_ic|                                   (network.py:360-361: .abs().sum(1).mean())
+ *   L_edge   = sum_i w_edge[i] sum_{j in N(i)} (|vp_i - vp_j| - |v_i - v_j|)^2
+ * w_lap / w_edge [V] are per-ROW weights: 1 / (B n_mesh) and 1 / (B E_mesh) give the mean over the B meshes of a union
+ * batch of the per-mesh means; NULL: 1 / V and 1 / E (0 when E = 0), the plain means.  terms: bit 0 the Laplacian term,
+ * bit 1 the edge term (1, 2 or 3); a term that is off costs nothing and its output is 0.
+ *   geobi_mesh_reg_fwd   out[0] = L_lap, out[1] = L_edge: one pass over the rows (a neighbour's two points are gathered once
+ *                        for both terms), sums of coordinate differences in ascending column order, fp64 block sums added in
+ *                        a fixed order.  With bit 0 it also writes the backward seed u [V,3] (NULL without bit 0):
+ *                        u_i = w_lap[i] g_i / m_i,  g_i = sign(d_i), or n_i (n_i . sign(d_i)) with a normal; sign(0) = 0.
+ *                        ws: geobi_mesh_reg_ws_bytes(V)
+ *   geobi_mesh_reg_bwd   gvp_k = gout[0] (deg_k u_k - sum_{i in N(k)} u_i)
+ *                                + gout[1] sum_{j in N(k)} (w_edge[k] + w_edge[j]) 2 (|e_p| - |e_g|) e_p / |e_p|,
+ *                        e_p = vp_k - vp_j, e_g = v_k - v_j; an entry with |e_p| = 0 adds nothing.  gout: DEVICE float[2],
+ *                        the gradients of the two outputs (the one of a term that is off is not read).  One gather per
+ *                        row, every row of gvp written once, no atomics: it relies on k in N(i) <=> i in N(k), so the
+ *                        CALLER must know the graph to be symmetric (the Python layer refuses any other).  The gradient
+ *                        goes to vp only.
+ * Same input, same bits.  What is read through rowptr / col is clamped to the arrays.  V >= 1.                          */
+size_t geobi_mesh_reg_ws_bytes(int64_t V);
+int geobi_mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int32_t* rowptr, const int32_t* col,
+                       int64_t V, int64_t E, const float* w_lap, const float* w_edge, int terms, float* out, float* u,
+                       void* ws, size_t ws_bytes, void* stream);
+int geobi_mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const int32_t* col, int64_t V, int64_t E,
+                       const float* u, const float* w_edge, const float* gout, int terms, float* gvp, void* stream);
+
 /* ---------------------------------------------------------------- rigid ICP alignment ----
  * Point-to-point ICP of x [Q, 3] onto y [M, 3] per part of a disjoint-union batch (host part pointers as above): what
  * loss_v(..., apply_icp=True) asks of pytorch3d's iterative_closest_point (code/network.py:15,364-367).  The convention is

@@ -22,7 +22,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from geobi_gnn_amd import network, meshgen, train_util          # noqa: E402
 from geobi_gnn_amd.data import union_batch_graphs, RandomRotate   # noqa: E402
-from geobi_gnn_amd.parallel import init_distributed, FlatParameters, shard_indices, batched_losses   # noqa: E402
+from geobi_gnn_amd.parallel import (init_distributed, FlatParameters, shard_indices, batched_losses,   # noqa: E402
+                                    add_regularisers)
 
 
 def parse_arguments(argv=None):
@@ -86,6 +87,7 @@ def main(argv=None):
             vp, npred, _ = net((dv.shallow_copy(), df.shallow_copy()))
             lv, ln = batched_losses(vp, npred, dv, df, opt.loss_v, opt.loss_n)
             loss = network.dual_loss(lv, ln, opt.loss_v_scale, opt.loss_n_scale)
+            loss, _ = add_regularisers(loss, vp, dv, opt.loss_lap_scale, opt.loss_edge_scale)
             loss.backward()
             flat.bucket.all_reduce_mean()
             optimizer.step()
