@@ -11,6 +11,9 @@
   python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold] [--orient] [--min_component N]
   python -m geobi_gnn_amd clean ... [--orient] [--min_component N]
   python -m geobi_gnn_amd info --data_dir DIR [--weld_tol 0] [--no_weld] [--gpu -1]
+  python -m geobi_gnn_amd sample --data_dir DIR [--out_dir DIR/samples] --n N [--seed 1] [--normals] [--gpu -1]
+  python -m geobi_gnn_amd eval ... --free --samples N [--seed 1]
+  python -m geobi_gnn_amd align ... --samples N [--seed 1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -32,7 +35,11 @@ neighbours wound in opposite senses; `--min_component N` drops the edge-connecte
 it is closed and orientable.  `align` (ops.icp) brings every DIR/NAME_*.obj -- or DIR/NAME.obj where a stem has none -- into
 the frame of DIR2/NAME.obj by rigid point-to-point ICP and writes it with its own faces; the two meshes may differ in size.
 `eval --align` does the same before it scores (AlignInfo.txt beside ErrorInfo_h.txt), `eval --free` scores pairs whose
-vertex counts or face tables differ (ErrorInfo_free.txt).  All device work runs in this one process.
+vertex counts or face tables differ (ErrorInfo_free.txt).  `sample` (meshsample.py) writes N points drawn uniformly by
+area on the surface of every DIR/original/*.obj (or DIR/*.obj) as OUT/NAME.obj with `v` lines only (`--normals`: a `vn`
+line per point); `eval --free --samples N` also scores from such points of both surfaces (ErrorInfo_sampled.txt beside
+an unchanged ErrorInfo_free.txt), `align --samples N` aligns to the target's vertices followed by N points of its
+surface -- what a CAD target of a few large triangles needs.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -180,7 +187,7 @@ def evaluate(opt):
     t0 = time.time()
     try:
         rows, _ = mesheval.eval_dirs(opt.result_dir, opt.original_dir, device=dev, stats=stats, align=opt.align, free=opt.free,
-                                     estimate_scale=opt.scale)
+                                     estimate_scale=opt.scale, samples=opt.samples, seed=opt.seed)
     except (ValueError, OSError, GeobiError) as e:
         print('eval failed: %s' % e, file=sys.stderr)
         return 1
@@ -206,7 +213,7 @@ def align_list(data_dir, target_dir):
 def align(opt):
     """Every source mesh of --data_dir aligned to its target of --target_dir by rigid ICP on the device (mesheval.align),
     written to --out_dir with aligned vertices and its own faces."""
-    from . import mesheval, meshio
+    from . import mesheval, meshio, meshnoise
     from ._lib import GeobiError
     dev = _device(opt.gpu)
     jobs = align_list(opt.data_dir, opt.target_dir)
@@ -219,11 +226,15 @@ def align(opt):
         t0 = time.time()
         try:
             points, faces = meshio.read_obj(source)
-            t_points, _ = meshio.read_obj(target)
+            t_points, t_faces = meshio.read_obj(target)
             if points.shape[0] == 0 or t_points.shape[0] == 0:
                 raise ValueError('%s or its target %s has no vertices' % (source, target))
+            sampling = {}
+            if opt.samples:         # the target's surface joins its vertices: the stream is the target's name
+                sampling = {'target_faces': t_faces, 'samples': opt.samples, 'seed': opt.seed,
+                            'stream_id': meshnoise.stream_of(os.path.basename(target)[:-4])}
             res = mesheval.align(points, t_points, device=dev, estimate_scale=opt.scale, allow_reflection=opt.reflect,
-                                 max_iterations=opt.max_iter, relative_rmse_thr=opt.rmse_thr)
+                                 max_iterations=opt.max_iter, relative_rmse_thr=opt.rmse_thr, **sampling)
             out_file = os.path.join(out_dir, os.path.basename(source))
             meshio.write_obj(out_file, res.xt.cpu().numpy(), faces)
         except (ValueError, OSError, GeobiError) as e:
@@ -278,6 +289,44 @@ def noise(opt):
     if failed:
         print('%d of %d files skipped' % (failed, len(originals)), file=sys.stderr)
     return 1 if failed or not originals else 0
+
+
+def sample(opt):
+    """Every DIR/original/*.obj, or else DIR/*.obj -> OUT/NAME.obj: --n points drawn by area on its surface (meshsample),
+    `v` lines only, with --normals a `vn` line per point (the normal of the point's face)."""
+    from . import meshin, meshio, meshnoise, meshsample
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    original_dir = os.path.join(opt.data_dir, 'original')
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if os.path.isdir(original_dir) else opt.data_dir), '*.obj')))
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'samples')
+    os.makedirs(out_dir, exist_ok=True)
+    print('\nSample, n %d, seed %d, normals %s, %d files ...\n' % (opt.n, opt.seed, 'on' if opt.normals else 'off', len(files)),
+          flush=True)
+    failed = 0
+    for path in files:
+        name = os.path.basename(path)[:-4]
+        try:
+            points, faces = meshio.read_obj(path)
+            if faces.shape[0] == 0:
+                raise ValueError('%s: no faces' % path)
+            p, fv = meshin.device_mesh(points, faces, dev)
+            weights = meshsample.surface_weights(p, fv, check=False)
+            area, zero = meshsample.surface_info(weights)
+            drawn = meshsample.sample_surface(p, fv, opt.n, seed=opt.seed, stream_id=meshnoise.stream_of(name), weights=weights,
+                                              check=False)
+            normals = meshsample.sample_normals(p, fv, drawn).cpu().numpy() if opt.normals else None
+            out_file = os.path.join(out_dir, name + '.obj')
+            meshio.write_obj(out_file, drawn.points.cpu().numpy(), np.zeros((0, 3), dtype=np.int32), normals=normals)
+            print("V: %7d,  F: %7d,  area: %.6g,  zero_faces: %d,  samples: %d,  '%s'"
+                  % (points.shape[0], faces.shape[0], area, zero, opt.n, os.path.basename(out_file)), flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d of %d files skipped' % (failed, len(files)), file=sys.stderr)
+    return 1 if failed or not files else 0
 
 
 def _weld_tol(opt):
@@ -406,6 +455,13 @@ def _min_component_arg(text):
     return v
 
 
+def _samples_arg(text):
+    v = int(text)
+    if not 0 <= v <= (1 << 24) - 1:
+        raise argparse.ArgumentTypeError('a number of samples is between 0 and 16 777 215, not %r' % text)
+    return v
+
+
 class _TrueGiven(argparse.Action):
     """store_true, and note in <dest>_given that the flag was on the command line"""
 
@@ -467,6 +523,10 @@ def build_parser():
     e.add_argument('--free', action='store_true',
                    help='score pairs whose vertex counts or face tables differ (surface distances both ways, normals by the '
                         'nearest ground-truth triangle); writes ErrorInfo_free.txt')
+    e.add_argument('--samples', type=_samples_arg, default=0, metavar='N',
+                   help='with --free: also score from N points drawn by area on each surface; writes ErrorInfo_sampled.txt '
+                        '(with --align the ground truth is aligned to as its vertices plus its samples)')
+    e.add_argument('--seed', type=int, default=1, help='with --samples: the seed of the draw')
     e.set_defaults(fn=evaluate)
     a = sub.add_parser('align', help='align every mesh of a folder to its target by rigid ICP and write it with its own faces')
     a.add_argument('--data_dir', type=str, required=True, help='the meshes to move: NAME_*.obj, or NAME.obj')
@@ -476,8 +536,20 @@ def build_parser():
     a.add_argument('--reflect', action='store_true', help='allow reflections (det R = -1)')
     a.add_argument('--max_iter', type=int, default=100, help='iterations at most; a pair that hits it is written and reported')
     a.add_argument('--rmse_thr', type=float, default=1e-6, help='stop once the relative change of the rmse is at most this')
+    a.add_argument('--samples', type=_samples_arg, default=0, metavar='N',
+                   help="align to the target's vertices followed by N points drawn by area on its surface (a CAD target of "
+                        'a few large triangles has no vertices inside its faces)')
+    a.add_argument('--seed', type=int, default=1, help='with --samples: the seed of the draw')
     a.add_argument('--gpu', type=int, default=-1)
     a.set_defaults(fn=align)
+    s = sub.add_parser('sample', help='write N points drawn uniformly by area on the surface of every mesh of a folder')
+    s.add_argument('--data_dir', type=str, required=True, help='holds original/, or the OBJ files themselves')
+    s.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/samples')
+    s.add_argument('--n', type=_samples_arg, required=True, help='points per mesh')
+    s.add_argument('--seed', type=int, default=1)
+    s.add_argument('--normals', action='store_true', help="a `vn` line per point: the unit normal of the point's face")
+    s.add_argument('--gpu', type=int, default=-1)
+    s.set_defaults(fn=sample)
     n = sub.add_parser('noise', help='write noisy/NAME_n<k>.obj for every original/NAME.obj, drawn on the device')
     from .meshnoise import DIRECTIONS, KINDS
     from .trainer import noise_levels_arg
@@ -524,6 +596,10 @@ def parse_args(argv=None):
                     ap.error('denoise: --%s needs --clean' % flag)
     if opt.command == 'eval' and opt.scale and not opt.align:
         ap.error('eval: --scale needs --align')
+    if opt.command == 'eval' and opt.samples and not opt.free:
+        ap.error('eval: --samples needs --free')
+    if opt.command in ('eval', 'align', 'sample') and not 0 <= opt.seed < 2 ** 64:
+        ap.error('%s: --seed is a 64-bit number that is not negative, got %d' % (opt.command, opt.seed))
     if opt.command == 'align':
         if opt.max_iter < 1:
             ap.error('align: --max_iter is at least 1, not %d' % opt.max_iter)

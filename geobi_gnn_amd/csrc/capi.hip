@@ -620,6 +620,31 @@ int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float
   return mesh_noise(points, vnormal, V, sigma, kind, direction, fraction, seed, stream_id, draw, out, S(stream));
 }
 
+int geobi_sample_table_entries(void) { return sample_table_entries(); }
+size_t geobi_sample_ws_bytes(int64_t F) { return F < 1 || F > GEOBI_MAX_NODES ? 0 : sample_ws_bytes(F); }
+int geobi_sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, void* weight, void* cum,
+                         int32_t* exponent, void* ws, size_t ws_bytes, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  GEOBI_REQUIRE(F >= 1 && V >= 1, "%s: F = %lld faces, V = %lld vertices (at least one of each)", __func__, (long long)F,
+                (long long)V);
+  NOTNULL(points); NOTNULL(fv); NOTNULL(weight); NOTNULL(cum); NOTNULL(exponent); NOTNULL(ws);
+  return sample_weights(points, fv, F, V, (int64_t*)weight, (int64_t*)cum, exponent, ws, ws_bytes, S(stream));
+}
+int geobi_sample_surface(const float* points, const int32_t* fv, const void* cum, int64_t F, int64_t V, int64_t N,
+                         int64_t first, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points,
+                         int32_t* out_face, float* out_bary, void* stream) {
+  SIZES(F > V ? F : V, 0);
+  SIZES(N, 0);
+  GEOBI_REQUIRE(first >= 0 && first + N <= GEOBI_MAX_NODES, "%s: first = %lld, first + N = %lld outside [0, GEOBI_MAX_NODES = %d]",
+                __func__, (long long)first, (long long)(first + N), GEOBI_MAX_NODES);
+  GEOBI_REQUIRE(F >= 1 && V >= 1, "%s: F = %lld faces, V = %lld vertices (at least one of each)", __func__, (long long)F,
+                (long long)V);
+  if (N == 0) return 0;
+  NOTNULL(points); NOTNULL(fv); NOTNULL(cum); NOTNULL(out_points); NOTNULL(out_face); NOTNULL(out_bary);
+  return sample_surface(points, fv, (const int64_t*)cum, F, V, N, first, seed, stream_id, draw, out_points, out_face, out_bary,
+                        S(stream));
+}
+
 int geobi_bnf_prepare(const float* points, const int32_t* fv, int64_t F, int64_t V, float* rec_c, float* rec_n,
                       void* stream) {
   SIZES(F > V ? F : V, 0);

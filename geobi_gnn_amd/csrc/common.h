@@ -501,6 +501,14 @@ int icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* 
 // noise.hip (synthetic mesh noise: counter-based Philox4x32-10, one counter per vertex)
 int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
                uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s);
+// sample.hip (points drawn uniformly by area on a mesh surface: integer face weights, Philox block 2)
+int sample_table_entries();
+size_t sample_ws_bytes(int64_t F);
+int sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, int64_t* weight, int64_t* cum,
+                   int32_t* exponent, void* ws, size_t ws_bytes, hipStream_t s);
+int sample_surface(const float* points, const int32_t* fv, const int64_t* cum, int64_t F, int64_t V, int64_t N, int64_t first,
+                   uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points, int32_t* out_face, float* out_bary,
+                   hipStream_t s);
 // filter.hip (bilateral normal filter over the facet graph: the model-free baseline of `denoise`)
 int bnf_prepare(const float* points, const int32_t* fv, int64_t F, float* rec_c, float* rec_n, hipStream_t s);
 size_t bnf_filter_ws_bytes(int64_t F, int64_t E);

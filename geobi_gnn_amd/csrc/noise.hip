@@ -24,6 +24,7 @@
 // LDS.  ALU-bound (ten rounds, two logs, two sincos) at 12-24 bytes in and 12 bytes out per vertex.  `out` may alias
 // `points`: a thread reads its own row before it writes it and touches no other.
 #include "common.h"
+#include "philox.h"
 
 #include <math.h>
 
@@ -33,26 +34,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;                    // 256 CUs x 8 workgroups; the rest by grid stride
-
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += W0;
-    k1 += W1;
-  }
-  return U4{c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ float word_uniform(uint32_t w) { return ((float)(w >> 9) + 0.5f) * 0x1p-23f; }
 
 __global__ __launch_bounds__(kThreads) void mesh_noise_kernel(const float* points, const float* vnormal, int V, float sigma,
                                                               int kind, int direction, float fraction, uint32_t k0,

@@ -1,5 +1,5 @@
-// Temporary-storage sizes of the rocPRIM calls of graph.hip, pool.hip, clean.hip and topo.hip, for Arena::take_ws.
-// Kept out of common.h: only these four units compile rocPRIM.
+// Temporary-storage sizes of the rocPRIM calls of graph.hip, pool.hip, clean.hip, topo.hip and sample.hip, for
+// Arena::take_ws.  Kept out of common.h: only these five units compile rocPRIM.
 // 0: the size query failed (it asks the device for its properties, so it fails on a host without one); take_ws then
 // fails the carve and the enclosing *_ws_bytes answers 0.  A query that succeeds answers at least 16.
 #pragma once
@@ -35,6 +35,13 @@ static inline size_t scan_temp_bytes(int64_t n) {
   size_t tb = 0;
   return temp_bytes_or_0(rocprim::exclusive_scan(nullptr, tb, (T*)nullptr, (T*)nullptr, (T)0, (size_t)n,
                                                  rocprim::plus<T>(), (hipStream_t)0, false), tb);
+}
+// inclusive plus-scan of n values T
+template <typename T>
+static inline size_t inclusive_scan_temp_bytes(int64_t n) {
+  size_t tb = 0;
+  return temp_bytes_or_0(rocprim::inclusive_scan(nullptr, tb, (T*)nullptr, (T*)nullptr, (size_t)n, rocprim::plus<T>(),
+                                                 (hipStream_t)0, false), tb);
 }
 
 }  // namespace geobi

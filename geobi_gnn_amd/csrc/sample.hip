@@ -1,0 +1,199 @@
+// Points drawn uniformly by area on a mesh surface: integer face weights and their inclusive scan, then one
+// Philox call, one upper-bound search and one barycentric combination per sample.
+//
+// The reference has no call site for this: every distance of its evaluation starts from a vertex
+// (code/data_util.py:584-616).  A CAD face of a few large triangles has no vertex inside it; samples do.
+//
+// Weights (sample_weights), integer-exact so that two runs, two grid shapes and the host model agree on every face:
+//   d[f]       |e1 x e2| of the float32 corners widened to fp64, every product and difference rounded on its own (no FMA
+//              contraction, "as numpy does"); a non-finite d counts as 0
+//   dmax       max_f d by a fixed-shape reduction (a block's LDS tree, then one block over the blocks' maxima)
+//   e          frexp(dmax) = m * 2^e; exponent[0] = e (0 for dmax == 0)
+//   weight[f]  floor(ldexp(d[f], 32 - e)): the largest face lands in [2^31, 2^32), a face below 2^-32 of it gets 0
+//   cum        inclusive scan of weight in 64-bit integers (rocPRIM; integer sums are exact in any order), < 2^56
+//
+// Draw (sample_surface): sample i uses the counter (first + i, stream_id, draw, 2) -- blocks 0 and 1 are noise.hip's --
+// and the key (seed lo, seed hi).  r = w0 << 32 | w1, t = umul64hi(r, total) with total = cum[F - 1] read on the device,
+// face = the first f with cum[f] > t (an upper bound: zero-weight faces, runs of equal cum, are never chosen);
+// u1 = uniform(w2), u2 = uniform(w3), folded into the triangle (u1 + u2 > 1: both become 1 - u); b = (1 - u1 - u2, u1, u2)
+// is exact in fp32 for uniforms of the form (k + 0.5) 2^-23; p = fma(b2, c, fma(b1, b, b0 * a)).  total == 0: face -1, zeros.
+//
+// Shape of the search: a block stages kTable evenly spaced entries of cum in LDS (16 KB; all of cum for F <= kTable),
+// finds the bucket there and finishes inside it from global memory: log2(F / kTable) dependent global loads per sample
+// instead of log2 F.  The bucket bounds are entries of cum themselves, so the result is that of the plain search.  One
+// thread per sample, grid-stride; plain vector stores, no atomics.  Corner ids are clamped into [0, V): a foreign table
+// never reads outside points.
+#include "common.h"
+#include "philox.h"
+#include "rocprim_temp.h"
+
+#include <math.h>
+
+namespace geobi {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 1024;                    // 256 CUs x 4 workgroups; the rest by grid stride
+constexpr int kTable = 2048;                        // LDS table of the draw: 2048 x 8 bytes = 16 KB
+
+__device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// max over the block, every thread gets it: an LDS tree of fixed shape (a maximum does not depend on it anyway)
+__device__ __forceinline__ double block_max_fp64(double v) {
+  __shared__ double s[kThreads];
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = kThreads / 2; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + h]);
+    __syncthreads();
+  }
+  return s[0];
+}
+
+__global__ __launch_bounds__(kThreads) void face_norm_kernel(const float* __restrict__ points, const int* __restrict__ fv,
+                                                             int F, int V, double* __restrict__ d,
+                                                             double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  double m = 0.0;
+  for (int f = blockIdx.x * kThreads + threadIdx.x; f < F; f += gridDim.x * kThreads) {
+    const size_t ia = 3 * (size_t)clampi(fv[3 * (size_t)f], V), ib = 3 * (size_t)clampi(fv[3 * (size_t)f + 1], V),
+                 ic = 3 * (size_t)clampi(fv[3 * (size_t)f + 2], V);
+    const double ax = points[ia], ay = points[ia + 1], az = points[ia + 2];
+    const double e1x = (double)points[ib] - ax, e1y = (double)points[ib + 1] - ay, e1z = (double)points[ib + 2] - az;
+    const double e2x = (double)points[ic] - ax, e2y = (double)points[ic + 1] - ay, e2z = (double)points[ic + 2] - az;
+    const double cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+    double v = sqrt((cx * cx + cy * cy) + cz * cz);
+    if (!(v <= 1.7976931348623157e308)) v = 0.0;    // NaN or infinity
+    d[f] = v;
+    m = fmax(m, v);
+  }
+  m = block_max_fp64(m);
+  if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+
+// one block: dmax over the blocks' maxima -> exponent[0]
+__global__ __launch_bounds__(kThreads) void face_exponent_kernel(const double* __restrict__ partial, int n,
+                                                                 int* __restrict__ exponent) {
+  double m = 0.0;
+  for (int b = threadIdx.x; b < n; b += kThreads) m = fmax(m, partial[b]);
+  m = block_max_fp64(m);
+  if (threadIdx.x == 0) {
+    int e = 0;
+    (void)frexp(m, &e);
+    exponent[0] = m > 0.0 ? e : 0;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void face_weight_kernel(const double* __restrict__ d, int F,
+                                                               const int* __restrict__ exponent,
+                                                               long long* __restrict__ weight) {
+  const int shift = 32 - exponent[0];
+  for (int f = blockIdx.x * kThreads + threadIdx.x; f < F; f += gridDim.x * kThreads)
+    weight[f] = (long long)floor(ldexp(d[f], shift));      // d < 2^e: below 2^32
+}
+
+// entry k of the table is cum[table_pos(k, F)]; the last entry is cum[F - 1].  F > kTable: strictly increasing from >= 0.
+__device__ __forceinline__ int table_pos(int k, int F) { return (int)(((long long)(k + 1) * F) / kTable) - 1; }
+
+__global__ __launch_bounds__(kThreads) void sample_surface_kernel(
+    const float* __restrict__ points, const int* __restrict__ fv, const unsigned long long* __restrict__ cum, int F, int V,
+    int N, uint32_t first, uint32_t k0, uint32_t k1, uint32_t stream_id, uint32_t draw, float* __restrict__ out_points,
+    int* __restrict__ out_face, float* __restrict__ out_bary) {
+#pragma clang fp contract(off)
+  __shared__ unsigned long long s_tab[kTable];
+  const bool whole = F <= kTable;                   // all of cum sits in the table
+  const int n_tab = whole ? F : kTable;
+  for (int k = threadIdx.x; k < n_tab; k += kThreads) s_tab[k] = cum[whole ? k : table_pos(k, F)];
+  __syncthreads();
+  const unsigned long long total = s_tab[n_tab - 1];
+  for (int i = blockIdx.x * kThreads + threadIdx.x; i < N; i += gridDim.x * kThreads) {
+    const size_t o = 3 * (size_t)i;
+    if (total == 0) {
+      out_face[i] = -1;
+      out_points[o] = out_points[o + 1] = out_points[o + 2] = 0.f;
+      out_bary[o] = out_bary[o + 1] = out_bary[o + 2] = 0.f;
+      continue;
+    }
+    const U4 w = philox4x32_10(first + (uint32_t)i, stream_id, draw, 2u, k0, k1);
+    const unsigned long long r = (unsigned long long)w.x << 32 | w.y;
+    const unsigned long long t = __umul64hi(r, total);     // < total = the last entry: the searches below always end
+    int lo = 0, hi = n_tab - 1;                            // first table entry > t
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_tab[mid] > t) hi = mid; else lo = mid + 1;
+    }
+    int face = lo;
+    if (!whole) {                                          // cum[pos(lo - 1)] <= t < cum[pos(lo)]: finish inside the bucket
+      int a = lo == 0 ? 0 : table_pos(lo - 1, F) + 1, b = table_pos(lo, F);
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (cum[mid] > t) b = mid; else a = mid + 1;
+      }
+      face = a;
+    }
+    float u1 = word_uniform(w.z), u2 = word_uniform(w.w);
+    if (u1 + u2 > 1.0f) {
+      u1 = 1.0f - u1;
+      u2 = 1.0f - u2;
+    }
+    const float b0 = (1.0f - u1) - u2;
+    const size_t ia = 3 * (size_t)clampi(fv[3 * (size_t)face], V), ib = 3 * (size_t)clampi(fv[3 * (size_t)face + 1], V),
+                 ic = 3 * (size_t)clampi(fv[3 * (size_t)face + 2], V);
+    out_face[i] = face;
+    out_bary[o] = b0;
+    out_bary[o + 1] = u1;
+    out_bary[o + 2] = u2;
+    for (int k = 0; k < 3; ++k) out_points[o + k] = fmaf(u2, points[ic + k], fmaf(u1, points[ib + k], b0 * points[ia + k]));
+  }
+}
+
+struct WeightBuffers {
+  double *d, *partial;
+  SubWs scan;
+};
+WeightBuffers carve_weights(Arena& a, int64_t F) {
+  return {a.take<double>(F), a.take<double>(kMaxBlocks), a.take_ws(inclusive_scan_temp_bytes<long long>(F))};
+}
+
+}  // namespace
+
+int sample_table_entries() { return kTable; }
+
+size_t sample_ws_bytes(int64_t F) {
+  return carve_bytes([&](Arena& a) { carve_weights(a, F); });
+}
+
+int sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, int64_t* weight, int64_t* cum,
+                   int32_t* exponent, void* ws, size_t ws_bytes, hipStream_t s) {
+  Arena a(ws, ws_bytes);
+  const WeightBuffers w = carve_weights(a, F);
+  GEOBI_WS_CHECK("sample_weights", a, ws, ws_bytes);
+  int blocks = cdiv(F, kThreads);
+  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+  face_norm_kernel<<<blocks, kThreads, 0, s>>>(points, fv, (int)F, (int)V, w.d, w.partial);
+  GEOBI_LAUNCH_OK();
+  face_exponent_kernel<<<1, kThreads, 0, s>>>(w.partial, blocks, exponent);
+  GEOBI_LAUNCH_OK();
+  face_weight_kernel<<<blocks, kThreads, 0, s>>>(w.d, (int)F, exponent, (long long*)weight);
+  GEOBI_LAUNCH_OK();
+  size_t tb = w.scan.bytes;
+  GEOBI_HIP(rocprim::inclusive_scan(w.scan.p, tb, (long long*)weight, (long long*)cum, (size_t)F, rocprim::plus<long long>(), s,
+                                    false));
+  return 0;
+}
+
+int sample_surface(const float* points, const int32_t* fv, const int64_t* cum, int64_t F, int64_t V, int64_t N, int64_t first,
+                   uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points, int32_t* out_face, float* out_bary,
+                   hipStream_t s) {
+  if (N == 0) return 0;
+  int blocks = cdiv(N, kThreads);
+  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+  sample_surface_kernel<<<blocks, kThreads, 0, s>>>(points, fv, (const unsigned long long*)cum, (int)F, (int)V, (int)N,
+                                                    (uint32_t)first, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
+                                                    stream_id, draw, out_points, out_face, out_bary);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+}  // namespace geobi

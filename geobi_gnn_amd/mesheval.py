@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib as L
-from . import meshin, meshio, meshprep, network, ops
+from . import meshin, meshio, meshnoise, meshprep, network, ops
 from .data_util import computer_face_normal, face_centroids
 
 
@@ -80,12 +80,32 @@ def mean_edge_length(points, faces):
     return meshprep.mean_edge_length(points, meshprep.ring_graph(0, faces, rowptr, lst, V))
 
 
+def align_target(target_points, target_faces, samples, seed=1, stream_id=0, device=None):
+    """The ICP target of align(samples=): the target's vertices followed by `samples` points drawn by area on its surface
+    (meshsample.sample_surface, draw 0) -> device float32 [V + samples, 3]."""
+    from . import meshsample
+    if target_faces is None:
+        raise ValueError('align: samples = %d needs target_faces (the surface to sample)' % samples)
+    t, tf = meshin.device_mesh(target_points, target_faces, meshin.default_device(device, target_points))
+    drawn = meshsample.sample_surface(t, tf, samples, seed=seed, stream_id=stream_id, draw=0, check=False)
+    return torch.cat([_points(t, 'target points'), drawn.points])
+
+
 def align(points, target_points, device=None, estimate_scale=False, allow_reflection=False, max_iterations=100,
-          relative_rmse_thr=1e-6):
+          relative_rmse_thr=1e-6, target_faces=None, samples=0, seed=1, stream_id=0):
     """Rigid ICP of one point set onto another (ops.icp; arrays or tensors, sizes may differ) -> ops.IcpResult: xt the
-    aligned points on the device, R [1,3,3], T [1,3], s, rmse, iterations, converged [1] on the host."""
+    aligned points on the device, R [1,3,3], T [1,3], s, rmse, iterations, converged [1] on the host.
+    samples > 0: the target is align_target(): its vertices followed by that many points drawn by area on its surface
+    (target_faces) -- a CAD target of a few large triangles has no vertex inside a face to be nearest to.  The source stays
+    its vertices; everything else is ops.icp as without samples."""
     dev = meshin.default_device(device, points)
-    p, t = meshin.to_device(points, dev, torch.float32), meshin.to_device(target_points, dev, torch.float32)
+    p = meshin.to_device(points, dev, torch.float32)
+    if int(samples) < 0:
+        raise ValueError('align: samples = %d is negative' % samples)
+    if int(samples) > 0:
+        t = align_target(target_points, target_faces, int(samples), seed, stream_id, dev)
+    else:
+        t = meshin.to_device(target_points, dev, torch.float32)
     return ops.icp(_points(p, 'points'), _points(t, 'target points'), estimate_scale=estimate_scale,
                    allow_reflection=allow_reflection, max_iterations=max_iterations, relative_rmse_thr=relative_rmse_thr)
 
@@ -189,6 +209,59 @@ def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, ali
     return row
 
 
+def eval_sampled(result_points, result_faces, gt_points, gt_faces, n_samples, seed=1, stream_id=0, device=None):
+    """eval_free's distances measured from points drawn by area on the two SURFACES (meshsample.sample_surface) instead of
+    from their vertices: two meshes that share every vertex and differ inside their triangles are `surf = 0` to eval_free
+    and not to this.  Returns a dict:
+
+      num_s (= n_samples),
+      surf_s (mean distance from n_samples points of the result's surface, draw 1, to the ground-truth surface),
+      surf_back_s (from n_samples points of the ground truth's surface, draw 0, to the result's surface),
+      hausdorff_s (the larger of the two directed maxima),
+      angle_s (mean angle in degrees between a result sample's face normal and the normal of the ground-truth triangle
+      nearest to the sample: area-weighted, so it does not depend on the tessellation),
+      scale (the ground truth's mean edge length), surf_s_norm, surf_back_s_norm (over scale).
+
+    The sums go through dist_summary; one host read brings the pair's numbers (beside the one read per sampled mesh that
+    refuses a mesh without area)."""
+    from . import meshsample
+    n = int(n_samples)
+    if n < 1:
+        raise ValueError('eval_sampled: n_samples = %d (at least one)' % n)
+    dev = meshin.default_device(device, result_points)
+    pr, fr = meshin.device_mesh(result_points, result_faces, dev)
+    po, fo = meshin.device_mesh(gt_points, gt_faces, dev)
+    if min(pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]) == 0:
+        raise ValueError('eval_sampled: empty mesh (result V = %d, F = %d, ground truth V = %d, F = %d)'
+                         % (pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]))
+    sr = meshsample.sample_surface(pr, fr, n, seed=seed, stream_id=stream_id, draw=1, check=False)
+    so = meshsample.sample_surface(po, fo, n, seed=seed, stream_id=stream_id, draw=0, check=False)
+    d_ro, near = point_to_mesh(sr.points, po, fo)
+    d_or, _ = point_to_mesh(so.points, pr, fr)
+    no = computer_face_normal(po, fo).contiguous()
+    ng = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    L.call('geobi_gather_rows', L.ptr(no), L.ptr(near), 3, n, L.ptr(ng), L.stream())
+    angle = network.error_n(meshsample.sample_normals(pr, fr, sr), ng)
+    scale = mean_edge_length(po, fo)
+    host = torch.cat([angle.reshape(1).double(), scale.double(), dist_summary(d_ro), dist_summary(d_or)]).tolist()
+    scale = host[1]
+    surf, back = host[2] / n, host[4] / n
+    return {'num_s': n, 'surf_s': surf, 'surf_back_s': back, 'hausdorff_s': max(host[3], host[5]), 'angle_s': host[0],
+            'scale': scale, 'surf_s_norm': surf / scale, 'surf_back_s_norm': back / scale}
+
+
+_SAMPLED_COLUMNS = ('num_s', 'angle_s', 'surf_s', 'surf_s_norm', 'surf_back_s', 'surf_back_s_norm', 'hausdorff_s')
+_SAMPLED_FMT = '{0:<{1}}  {2:>7}  {3:9.6f}  {4:.6f}  {5:9.6f}  {6:.6f}  {7:9.6f}  {8:.6f}\n'
+
+
+def sampled_totals(rows):
+    """Sample-count weighted means of eval_sampled's columns; hausdorff_s is the maximum over the files."""
+    n = sum(r['num_s'] for r in rows)
+    tot = {k: sum(r[k] * r['num_s'] for r in rows) / n for k in _SAMPLED_COLUMNS[1:-1]}
+    tot.update(num_s=n, hausdorff_s=max(r['hausdorff_s'] for r in rows))
+    return tot
+
+
 def pair_files(dir_result, dir_original):
     """The reference's pairing (code/data_util.py:563-567), sorted: every dir_original/NAME.obj with every
     dir_result/NAME_*.obj -> [(result file, original file)]."""
@@ -245,7 +318,8 @@ def align_line(name, width, info):
                              info['icp_scale'], info['icp_angle'], info['icp_shift'])
 
 
-def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, free=False, estimate_scale=False):
+def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, free=False, estimate_scale=False, samples=0,
+              seed=1):
     """eval_denoising_result(dir_result, dir_original): every pair of pair_files scored with eval_pair, the per-file
     and totals lines printed and written to dir_result/ErrorInfo_h.txt in the reference's format with three columns
     appended (surf, surf_norm, hausdorff).  A result whose V or F differs from its ground truth is a ValueError naming
@@ -253,8 +327,15 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
     align: every result is first aligned to its ground truth by rigid ICP (estimate_scale: with a scale) and
     dir_result/AlignInfo.txt lists per file: iterations, converged, rmse, scale, rotation angle in degrees, |T|.
     free: every pair is scored with eval_free instead (sizes may differ) and dir_result/ErrorInfo_free.txt is written;
-    ErrorInfo_h.txt is not.  Returns (rows, totals) -- rows carry 'file'."""
+    ErrorInfo_h.txt is not.  samples > 0 (with free): every pair is ALSO scored with eval_sampled from that many points
+    per surface (seed; the Philox stream is meshnoise.stream_of the ground-truth file's stem) and
+    dir_result/ErrorInfo_sampled.txt is written beside ErrorInfo_free.txt, whose bytes the flag does not change; with align
+    as well, the alignment target is the ground truth's vertices followed by its draw-0 samples (align(samples=)), which
+    is another alignment and so other numbers in both files.  Returns (rows, totals) -- rows carry 'file', and with
+    samples eval_sampled's keys."""
     import time
+    if samples and not free:
+        raise ValueError('eval: samples need the free scoring (eval_free pairs nothing by index; neither do samples)')
     pairs = pair_files(dir_result, dir_original)
     if not pairs:
         print('--- empty data ---')
@@ -270,11 +351,16 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
         if not free and (pr.shape != po.shape or fr.shape != fo.shape):
             raise ValueError('%s (V = %d, F = %d) and its ground truth %s (V = %d, F = %d) differ in size'
                              % (file_r, pr.shape[0], fr.shape[0], file_o, po.shape[0], fo.shape[0]))
+        stream_id = meshnoise.stream_of(os.path.basename(file_o)[:-4]) if samples else 0
         if align:
-            res = _align_points(pr, po, dev, estimate_scale=estimate_scale)
+            res = _align_points(pr, po, dev, estimate_scale=estimate_scale, target_faces=fo if samples else None,
+                                samples=samples, seed=seed, stream_id=stream_id)
             infos.append(align_info(res))
             pr = res.xt
         row = eval_free(pr, fr, po, fo, device=dev) if free else eval_pair(pr, fr, po, gt_faces=fo, device=dev)
+        if samples:
+            sampled = eval_sampled(pr, fr, po, fo, samples, seed=seed, stream_id=stream_id, device=dev)
+            row.update((k, sampled[k]) for k in _SAMPLED_COLUMNS)
         if align:
             row.update((k, infos[-1][k]) for k in _ALIGN_KEYS)
         row['file'] = os.path.basename(file_r)
@@ -307,6 +393,17 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
             for row in rows:
                 f.write(_FREE_FMT.format(row['file'], width, *[row[k] for k in _FREE_COLUMNS]))
         print('%s saved.' % file_txt)
+        if samples:
+            tot_s = sampled_totals(rows)
+            tot.update(tot_s)
+            file_txt = os.path.join(dir_result, 'ErrorInfo_sampled.txt')
+            with open(file_txt, 'w') as f:
+                f.write('Error_sampled:  num_s  angle_mean  surf  surf_norm  surf_back  surf_back_norm  hausdorff \n')
+                f.write(_SAMPLED_FMT.format('', width, *[tot_s[k] for k in _SAMPLED_COLUMNS]))
+                f.write('\n')
+                for row in rows:
+                    f.write(_SAMPLED_FMT.format(row['file'], width, *[row[k] for k in _SAMPLED_COLUMNS]))
+            print('%s saved.' % file_txt)
         return rows, tot
     tot = totals(rows)
     print('{0:>8}  {1:.4f}  {2:7.4f}  {3:>8}  {4:7.4f}  {5:.4f}  {6:7.4f}  {7:.4f}  {8:7.4f} \n'.format(

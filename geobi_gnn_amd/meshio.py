@@ -66,13 +66,20 @@ def read_obj(path):
     return pts, fv.astype(np.int32)
 
 
-def write_obj(path, points, faces):
+def write_obj(path, points, faces, normals=None):
     """`v %.9g %.9g %.9g` and 1-based `f a b c`: nine significant digits identify a float32, so a float32 mesh survives
-    write_obj -> read_obj bit for bit."""
+    write_obj -> read_obj bit for bit.  normals (optional, one row per point): a `vn %.9g %.9g %.9g` line per point after
+    the `v` lines -- a point cloud with normals; read_obj skips them."""
     pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
     fv = np.asarray(faces).reshape(-1, 3).astype(np.int64) + 1
+    if normals is not None:
+        vn = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+        if vn.shape != pts.shape:
+            raise ValueError('%s: %d normals for %d points' % (path, vn.shape[0], pts.shape[0]))
     with open(path, 'w') as fh:
         fh.write(''.join('v %.9g %.9g %.9g\n' % (x, y, z) for x, y, z in pts.tolist()))
+        if normals is not None:
+            fh.write(''.join('vn %.9g %.9g %.9g\n' % (x, y, z) for x, y, z in vn.tolist()))
         fh.write(''.join('f %d %d %d\n' % (a, b, c) for a, b, c in fv.tolist()))
 
 

@@ -424,6 +424,36 @@ int geobi_icp_step(const float* x, const float* y, const int32_t* idx, const int
 int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction,
                      float fraction, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, void* stream);
 
+/* ---------------------------------------------------------------- surface sampling ----
+ * The reference has NO call site for this: every distance of its evaluation starts from a vertex (code/data_util.py:
+ * 584-616).  Points drawn uniformly by area on the surface (points [V, 3], fv [F, 3], ids in [0, V): range-check them
+ * first; what is read through fv is clamped to points).  F, V >= 1; F, V, N and first + N <= GEOBI_MAX_NODES.
+ *   geobi_sample_weights  integer face weights, exact from here on: d[f] = |e1 x e2| of the float32 corners widened to
+ *                         fp64, every product and difference rounded on its own (no FMA contraction), non-finite -> 0;
+ *                         dmax = max d, frexp(dmax) = m 2^e, exponent[0] = e (DEVICE int32, 0 for dmax == 0);
+ *                         weight[f] = floor(ldexp(d[f], 32 - e)) (DEVICE int64 [F]): the largest face lands in [2^31,
+ *                         2^32), a degenerate face and one below 2^-32 of the largest get 0; cum (DEVICE int64 [F]) is the
+ *                         inclusive scan of weight, cum[F - 1] < 2^56.  The area is ldexp(cum[F - 1], e - 33) up to the
+ *                         floors.  ws: geobi_sample_ws_bytes(F)
+ *   geobi_sample_surface  sample i of the call: Philox4x32-10 with key = (seed lo, seed hi) and counter (first + i,
+ *                         stream_id, draw, 2) -- blocks 0 and 1 are geobi_mesh_noise's -- gives words w0..w3;
+ *                         r = w0 << 32 | w1, t = umul64hi(r, total), total = cum[F - 1] read on the device (no host sync);
+ *                         out_face[i] = the first f with cum[f] > t, so a zero-weight face is never drawn; u1 = u(w2),
+ *                         u2 = u(w3) with the word -> uniform map above, both replaced by 1 - u if u1 + u2 > 1;
+ *                         out_bary[i] = (1 - u1 - u2, u1, u2), exact in fp32 and not negative; out_points[i] =
+ *                         fma(b2, c, fma(b1, b, b0 * a)) per coordinate.  total == 0 (a mesh without area): face -1 and
+ *                         zeros.  A sample depends on (seed, stream_id, draw, first + i) and the mesh only -- never on N,
+ *                         the grid or how a draw is cut into calls.  N == 0 is a no-op.  Each block stages
+ *                         geobi_sample_table_entries() evenly spaced entries of cum in LDS (all of cum for an F up to
+ *                         that) and finishes inside the bucket from global memory: the result is the plain search's.  */
+int geobi_sample_table_entries(void);
+size_t geobi_sample_ws_bytes(int64_t F);
+int geobi_sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, void* weight, void* cum,
+                         int32_t* exponent, void* ws, size_t ws_bytes, void* stream);
+int geobi_sample_surface(const float* points, const int32_t* fv, const void* cum, int64_t F, int64_t V, int64_t N,
+                         int64_t first, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points,
+                         int32_t* out_face, float* out_bary, void* stream);
+
 /* ---------------------------------------------------------------- bilateral normal filter ----
  * The reference has NO call site for this: its scratch code only lists result folders of classical filters beside its own
  * (code/data_util.py:732-745).  Zheng et al. 2011, local iterative scheme, over the loop-free (row, col)-sorted facet graph
