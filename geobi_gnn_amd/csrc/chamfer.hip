@@ -12,6 +12,7 @@
 // The part tables ride in the kernel arguments (PartTable, common.h), kMaxParts parts per launch, with the weights.
 // The part pointers were checked once, by the entry point (parts_check).
 #include "common.h"
+#include "../../include/geobi_hip.h"
 
 namespace geobi {
 
@@ -113,10 +114,19 @@ double* carve_partials(Arena& a, int P) {
 
 }  // namespace
 
-size_t chamfer_ws_bytes(int P) { return carve_bytes([&](Arena& a) { carve_partials(a, P); }); }
+}  // namespace geobi
 
-int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out, void* ws,
-                size_t ws_bytes, hipStream_t s) {
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_chamfer_ws_bytes(int P) { return carve_bytes([&](Arena& a) { carve_partials(a, P); }); }
+
+int geobi_chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out,
+                      void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_TRY(parts_check(__func__, qptr, tptr, P));
+  GEOBI_NOTNULL(d2a); GEOBI_NOTNULL(d2b); GEOBI_NOTNULL(out); GEOBI_NOTNULL(ws);
+  hipStream_t s = as_stream(stream);
   Arena ar(ws, ws_bytes);
   double* partial = carve_partials(ar, P);
   GEOBI_WS_CHECK("chamfer_fwd", ar, ws, ws_bytes);
@@ -134,10 +144,14 @@ int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const i
   return 0;
 }
 
-int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
-                const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, hipStream_t s) {
+int geobi_chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
+                      const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, void* stream) {
+  GEOBI_TRY(parts_check(__func__, qptr, tptr, P));
+  GEOBI_NOTNULL(p); GEOBI_NOTNULL(t); GEOBI_NOTNULL(idx_a); GEOBI_NOTNULL(segptr); GEOBI_NOTNULL(members);
+  GEOBI_NOTNULL(gout); GEOBI_NOTNULL(gp);
   GEOBI_REQUIRE(qptr[0] == 0 && tptr[0] == 0, "chamfer_bwd: qptr / tptr start at %lld / %lld (the inverse lists are indexed by "
                 "the rows themselves: both 0)", (long long)qptr[0], (long long)tptr[0]);
+  hipStream_t s = as_stream(stream);
   for (int base = 0; base < P; base += kMaxParts) {
     ChamferJob job;
     fill_job(&job, qptr, tptr, base, P);
@@ -148,4 +162,4 @@ int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int3
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

@@ -241,14 +241,23 @@ CompactBuffers carve_compact(Arena& a, int64_t V, int64_t F) {
 
 }  // namespace
 
-size_t clean_weld_ws_bytes(int64_t V) {
-  return carve_bytes([&](Arena& a) { carve_weld(a, V); });
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_clean_weld_ws_bytes(int64_t V) {
+  return V < 0 || V > GEOBI_MAX_NODES ? 0 : carve_bytes([&](Arena& a) { carve_weld(a, V); });
 }
 
-int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
-               size_t ws_bytes, hipStream_t s) {
+int geobi_clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
+                     size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(V, 0);
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(canon); GEOBI_NOTNULL(counts);
   GEOBI_REQUIRE(mode >= 0 && mode <= 2, "clean_weld: mode %d (0 none, 1 exact, 2 grid)", mode);
   GEOBI_REQUIRE(mode != 2 || (weld_tol > 0.0f && weld_tol <= 3.0e38f), "clean_weld: grid mode needs a finite weld_tol > 0");
+  hipStream_t s = as_stream(stream);
   const int n = (int)V, blocks = cdiv(V > 0 ? V : 1, kT);
   if (mode == 0 || V == 0) {
     weld_identity_kernel<<<blocks, kT, 0, s>>>(n, canon, counts);
@@ -282,13 +291,16 @@ int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t
   return 0;
 }
 
-size_t clean_faces_ws_bytes(int64_t F) {
-  return carve_bytes([&](Arena& a) { carve_faces(a, F); });
+size_t geobi_clean_faces_ws_bytes(int64_t F) {
+  return F < 0 || F > GEOBI_MAX_NODES ? 0 : carve_bytes([&](Arena& a) { carve_faces(a, F); });
 }
 
-int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
-                int32_t* faces_canon, int32_t* state, int32_t* rounds, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
+                      int32_t* faces_canon, int32_t* state, int32_t* rounds, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(canon); GEOBI_NOTNULL(faces_canon); GEOBI_NOTNULL(state); GEOBI_NOTNULL(rounds);
   GEOBI_REQUIRE(max_rounds >= 1, "clean_faces: max_rounds = %d (at least 1)", max_rounds);
+  hipStream_t s = as_stream(stream);
   *rounds = 0;
   if (F == 0) return 0;
   Arena a(ws, ws_bytes);
@@ -332,13 +344,19 @@ int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V
   return 0;
 }
 
-size_t clean_compact_ws_bytes(int64_t V, int64_t F) {
+size_t geobi_clean_compact_ws_bytes(int64_t V, int64_t F) {
+  if (V < 0 || F < 0 || V > GEOBI_MAX_NODES || F > GEOBI_MAX_NODES) return 0;
   return carve_bytes([&](Arena& a) { carve_compact(a, V, F); });
 }
 
-int clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon, int64_t V,
-                  int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map, int32_t* vertex_src,
-                  int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon,
+                        int64_t V, int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map,
+                        int32_t* vertex_src, int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(faces_canon); GEOBI_NOTNULL(state); GEOBI_NOTNULL(canon);
+  GEOBI_NOTNULL(points_out); GEOBI_NOTNULL(faces_out);
+  GEOBI_NOTNULL(vertex_map); GEOBI_NOTNULL(vertex_src); GEOBI_NOTNULL(face_map); GEOBI_NOTNULL(counts);
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   const CompactBuffers c = carve_compact(a, V, F);
   GEOBI_WS_CHECK("clean_compact", a, ws, ws_bytes);
@@ -359,4 +377,4 @@ int clean_compact(const float* points, const int32_t* faces_canon, const int32_t
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

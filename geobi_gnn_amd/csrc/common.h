@@ -34,6 +34,17 @@ int set_error(const char* fmt, ...);
     if (!(cond)) return ::geobi::set_error(__VA_ARGS__);  \
   } while (0)
 
+// ---- argument checks of the extern "C" entry points: an entry point is defined in the unit that implements
+// it and runs these first.  Size limits of the header (GEOBI_MAX_NODES / GEOBI_MAX_EDGES): every entry point that takes a
+// node or edge count rejects what is above them, so that no kernel ever forms a 32-bit element index beyond its range.
+int sizes_ok(const char* fn, int64_t nodes, int64_t edges);      // capi.hip
+#define GEOBI_NOTNULL(p)                                                          \
+  do {                                                                            \
+    if ((p) == nullptr) return ::geobi::set_error("%s: %s is NULL", __func__, #p); \
+  } while (0)
+#define GEOBI_SIZES(nodes, edges) GEOBI_TRY(::geobi::sizes_ok(__func__, (int64_t)(nodes), (int64_t)(edges)))
+static inline hipStream_t as_stream(void* stream) { return (hipStream_t)stream; }
+
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
@@ -215,13 +226,9 @@ Fork fork_side_stream(hipStream_t main);       // side stream waits for everythi
 int join_side_stream(const Fork& f, hipStream_t main);   // `main` waits for the side stream
 int side_wait_main(const Fork& f, hipStream_t main);     // side stream waits for `main` as of now
 
-// ---- launchers implemented across the translation units (all enqueue on `s`, never sync)
-// graph.hip
-size_t csr_ws_bytes(int64_t E, int64_t N);
-int csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, int drop_self, int32_t* rowptr,
-                 int32_t* col, int32_t* eid, int32_t* bad, void* ws, size_t ws_bytes, hipStream_t s);
-int csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t Ecap, int32_t* rowptr_t,
-                  int32_t* col_t, int32_t* pos_t, int32_t* inv_pos, void* ws, size_t ws_bytes, hipStream_t s);
+// ---- launchers that ANOTHER translation unit calls (all enqueue on `s`, never sync).  A launcher only its own entry point
+// reaches has no prototype here: it is the body of that entry point
+// graph.hip (also called by executor.hip)
 int csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int32_t* col, int64_t E, int32_t* pos_rev,
                       int32_t* flag, hipStream_t s);
 // gemm.hip
@@ -427,125 +434,15 @@ size_t pool_edge_ws_bytes(int64_t E);
 int pool_edge(const int32_t* cnew, const int32_t* row, const int32_t* col, const float* w, int64_t E, int64_t nmax,
               int32_t* rowptr_c, int32_t* row_c, int32_t* col_c, float* w_c, int32_t* count, void* ws,
               size_t ws_bytes, hipStream_t s);
-// meshprep.hip (mesh -> graphs / normals / bilateral weights on the device)
-size_t vertex_faces_ws_bytes(int64_t F, int64_t V);
-int vertex_faces(const int32_t* fv, int64_t F, int64_t V, int32_t* rowptr, int32_t* list, void* ws, size_t ws_bytes,
-                 hipStream_t s);
-int vf_padded(const int32_t* rowptr, const int32_t* list, int64_t V, int maxval, int32_t* vf, hipStream_t s);
-int max_degree(const int32_t* rowptr, int64_t N, int32_t* out, hipStream_t s);
-int mesh_normals(const float* points, const int32_t* fv, int64_t F, int64_t V, const int32_t* rowptr,
-                 const int32_t* list, float* fnormal, float* centroid, float* vnormal, hipStream_t s);
-size_t ring_graph_ws_bytes(int64_t n_nodes);
-int ring_graph_count(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list, int64_t n_nodes,
-                     int32_t* rowptr_g, void* ws, size_t ws_bytes, hipStream_t s);
-int ring_graph_fill(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list, int64_t n_nodes,
-                    const int32_t* rowptr_g, int32_t* col, hipStream_t s);
-size_t calc_weight_parts_ws_bytes(int n_parts);
-int calc_weight_parts(const float* pos, const float* normal, const int32_t* rowptr, const int32_t* row, const int32_t* col,
-                      int64_t E, const int32_t* node_ptr, int n_parts, float* w, void* ws, size_t ws_bytes, hipStream_t s);
-size_t calc_weight_ws_bytes();
-int calc_weight(const float* pos, const float* normal, const int32_t* row, const int32_t* col, int64_t E,
-                int64_t extra_zero_edges, float* w, float* mean_len, void* ws, size_t ws_bytes, hipStream_t s);
-// patch.hip (patch split / merge for large meshes)
-size_t patch_grow_state_ints(int64_t F, int64_t V);
-int patch_grow_init(int32_t* state, int64_t F, int64_t V, const float* d2, hipStream_t s);
-int patch_grow(const int32_t* fv, const int32_t* vf, int maxval, int64_t F, int64_t V, const float* d2, int64_t seed,
-               int64_t neighbor_count, int64_t ring_count, int patch_id, int32_t* state, int32_t* sel_out, int32_t* n_out,
-               int32_t* mailbox, int pick_next, hipStream_t s);
-size_t submesh_ws_bytes(int64_t n_sel, int64_t V);
-int submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t V, int32_t* v_idx, int32_t* f_sub,
-            int32_t* count, void* ws, size_t ws_bytes, hipStream_t s);
-int patch_accumulate(const float* vert_p, const float* norm_p, const int32_t* v_idx, const int32_t* f_idx, int64_t nv,
-                     int64_t nf, float* Vp, float* Np, int32_t* sum_v, hipStream_t s);
-int patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, int64_t F, float scale, float cx, float cy,
-                   float cz, hipStream_t s);
 // pool.hip: exclusive int scan shared with meshprep.hip (single launch below 2^18 elements)
 size_t scan_ws_bytes(int64_t n);
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s);
-// dist.hip (nearest point / nearest triangle by brute force, distance summary)
-int nearest_slices(int64_t Q, int64_t T, int triangles);
-size_t nearest_ws_bytes(int64_t Q, int64_t T);
-int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
-                  size_t ws_bytes, hipStream_t s);
-int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int64_t Q, int64_t V, int64_t F, float* dist,
-                     int32_t* face, void* ws, size_t ws_bytes, hipStream_t s);
-size_t dist_summary_ws_bytes(int64_t n);
-int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s);
-// dist.hip: the point search confined to the parts of a union batch (host part pointers, 32 parts per launch)
 // capi.hip: the one check of host part pointers (P >= 1, not NULL, start >= 0, no empty part, GEOBI_MAX_NODES rows);
-// the entry points run it once, the functions below rely on it
+// the entry points that take a union batch (dist.hip, chamfer.hip, icp.hip) run it first and rely on it
 int parts_check(const char* fn, const int64_t* qptr, const int64_t* tptr, int P);
-int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P);
-size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P);
-int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,
-                  void* ws, size_t ws_bytes, hipStream_t s);
-// chamfer.hip (Chamfer distance of a union batch: value and gradient on top of the two searches)
-size_t chamfer_ws_bytes(int P);
-int chamfer_fwd(const float* d2a, const float* d2b, const int64_t* qptr, const int64_t* tptr, int P, float* out, void* ws,
-                size_t ws_bytes, hipStream_t s);
-int chamfer_bwd(const float* p, const float* t, const int32_t* idx_a, const int32_t* segptr, const int32_t* members,
-                const int64_t* qptr, const int64_t* tptr, int P, const float* gout, float* gp, hipStream_t s);
-// reg.hip (mesh regularisers over the symmetric vertex CSR: Laplacian and edge-length terms)
-size_t mesh_reg_ws_bytes(int64_t V);
-int mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int32_t* rowptr, const int32_t* col, int64_t V,
-                 int64_t E, const float* w_lap, const float* w_edge, int terms, float* out, float* u, void* ws,
-                 size_t ws_bytes, hipStream_t s);
-int mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const int32_t* col, int64_t V, int64_t E,
-                 const float* u, const float* w_edge, const float* gout, int terms, float* gvp, hipStream_t s);
-// icp.hip (rigid point-to-point ICP of a union batch on top of nearest_parts)
-size_t icp_ws_bytes(int P);
-int icp_init(double* state, int P, const double* init, hipStream_t s);
-int icp_apply(const float* x, const int64_t* xptr, int P, const double* state, int mode, float* out, hipStream_t s);
-int icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P, int flags,
-             double relative_rmse_thr, double* state, float* xt, void* ws, size_t ws_bytes, hipStream_t s);
-// noise.hip (synthetic mesh noise: counter-based Philox4x32-10, one counter per vertex)
-int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
-               uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s);
-// sample.hip (points drawn uniformly by area on a mesh surface: integer face weights, Philox block 2)
-int sample_table_entries();
-size_t sample_ws_bytes(int64_t F);
-int sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, int64_t* weight, int64_t* cum,
-                   int32_t* exponent, void* ws, size_t ws_bytes, hipStream_t s);
-int sample_surface(const float* points, const int32_t* fv, const int64_t* cum, int64_t F, int64_t V, int64_t N, int64_t first,
-                   uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points, int32_t* out_face, float* out_bary,
-                   hipStream_t s);
-// filter.hip (bilateral normal filter over the facet graph: the model-free baseline of `denoise`)
-int bnf_prepare(const float* points, const int32_t* fv, int64_t F, float* rec_c, float* rec_n, hipStream_t s);
-size_t bnf_filter_ws_bytes(int64_t F, int64_t E);
-int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
-               const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes, hipStream_t s);
+// filter.hip (also called by guided.hip)
 int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
                         const float* inv2ss, float* wsp, hipStream_t s);
-// guided.hip (guided normal filter: patch search, selection and guidance, the sweep with the range term on the guidance)
-int gnf_edge_flags(const int32_t* fv, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E, uint8_t* flags,
-                   hipStream_t s);
-int gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* rowptr, const int32_t* col,
-                      const uint8_t* flags, int64_t F, float* H, float* pmean, hipStream_t s);
-size_t gnf_filter_ws_bytes(int64_t F, int64_t E);
-int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
-               int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out, void* ws,
-               size_t ws_bytes, hipStream_t s);
-// clean.hip (mesh repair: weld, degenerate faces, one owner per directed half-edge, compaction)
-size_t clean_weld_ws_bytes(int64_t V);
-int clean_weld(const float* points, int64_t V, int mode, float weld_tol, int32_t* canon, int32_t* counts, void* ws,
-               size_t ws_bytes, hipStream_t s);
-size_t clean_faces_ws_bytes(int64_t F);
-int clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int64_t V, int manifold, int max_rounds,
-                int32_t* faces_canon, int32_t* state, int32_t* rounds, void* ws, size_t ws_bytes, hipStream_t s);
-size_t clean_compact_ws_bytes(int64_t V, int64_t F);
-int clean_compact(const float* points, const int32_t* faces_canon, const int32_t* state, const int32_t* canon, int64_t V,
-                  int64_t F, float* points_out, int32_t* faces_out, int32_t* vertex_map, int32_t* vertex_src,
-                  int32_t* face_map, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s);
-// topo.hip (mesh topology: consistent winding, connected components, the edge report)
-size_t topo_ws_bytes(int64_t F, int64_t V);
-int topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* faces_out,
-                int32_t* flip, int32_t* label, int32_t* counts, int32_t* rounds, float* stage_ms, void* ws, size_t ws_bytes,
-                hipStream_t s);
-int topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int min_component, int max_rounds,
-                    int32_t* comp, int32_t* state_out, int32_t* counts, int32_t* rounds, float* stage_ms, void* ws,
-                    size_t ws_bytes, hipStream_t s);
-int topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
-                int32_t* rounds, void* ws, size_t ws_bytes, hipStream_t s);
 // geom.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);

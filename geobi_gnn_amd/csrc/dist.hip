@@ -23,6 +23,7 @@
 // written out), the result is bit-identical for every S.  d2 is formed from coordinate DIFFERENCES, never
 // |q|^2 + |t|^2 - 2 q.t; one sqrt per query at the end.
 #include "common.h"
+#include "../../include/geobi_hip.h"
 
 #include <math.h>
 
@@ -371,34 +372,6 @@ Partials carve_partials(Arena& a, int slices, int64_t rows) {
 size_t partials_bytes(int slices, int64_t rows) { return carve_bytes([&](Arena& a) { carve_partials(a, slices, rows); }); }
 double* carve_summary(Arena& a, int blocks) { return a.take<double>((size_t)2 * blocks); }
 
-}  // namespace
-
-int nearest_slices(int64_t Q, int64_t T, int triangles) {
-  if (Q <= 0 || T <= 0) return 0;
-  return triangles ? choose_slices(Q, T, kTriQpl, kTriTile).slices : choose_slices(Q, T, kPointQpl, kPointTile).slices;
-}
-
-size_t nearest_ws_bytes(int64_t Q, int64_t T) {
-  if (Q <= 0 || T <= 0) return partials_bytes(0, 0);
-  // enough for either kernel
-  return std::max(partials_bytes(choose_slices(Q, T, kPointQpl, kPointTile).slices, Q),
-                  partials_bytes(choose_slices(Q, T, kTriQpl, kTriTile).slices, Q));
-}
-
-int nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
-                  size_t ws_bytes, hipStream_t s) {
-  GEOBI_REQUIRE(Q > 0 && T > 0, "nearest_point: empty query or target set (Q = %lld, T = %lld)", (long long)Q, (long long)T);
-  const Slicing c = choose_slices(Q, T, kPointQpl, kPointTile);
-  Arena ar(ws, ws_bytes);
-  const Partials p = carve_partials(ar, c.slices, Q);
-  GEOBI_WS_CHECK("nearest_point", ar, ws, ws_bytes);
-  nearest_point_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, t, (int)Q, (int)T, c.tiles_per_slice, p.d2, p.idx);
-  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, p.d2, p.idx, (int)Q, dist, idx);
-  GEOBI_LAUNCH_OK();
-  return 0;
-}
-
-namespace {
 // every part is sliced as a single mesh would be, but for the workgroups of ALL parts together (P = 1: choose_slices)
 int parts_want(const int64_t* qptr, int P) {
   int64_t qblocks = 0;
@@ -414,19 +387,57 @@ int max_part_slices(const int64_t* qptr, const int64_t* tptr, int P) {
   for (int p = 0; p < P; ++p) smax = std::max(smax, part_slices(qptr, tptr, p, want).slices);
   return smax;
 }
+
 }  // namespace
 
-int nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P) {
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+int geobi_nearest_slices(int64_t Q, int64_t T, int triangles) {
+  if (Q <= 0 || T <= 0) return 0;
+  return triangles ? choose_slices(Q, T, kTriQpl, kTriTile).slices : choose_slices(Q, T, kPointQpl, kPointTile).slices;
+}
+
+size_t geobi_nearest_ws_bytes(int64_t Q, int64_t T) {
+  if (Q <= 0 || T <= 0) return partials_bytes(0, 0);
+  // enough for either kernel
+  return std::max(partials_bytes(choose_slices(Q, T, kPointQpl, kPointTile).slices, Q),
+                  partials_bytes(choose_slices(Q, T, kTriQpl, kTriTile).slices, Q));
+}
+
+int geobi_nearest_point(const float* q, const float* t, int64_t Q, int64_t T, float* dist, int32_t* idx, void* ws,
+                        size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(Q > T ? Q : T, 0);
+  GEOBI_NOTNULL(q); GEOBI_NOTNULL(t); GEOBI_NOTNULL(dist); GEOBI_NOTNULL(ws);
+  GEOBI_REQUIRE(Q > 0 && T > 0, "nearest_point: empty query or target set (Q = %lld, T = %lld)", (long long)Q, (long long)T);
+  hipStream_t s = as_stream(stream);
+  const Slicing c = choose_slices(Q, T, kPointQpl, kPointTile);
+  Arena ar(ws, ws_bytes);
+  const Partials p = carve_partials(ar, c.slices, Q);
+  GEOBI_WS_CHECK("nearest_point", ar, ws, ws_bytes);
+  nearest_point_kernel<<<dim3(c.qblocks, c.slices), kThreads, 0, s>>>(q, t, (int)Q, (int)T, c.tiles_per_slice, p.d2, p.idx);
+  nearest_reduce_kernel<<<cdiv(Q, kThreads), kThreads, 0, s>>>(OneRange{(int)Q, c.slices}, p.d2, p.idx, (int)Q, dist, idx);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+int geobi_nearest_parts_slices(const int64_t* qptr, const int64_t* tptr, int P) {
   return parts_check("nearest_parts_slices", qptr, tptr, P) == 0 ? max_part_slices(qptr, tptr, P) : 0;
 }
 
-size_t nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
-  const int smax = nearest_parts_slices(qptr, tptr, P);      // 0: the part pointers failed their check
+size_t geobi_nearest_parts_ws_bytes(const int64_t* qptr, const int64_t* tptr, int P) {
+  const int smax = geobi_nearest_parts_slices(qptr, tptr, P);      // 0: the part pointers failed their check
   return partials_bytes(smax, smax == 0 ? 0 : qptr[P]);
 }
 
-int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2, int32_t* idx,
-                  void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_nearest_parts(const float* q, const float* t, const int64_t* qptr, const int64_t* tptr, int P, float* d2,
+                        int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_TRY(parts_check(__func__, qptr, tptr, P));
+  GEOBI_NOTNULL(q); GEOBI_NOTNULL(t); GEOBI_NOTNULL(d2); GEOBI_NOTNULL(idx); GEOBI_NOTNULL(ws);
+  hipStream_t s = as_stream(stream);
   const int want = parts_want(qptr, P);
   const int smax = max_part_slices(qptr, tptr, P);
   const int ld = (int)qptr[P];
@@ -453,10 +464,14 @@ int nearest_parts(const float* q, const float* t, const int64_t* qptr, const int
   return 0;
 }
 
-int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int64_t Q, int64_t V, int64_t F, float* dist,
-                     int32_t* face, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_nearest_triangle(const float* q, const float* verts, const int32_t* fv, int64_t Q, int64_t V, int64_t F,
+                           float* dist, int32_t* face, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(Q > V ? Q : V, 0);
+  GEOBI_SIZES(F, 0);
+  GEOBI_NOTNULL(q); GEOBI_NOTNULL(verts); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(dist); GEOBI_NOTNULL(ws);
   GEOBI_REQUIRE(Q > 0 && V > 0 && F > 0, "nearest_triangle: empty query set or mesh (Q = %lld, V = %lld, F = %lld)",
                 (long long)Q, (long long)V, (long long)F);
+  hipStream_t s = as_stream(stream);
   const Slicing c = choose_slices(Q, F, kTriQpl, kTriTile);
   Arena ar(ws, ws_bytes);
   const Partials p = carve_partials(ar, c.slices, Q);
@@ -468,18 +483,21 @@ int nearest_triangle(const float* q, const float* verts, const int32_t* fv, int6
   return 0;
 }
 
-size_t dist_summary_ws_bytes(int64_t n) { return carve_bytes([&](Arena& a) { carve_summary(a, summary_blocks(n)); }); }
+size_t geobi_dist_summary_ws_bytes(int64_t n) { return carve_bytes([&](Arena& a) { carve_summary(a, summary_blocks(n)); }); }
 
-int dist_summary(const float* dist, int64_t n, double* out, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_dist_summary(const float* dist, int64_t n, void* out, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(n, 0);
+  GEOBI_NOTNULL(dist); GEOBI_NOTNULL(out); GEOBI_NOTNULL(ws);
   GEOBI_REQUIRE(n > 0, "dist_summary: empty vector");
+  hipStream_t s = as_stream(stream);
   Arena ar(ws, ws_bytes);
   const int blocks = summary_blocks(n);
   double* partial = carve_summary(ar, blocks);
   GEOBI_WS_CHECK("dist_summary", ar, ws, ws_bytes);
   dist_summary_partial_kernel<<<blocks, kThreads, 0, s>>>(dist, n, partial);
-  dist_summary_final_kernel<<<1, 64, 0, s>>>(partial, blocks, out);
+  dist_summary_final_kernel<<<1, 64, 0, s>>>(partial, blocks, (double*)out);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

@@ -29,6 +29,7 @@
 //              arguments -a d^2 and -b |dn|^2 are never positive and formed from DIFFERENCES (translation-invariant).
 //   a          read from device memory (sigma_s comes from the mesh's mean centroid distance and never visits the host)
 #include "common.h"
+#include "../../include/geobi_hip.h"
 #include "feast_dev.h"
 
 namespace geobi {
@@ -122,14 +123,11 @@ __global__ __launch_bounds__(kThreads) void bnf_sweep_kernel(const float4* __res
   ndst[f] = len > 1e-6f * sw ? make_float4(sx / len, sy / len, sz / len, 0.f) : make_float4(ni.x, ni.y, ni.z, 0.f);
 }
 
-}  // namespace
+// one buffer of normals (the sweeps alternate between it and `out`) and the per-edge spatial factors
+struct BnfBuffers { float4* tmp; float* wsp; };
+BnfBuffers carve_bnf(Arena& a, int64_t F, int64_t E) { return {a.take<float4>(F), a.take<float>(E)}; }
 
-int bnf_prepare(const float* points, const int32_t* fv, int64_t F, float* rec_c, float* rec_n, hipStream_t s) {
-  if (F == 0) return 0;
-  bnf_prepare_kernel<<<cdiv(F, kThreads), kThreads, 0, s>>>(points, fv, (int)F, (float4*)rec_c, (float4*)rec_n);
-  GEOBI_LAUNCH_OK();
-  return 0;
-}
+}  // namespace
 
 // wsp [E]: the per-edge spatial factors, once per call (guided.hip's sweep reads the same array)
 int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
@@ -140,19 +138,38 @@ int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t
   return 0;
 }
 
-namespace {
-// one buffer of normals (the sweeps alternate between it and `out`) and the per-edge spatial factors
-struct BnfBuffers { float4* tmp; float* wsp; };
-BnfBuffers carve_bnf(Arena& a, int64_t F, int64_t E) { return {a.take<float4>(F), a.take<float>(E)}; }
-}  // namespace
+}  // namespace geobi
 
-size_t bnf_filter_ws_bytes(int64_t F, int64_t E) { return carve_bytes([&](Arena& a) { carve_bnf(a, F, E); }); }
+using namespace geobi;
 
-int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
-               const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" {
+
+int geobi_bnf_prepare(const float* points, const int32_t* fv, int64_t F, int64_t V, float* rec_c, float* rec_n,
+                      void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  if (F == 0) return 0;
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(rec_c); GEOBI_NOTNULL(rec_n);
+  hipStream_t s = as_stream(stream);
+  if (F == 0) return 0;
+  bnf_prepare_kernel<<<cdiv(F, kThreads), kThreads, 0, s>>>(points, fv, (int)F, (float4*)rec_c, (float4*)rec_n);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+size_t geobi_bnf_filter_ws_bytes(int64_t F, int64_t E) { return carve_bytes([&](Arena& a) { carve_bnf(a, F, E); }); }
+
+int geobi_bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, const int32_t* col, int64_t F,
+                     int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, void* ws, size_t ws_bytes,
+                     void* stream) {
+  GEOBI_SIZES(F, E);
+  if (F == 0) return 0;
+  GEOBI_NOTNULL(rec_c); GEOBI_NOTNULL(rec_n); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(inv2ss); GEOBI_NOTNULL(out);
+  GEOBI_NOTNULL(ws);
+  if (E > 0) GEOBI_NOTNULL(col);
   GEOBI_REQUIRE(n_sweeps >= 0, "bnf_filter: n_sweeps = %d (not negative)", n_sweeps);
   GEOBI_REQUIRE(inv2sr >= 0.f && inv2sr <= 3.0e38f, "bnf_filter: inv2sr = %g (finite and not negative)", (double)inv2sr);
   GEOBI_REQUIRE(out != rec_n && out != rec_c, "bnf_filter: out aliases a record array");
+  hipStream_t s = as_stream(stream);
   if (F == 0) return 0;
   if (n_sweeps == 0) {
     GEOBI_HIP(hipMemcpyAsync(out, rec_n, (size_t)F * sizeof(float4), hipMemcpyDeviceToDevice, s));
@@ -173,4 +190,4 @@ int bnf_filter(const float* rec_c, const float* rec_n, const int32_t* rowptr, co
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

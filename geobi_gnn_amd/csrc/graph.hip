@@ -9,6 +9,7 @@
 // (/root/reference/code/net_util.py:163).
 #include "common.h"
 #include "rocprim_temp.h"
+#include "../../include/geobi_hip.h"
 
 #include <cstring>
 
@@ -119,13 +120,33 @@ SortBuffers carve_sort(Arena& a, int64_t E) {
 
 }  // namespace
 
-size_t csr_ws_bytes(int64_t E, int64_t N) {
+// executor.hip calls it too: the one launcher of this unit with a prototype in common.h
+int csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int32_t* col, int64_t E, int32_t* pos_rev,
+                      int32_t* flag, hipStream_t s) {
+  if (flag != nullptr) GEOBI_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+  if (E <= 0) return 0;
+  reverse_index_kernel<<<cdiv(E, 256), 256, 0, s>>>(rowptr, row, col, E, pos_rev, flag);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_csr_ws_bytes(int64_t E, int64_t N) {
   (void)N;
   return carve_bytes([&](Arena& a) { carve_sort(a, E); });
 }
 
-int csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, int drop_self, int32_t* rowptr,
-                 int32_t* col, int32_t* eid, int32_t* bad, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, int drop_self, int32_t* rowptr,
+                       int32_t* col, int32_t* eid, int32_t* bad, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(N, E);
+  GEOBI_NOTNULL(rowptr);
+  if (E > 0) { GEOBI_NOTNULL(seg); GEOBI_NOTNULL(nbr); GEOBI_NOTNULL(col); GEOBI_NOTNULL(eid); }
+  hipStream_t s = as_stream(stream);
   GEOBI_REQUIRE(N >= 0 && E >= 0 && N < (1ll << 31) && E < (1ll << 31), "csr_from_coo: sizes out of int32 range");
   if (bad != nullptr) GEOBI_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
   if (E == 0) {
@@ -149,20 +170,15 @@ int csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, i
   return 0;
 }
 
-int csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int32_t* col, int64_t E, int32_t* pos_rev,
-                      int32_t* flag, hipStream_t s) {
-  if (flag != nullptr) GEOBI_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
-  if (E <= 0) return 0;
-  reverse_index_kernel<<<cdiv(E, 256), 256, 0, s>>>(rowptr, row, col, E, pos_rev, flag);
-  GEOBI_LAUNCH_OK();
-  return 0;
-}
-
 // Transposed CSR of a CSR whose valid edge count lives on the device (rowptr[N]); `Ecap` is the
 // allocated length of col.  pos_t[e_t] = position of that edge in the input CSR; inv_pos[e] =
 // position of input edge e in the transposed CSR.
-int csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t Ecap, int32_t* rowptr_t,
-                  int32_t* col_t, int32_t* pos_t, int32_t* inv_pos, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t Ecap, int32_t* rowptr_t,
+                        int32_t* col_t, int32_t* pos_t, int32_t* inv_pos, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(N, Ecap);
+  GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(rowptr_t);
+  if (Ecap > 0) { GEOBI_NOTNULL(col); GEOBI_NOTNULL(col_t); GEOBI_NOTNULL(pos_t); }
+  hipStream_t s = as_stream(stream);
   if (Ecap == 0) {
     GEOBI_HIP(hipMemsetAsync(rowptr_t, 0, sizeof(int32_t) * (N + 1), s));
     return 0;
@@ -190,8 +206,18 @@ int csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t 
   return 0;
 }
 
+int geobi_csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int32_t* col, int64_t E,
+                            int32_t* pos_rev, int32_t* flag, void* stream) {
+  GEOBI_SIZES(0, E);
+  GEOBI_NOTNULL(rowptr);                         // flag may be NULL: the caller knows the graph is symmetric
+  if (E > 0) { GEOBI_NOTNULL(row); GEOBI_NOTNULL(col); GEOBI_NOTNULL(pos_rev); }
+  return csr_reverse_index(rowptr, row, col, E, pos_rev, flag, as_stream(stream));
+}
+
+}  // extern "C"
 
 // ---------------------------------------------------------------- batched union copy (geobi_concat32)
+namespace geobi {
 namespace {
 constexpr int kMaxSegs = 96;
 struct ConcatJob {

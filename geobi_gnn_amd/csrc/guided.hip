@@ -36,6 +36,7 @@
 //   sweep      gnf_sweep_kernel: filter.hip's sweep with the range term on g; the per-edge spatial factor is the one
 //              bnf_spatial_factors writes once per call
 #include "common.h"
+#include "../../include/geobi_hip.h"
 #include "feast_dev.h"
 
 namespace geobi {
@@ -261,8 +262,7 @@ __global__ __launch_bounds__(kThreads) void gnf_sweep_kernel(const float4* __res
   ndst[f] = len > 1e-6f * sw ? make_float4(sx / len, sy / len, sz / len, 0.f) : make_float4(ni.x, ni.y, ni.z, 0.f);
 }
 
-}  // namespace
-
+// the two launchers gnf_filter shares with their own entry points
 int gnf_edge_flags(const int32_t* fv, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E, uint8_t* flags,
                    hipStream_t s) {
   if (F == 0 || E == 0) return 0;
@@ -280,23 +280,53 @@ int gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* r
   return 0;
 }
 
-namespace {
 // one buffer of normals (the sweeps alternate between it and `out`), the per-edge spatial factors and edge-pair flags,
 // and per face H, the patch means and the guidance normals
 struct GnfBuffers { float4 *tmp, *pmean, *g; float *H, *wsp; uint8_t* flags; };
 GnfBuffers carve_gnf(Arena& a, int64_t F, int64_t E) {
   return {a.take<float4>(F), a.take<float4>(F), a.take<float4>(F), a.take<float>(F), a.take<float>(E), a.take<uint8_t>(E)};
 }
+
 }  // namespace
 
-size_t gnf_filter_ws_bytes(int64_t F, int64_t E) { return carve_bytes([&](Arena& a) { carve_gnf(a, F, E); }); }
+}  // namespace geobi
 
-int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
-               int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out, void* ws,
-               size_t ws_bytes, hipStream_t s) {
+using namespace geobi;
+
+extern "C" {
+
+int geobi_gnf_edge_flags(const int32_t* fv, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E, uint8_t* flags,
+                         void* stream) {
+  GEOBI_SIZES(F, E);
+  if (F == 0 || E == 0) return 0;
+  GEOBI_NOTNULL(fv); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(col); GEOBI_NOTNULL(flags);
+  return gnf_edge_flags(fv, rowptr, col, F, E, flags, as_stream(stream));
+}
+
+int geobi_gnf_patch_measure(const float* rec_c, const float* normals, const int32_t* rowptr, const int32_t* col,
+                            const uint8_t* flags, int64_t F, int64_t E, float* H, void* stream) {
+  GEOBI_SIZES(F, E);
+  if (F == 0) return 0;
+  GEOBI_NOTNULL(rec_c); GEOBI_NOTNULL(normals); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(H);
+  if (E > 0) { GEOBI_NOTNULL(col); GEOBI_NOTNULL(flags); }
+  if ((const float*)H == rec_c || (const float*)H == normals) return set_error("%s: H aliases an input", __func__);
+  return gnf_patch_measure(rec_c, normals, rowptr, col, flags, F, H, nullptr, as_stream(stream));
+}
+
+size_t geobi_gnf_filter_ws_bytes(int64_t F, int64_t E) { return carve_bytes([&](Arena& a) { carve_gnf(a, F, E); }); }
+
+int geobi_gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const int32_t* rowptr, const int32_t* col,
+                     int64_t F, int64_t E, const float* inv2ss, float inv2sr, int n_sweeps, float* out, int32_t* sel_out,
+                     void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F, E);
+  if (F == 0) return 0;
+  GEOBI_NOTNULL(rec_c); GEOBI_NOTNULL(rec_n); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(inv2ss);
+  GEOBI_NOTNULL(out); GEOBI_NOTNULL(ws);
+  if (E > 0) GEOBI_NOTNULL(col);
   GEOBI_REQUIRE(n_sweeps >= 0, "gnf_filter: n_sweeps = %d (not negative)", n_sweeps);
   GEOBI_REQUIRE(inv2sr >= 0.f && inv2sr <= 3.0e38f, "gnf_filter: inv2sr = %g (finite and not negative)", (double)inv2sr);
   GEOBI_REQUIRE(out != rec_n && out != rec_c, "gnf_filter: out aliases a record array");
+  hipStream_t s = as_stream(stream);
   if (F == 0) return 0;
   if (n_sweeps == 0) {
     GEOBI_HIP(hipMemcpyAsync(out, rec_n, (size_t)F * sizeof(float4), hipMemcpyDeviceToDevice, s));
@@ -322,4 +352,4 @@ int gnf_filter(const float* rec_c, const float* rec_n, const int32_t* fv, const 
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

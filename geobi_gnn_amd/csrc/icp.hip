@@ -16,6 +16,7 @@
 // its state and its xt rows are not written again.  The part tables ride in the kernel arguments (PartTable), kMaxParts
 // parts per launch; the part pointers were checked once, by the entry point (parts_check).
 #include "common.h"
+#include "../../include/geobi_hip.h"
 #include "icp_solve.h"
 
 namespace geobi {
@@ -190,31 +191,52 @@ IcpBuffers carve_icp(Arena& a, int P) {
 
 }  // namespace
 
-size_t icp_ws_bytes(int P) { return carve_bytes([&](Arena& a) { carve_icp(a, P); }); }
+}  // namespace geobi
 
-int icp_init(double* state, int P, const double* init, hipStream_t s) {
-  icp_init_kernel<<<cdiv(P, 64), 64, 0, s>>>(state, P, init);
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_icp_ws_bytes(const int64_t* xptr, int P) {
+  (void)xptr;
+  return carve_bytes([&](Arena& a) { carve_icp(a, P); });
+}
+
+int geobi_icp_init(void* state, int P, const double* init, void* stream) {
+  GEOBI_REQUIRE(P >= 1, "%s: P = %d parts (at least one)", __func__, P);
+  GEOBI_NOTNULL(state);
+  hipStream_t s = as_stream(stream);
+  icp_init_kernel<<<cdiv(P, 64), 64, 0, s>>>((double*)state, P, init);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-int icp_apply(const float* x, const int64_t* xptr, int P, const double* state, int mode, float* out, hipStream_t s) {
+int geobi_icp_apply(const float* x, const int64_t* xptr, int P, const void* state, int mode, float* out, void* stream) {
+  GEOBI_TRY(parts_check(__func__, xptr, xptr, P));
+  GEOBI_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0: s x R + T, 1: s x R^T)", __func__, mode);
+  GEOBI_NOTNULL(x); GEOBI_NOTNULL(state); GEOBI_NOTNULL(out);
+  hipStream_t s = as_stream(stream);
   for (int base = 0; base < P; base += kMaxParts) {
     PartTable<int> tab;
     fill_parts(&tab, xptr, base, P);
     const int rows = tab.begin[tab.n] - tab.begin[0];
-    icp_transform_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(tab, base, x, state, mode, out);
+    icp_transform_kernel<<<cdiv(rows, kThreads), kThreads, 0, s>>>(tab, base, x, (const double*)state, mode, out);
   }
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-int icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P, int flags,
-             double relative_rmse_thr, double* state, float* xt, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* xptr, const int64_t* yptr, int P,
+                   int flags, double relative_rmse_thr, void* state, float* xt, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_TRY(parts_check(__func__, xptr, yptr, P));
+  GEOBI_REQUIRE((flags & ~3) == 0, "%s: flags %d (bit 0 estimate_scale, bit 1 allow_reflection)", __func__, flags);
+  GEOBI_REQUIRE(relative_rmse_thr >= 0.0, "%s: relative_rmse_thr %g is negative", __func__, relative_rmse_thr);
+  GEOBI_NOTNULL(x); GEOBI_NOTNULL(y); GEOBI_NOTNULL(idx); GEOBI_NOTNULL(state); GEOBI_NOTNULL(xt); GEOBI_NOTNULL(ws);
+  hipStream_t s = as_stream(stream);
   Arena ar(ws, ws_bytes);
   const IcpBuffers b = carve_icp(ar, P);
   GEOBI_WS_CHECK("icp_step", ar, ws, ws_bytes);
-  double *partial = b.partial, *residual = b.residual;
+  double *st = (double*)state, *partial = b.partial, *residual = b.residual;
   for (int base = 0; base < P; base += kMaxParts) {
     IcpJob job;
     fill_parts(&job.x, xptr, base, P);
@@ -226,13 +248,13 @@ int icp_step(const float* x, const float* y, const int32_t* idx, const int64_t* 
       if (b > blocks) blocks = b;
     }
     const dim3 grid(blocks, job.x.n);
-    icp_moments_kernel<<<grid, kThreads, 0, s>>>(job, x, y, idx, state, partial);
-    icp_solve_kernel<<<1, 64, 0, s>>>(job, x, y, idx, flags, state, partial);
-    icp_apply_kernel<<<grid, kThreads, 0, s>>>(job, x, y, idx, state, xt, residual);
-    icp_finish_kernel<<<1, 64, 0, s>>>(job, relative_rmse_thr, state, residual);
+    icp_moments_kernel<<<grid, kThreads, 0, s>>>(job, x, y, idx, st, partial);
+    icp_solve_kernel<<<1, 64, 0, s>>>(job, x, y, idx, flags, st, partial);
+    icp_apply_kernel<<<grid, kThreads, 0, s>>>(job, x, y, idx, st, xt, residual);
+    icp_finish_kernel<<<1, 64, 0, s>>>(job, relative_rmse_thr, st, residual);
   }
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

@@ -8,6 +8,7 @@
 // Integer results are exact; the graphs come out sorted and duplicate-free by construction (each node
 // repeatedly selects the smallest not-yet-emitted neighbour of its 1-ring), no global sort.
 #include "common.h"
+#include "../../include/geobi_hip.h"
 
 namespace geobi {
 
@@ -258,14 +259,23 @@ double* carve_partials(Arena& a, size_t n_parts) { return a.take<double>(n_parts
 
 }  // namespace
 
-size_t vertex_faces_ws_bytes(int64_t F, int64_t V) {
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_vertex_faces_ws_bytes(int64_t F, int64_t V) {
   (void)F;
   return carve_bytes([&](Arena& a) { carve_counts(a, V, true); });
 }
 
-int vertex_faces(const int32_t* fv, int64_t F, int64_t V, int32_t* rowptr, int32_t* list, void* ws, size_t ws_bytes,
-                 hipStream_t s) {
+int geobi_vertex_faces(const int32_t* fv, int64_t F, int64_t V, int32_t* rowptr, int32_t* list, void* ws,
+                       size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(fv); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(list); GEOBI_NOTNULL(ws);
   GEOBI_REQUIRE(F >= 0 && V > 0, "vertex_faces: empty mesh");
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   const CountBuffers c = carve_counts(a, V, true);
   GEOBI_WS_CHECK("vertex_faces", a, ws, ws_bytes);
@@ -284,14 +294,20 @@ int vertex_faces(const int32_t* fv, int64_t F, int64_t V, int32_t* rowptr, int32
   return 0;
 }
 
-int vf_padded(const int32_t* rowptr, const int32_t* list, int64_t V, int maxval, int32_t* vf, hipStream_t s) {
+int geobi_vf_padded(const int32_t* rowptr, const int32_t* list, int64_t V, int maxval, int32_t* vf, void* stream) {
+  GEOBI_SIZES(V, 0);
+  GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(list); GEOBI_NOTNULL(vf);
+  hipStream_t s = as_stream(stream);
   if (V <= 0 || maxval <= 0) return 0;
   vf_pad_kernel<<<cdiv(V * maxval, 256), 256, 0, s>>>(rowptr, list, (int)V, maxval, vf);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-int max_degree(const int32_t* rowptr, int64_t N, int32_t* out, hipStream_t s) {
+int geobi_max_degree(const int32_t* rowptr, int64_t N, int32_t* out, void* stream) {
+  GEOBI_SIZES(N, 0);
+  GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(out);
+  hipStream_t s = as_stream(stream);
   GEOBI_HIP(hipMemsetAsync(out, 0, sizeof(int), s));
   if (N <= 0) return 0;
   max_degree_kernel<<<cdiv(N, 256), 256, 0, s>>>(rowptr, (int)N, out);
@@ -299,8 +315,12 @@ int max_degree(const int32_t* rowptr, int64_t N, int32_t* out, hipStream_t s) {
   return 0;
 }
 
-int mesh_normals(const float* points, const int32_t* fv, int64_t F, int64_t V, const int32_t* rowptr,
-                 const int32_t* list, float* fnormal, float* centroid, float* vnormal, hipStream_t s) {
+int geobi_mesh_normals(const float* points, const int32_t* fv, int64_t F, int64_t V, const int32_t* rowptr,
+                       const int32_t* list, float* fnormal, float* centroid, float* vnormal, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(fnormal); GEOBI_NOTNULL(centroid);
+  if (vnormal != nullptr) { GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(list); }
+  hipStream_t s = as_stream(stream);
   if (F > 0) {
     face_geometry_kernel<<<cdiv(F, 256), 256, 0, s>>>(points, fv, (int)F, fnormal, centroid);
     GEOBI_LAUNCH_OK();
@@ -312,12 +332,15 @@ int mesh_normals(const float* points, const int32_t* fv, int64_t F, int64_t V, c
   return 0;
 }
 
-size_t ring_graph_ws_bytes(int64_t n_nodes) { return carve_bytes([&](Arena& a) { carve_counts(a, n_nodes, false); }); }
+size_t geobi_ring_graph_ws_bytes(int64_t n_nodes) { return carve_bytes([&](Arena& a) { carve_counts(a, n_nodes, false); }); }
 
-int ring_graph_count(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list, int64_t n_nodes,
-                     int32_t* rowptr_g, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_ring_graph_count(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list,
+                           int64_t n_nodes, int32_t* rowptr_g, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(n_nodes, 0);
+  GEOBI_NOTNULL(fv); GEOBI_NOTNULL(rowptr_vf); GEOBI_NOTNULL(list); GEOBI_NOTNULL(rowptr_g); GEOBI_NOTNULL(ws);
   GEOBI_REQUIRE(kind == 0 || kind == 1, "ring_graph: kind is 0 (vertex graph) or 1 (facet graph)");
   GEOBI_REQUIRE(n_nodes > 0, "ring_graph: empty");
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   const CountBuffers c = carve_counts(a, n_nodes, false);
   GEOBI_WS_CHECK("ring_graph_count", a, ws, ws_bytes);
@@ -332,9 +355,12 @@ int ring_graph_count(int kind, const int32_t* fv, const int32_t* rowptr_vf, cons
   return 0;
 }
 
-int ring_graph_fill(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list, int64_t n_nodes,
-                    const int32_t* rowptr_g, int32_t* col, hipStream_t s) {
+int geobi_ring_graph_fill(int kind, const int32_t* fv, const int32_t* rowptr_vf, const int32_t* list,
+                          int64_t n_nodes, const int32_t* rowptr_g, int32_t* col, void* stream) {
+  GEOBI_SIZES(n_nodes, 0);
+  GEOBI_NOTNULL(fv); GEOBI_NOTNULL(rowptr_vf); GEOBI_NOTNULL(list); GEOBI_NOTNULL(rowptr_g); GEOBI_NOTNULL(col);
   GEOBI_REQUIRE(kind == 0 || kind == 1, "ring_graph: kind is 0 (vertex graph) or 1 (facet graph)");
+  hipStream_t s = as_stream(stream);
   if (n_nodes <= 0) return 0;
   const int blocks = cdiv(n_nodes, 128);
   if (kind == 0)
@@ -345,10 +371,15 @@ int ring_graph_fill(int kind, const int32_t* fv, const int32_t* rowptr_vf, const
   return 0;
 }
 
-size_t calc_weight_ws_bytes() { return calc_weight_parts_ws_bytes(1); }
+size_t geobi_calc_weight_ws_bytes(void) { return geobi_calc_weight_parts_ws_bytes(1); }
 
-int calc_weight(const float* pos, const float* normal, const int32_t* row, const int32_t* col, int64_t E,
-                int64_t extra_zero_edges, float* w, float* mean_len, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_calc_weight(const float* pos, const float* normal, const int32_t* row, const int32_t* col, int64_t E,
+                      int64_t extra_zero_edges, float* w, float* mean_len, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(0, E);
+  GEOBI_NOTNULL(pos); GEOBI_NOTNULL(ws);
+  if (E > 0) { GEOBI_NOTNULL(row); GEOBI_NOTNULL(col); }
+  if (w != nullptr) GEOBI_NOTNULL(normal);
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   double* partial = carve_partials(a, 1);
   GEOBI_WS_CHECK("calc_weight", a, ws, ws_bytes);
@@ -366,13 +397,18 @@ int calc_weight(const float* pos, const float* normal, const int32_t* row, const
   return 0;
 }
 
-size_t calc_weight_parts_ws_bytes(int n_parts) {
+size_t geobi_calc_weight_parts_ws_bytes(int n_parts) {
   return carve_bytes([&](Arena& a) { carve_partials(a, n_parts > 0 ? n_parts : 1); });
 }
 
-int calc_weight_parts(const float* pos, const float* normal, const int32_t* rowptr, const int32_t* row, const int32_t* col,
-                      int64_t E, const int32_t* node_ptr, int n_parts, float* w, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_calc_weight_parts(const float* pos, const float* normal, const int32_t* rowptr, const int32_t* row,
+                            const int32_t* col, int64_t E, const int32_t* node_ptr, int n_parts, float* w, void* ws,
+                            size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(0, E);
+  GEOBI_NOTNULL(pos); GEOBI_NOTNULL(normal); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(node_ptr); GEOBI_NOTNULL(ws);
+  if (E > 0) { GEOBI_NOTNULL(row); GEOBI_NOTNULL(col); GEOBI_NOTNULL(w); }
   GEOBI_REQUIRE(n_parts > 0 && n_parts <= 4096, "calc_weight_parts: 1 .. 4096 parts (got %d)", n_parts);
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   double* partial = carve_partials(a, n_parts);
   GEOBI_WS_CHECK("calc_weight_parts", a, ws, ws_bytes);
@@ -384,4 +420,4 @@ int calc_weight_parts(const float* pos, const float* normal, const int32_t* rowp
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

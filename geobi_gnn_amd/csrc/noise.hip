@@ -24,6 +24,7 @@
 // LDS.  ALU-bound (ten rounds, two logs, two sincos) at 12-24 bytes in and 12 bytes out per vertex.  `out` may alias
 // `points`: a thread reads its own row before it writes it and touches no other.
 #include "common.h"
+#include "../../include/geobi_hip.h"
 #include "philox.h"
 
 #include <math.h>
@@ -74,13 +75,23 @@ __global__ __launch_bounds__(kThreads) void mesh_noise_kernel(const float* point
 
 }  // namespace
 
-int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction, float fraction,
-               uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, hipStream_t s) {
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+int geobi_mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma, int kind, int direction,
+                     float fraction, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out, void* stream) {
+  GEOBI_SIZES(V, 0);
+  if (V == 0) return 0;
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(out);
   GEOBI_REQUIRE(kind == 0 || kind == 1, "mesh_noise: kind = %d (0 gaussian, 1 impulsive)", kind);
   GEOBI_REQUIRE(direction == 0 || direction == 1, "mesh_noise: direction = %d (0 normal, 1 random)", direction);
   GEOBI_REQUIRE(direction == 1 || vnormal != nullptr, "mesh_noise: vnormal is NULL (direction 0 moves along the vertex normal)");
   GEOBI_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, "mesh_noise: sigma = %g (finite and not negative)", (double)sigma);
   GEOBI_REQUIRE(fraction >= 0.f && fraction <= 1.f, "mesh_noise: fraction = %g outside [0, 1]", (double)fraction);
+  hipStream_t s = as_stream(stream);
   if (V == 0) return 0;
   int blocks = cdiv(V, kThreads);
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;
@@ -91,4 +102,4 @@ int mesh_noise(const float* points, const float* vnormal, int64_t V, float sigma
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

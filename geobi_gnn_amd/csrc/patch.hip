@@ -8,6 +8,7 @@
 // slot numbers (patch_grow_kernel).  Its sequential statement lives with the test infrastructure (oracle/oracle_c.c).
 
 #include "common.h"
+#include "../../include/geobi_hip.h"
 
 namespace geobi {
 
@@ -433,27 +434,44 @@ __global__ __launch_bounds__(kGrowThreads) void patch_grow_kernel(
   }
 }
 
+struct SubmeshBuffers { int *first, *flag, *rank; SubWs temp; };
+SubmeshBuffers carve_submesh(Arena& a, int64_t n_sel, int64_t V) {
+  return {a.take<int>(V), a.take<int>(3 * n_sel + 1), a.take<int>(3 * n_sel + 1), a.take_ws(scan_ws_bytes(3 * n_sel + 1))};
+}
+
 }  // namespace
 
-size_t patch_grow_state_ints(int64_t F, int64_t V) { return (size_t)2 * (size_t)F + (size_t)V + 8; }
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_patch_grow_state_ints(int64_t F, int64_t V) { return (size_t)2 * (size_t)F + (size_t)V + 8; }
 
 // state (int32): [stamp F | visited F | vertex stamp V | seed, patches, unvisited, error, ...]
-int patch_grow_init(int32_t* state, int64_t F, int64_t V, const float* d2, hipStream_t s) {
+int geobi_patch_grow_init(int32_t* state, int64_t F, int64_t V, const float* d2, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(state); GEOBI_NOTNULL(d2);
   GEOBI_REQUIRE(F > 0 && V > 0, "patch_grow_init: empty mesh");
+  hipStream_t s = as_stream(stream);
   GEOBI_HIP(hipMemsetAsync(state, 0, sizeof(int) * ((size_t)2 * F + V + 8), s));      // no patch has id 0
   patch_grow_init_kernel<<<1, kGrowThreads, 0, s>>>(d2, (int)F, state + F, state + 2 * F + V);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
-int patch_grow(const int32_t* fv, const int32_t* vf, int maxval, int64_t F, int64_t V, const float* d2, int64_t seed,
-               int64_t neighbor_count, int64_t ring_count, int patch_id, int32_t* state, int32_t* sel_out, int32_t* n_out,
-               int32_t* mailbox, int pick_next, hipStream_t s) {
+int geobi_patch_grow(const int32_t* fv, const int32_t* vf, int maxval, int64_t F, int64_t V, const float* d2, int64_t seed,
+                     int64_t neighbor_count, int64_t ring_count, int patch_id, int32_t* state, int32_t* sel_out,
+                     int32_t* n_out, int32_t* mailbox, int pick_next, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(fv); GEOBI_NOTNULL(vf); GEOBI_NOTNULL(state); GEOBI_NOTNULL(sel_out);
   GEOBI_REQUIRE(F > 0 && V > 0 && maxval > 0, "patch_grow: empty mesh");
   GEOBI_REQUIRE(patch_id > 0, "patch_grow: patch ids start at 1 (0 marks a face no patch of this split holds)");
   GEOBI_REQUIRE(seed < F, "patch_grow: seed %lld outside [0, %lld)", (long long)seed, (long long)F);
   GEOBI_REQUIRE(maxval <= kGrowIter2 * kGrowThreads, "patch_grow: a vertex with %d incident faces", maxval);
   GEOBI_REQUIRE(pick_next == 0 || d2 != nullptr, "patch_grow: picking the next seed needs d2");
+  hipStream_t s = as_stream(stream);
   const int nc = (neighbor_count <= 0 || neighbor_count > F) ? (int)F : (int)neighbor_count;
   const int rc = (ring_count <= 0 || ring_count > F) ? (int)F : (int)ring_count;
   constexpr size_t lds = (size_t)kGrowLdsInts * sizeof(int);
@@ -472,20 +490,17 @@ int patch_grow(const int32_t* fv, const int32_t* vf, int maxval, int64_t F, int6
   return 0;
 }
 
-namespace {
-struct SubmeshBuffers { int *first, *flag, *rank; SubWs temp; };
-SubmeshBuffers carve_submesh(Arena& a, int64_t n_sel, int64_t V) {
-  return {a.take<int>(V), a.take<int>(3 * n_sel + 1), a.take<int>(3 * n_sel + 1), a.take_ws(scan_ws_bytes(3 * n_sel + 1))};
-}
-}  // namespace
-
-size_t submesh_ws_bytes(int64_t n_sel, int64_t V) {
+size_t geobi_submesh_ws_bytes(int64_t n_sel, int64_t V) {
   return carve_bytes([&](Arena& a) { carve_submesh(a, n_sel, V); });
 }
 
-int submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t V, int32_t* v_idx, int32_t* f_sub,
-            int32_t* count, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t V, int32_t* v_idx, int32_t* f_sub,
+                  int32_t* count, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(V > n_sel ? V : n_sel, 0);
+  GEOBI_NOTNULL(fv); GEOBI_NOTNULL(sel); GEOBI_NOTNULL(v_idx); GEOBI_NOTNULL(f_sub); GEOBI_NOTNULL(count);
+  GEOBI_NOTNULL(ws);
   GEOBI_REQUIRE(n_sel > 0 && V > 0, "submesh: empty selection");
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   const SubmeshBuffers b = carve_submesh(a, n_sel, V);
   GEOBI_WS_CHECK("submesh", a, ws, ws_bytes);
@@ -502,8 +517,12 @@ int submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t V, int
   return 0;
 }
 
-int patch_accumulate(const float* vert_p, const float* norm_p, const int32_t* v_idx, const int32_t* f_idx, int64_t nv,
-                     int64_t nf, float* Vp, float* Np, int32_t* sum_v, hipStream_t s) {
+int geobi_patch_accumulate(const float* vert_p, const float* norm_p, const int32_t* v_idx, const int32_t* f_idx,
+                           int64_t nv, int64_t nf, float* Vp, float* Np, int32_t* sum_v, void* stream) {
+  GEOBI_SIZES(nv > nf ? nv : nf, 0);
+  GEOBI_NOTNULL(vert_p); GEOBI_NOTNULL(norm_p); GEOBI_NOTNULL(v_idx); GEOBI_NOTNULL(f_idx); GEOBI_NOTNULL(Vp);
+  GEOBI_NOTNULL(Np); GEOBI_NOTNULL(sum_v);
+  hipStream_t s = as_stream(stream);
   const int64_t n = nv > nf ? nv : nf;
   if (n <= 0) return 0;
   patch_accumulate_kernel<<<cdiv(n, 256), 256, 0, s>>>(vert_p, norm_p, v_idx, f_idx, (int)nv, (int)nf, Vp, Np, sum_v);
@@ -511,8 +530,11 @@ int patch_accumulate(const float* vert_p, const float* norm_p, const int32_t* v_
   return 0;
 }
 
-int patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, int64_t F, float scale, float cx, float cy,
-                   float cz, hipStream_t s) {
+int geobi_patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, int64_t F, float scale, float cx,
+                         float cy, float cz, void* stream) {
+  GEOBI_SIZES(V > F ? V : F, 0);
+  GEOBI_NOTNULL(Vp); GEOBI_NOTNULL(Np); GEOBI_NOTNULL(sum_v);
+  hipStream_t s = as_stream(stream);
   const int64_t n = V > F ? V : F;
   if (n <= 0) return 0;
   patch_finalize_kernel<<<cdiv(n, 256), 256, 0, s>>>(Vp, Np, sum_v, (int)V, (int)F, scale, cx, cy, cz);
@@ -520,4 +542,4 @@ int patch_finalize(float* Vp, float* Np, const int32_t* sum_v, int64_t V, int64_
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

@@ -22,6 +22,7 @@
 // degrees are 6-7, a hub is only slower.  What the kernels read is clamped to the arrays (row ends to [0, E], column ids
 // to [0, V)): a foreign CSR gives wrong numbers, never a read outside.
 #include "common.h"
+#include "../../include/geobi_hip.h"
 
 #include <math.h>
 
@@ -163,11 +164,26 @@ float uniform_weight(int64_t n) { return n > 0 ? (float)(1.0 / (double)n) : 0.f;
 
 }  // namespace
 
-size_t mesh_reg_ws_bytes(int64_t V) { return carve_bytes([&](Arena& a) { carve_partials(a, V); }); }
+}  // namespace geobi
 
-int mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int32_t* rowptr, const int32_t* col, int64_t V,
-                 int64_t E, const float* w_lap, const float* w_edge, int terms, float* out, float* u, void* ws,
-                 size_t ws_bytes, hipStream_t s) {
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_mesh_reg_ws_bytes(int64_t V) {
+  return V < 0 || V > GEOBI_MAX_NODES ? 0 : carve_bytes([&](Arena& a) { carve_partials(a, V); });
+}
+
+int geobi_mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int32_t* rowptr, const int32_t* col,
+                       int64_t V, int64_t E, const float* w_lap, const float* w_edge, int terms, float* out, float* u,
+                       void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(V, E);
+  GEOBI_REQUIRE(V >= 1, "%s: V = %lld vertices (at least one)", __func__, (long long)V);
+  GEOBI_REQUIRE(terms >= 1 && terms <= 3, "%s: terms %d (bit 0 Laplacian, bit 1 edge length, at least one)", __func__, terms);
+  GEOBI_NOTNULL(vp); GEOBI_NOTNULL(v); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(out); GEOBI_NOTNULL(ws);
+  if (E > 0) GEOBI_NOTNULL(col);
+  if (terms & 1) GEOBI_NOTNULL(u);
+  hipStream_t s = as_stream(stream);
   Arena ar(ws, ws_bytes);
   double* partial = carve_partials(ar, V);
   GEOBI_WS_CHECK("mesh_reg_fwd", ar, ws, ws_bytes);
@@ -179,8 +195,15 @@ int mesh_reg_fwd(const float* vp, const float* v, const float* normal, const int
   return 0;
 }
 
-int mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const int32_t* col, int64_t V, int64_t E,
-                 const float* u, const float* w_edge, const float* gout, int terms, float* gvp, hipStream_t s) {
+int geobi_mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const int32_t* col, int64_t V, int64_t E,
+                       const float* u, const float* w_edge, const float* gout, int terms, float* gvp, void* stream) {
+  GEOBI_SIZES(V, E);
+  GEOBI_REQUIRE(V >= 1, "%s: V = %lld vertices (at least one)", __func__, (long long)V);
+  GEOBI_REQUIRE(terms >= 1 && terms <= 3, "%s: terms %d (bit 0 Laplacian, bit 1 edge length, at least one)", __func__, terms);
+  GEOBI_NOTNULL(vp); GEOBI_NOTNULL(v); GEOBI_NOTNULL(rowptr); GEOBI_NOTNULL(gout); GEOBI_NOTNULL(gvp);
+  if (E > 0) GEOBI_NOTNULL(col);
+  if (terms & 1) GEOBI_NOTNULL(u);
+  hipStream_t s = as_stream(stream);
   const int blocks = cdiv(V, kThreads);
   const float we_all = uniform_weight(E);
   if ((terms & kTermLap) && (terms & kTermEdge))
@@ -193,4 +216,4 @@ int mesh_reg_bwd(const float* vp, const float* v, const int32_t* rowptr, const i
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

@@ -24,6 +24,7 @@
 // thread per sample, grid-stride; plain vector stores, no atomics.  Corner ids are clamped into [0, V): a foreign table
 // never reads outside points.
 #include "common.h"
+#include "../../include/geobi_hip.h"
 #include "philox.h"
 #include "rocprim_temp.h"
 
@@ -158,14 +159,26 @@ WeightBuffers carve_weights(Arena& a, int64_t F) {
 
 }  // namespace
 
-int sample_table_entries() { return kTable; }
+}  // namespace geobi
 
-size_t sample_ws_bytes(int64_t F) {
-  return carve_bytes([&](Arena& a) { carve_weights(a, F); });
+using namespace geobi;
+
+extern "C" {
+
+int geobi_sample_table_entries(void) { return kTable; }
+
+size_t geobi_sample_ws_bytes(int64_t F) {
+  return F < 1 || F > GEOBI_MAX_NODES ? 0 : carve_bytes([&](Arena& a) { carve_weights(a, F); });
 }
 
-int sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, int64_t* weight, int64_t* cum,
-                   int32_t* exponent, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V, void* weight, void* cum,
+                         int32_t* exponent, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_REQUIRE(F >= 1 && V >= 1, "%s: F = %lld faces, V = %lld vertices (at least one of each)", __func__, (long long)F,
+                (long long)V);
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(weight); GEOBI_NOTNULL(cum); GEOBI_NOTNULL(exponent);
+  GEOBI_NOTNULL(ws);
+  hipStream_t s = as_stream(stream);
   Arena a(ws, ws_bytes);
   const WeightBuffers w = carve_weights(a, F);
   GEOBI_WS_CHECK("sample_weights", a, ws, ws_bytes);
@@ -183,9 +196,19 @@ int sample_weights(const float* points, const int32_t* fv, int64_t F, int64_t V,
   return 0;
 }
 
-int sample_surface(const float* points, const int32_t* fv, const int64_t* cum, int64_t F, int64_t V, int64_t N, int64_t first,
-                   uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points, int32_t* out_face, float* out_bary,
-                   hipStream_t s) {
+int geobi_sample_surface(const float* points, const int32_t* fv, const void* cum, int64_t F, int64_t V, int64_t N,
+                         int64_t first, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points,
+                         int32_t* out_face, float* out_bary, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_SIZES(N, 0);
+  GEOBI_REQUIRE(first >= 0 && first + N <= GEOBI_MAX_NODES, "%s: first = %lld, first + N = %lld outside [0, GEOBI_MAX_NODES = %d]",
+                __func__, (long long)first, (long long)(first + N), GEOBI_MAX_NODES);
+  GEOBI_REQUIRE(F >= 1 && V >= 1, "%s: F = %lld faces, V = %lld vertices (at least one of each)", __func__, (long long)F,
+                (long long)V);
+  if (N == 0) return 0;
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(cum); GEOBI_NOTNULL(out_points); GEOBI_NOTNULL(out_face);
+  GEOBI_NOTNULL(out_bary);
+  hipStream_t s = as_stream(stream);
   if (N == 0) return 0;
   int blocks = cdiv(N, kThreads);
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;
@@ -196,4 +219,4 @@ int sample_surface(const float* points, const int32_t* fv, const int64_t* cum, i
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"

@@ -331,14 +331,25 @@ int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_by
 
 }  // namespace
 
-size_t topo_ws_bytes(int64_t F, int64_t V) {
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_topo_ws_bytes(int64_t F, int64_t V) {
+  if (V < 0 || F < 0 || V > GEOBI_MAX_NODES || F > GEOBI_MAX_NODES) return 0;
   return carve_bytes([&](Arena& a) { carve_topo(a, F, V); });
 }
 
-int topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* faces_out,
-                int32_t* flip, int32_t* label, int32_t* counts, int32_t* rounds, float* stage_ms, void* ws, size_t ws_bytes,
-                hipStream_t s) {
+int geobi_topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds,
+                      int32_t* faces_out, int32_t* flip, int32_t* label, int32_t* counts, int32_t* rounds,
+                      float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(faces_out); GEOBI_NOTNULL(flip); GEOBI_NOTNULL(label); GEOBI_NOTNULL(counts);
+  GEOBI_NOTNULL(rounds);
   GEOBI_REQUIRE(max_rounds >= 1, "topo_orient: max_rounds = %d (at least 1)", max_rounds);
+  hipStream_t s = as_stream(stream);
   *rounds = 0;
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 3, s));
   if (F == 0) return 0;
@@ -360,11 +371,14 @@ int topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int64_t V
   return timer.finish();
 }
 
-int topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int min_component, int max_rounds,
-                    int32_t* comp, int32_t* state_out, int32_t* counts, int32_t* rounds, float* stage_ms, void* ws,
-                    size_t ws_bytes, hipStream_t s) {
+int geobi_topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int min_component,
+                          int max_rounds, int32_t* comp, int32_t* state_out, int32_t* counts, int32_t* rounds,
+                          float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(comp); GEOBI_NOTNULL(state_out); GEOBI_NOTNULL(counts); GEOBI_NOTNULL(rounds);
   GEOBI_REQUIRE(max_rounds >= 1, "topo_components: max_rounds = %d (at least 1)", max_rounds);
   GEOBI_REQUIRE(min_component >= 0, "topo_components: min_component = %d (0 or more)", min_component);
+  hipStream_t s = as_stream(stream);
   *rounds = 0;
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 3, s));
   if (F == 0) return 0;
@@ -386,9 +400,12 @@ int topo_components(const int32_t* faces, const int32_t* state, int64_t F, int64
   return timer.finish();
 }
 
-int topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
-                int32_t* rounds, void* ws, size_t ws_bytes, hipStream_t s) {
+int geobi_topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
+                      int32_t* rounds, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(counts); GEOBI_NOTNULL(rounds);
   GEOBI_REQUIRE(max_rounds >= 1, "topo_report: max_rounds = %d (at least 1)", max_rounds);
+  hipStream_t s = as_stream(stream);
   rounds[0] = rounds[1] = 0;
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 16, s));
   if (F == 0) return 0;
@@ -420,4 +437,4 @@ int topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V
   return 0;
 }
 
-}  // namespace geobi
+}  // extern "C"
