@@ -435,7 +435,8 @@ class TrainGroups(object):
     def __init__(self, net, bucket, loss_v='L1', loss_n='L1', v_scale=1.0, n_scale=1.0):
         if loss_v not in _KINDS or loss_n not in _KINDS:
             raise NotImplementedError("TrainGroups: L1 / L2 losses only; 'CD' and 'sided' (network.loss_v / loss_n, "
-                                      'parallel.batched_losses) are not supported by the group path')
+                                      'parallel.batched_losses) are not supported by the group path'
+                                      "; neither is the sampled 'SCD'")
         self.net, self.bucket = net, bucket
         self.kinds = (loss_v, loss_n)
         self.scales = (float(v_scale), float(n_scale))

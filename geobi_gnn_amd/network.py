@@ -188,7 +188,7 @@ class DualGNNFn(torch.autograd.Function):
 
 # ---------------------------------------------------------------------------------------
 _KIND = {'L1': 0, 'L2': 1}
-LOSS_V_NAMES = ('L1', 'L2', 'CD')
+LOSS_V_NAMES = ('L1', 'L2', 'CD', 'SCD')
 LOSS_N_NAMES = ('L1', 'L2', 'sided')
 
 
@@ -200,9 +200,12 @@ def check_loss_names(loss_v=None, loss_n=None):
         raise ValueError('loss_n: unknown norm %r (valid: %s)' % (loss_n, ', '.join(LOSS_N_NAMES)))
 
 
-def loss_v(vp, v, dis='L2', apply_icp=False):
+def loss_v(vp, v, dis='L2', apply_icp=False, faces=None, samples=10000, seed=0, draw=0, stream_id=0):
     """network.py:364-377: mean over vertices of sum_c |d| ('L1') or sum_c d^2 ('L2'); 'CD': the Chamfer distance
-    mean_i min_j |vp_i - v_j|^2 + mean_j min_i |vp_i - v_j|^2 (kaolin's chamfer_distance, :369-370; gradient to vp)."""
+    mean_i min_j |vp_i - v_j|^2 + mean_j min_i |vp_i - v_j|^2 (kaolin's chamfer_distance, :369-370; gradient to vp).
+    'SCD' (no counterpart in the reference): the same distance between ``samples`` points drawn by area on the predicted
+    surface and as many on the ground truth's (ops.sampled_chamfer_loss); it needs the face table ``faces`` [F, 3] the two
+    vertex sets share, and (seed, draw, stream_id) name the draw."""
     if apply_icp:
         raise NotImplementedError('ICP alignment needs pytorch3d, which the reference treats as optional')
     if dis == 'EMD':
@@ -210,6 +213,10 @@ def loss_v(vp, v, dis='L2', apply_icp=False):
     check_loss_names(loss_v=dis)
     if dis == 'CD':
         return ops.chamfer_loss(vp, v)
+    if dis == 'SCD':
+        if faces is None:
+            raise ValueError("loss_v: dis='SCD' needs the face table `faces` that vp and v share")
+        return ops.sampled_chamfer_loss(vp, v, faces, None, None, samples, seed, [stream_id], draw)
     return ops.row_loss(vp, v, _KIND[dis])
 
 

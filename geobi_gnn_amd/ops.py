@@ -594,6 +594,77 @@ def sided_loss(np_, n, fc_p, fc, fptr=None, weights=None):
     return row_loss(np_, ng, 0, weights, 1.0 if weights is not None else None)
 
 
+# ------------------------------------------------------- sampled surface Chamfer loss (SCD)
+class BaryPointsFn(Function):
+    """x_i = sum_k bary[i, k] * p[fv[face[i], k]] (geobi_bary_points: the sampler's own formula, so on the sampler's
+    (face, bary) its points come back bit for bit; a row with face = -1 is zeros).  face and bary are constants of the
+    gradient, which goes to p only: gp_v = the fp64 sum over the inverse lists vertex -> (sample, corner), built in the
+    backward (geobi_bary_keys, SegmentIndex, geobi_bary_points_bwd); no atomics, the same bits for every run."""
+
+    @staticmethod
+    def forward(ctx, p, fv, face, bary):
+        L.require_device(p, 'points')
+        for what, t in (('faces', fv), ('sample faces', face), ('barycentrics', bary)):
+            L.require_device(t, what)
+        p, bary = _f32c(p.detach()), _f32c(bary.detach())
+        fv, face = fv.to(torch.int32).contiguous(), face.to(torch.int32).contiguous()
+        n = face.shape[0]
+        if (p.dim() != 2 or p.shape[1] != 3 or fv.dim() != 2 or fv.shape[1] != 3 or face.dim() != 1
+                or tuple(bary.shape) != (n, 3)):
+            raise L.GeobiError('bary_points expects p [V,3], fv [F,3], face [n], bary [n,3], got %s, %s, %s, %s'
+                               % (tuple(p.shape), tuple(fv.shape), tuple(face.shape), tuple(bary.shape)))
+        if p.shape[0] == 0 or fv.shape[0] == 0:
+            raise L.GeobiError('bary_points: an empty mesh (V = %d, F = %d)' % (p.shape[0], fv.shape[0]))
+        out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+        L.call('geobi_bary_points', L.ptr(p), L.ptr(fv), L.ptr(face), L.ptr(bary), p.shape[0], fv.shape[0], n, L.ptr(out),
+               L.stream())
+        ctx.V = p.shape[0]
+        ctx.save_for_backward(fv, face, bary)
+        return out
+
+    @staticmethod
+    def backward(ctx, gx):
+        fv, face, bary = ctx.saved_tensors
+        gx = _f32c(gx)
+        n, V = face.shape[0], ctx.V
+        keys = torch.empty(3 * n, dtype=torch.int32, device=gx.device)
+        L.call('geobi_bary_keys', L.ptr(fv), L.ptr(face), V, fv.shape[0], n, L.ptr(keys), L.stream())
+        sidx = SegmentIndex(keys, V)                 # vertex -> the entries 3 i + k that it carries, ascending
+        gp = torch.empty((V, 3), dtype=torch.float32, device=gx.device)
+        L.call('geobi_bary_points_bwd', L.ptr(bary), L.ptr(gx), L.ptr(sidx.segptr), L.ptr(sidx.members), V, n, L.ptr(gp),
+               L.stream())
+        return gp, None, None, None
+
+
+def bary_points(p, fv, face, bary):
+    return BaryPointsFn.apply(p, fv, face, bary)
+
+
+def sampled_chamfer_loss(p, t, fv, fptr=None, vptr=None, n=10000, seed=0, stream_ids=None, draw=0, check=True):
+    """The Chamfer distance between n points drawn by area on each predicted SURFACE and n on each ground-truth surface
+    of a union batch (p, t [V,3]; fv [F,3] with global vertex ids; host pointers fptr [P+1] over the faces and vptr [P+1]
+    over the vertices, None: one mesh), averaged over the meshes.  The ground truth is drawn with draw 2 * draw, the
+    prediction with 2 * draw + 1 (the parities of mesheval.eval_sampled) and stream_ids[k] for mesh k (None: 0, 1, ...).
+    The predicted samples are bary_points(p, ...) of (face, bary) drawn on p.detach(): constants of the gradient, as the two
+    arg-min maps of chamfer_loss are; the gradient goes to p only.  check=False: fv is known to be in range (a dataset's
+    own table), no host read for it."""
+    from . import meshsample
+    pd, t = _points3(p, 'prediction'), _points3(t, 'target')
+    if t.shape != pd.shape:
+        raise L.GeobiError('sampled_chamfer_loss: prediction %s and target %s share one face table'
+                           % (tuple(pd.shape), tuple(t.shape)))
+    fp = _part_ptr(fptr, fv.shape[0], 'fptr')
+    _part_ptr(vptr, pd.shape[0], 'vptr')             # the face table holds global ids: vptr only has to cover the rows
+    P, n = len(fp) - 1, int(n)
+    if n < 1:
+        raise ValueError('sampled_chamfer_loss: n = %d samples per mesh (at least one)' % n)
+    sid = list(range(P)) if stream_ids is None else stream_ids
+    sp = meshsample.sample_surface_parts(pd, fv, fp, n, seed=seed, stream_ids=sid, draw=2 * int(draw) + 1, check=check)
+    st = meshsample.sample_surface_parts(t, fv, fp, n, seed=seed, stream_ids=sid, draw=2 * int(draw), check=False)
+    sptr = [k * n for k in range(P + 1)]
+    return chamfer_loss(bary_points(p, fv, sp.face, sp.bary), st.points, sptr, sptr)
+
+
 # ------------------------------------------------------- mesh regularisers (Laplacian / edge length)
 TERM_LAP, TERM_EDGE = 1, 2   # bits of `terms` (include/geobi_hip.h)
 

@@ -235,15 +235,22 @@ def _cpu_chamfer(p, t):
     return (p - t[a]).pow(2).sum(1).mean() + (p[b] - t).pow(2).sum(1).mean()
 
 
-def batched_losses(vp, npred, data_v, data_f, loss_v='L1', loss_n='L1'):
+def batched_losses(vp, npred, data_v, data_f, loss_v='L1', loss_n='L1', sampling=None):
     """Per-mesh mean losses averaged over the meshes of a disjoint-union batch.
 
     Identical to accumulating ``loss / batch_size`` over sequential single-mesh steps
     (train_dual.py:204-212).  Without ``mesh_ptr`` it is the plain per-node mean.  On the MI355X
     this is the fused reduction kernel (geobi_row_loss_*), for 'CD' / 'sided' on top of the per-mesh search
-    (geobi_nearest_parts, geobi_chamfer_*); CPU tensors (gloo tests) use torch ops."""
+    (geobi_nearest_parts, geobi_chamfer_*); CPU tensors (gloo tests) use torch ops.
+
+    'SCD' (device only: the sampler has no CPU form) draws per mesh through the ``mesh_ptr`` of both bags over
+    ``data_f.fv_indices``; sampling = dict(n, seed, draw, stream_ids) names the draw (ops.sampled_chamfer_loss; missing
+    keys take its defaults)."""
     from . import network
     network.check_loss_names(loss_v, loss_n)
+    if loss_v == 'SCD' and not vp.is_cuda:
+        raise ValueError("batched_losses: loss_v = 'SCD' draws its points with the surface sampler, which runs on the device "
+                         'only (no CPU fallback); the tensors are on %s' % vp.device)
     kinds = {'L1': 0, 'L2': 1}
     ptr_v, ptr_f = getattr(data_v, 'mesh_ptr', None), getattr(data_f, 'mesh_ptr', None)
     if vp.is_cuda:
@@ -251,6 +258,9 @@ def batched_losses(vp, npred, data_v, data_f, loss_v='L1', loss_n='L1'):
         wv, wn = _mesh_weights(data_v), _mesh_weights(data_f)
         if loss_v == 'CD':
             lv = ops.chamfer_loss(vp, data_v.y, ptr_v, ptr_v)
+        elif loss_v == 'SCD':
+            # the face table is the bag's own (union_batch_graphs offsets it with the vertices): no range check, no read
+            lv = ops.sampled_chamfer_loss(vp, data_v.y, data_f.fv_indices, ptr_f, ptr_v, check=False, **(sampling or {}))
         else:
             lv = ops.row_loss(vp, data_v.y, kinds[loss_v], wv, 1.0 if wv is not None else None)
         if loss_n == 'sided':

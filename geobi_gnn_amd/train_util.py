@@ -25,14 +25,26 @@ def non_negative_float(text):
     return value
 
 
+def loss_samples_arg(text):
+    """argparse type of --loss_samples: the sample counts the `sample` command takes, without its 0 (no loss from nothing)."""
+    value = int(text)
+    if not 1 <= value <= (1 << 24) - 1:
+        raise argparse.ArgumentTypeError('a number of samples is between 1 and 16 777 215, not %r' % text)
+    return value
+
+
 def add_training_flags(parser):
     """The optimiser / schedule / loss flags of train_dual.py:57-82, same names, types and defaults."""
     parser.add_argument('--loss_v', type=str, default='L1',
-                        help="vertex loss: L1, L2 (row by row against the ground truth) or CD (Chamfer distance: squared "
-                             'distance to the nearest ground-truth vertex and back, no correspondence needed)')
+                        help="vertex loss: L1, L2 (row by row against the ground truth), CD (Chamfer distance: squared "
+                             'distance to the nearest ground-truth vertex and back, no correspondence needed) or SCD (the '
+                             'same between --loss_samples points drawn by area on each of the two surfaces)')
     parser.add_argument('--loss_n', type=str, default='L1',
                         help='normal loss: L1, L2 (face by face) or sided (L1 against the normal of the ground-truth face '
                              'whose centroid is nearest to the predicted face)')
+    parser.add_argument('--loss_samples', type=loss_samples_arg, default=10000, metavar='N',
+                        help='--loss_v SCD: points drawn per mesh and side (default 10000, the vertex count of a 20 000-face '
+                             'patch: the pair work of CD); a draw depends on --seed, the epoch and the mesh, not on the batch')
     parser.add_argument('--loss_v_scale', type=float, default=1)
     parser.add_argument('--loss_n_scale', type=float, default=1)
     parser.add_argument('--loss_lap_scale', type=non_negative_float, default=0,
@@ -152,12 +164,14 @@ class EvalMeter(object):
                                float(error_f) * num_f, num_v, num_f)):
             self.sums[i] += v
 
-    def add_prediction(self, vert_p, norm_p, data_v, data_f, loss_v='L1', loss_n='L1'):
+    def add_prediction(self, vert_p, norm_p, data_v, data_f, loss_v='L1', loss_n='L1', samples=10000, seed=0):
+        """'SCD' is evaluated with draw 0, stream 0 and ``seed``: the same points every epoch, so the numbers compare."""
         fc_p = fc = None
         if loss_n == 'sided':
             from .data_util import face_centroids
             fc_p, fc = face_centroids(vert_p, data_f.fv_indices), face_centroids(data_v.y, data_f.fv_indices)
-        self.add(network.loss_v(vert_p, data_v.y, loss_v), network.loss_n(norm_p, data_f.y, loss_n, fc_p, fc),
+        scd = dict(faces=data_f.fv_indices, samples=samples, seed=seed) if loss_v == 'SCD' else {}
+        self.add(network.loss_v(vert_p, data_v.y, loss_v, **scd), network.loss_n(norm_p, data_f.y, loss_n, fc_p, fc),
                  network.error_v(vert_p, data_v.y), network.error_n(norm_p, data_f.y),
                  data_v.y.shape[0], data_f.y.shape[0])
 

@@ -87,12 +87,22 @@ def train_tags(opt):
     return TRAIN_TAGS + tuple(tag for (tag, _), scale in zip(REG_TAGS, reg_scales(opt)) if scale != 0)
 
 
+def loss_sampling(opt, epoch, batch):
+    """What ``--loss_v SCD`` draws in a step, as parallel.batched_losses takes it (None for every other loss): seed =
+    opt.seed, draw = the epoch, the stream of a mesh = its index in the dataset -- a mesh's points depend on (seed, epoch,
+    which mesh) and never on the batch it lands in.  Options from before the flag existed: 10 000 points."""
+    if opt.loss_v != 'SCD':
+        return None
+    return dict(n=int(getattr(opt, 'loss_samples', 10000)), seed=int(opt.seed), draw=int(epoch),
+                stream_ids=[int(i) for i in batch])
+
+
 def train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=None, scalars=None, iteration=0):
     """One pass over ``samples`` (a DualDataset or a list of resident pairs) in parallel.shard_indices order (seed,
     epoch), ``opt.batch_size`` samples per step; the last, short batch still steps.  scalars: optional list that takes
     (iteration, device tensor of the train_tags(opt) values: the five TRAIN_TAGS, then the unscaled term of every
     regulariser that is on) per step -- nothing is read back here.  A regulariser (``opt.loss_lap_scale``,
-    ``opt.loss_edge_scale``) whose scale is 0 is not computed.
+    ``opt.loss_edge_scale``) whose scale is 0 is not computed.  ``opt.loss_v == 'SCD'`` draws as loss_sampling says.
     -> (iteration, loss of the last step as a device scalar)"""
     net.train()
     order = shard_indices(len(samples), 0, 1, seed=opt.seed, epoch=epoch)
@@ -105,7 +115,7 @@ def train_epoch(net, flat, optimizer, samples, opt, epoch, rotate=None, scalars=
             rotate_union(dv, df, rotate.matrices(len(batch)))
         flat.bucket.zero()
         vp, npred, _ = net((dv.shallow_copy(), df.shallow_copy()))
-        lv, ln = batched_losses(vp, npred, dv, df, opt.loss_v, opt.loss_n)
+        lv, ln = batched_losses(vp, npred, dv, df, opt.loss_v, opt.loss_n, sampling=loss_sampling(opt, epoch, batch))
         loss = network.dual_loss(lv, ln, opt.loss_v_scale, opt.loss_n_scale)
         loss, regs = add_regularisers(loss, vp, dv, lap_scale, edge_scale)
         loss.backward()
@@ -128,7 +138,8 @@ def evaluate(net, samples, opt):
         for i in range(len(samples)):
             a, b = samples[i]
             vp, npred, _ = net((a.shallow_copy(), b.shallow_copy()))
-            meter.add_prediction(vp, npred, a, b, opt.loss_v, opt.loss_n)
+            meter.add_prediction(vp, npred, a, b, opt.loss_v, opt.loss_n, samples=int(getattr(opt, 'loss_samples', 10000)),
+                                 seed=int(opt.seed or 0))
     return meter.result()
 
 

@@ -453,6 +453,44 @@ int geobi_sample_weights(const float* points, const int32_t* fv, int64_t F, int6
 int geobi_sample_surface(const float* points, const int32_t* fv, const void* cum, int64_t F, int64_t V, int64_t N,
                          int64_t first, uint64_t seed, uint32_t stream_id, uint32_t draw, float* out_points,
                          int32_t* out_face, float* out_bary, void* stream);
+/* The same for every mesh of a disjoint-union batch in one call: fv [F, 3] holds GLOBAL vertex ids into points [V, 3], the
+ * HOST pointer fptr [P + 1] cuts its rows into the P meshes (fptr[0] = 0, no empty part, F = fptr[P] <= GEOBI_MAX_NODES).
+ *   geobi_sample_weights_parts  every part gets its own dmax, its own exponent[p] (DEVICE int32 [P]) and its own inclusive
+ *                         scan: the rows fptr[p] .. fptr[p + 1] of weight and cum (DEVICE int64 [F]) hold exactly what
+ *                         geobi_sample_weights gives on mesh p alone.  cum is one scan over the union's weights (into the
+ *                         workspace) minus the scan's entry before the part's first row: integer sums are exact.
+ *                         ws: geobi_sample_parts_ws_bytes(F, P)
+ *   geobi_sample_surface_parts  N samples per part, row p * N + i is sample i of part p: the counter is (first + i,
+ *                         stream_id[p], draw, 2) with the HOST array stream_id [P], the key (seed lo, seed hi), the search
+ *                         runs over the part's rows of cum.  Rows p * N .. (p + 1) * N of out_bary and out_points
+ *                         ([P * N, 3]) equal, bit for bit, geobi_sample_surface on mesh p alone with stream_id[p] and the
+ *                         same seed, draw and first; out_face ([P * N]) is that face plus fptr[p], a row of fv.  A part
+ *                         whose total is 0: face -1 and zeros.  P * N and first + N <= GEOBI_MAX_NODES; N == 0 is a
+ *                         no-op.  Workgroups are formed per part (each stages its own part's table entries in LDS), the
+ *                         part table rides in the kernel arguments: more than 32 parts take several launches.            */
+size_t geobi_sample_parts_ws_bytes(int64_t F, int P);
+int geobi_sample_weights_parts(const float* points, const int32_t* fv, const int64_t* fptr, int P, int64_t V, void* weight,
+                               void* cum, int32_t* exponent, void* ws, size_t ws_bytes, void* stream);
+int geobi_sample_surface_parts(const float* points, const int32_t* fv, const void* cum, const int64_t* fptr, int P, int64_t V,
+                               int64_t N, int64_t first, uint64_t seed, const uint32_t* stream_id, uint32_t draw,
+                               float* out_points, int32_t* out_face, float* out_bary, void* stream);
+
+/* ---------------------------------------------------------------- points on faces (sampled Chamfer loss) ----
+ * The differentiable step from (face, barycentric) pairs, as the sampler writes them, to points and back to the vertices
+ * (points [V, 3], fv [F, 3], face [n], bary [n, 3]; F, V >= 1; F, V, n <= GEOBI_MAX_NODES; ids read through fv are clamped
+ * to points).  face and bary are constants of the gradient.
+ *   geobi_bary_points      out[i] = fma(b2, c, fma(b1, b, b0 * a)) per coordinate, (a, b, c) = points[fv[face[i]]]: the
+ *                          sampler's formula, so its out_points come back bit for bit.  face[i] outside [0, F): zeros.
+ *   geobi_bary_keys        keys[3 i + k] = fv[face[i]][k] (int32 [3 n]); V for a row whose face is outside [0, F).
+ *                          (segptr [V + 1], members [3 n]) = geobi_segment_csr(keys, 3 n, nseg = V): the key V is in no list.
+ *   geobi_bary_points_bwd  gp[v] = sum over the entries e = 3 i + k of v's list, ascending, of bary[e] * gx[i] ([n, 3]),
+ *                          products and sum in fp64, rounded once.  Every row of gp [V, 3] is written exactly once (zeros
+ *                          for a vertex no sample touches); no atomics: the same bits for every run.                      */
+int geobi_bary_points(const float* points, const int32_t* fv, const int32_t* face, const float* bary, int64_t V, int64_t F,
+                      int64_t n, float* out, void* stream);
+int geobi_bary_keys(const int32_t* fv, const int32_t* face, int64_t V, int64_t F, int64_t n, int32_t* keys, void* stream);
+int geobi_bary_points_bwd(const float* bary, const float* gx, const int32_t* segptr, const int32_t* members, int64_t V,
+                          int64_t n, float* gp, void* stream);
 
 /* ---------------------------------------------------------------- bilateral normal filter ----
  * The reference has NO call site for this: its scratch code only lists result folders of classical filters beside its own
