@@ -14,6 +14,8 @@
   python -m geobi_gnn_amd sample --data_dir DIR [--out_dir DIR/samples] --n N [--seed 1] [--normals] [--gpu -1]
   python -m geobi_gnn_amd eval ... --free --samples N [--seed 1]
   python -m geobi_gnn_amd align ... --samples N [--seed 1]
+  python -m geobi_gnn_amd subdivide --data_dir DIR [--out_dir DIR/subdivided] [--levels 1] [--scheme midpoint|loop]
+  python -m geobi_gnn_amd subdivide --data_dir DIR (--max_edge L | --max_edge_diag R) [--max_rounds 16]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -39,7 +41,11 @@ vertex counts or face tables differ (ErrorInfo_free.txt).  `sample` (meshsample.
 area on the surface of every DIR/original/*.obj (or DIR/*.obj) as OUT/NAME.obj with `v` lines only (`--normals`: a `vn`
 line per point); `eval --free --samples N` also scores from such points of both surfaces (ErrorInfo_sampled.txt beside
 an unchanged ErrorInfo_free.txt), `align --samples N` aligns to the target's vertices followed by N points of its
-surface -- what a CAD target of a few large triangles needs.  All device work runs in this one process.
+surface -- what a CAD target of a few large triangles needs.  `subdivide` (meshsubdiv.py) makes every mesh denser:
+`--levels K` passes that split every edge (at its midpoint, or with `--scheme loop` by Loop's masks), or `--max_edge L` /
+`--max_edge_diag R` (L = R times the diagonal of the mesh's bounding box) rounds that split only the edges longer than L;
+with DIR/original present the refinement is planned on original/NAME.obj and applied to every noisy/NAME_n*.obj of equal
+size, which keeps the pairs in correspondence.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -403,6 +409,75 @@ def clean(opt):
     return 1 if failed or not files else 0
 
 
+def _subdivide_line(refined, V, F, out_file):
+    c = refined.counts
+    return ("V: %7d -> %7d,  F: %7d -> %7d,  edges: %d,  split: %d,  boundary: %d,  complex: %d,  passes: %d,  '%s'"
+            % (V, refined.points.shape[0], F, refined.faces.shape[0], c['edges'], c['split'], c['boundary_edges'],
+               c['complex_edges'], c['passes'], os.path.basename(out_file)))
+
+
+def bbox_diagonal(points):
+    """the diagonal of the bounding box of points [V, 3], in fp64 on the host (0 without points)"""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    return float(np.sqrt(((p.max(axis=0) - p.min(axis=0)) ** 2).sum())) if p.shape[0] else 0.0
+
+
+def subdivide(opt):
+    """Refine every mesh of a folder on the device (meshsubdiv), with the folders of `clean`: with DIR/original,
+    original/NAME.obj -> OUT/original/NAME.obj and the same plan on every noisy/NAME_n*.obj of the same size -> OUT/noisy/;
+    else DIR/*.obj -> OUT/NAME.obj."""
+    from . import meshio, meshsubdiv
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'subdivided')
+    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
+    paired = os.path.isdir(original_dir)
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
+    out_original = os.path.join(out_dir, 'original') if paired else out_dir
+    os.makedirs(out_original, exist_ok=True)
+    if paired:
+        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
+    mode = ('max_edge %g' % opt.max_edge if opt.max_edge is not None else
+            'max_edge %g of the diagonal' % opt.max_edge_diag if opt.max_edge_diag is not None else
+            '%s, levels %d' % (opt.scheme, opt.levels))
+    print('\nSubdivide, %s, %d files ...\n' % (mode, len(files)), flush=True)
+    failed = 0
+    for path in files:
+        name = os.path.basename(path)[:-4]
+        try:
+            points, faces = meshio.read_obj(path)
+            max_edge = opt.max_edge
+            if opt.max_edge_diag is not None:
+                max_edge = opt.max_edge_diag * bbox_diagonal(points)
+            refined = meshsubdiv.subdivide(points, faces, levels=opt.levels, scheme=opt.scheme, max_edge=max_edge,
+                                           max_rounds=opt.max_rounds, device=dev)
+            faces_out = refined.faces.cpu().numpy()
+            out_file = os.path.join(out_original, name + '.obj')
+            meshio.write_obj(out_file, refined.points.cpu().numpy(), faces_out)
+            print(_subdivide_line(refined, points.shape[0], faces.shape[0], out_file), flush=True)
+            if not paired:
+                continue
+            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
+                try:
+                    n_points, n_faces = meshio.read_obj(noisy)
+                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
+                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
+                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
+                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
+                    meshio.write_obj(out_file, meshsubdiv.apply(refined, n_points).cpu().numpy(), faces_out)
+                    print(_subdivide_line(refined, points.shape[0], faces.shape[0], out_file), flush=True)
+                except (ValueError, OSError) as e:
+                    failed += 1
+                    print('skipped: %s' % e, file=sys.stderr, flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d files skipped' % failed, file=sys.stderr)
+    return 1 if failed or not files else 0
+
+
 INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 'complex_edges', 'inconsistent_edges',
              'components', 'orient_components', 'nonorientable', 'would_flip', 'euler')
 
@@ -459,6 +534,20 @@ def _samples_arg(text):
     v = int(text)
     if not 0 <= v <= (1 << 24) - 1:
         raise argparse.ArgumentTypeError('a number of samples is between 0 and 16 777 215, not %r' % text)
+    return v
+
+
+def _positive_arg(text):
+    v = float(text)
+    if not (v > 0.0 and v < float('inf')):
+        raise argparse.ArgumentTypeError('a positive length, not %r' % text)
+    return v
+
+
+def _at_least_one_arg(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError('a whole number, at least 1, not %r' % text)
     return v
 
 
@@ -575,6 +664,22 @@ def build_parser():
     i.add_argument('--no_weld', action='store_true', help='keep every vertex apart')
     i.add_argument('--gpu', type=int, default=-1)
     i.set_defaults(fn=info)
+    u = sub.add_parser('subdivide', help='make every mesh denser on the device: midpoint or Loop passes, or split the edges '
+                                         'longer than a length')
+    u.add_argument('--data_dir', type=str, required=True, help='holds original/ (and noisy/), or the OBJ files themselves')
+    u.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/subdivided')
+    u.add_argument('--levels', type=_at_least_one_arg, default=1, action=_StoreGiven,
+                   help='uniform passes; each splits every edge and makes four faces of one')
+    u.add_argument('--scheme', type=str, default='midpoint', choices=['midpoint', 'loop'],
+                   help='midpoint: the surface stays as it is (default); loop: smoothed positions, edges that are not shared '
+                        'by exactly two faces are creases')
+    u.add_argument('--max_edge', type=_positive_arg, default=None, metavar='L',
+                   help='split only the edges longer than L, in rounds, until none is left')
+    u.add_argument('--max_edge_diag', type=_positive_arg, default=None, metavar='R',
+                   help="--max_edge as R times the diagonal of the mesh's bounding box")
+    u.add_argument('--max_rounds', type=_at_least_one_arg, default=16, help='with --max_edge*: rounds at most')
+    u.add_argument('--gpu', type=int, default=-1)
+    u.set_defaults(fn=subdivide)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)
@@ -605,6 +710,14 @@ def parse_args(argv=None):
             ap.error('align: --max_iter is at least 1, not %d' % opt.max_iter)
         if not opt.rmse_thr >= 0:
             ap.error('align: --rmse_thr is not negative, got %r' % opt.rmse_thr)
+    if opt.command == 'subdivide':
+        if opt.max_edge is not None and opt.max_edge_diag is not None:
+            ap.error('subdivide: --max_edge and --max_edge_diag exclude each other')
+        if opt.max_edge is not None or opt.max_edge_diag is not None:
+            if getattr(opt, 'levels_given', False):
+                ap.error('subdivide: --max_edge / --max_edge_diag run rounds until no edge is longer; --levels does not apply')
+            if opt.scheme == 'loop':
+                ap.error('subdivide: --max_edge / --max_edge_diag split at midpoints; --scheme loop does not apply')
     return opt
 
 

@@ -16,7 +16,9 @@
 //            component sizes by integer adds, the lanes of a wave that share a label first summed in the wave
 // Every value used as an index is a face index below F: keys only ever hold 2 * face + bit, links hold slot / 3.
 #include "common.h"
+#include "edge_table.h"
 #include "rocprim_temp.h"
+#include "stage_timer.h"
 #include "../../include/geobi_hip.h"
 
 namespace geobi {
@@ -25,29 +27,6 @@ namespace {
 
 constexpr int kT = 256;
 constexpr int kBatch = 8;            // rounds enqueued per read of the changed flags
-
-__device__ __forceinline__ bool face_included(const int* __restrict__ fv, const int* __restrict__ state, int f, int V,
-                                              int& a, int& b, int& c) {
-  a = fv[3 * (size_t)f]; b = fv[3 * (size_t)f + 1]; c = fv[3 * (size_t)f + 2];
-  const bool in_range = (unsigned)a < (unsigned)V && (unsigned)b < (unsigned)V && (unsigned)c < (unsigned)V;
-  return in_range && a != b && b != c && c != a && (state == nullptr || state[f] == kKept);
-}
-
-// the three edge slots of every face
-__global__ void topo_edges_kernel(const int* __restrict__ fv, const int* __restrict__ state, int F, int V,
-                                  uint64_t* __restrict__ keys, int* __restrict__ vals) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  int c[3];
-  const bool inc = face_included(fv, state, f, V, c[0], c[1], c[2]);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int a = c[k], b = c[(k + 1) % 3];
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    keys[3 * (size_t)f + k] = inc ? edge_key(lo, hi) : kNoEdge;
-    vals[3 * f + k] = (3 * f + k) << 1 | (a < b ? 0 : 1);
-  }
-}
 
 // per sorted position: the links of its slot.  olink[s] = (face << 1 | odd) or -1; clink[2s], clink[2s + 1] = the previous
 // and the next claimant (face << 1) or -1
@@ -257,7 +236,7 @@ TopoBuffers carve_topo(Arena& a, int64_t F, int64_t V) {
 
 int build_table(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, const TopoBuffers& b, hipStream_t s) {
   const int n = (int)F;
-  topo_edges_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, state, n, (int)V, b.k_in, b.v_in);
+  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, state, n, (int)V, b.k_in, b.v_in);
   GEOBI_LAUNCH_OK();
   size_t tb = b.sort_temp.bytes;
   GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
@@ -295,32 +274,6 @@ int run_rounds(const char* what, const int* links, int L, int64_t F, int max_rou
                        "the file works against the hooking)", what, max_rounds);
   }
 }
-
-// measurement only (tools/bench_topo.py): device events at the stage borders of one call, read after a wait for the last
-struct StageTimer {
-  float* out;
-  hipStream_t s;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  int n = 0;
-  StageTimer(float* out_ms, hipStream_t stream) : out(out_ms), s(stream) {}
-  ~StageTimer() {
-    for (hipEvent_t e : ev)
-      if (e != nullptr) (void)hipEventDestroy(e);
-  }
-  int mark() {
-    if (out == nullptr || n >= 4) return 0;
-    GEOBI_HIP(hipEventCreate(&ev[n]));
-    GEOBI_HIP(hipEventRecord(ev[n], s));
-    ++n;
-    return 0;
-  }
-  int finish() {
-    if (out == nullptr) return 0;
-    GEOBI_HIP(hipEventSynchronize(ev[n - 1]));
-    for (int k = 0; k + 1 < n; ++k) GEOBI_HIP(hipEventElapsedTime(out + k, ev[k], ev[k + 1]));
-    return 0;
-  }
-};
 
 int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, TopoBuffers& b) {
   Arena a(ws, ws_bytes);

@@ -12,7 +12,8 @@
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
  *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
  *     (reads its undecided counts through it), geobi_topo_orient / _components / _report (read the changed flags of
- *     their rounds through it), the whole-network
+ *     their rounds through it), geobi_subdiv_plan with stage_ms (waits for its own end; without it the plan is only
+ *     enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -752,6 +753,70 @@ int geobi_topo_components(const int32_t* faces, const int32_t* state, int64_t F,
                           float* stage_ms, void* ws, size_t ws_bytes, void* stream);
 int geobi_topo_report(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, int max_rounds, int32_t* counts,
                       int32_t* rounds, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- mesh refinement (midpoint, Loop, max-edge) ----
+ * Makes a triangle mesh denser; no counterpart in the reference, whose CAD shapes were tessellated in
+ * another tool.  The topology is integer-exact, positions go through ONE stated sequence of roundings (no contraction into
+ * fused multiply-adds, no float atomics), nothing depends on launch geometry: tests/subdiv_model.py restates these rules
+ * sequentially and reproduces every output bit.  faces [F, 3] int32 index [0, V) (range-check them first), points [V, 3]
+ * float32 finite; V, F <= GEOBI_MAX_NODES.  One PASS is a plan and an emit; `loop` != 0 is the Loop scheme, `adaptive` != 0
+ * the max-edge mode (midpoint positions; the two exclude each other).
+ *   edge table           that of geobi_topo_*: a face is INCLUDED when its three corners differ; an included face lists
+ *                        its undirected edges {lo, hi} under the key lo << 24 | hi in the slots 3f + k, edge k joining the
+ *                        corners c_k and c_k+1 (indices mod 3); one stable 48-bit sort; a run of equal keys is one EDGE,
+ *                        its length the claimant count n_e, its claimants in ascending slot order; edge ids count the run
+ *                        heads, so they ascend with (lo, hi).  A face that is not included claims no edge and is copied
+ *                        through as its single child.
+ *   split edges          uniform (adaptive == 0): every edge.  Adaptive: the edges with len2 > (double)max_edge *
+ *                        (double)max_edge, len2 = (dx * dx + dy * dy) + dz * dz in fp64, d = hi - lo taken in fp64 from the
+ *                        float32 coordinates; strict, an edge of length exactly max_edge stays.
+ *   new vertices         split edge e becomes vertex V + rank(e), rank = its position among the split edges in edge-id
+ *                        order; old vertices keep the rows 0 .. V - 1.  vertex_parents [V', 2] = (v, v) for an old row,
+ *                        (lo, hi) for a new one.
+ *   new faces            the children of face f are consecutive rows that start at the exclusive scan of the child counts
+ *                        (1 + the number of split edges of f), face_parent [F'] = f, the winding is kept; m_k = the vertex
+ *                        of edge k:
+ *                          0 split   (c0, c1, c2)
+ *                          3 split   (c0, m0, m2) (c1, m1, m0) (c2, m2, m1) (m0, m1, m2)
+ *                          1 split   (edge k; a = c_k, b = c_k+1, c = c_k+2)   (a, m_k, c) (m_k, b, c)
+ *                          2 split   (edge u unsplit; a = c_u, b = c_u+1, c = c_u+2, p = m_u+1, q = m_u+2)   (p, c, q), then
+ *                                    (a, b, p) (a, p, q) if edge u+1 is the longer of the two split edges, else
+ *                                    (a, b, q) (b, p, q); "longer" compares the two len2, an exact tie goes to the lower
+ *                                    edge id
+ *                        One round conforms: a midpoint belongs to the edge, every claimant of the edge sees it.
+ *   midpoint position    0.5f * lo + 0.5f * hi in float32, per coordinate (the products are exact: one rounding).
+ *   Loop positions       per coordinate in fp64, rounded to float32 once at the end.  An edge is SHARP when n_e != 2; s_v =
+ *                        the number of sharp edges at vertex v; the valence n = the number of edges at v.
+ *                          new vertex, sharp edge       the midpoint expression above
+ *                          new vertex, n_e == 2         0.375 * (lo + hi) + 0.125 * (c + d), c and d the opposite corners
+ *                                                       (corner k + 2 of slot 3f + k) of its two claimants
+ *                          old vertex, s_v == 0, n >= 1 beta = (n == 3) ? 3.0 / 16.0 : 3.0 / (8.0 * n); sum = the neighbours
+ *                                                       added in ascending vertex id, starting from the first;
+ *                                                       (1.0 - n * beta) * v + beta * sum
+ *                          old vertex, s_v == 2         0.75 * v + 0.125 * (p + q), p and q the other ends of its two sharp
+ *                                                       edges
+ *                          old vertex otherwise         unchanged (s_v == 1, s_v >= 3, no edge)
+ *                        Sharpness comes from the table of the pass itself.
+ *   geobi_subdiv_plan    builds the table, the flags and the scans and leaves them in `ws`; counts (device int32 [8]): [0]
+ *                        edges, [1] split edges, [2] boundary edges (n_e == 1), [3] complex edges (n_e >= 3), [4] V' = V +
+ *                        split, [5] F'.  points may be NULL unless adaptive.  Nothing of the pass is written yet: the caller
+ *                        reads the counts (geobi_read_i32), stops when an adaptive round splits nothing, and sizes the
+ *                        outputs.  F == 0 is valid (V' = V, F' = 0, no workspace needed).  stage_ms (HOST float [3],
+ *                        normally NULL) is for measurement: the milliseconds of the slots, of the sort and of the rest,
+ *                        and the call then waits for its own end.
+ *   geobi_subdiv_emit    over the workspace of a plan of the same faces, F, V and scheme, with the V' and F' read from its
+ *                        counts (both checked against GEOBI_MAX_NODES before anything is written; a row beyond them is
+ *                        never written): faces_out [F', 3], face_parent [F'], vertex_parents [V', 2], points_out [V', 3].
+ *   geobi_subdiv_points  points_out [V', 3] alone, for another point array [V, 3] over the same stored plan: the same
+ *                        splits, the same masks (an adaptive plan does not measure the other array).                    */
+size_t geobi_subdiv_ws_bytes(int64_t F, int64_t V);
+int geobi_subdiv_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int adaptive,
+                      float max_edge, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_subdiv_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int64_t Vn, int64_t Fn,
+                      int32_t* faces_out, int32_t* face_parent, int32_t* vertex_parents, float* points_out,
+                      const void* ws, size_t ws_bytes, void* stream);
+int geobi_subdiv_points(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int64_t Vn,
+                        float* points_out, const void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
