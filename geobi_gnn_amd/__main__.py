@@ -16,6 +16,7 @@
   python -m geobi_gnn_amd align ... --samples N [--seed 1]
   python -m geobi_gnn_amd subdivide --data_dir DIR [--out_dir DIR/subdivided] [--levels 1] [--scheme midpoint|loop]
   python -m geobi_gnn_amd subdivide --data_dir DIR (--max_edge L | --max_edge_diag R) [--max_rounds 16]
+  python -m geobi_gnn_amd decimate --data_dir DIR [--out_dir DIR/decimated] (--ratio R | --faces N) [--max_cost C] [--max_rounds 256]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -45,7 +46,9 @@ surface -- what a CAD target of a few large triangles needs.  `subdivide` (meshs
 `--levels K` passes that split every edge (at its midpoint, or with `--scheme loop` by Loop's masks), or `--max_edge L` /
 `--max_edge_diag R` (L = R times the diagonal of the mesh's bounding box) rounds that split only the edges longer than L;
 with DIR/original present the refinement is planned on original/NAME.obj and applied to every noisy/NAME_n*.obj of equal
-size, which keeps the pairs in correspondence.  All device work runs in this one process.
+size, which keeps the pairs in correspondence.  `decimate` (meshdecim.py) is its inverse: rounds of quadric edge collapses
+until `--faces N` or `--ratio R` times the faces are left (`--max_cost C`: no collapse dearer than C), boundaries kept at
+full resolution, with the same folders and the same pairing of noisy files.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -516,6 +519,66 @@ def train(opt):
     return trainer.train(opt, _device(opt.gpu), predict=denoise)
 
 
+def _decimate_line(decimated, V, F, out_file):
+    c = decimated.counts
+    return ("V: %7d -> %7d,  F: %7d -> %7d,  rounds: %d,  reached: %s,  '%s'"
+            % (V, decimated.points.shape[0], F, decimated.faces.shape[0], c['rounds'], 'yes' if c['reached'] else 'no',
+               os.path.basename(out_file)))
+
+
+def decimate(opt):
+    """Simplify every mesh of a folder on the device (meshdecim), with the folders of `subdivide`: with DIR/original,
+    original/NAME.obj -> OUT/original/NAME.obj and the same collapses on every noisy/NAME_n*.obj of the same size ->
+    OUT/noisy/; else DIR/*.obj -> OUT/NAME.obj."""
+    from . import meshdecim, meshio
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'decimated')
+    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
+    paired = os.path.isdir(original_dir)
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
+    out_original = os.path.join(out_dir, 'original') if paired else out_dir
+    os.makedirs(out_original, exist_ok=True)
+    if paired:
+        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
+    mode = ('to %d faces' % opt.faces if opt.faces is not None else 'to %g of the faces' % opt.ratio)
+    if opt.max_cost is not None:
+        mode += ', max_cost %g' % opt.max_cost
+    print('\nDecimate, %s, %d files ...\n' % (mode, len(files)), flush=True)
+    failed = 0
+    for path in files:
+        name = os.path.basename(path)[:-4]
+        try:
+            points, faces = meshio.read_obj(path)
+            decimated = meshdecim.decimate(points, faces, target_faces=opt.faces, ratio=opt.ratio, max_cost=opt.max_cost,
+                                           max_rounds=opt.max_rounds, device=dev)
+            faces_out = decimated.faces.cpu().numpy()
+            out_file = os.path.join(out_original, name + '.obj')
+            meshio.write_obj(out_file, decimated.points.cpu().numpy(), faces_out)
+            print(_decimate_line(decimated, points.shape[0], faces.shape[0], out_file), flush=True)
+            if not paired:
+                continue
+            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
+                try:
+                    n_points, n_faces = meshio.read_obj(noisy)
+                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
+                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
+                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
+                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
+                    meshio.write_obj(out_file, meshdecim.apply(decimated, n_points).cpu().numpy(), faces_out)
+                    print(_decimate_line(decimated, points.shape[0], faces.shape[0], out_file), flush=True)
+                except (ValueError, OSError) as e:
+                    failed += 1
+                    print('skipped: %s' % e, file=sys.stderr, flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d files skipped' % failed, file=sys.stderr)
+    return 1 if failed or not files else 0
+
+
 def _weld_tol_arg(text):
     v = float(text)
     if not (v >= 0.0 and v < float('inf')):
@@ -541,6 +604,27 @@ def _positive_arg(text):
     v = float(text)
     if not (v > 0.0 and v < float('inf')):
         raise argparse.ArgumentTypeError('a positive length, not %r' % text)
+    return v
+
+
+def _ratio_arg(text):
+    v = float(text)
+    if not 0.0 < v < 1.0:
+        raise argparse.ArgumentTypeError('a part of the faces above 0 and below 1, not %r' % text)
+    return v
+
+
+def _not_negative_arg(text):
+    v = float(text)
+    if not (v >= 0.0 and v < float('inf')):
+        raise argparse.ArgumentTypeError('0 or a positive number, not %r' % text)
+    return v
+
+
+def _count_arg(text):
+    v = int(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError('a whole number, not negative, not %r' % text)
     return v
 
 
@@ -680,6 +764,18 @@ def build_parser():
     u.add_argument('--max_rounds', type=_at_least_one_arg, default=16, help='with --max_edge*: rounds at most')
     u.add_argument('--gpu', type=int, default=-1)
     u.set_defaults(fn=subdivide)
+    k = sub.add_parser('decimate', help='make every mesh coarser on the device: rounds of quadric edge collapses down to a '
+                                        'face count, boundaries kept')
+    k.add_argument('--data_dir', type=str, required=True, help='holds original/ (and noisy/), or the OBJ files themselves')
+    k.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/decimated')
+    stop = k.add_mutually_exclusive_group(required=True)
+    stop.add_argument('--ratio', type=_ratio_arg, default=None, metavar='R', help='stop at R times the faces of each mesh')
+    stop.add_argument('--faces', type=_count_arg, default=None, metavar='N', help='stop at N faces (or one below)')
+    k.add_argument('--max_cost', type=_not_negative_arg, default=None, metavar='C',
+                   help='collapse no edge whose quadric cost is above C (0: only what leaves the surface as it is)')
+    k.add_argument('--max_rounds', type=_at_least_one_arg, default=256, help='rounds at most')
+    k.add_argument('--gpu', type=int, default=-1)
+    k.set_defaults(fn=decimate)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)

@@ -1,0 +1,639 @@
+// Triangle-mesh simplification on the device: rounds of independent quadric edge collapses, one
+// round per plan + emit.  The rules are stated in include/geobi_hip.h (geobi_decim_*); tests/decim_model.py restates them
+// sequentially and every output is compared bit for bit.
+//
+// The topology is integer-exact and independent of launch geometry; every float step is fp64 in one stated order
+// (contraction off throughout, __dsqrt_rn / __ddiv_rn, no float atomics):
+//   tables   the slots and keys of topo.hip (edge_table.h) sorted stably on 48 bits: a run is an edge, and an edge is
+//            known by the sorted position of its head, which orders the edges as their ids do.  Two more 48-bit sorts: the
+//            corner keys v << 24 | f (the included faces at a vertex in ascending id) and the directed pairs src << 24 |
+//            dst of the run heads (the neighbours of a vertex in ascending id); both one binary search away
+//   values   one lane per vertex sums its quadric over its corner run; one lane per edge head picks the placement and
+//            runs the link, valence and flip tests; two stable sorts (hash, then cost) rank the valid candidates
+//   select   GEOBI_DECIM_SWEEPS sweeps of: atomicMin of the ranks into m1 (nobody reads m1 in that launch), m2 per vertex,
+//            select + block (writes `blocked`, reads m2), die (reads `blocked`)
+//   budget   the selected flags in rank order, scanned; roles of the vertices, keep flags of vertices and faces, scanned
+//   emit     one lane per vertex, per face and per output row
+// Every index is bounded: corners are below V (face_included), slots below 3F, vertices and faces taken out of a key were
+// put into it from such a corner or face, output rows are checked against the sizes the caller read from the counts.
+#include "common.h"
+#include "edge_table.h"
+#include "rocprim_temp.h"
+#include "stage_timer.h"
+#include "../../include/geobi_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace geobi {
+
+namespace {
+
+constexpr int kT = 256;
+enum Count { kEdges = 0, kLocked = 1, kValid = 2, kCollapses = 3, kVOut = 4, kFOut = 5, kNotIncluded = 6,
+             kSweepsSelected = 7, kCounts = 8, kSweepBase = 8, kDevCounts = 16 };   // [8 ..]: selected per sweep
+static_assert(kSweepBase + GEOBI_DECIM_SWEEPS <= kDevCounts, "one counter per sweep");
+constexpr int kNone = 0x7f7f7f7f;                   // no rank: what a memset of 0x7f leaves, above every position
+constexpr uint64_t kNoCost = ~0ull;                 // sorts last; the orderable form of no finite cost
+enum State { kLive = 1, kSelected = 2 };
+enum Role { kPlain = -1, kMergedAway = 3 };         // 0, 1, 2: the `lo` of a collapsed edge, its placement code
+
+struct P3 { double x, y, z; };
+
+__device__ __forceinline__ P3 point_of(const float* __restrict__ points, int v) {
+  return {(double)points[3 * (size_t)v], (double)points[3 * (size_t)v + 1], (double)points[3 * (size_t)v + 2]};
+}
+
+// n = (b - a) x (c - a), every component two products and one subtraction; -> s = (nx nx + ny ny) + nz nz
+__device__ __forceinline__ double normal_of(const P3& a, const P3& b, const P3& c, P3& n) {
+#pragma clang fp contract(off)
+  const double ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z;
+  const double wx = c.x - a.x, wy = c.y - a.y, wz = c.z - a.z;
+  n.x = uy * wz - uz * wy;
+  n.y = uz * wx - ux * wz;
+  n.z = ux * wy - uy * wx;
+  return (n.x * n.x + n.y * n.y) + n.z * n.z;
+}
+
+__device__ __forceinline__ double cost_of(const double* q, const P3& p) {
+#pragma clang fp contract(off)
+  const double diag = ((q[0] * p.x) * p.x + (q[4] * p.y) * p.y) + (q[7] * p.z) * p.z;
+  const double off = ((q[1] * p.x) * p.y + (q[2] * p.x) * p.z) + (q[5] * p.y) * p.z;
+  const double lin = (q[3] * p.x + q[6] * p.y) + q[8] * p.z;
+  return (diag + 2.0 * off) + (2.0 * lin + q[9]);
+}
+
+__device__ __forceinline__ float midpoint(float a, float b) {
+#pragma clang fp contract(off)
+  return 0.5f * a + 0.5f * b;
+}
+
+// the first position of a sorted list that is not below x
+__device__ __forceinline__ int lower_bound(const uint64_t* __restrict__ a, int n, uint64_t x) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// a corner key v << 24 | f or a directed pair src << 24 | dst: the owner (2^24 - 1 for kNoEdge: never a vertex) and the
+// other field as an index (edge_table.h: index_from_key)
+__device__ __forceinline__ int owner_of(uint64_t key) { return (int)(key >> 24); }
+__device__ __forceinline__ int item_of(uint64_t key) { return index_from_key((int)(key & 0xffffffull)); }
+
+struct Run { bool head, two, three; };
+__device__ __forceinline__ Run run_at(const uint64_t* __restrict__ keys, int n, int i) {
+  const uint64_t key = keys[i];
+  Run r;
+  r.head = key != kNoEdge && (i == 0 || keys[i - 1] != key);
+  r.two = i + 1 < n && keys[i + 1] == key;
+  r.three = r.two && i + 2 < n && keys[i + 2] == key;
+  return r;
+}
+
+// ---- tables
+// corner keys of every face, its keep flag (= included so far), the count of the faces that are not included
+__global__ void decim_corners_kernel(const int* __restrict__ fv, int F, int V, uint64_t* __restrict__ corners,
+                                     int* __restrict__ fkeep, int* __restrict__ counts) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  bool out = false;
+  if (f < F) {
+    int c[3];
+    const bool inc = face_included(fv, nullptr, f, V, c[0], c[1], c[2]);
+    for (int k = 0; k < 3; ++k) corners[3 * (size_t)f + k] = inc ? edge_key(c[k], f) : kNoEdge;
+    fkeep[f] = inc ? 1 : 0;
+    out = !inc;
+  }
+  count_lanes(out, counts + kNotIncluded);
+}
+
+// per sorted position: the two directed pairs of an edge head, the locked flags of the ends of an edge with n_e != 2
+// (every writer stores the same 1), the count of the edges
+__global__ void decim_heads_kernel(const uint64_t* __restrict__ keys, int n, uint64_t* __restrict__ pairs,
+                                   int* __restrict__ locked, int* __restrict__ counts) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool head = false;
+  if (i < n) {
+    const Run r = run_at(keys, n, i);
+    head = r.head;
+    uint64_t forth = kNoEdge, back = kNoEdge;
+    if (head) {
+      const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);
+      forth = keys[i];
+      back = edge_key(hi, lo);
+      if (!r.two || r.three) { locked[lo] = 1; locked[hi] = 1; }
+    }
+    pairs[2 * (size_t)i] = forth;
+    pairs[2 * (size_t)i + 1] = back;
+  }
+  count_lanes(head, counts + kEdges);
+}
+
+// ---- values
+// Q_v over the corner run of v, ascending face id
+__global__ void decim_quadrics_kernel(const float* __restrict__ points, const int* __restrict__ fv, int V,
+                                      const uint64_t* __restrict__ corners, int n, const int* __restrict__ locked,
+                                      double* __restrict__ Q, int* __restrict__ counts) {
+#pragma clang fp contract(off)
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  bool is_locked = false;
+  if (v < V) {
+    is_locked = locked[v] != 0;
+    double q[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int j = lower_bound(corners, n, (uint64_t)v << 24); j < n && owner_of(corners[j]) == v; ++j) {
+      const int f = item_of(corners[j]);
+      const P3 a = point_of(points, fv[3 * (size_t)f]), b = point_of(points, fv[3 * (size_t)f + 1]),
+               c = point_of(points, fv[3 * (size_t)f + 2]);
+      P3 nrm;
+      const double s = normal_of(a, b, c, nrm);
+      if (s == 0.0) continue;
+      const double l = __dsqrt_rn(s);
+      const double d = -((nrm.x * a.x + nrm.y * a.y) + nrm.z * a.z);
+      const double p[4] = {nrm.x, nrm.y, nrm.z, d};
+      int e = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int t = r; t < 4; ++t) {
+          q[e] = q[e] + __ddiv_rn(p[r] * p[t], l);
+          ++e;
+        }
+    }
+    for (int e = 0; e < 10; ++e) Q[10 * (size_t)v + e] = q[e];
+  }
+  count_lanes(is_locked, counts + kLocked);
+}
+
+// the faces at v other than those that hold both ends keep the side of their normal when v moves to `at`
+__device__ __forceinline__ bool no_flip(const float* __restrict__ points, const int* __restrict__ fv,
+                                        const uint64_t* __restrict__ corners, int n, int v, int other, const P3& at) {
+#pragma clang fp contract(off)
+  bool ok = true;
+  for (int j = lower_bound(corners, n, (uint64_t)v << 24); j < n && owner_of(corners[j]) == v; ++j) {
+    const int f = item_of(corners[j]);
+    const int c0 = fv[3 * (size_t)f], c1 = fv[3 * (size_t)f + 1], c2 = fv[3 * (size_t)f + 2];
+    if (c0 == other || c1 == other || c2 == other) continue;
+    const P3 a = point_of(points, c0), b = point_of(points, c1), c = point_of(points, c2);
+    P3 was, now;
+    if (normal_of(a, b, c, was) == 0.0) continue;
+    normal_of(c0 == v ? at : a, c1 == v ? at : b, c2 == v ? at : c, now);
+    if (!((was.x * now.x + was.y * now.y) + was.z * now.z > 0.0)) ok = false;
+  }
+  return ok;
+}
+
+// per sorted position: the head of an edge with two claimants whose ends are not both locked takes its placement and runs
+// the tests; cost_key = the orderable cost of a valid candidate (else kNoCost), hash, code, idx = the position itself
+__global__ void decim_candidates_kernel(const uint64_t* __restrict__ keys, int n, const float* __restrict__ points,
+                                        const int* __restrict__ fv, const uint64_t* __restrict__ corners,
+                                        const uint64_t* __restrict__ pairs, int n_pairs, const int* __restrict__ locked,
+                                        const double* __restrict__ Q, int use_max_cost, double max_cost,
+                                        uint64_t* __restrict__ cost_key, uint32_t* __restrict__ hash,
+                                        int* __restrict__ code_out, int* __restrict__ idx, int* __restrict__ counts) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool valid = false;
+  if (i < n) {
+    const Run r = run_at(keys, n, i);
+    uint64_t ck = kNoCost;
+    int code = 0;
+    const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);      // meaningful at a head
+    if (r.head && r.two && !r.three && !(locked[lo] != 0 && locked[hi] != 0)) {
+      double q[10];
+      for (int e = 0; e < 10; ++e) q[e] = Q[10 * (size_t)lo + e] + Q[10 * (size_t)hi + e];
+      const float* pl = points + 3 * (size_t)lo;
+      const float* ph = points + 3 * (size_t)hi;
+      const P3 place[3] = {point_of(points, lo), point_of(points, hi),
+                           {(double)midpoint(pl[0], ph[0]), (double)midpoint(pl[1], ph[1]), (double)midpoint(pl[2], ph[2])}};
+      const int first = locked[hi] != 0 ? 1 : 0, last = locked[lo] != 0 ? 0 : (locked[hi] != 0 ? 1 : 2);
+      double cost = cost_of(q, place[first]);
+      code = first;
+      for (int c = first + 1; c <= last; ++c) {
+        const double value = cost_of(q, place[c]);
+        if (value < cost) { cost = value; code = c; }
+      }
+      valid = isfinite(cost) && !(use_max_cost != 0 && cost > max_cost);
+      if (valid) {                                  // link and valence: one merge walk over the two neighbour lists
+        int a = lower_bound(pairs, n_pairs, (uint64_t)lo << 24), b = lower_bound(pairs, n_pairs, (uint64_t)hi << 24);
+        int shared = 0;
+        while (a < n_pairs && b < n_pairs && owner_of(pairs[a]) == lo && owner_of(pairs[b]) == hi) {
+          const int da = item_of(pairs[a]), db = item_of(pairs[b]);
+          if (da == db) {
+            ++shared;
+            const int w = lower_bound(pairs, n_pairs, (uint64_t)da << 24);
+            if (!(w + 3 < n_pairs && owner_of(pairs[w + 3]) == da)) valid = false;     // valence below 4
+            ++a; ++b;
+          } else if (da < db) {
+            ++a;
+          } else {
+            ++b;
+          }
+        }
+        if (shared != 2) valid = false;
+      }
+      if (valid) valid = no_flip(points, fv, corners, n, lo, hi, place[code]);
+      if (valid) valid = no_flip(points, fv, corners, n, hi, lo, place[code]);
+      if (valid) {
+        const uint64_t bits = (uint64_t)__double_as_longlong(cost);
+        ck = (bits >> 63) != 0 ? ~bits : bits | (1ull << 63);
+      }
+    }
+    cost_key[i] = ck;
+    hash[i] = valid ? (uint32_t)((keys[i] * 0x9E3779B97F4A7C15ull) >> 32) : 0xffffffffu;
+    code_out[i] = code;
+    idx[i] = i;
+  }
+  count_lanes(valid, counts + kValid);
+}
+
+__global__ void decim_gather_cost_kernel(const uint64_t* __restrict__ cost_key, const int* __restrict__ idx, int n,
+                                         uint64_t* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int i = idx[j];
+  out[j] = (unsigned)i < (unsigned)n ? cost_key[i] : kNoCost;
+}
+
+// order[j] = the position of the edge of rank j: rank and state per position
+__global__ void decim_rank_kernel(const uint64_t* __restrict__ sorted_cost, const int* __restrict__ order, int n,
+                                  int* __restrict__ rank, int* __restrict__ state) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int i = order[j];
+  if ((unsigned)i >= (unsigned)n) return;
+  const bool valid = sorted_cost[j] != kNoCost;
+  rank[i] = valid ? j : kNone;
+  state[i] = valid ? kLive : 0;
+}
+
+// ---- selection
+__global__ void decim_m1_kernel(const uint64_t* __restrict__ keys, int n, const int* __restrict__ state,
+                                const int* __restrict__ rank, int* __restrict__ m1) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (state[i] & kLive) == 0) return;
+  atomicMin(m1 + edge_key_lo(keys[i]), rank[i]);
+  atomicMin(m1 + edge_key_hi(keys[i]), rank[i]);
+}
+
+__global__ void decim_m2_kernel(const int* __restrict__ m1, int V, const uint64_t* __restrict__ pairs, int n_pairs,
+                                int* __restrict__ m2) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  int m = m1[v];
+  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j) {
+    const int w = m1[item_of(pairs[j])];
+    m = w < m ? w : m;
+  }
+  m2[v] = m;
+}
+
+__device__ __forceinline__ void block_ring(const uint64_t* __restrict__ pairs, int n_pairs, int v, int* __restrict__ blocked) {
+  blocked[v] = 1;
+  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j)
+    blocked[item_of(pairs[j])] = 1;
+}
+
+// a live candidate whose rank is the least of the closed rings of both ends is selected and blocks those rings
+__global__ void decim_select_kernel(const uint64_t* __restrict__ keys, int n, const int* __restrict__ rank,
+                                    const int* __restrict__ m2, const uint64_t* __restrict__ pairs, int n_pairs,
+                                    int* __restrict__ state, int* __restrict__ blocked, int* __restrict__ selected_count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool selected = false;
+  if (i < n && (state[i] & kLive) != 0) {
+    const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);
+    const int a = m2[lo], b = m2[hi];
+    selected = (a < b ? a : b) == rank[i];
+    if (selected) {
+      state[i] |= kSelected;
+      block_ring(pairs, n_pairs, lo, blocked);
+      block_ring(pairs, n_pairs, hi, blocked);
+    }
+  }
+  count_lanes(selected, selected_count);
+}
+
+__global__ void decim_die_kernel(const uint64_t* __restrict__ keys, int n, const int* __restrict__ blocked,
+                                 int* __restrict__ state) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (state[i] & kLive) == 0) return;
+  if (blocked[edge_key_lo(keys[i])] != 0 || blocked[edge_key_hi(keys[i])] != 0) state[i] &= ~kLive;
+}
+
+// ---- budget
+__global__ void decim_selected_in_rank_order_kernel(const int* __restrict__ order, const int* __restrict__ state, int n,
+                                                    int* __restrict__ flag) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int i = order[j];
+  flag[j] = (unsigned)i < (unsigned)n && (state[i] & kSelected) != 0 ? 1 : 0;
+}
+
+// the first k selected edges in rank order collapse: the roles of their ends, their two claimants go
+__global__ void decim_collapse_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ vals, int n,
+                                      const int* __restrict__ order, const int* __restrict__ flag,
+                                      const int* __restrict__ pos, const int* __restrict__ code, int F, int budget,
+                                      int* __restrict__ role, int* __restrict__ partner, int* __restrict__ fkeep,
+                                      int* __restrict__ counts) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  bool collapses = false;
+  if (j < n && flag[j] != 0) {
+    const int over = F - counts[kNotIncluded] - budget;            // counts[kNotIncluded]: written by an earlier launch
+    const int k = budget < 0 ? n : (over > 0 ? (over + 1) / 2 : 0);
+    const int i = order[j];
+    if (pos[j] < k && i + 1 < n) {
+      collapses = true;
+      const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);
+      role[lo] = code[i];
+      partner[lo] = hi;
+      role[hi] = kMergedAway;
+      partner[hi] = lo;
+      fkeep[(vals[i] >> 1) / 3] = 0;
+      fkeep[(vals[i + 1] >> 1) / 3] = 0;
+    }
+  }
+  count_lanes(collapses, counts + kCollapses);
+}
+
+__global__ void decim_keep_vertices_kernel(const int* __restrict__ role, int V, int* __restrict__ keep) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < V) keep[v] = role[v] != kMergedAway ? 1 : 0;
+}
+
+__global__ void decim_totals_kernel(const int* __restrict__ keepv, const int* __restrict__ vrow, int V,
+                                    const int* __restrict__ fkeep, const int* __restrict__ frow, int F,
+                                    int* __restrict__ counts) {
+  counts[kVOut] = V > 0 ? vrow[V - 1] + keepv[V - 1] : 0;
+  counts[kFOut] = frow[F - 1] + fkeep[F - 1];
+  int sweeps = 0;
+  for (int s = 0; s < GEOBI_DECIM_SWEEPS; ++s) sweeps += counts[kSweepBase + s] > 0 ? 1 : 0;
+  counts[kSweepsSelected] = sweeps;
+}
+
+__global__ void decim_no_faces_kernel(int V, int* __restrict__ counts) { counts[kVOut] = V; }
+
+// ---- emit
+__global__ void decim_vertices_kernel(const int* __restrict__ role, const int* __restrict__ partner,
+                                      const int* __restrict__ vrow, int V, int Vn, int* __restrict__ vertex_map,
+                                      int* __restrict__ parents, int8_t* __restrict__ place) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const int r = role[v], p = partner[v];
+  const bool has_partner = r != kPlain && (unsigned)p < (unsigned)V;
+  if (r == kMergedAway && has_partner) {
+    vertex_map[v] = vrow[p];
+    return;
+  }
+  const int row = vrow[v];
+  vertex_map[v] = row;
+  if ((unsigned)row >= (unsigned)Vn) return;
+  parents[2 * (size_t)row] = v;
+  parents[2 * (size_t)row + 1] = has_partner ? p : v;
+  place[row] = (int8_t)(has_partner ? r : 0);
+}
+
+// with no plan (F == 0): every row stays
+__global__ void decim_identity_kernel(int V, int* __restrict__ vertex_map, int* __restrict__ parents,
+                                      int8_t* __restrict__ place) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  vertex_map[v] = v;
+  parents[2 * (size_t)v] = v;
+  parents[2 * (size_t)v + 1] = v;
+  place[v] = 0;
+}
+
+__global__ void decim_faces_kernel(const int* __restrict__ fv, int F, int V, const int* __restrict__ fkeep,
+                                   const int* __restrict__ frow, const int* __restrict__ role,
+                                   const int* __restrict__ partner, const int* __restrict__ vrow, int Fn,
+                                   int* __restrict__ faces_out, int* __restrict__ face_map) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F || fkeep[f] == 0) return;
+  const int row = frow[f];
+  if ((unsigned)row >= (unsigned)Fn) return;
+  for (int k = 0; k < 3; ++k) {
+    int c = fv[3 * (size_t)f + k];                                  // below V: a kept face is an included one
+    if ((unsigned)c >= (unsigned)V) c = 0;                          // never, unless the faces are not those of the plan
+    const int p = partner[c];
+    const int from = role[c] == kMergedAway && (unsigned)p < (unsigned)V ? p : c;
+    faces_out[3 * (size_t)row + k] = vrow[from];
+  }
+  face_map[row] = f;
+}
+
+// one lane per output row: the placement of the row's parents
+__global__ void decim_points_kernel(const float* __restrict__ other, int V, int Vn, const int* __restrict__ parents,
+                                    const int8_t* __restrict__ place, float* __restrict__ out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= Vn) return;
+  const int a = parents[2 * (size_t)r], b = parents[2 * (size_t)r + 1];
+  if ((unsigned)a >= (unsigned)V || (unsigned)b >= (unsigned)V) return;
+  const int code = place[r];
+  for (int k = 0; k < 3; ++k) {
+    const float x = other[3 * (size_t)a + k], y = other[3 * (size_t)b + k];
+    out[3 * (size_t)r + k] = code == 0 ? x : (code == 1 ? y : midpoint(x, y));
+  }
+}
+
+struct DecimBuffers {
+  // the state of a plan, read by emit
+  int *role, *partner, *vrow, *fkeep, *frow, *counts;
+  // scratch of the plan: the three tables
+  uint64_t *k_in, *k_out, *c_in, *c_out, *p_in, *p_out;
+  int *v_in, *v_out;
+  // per vertex
+  double* Q;
+  int *locked, *blocked, *m1, *m2, *keepv;
+  // per sorted position
+  uint64_t *cost_key, *cost_in, *cost_out;
+  uint32_t *hash_in, *hash_out;
+  int *idx_in, *idx_mid, *order, *code, *rank, *state, *flag, *pos;
+  SubWs edge_sort, key_sort, pair_sort, hash_sort, cost_sort, slot_scan, vertex_scan, face_scan;
+};
+DecimBuffers carve_decim(Arena& a, int64_t F, int64_t V) {
+  const int64_t n = 3 * F;
+  return {a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(F), a.take<int>(F), a.take<int>(kDevCounts),
+          a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(2 * n),
+          a.take<uint64_t>(2 * n), a.take<int>(n), a.take<int>(n),
+          a.take<double>(10 * V),
+          a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V),
+          a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n),
+          a.take<uint32_t>(n), a.take<uint32_t>(n),
+          a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n),
+          a.take<int>(n),
+          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, kEdgeKeyBits)),
+          a.take_ws(sort_keys_temp_bytes<uint64_t>(n, kEdgeKeyBits)),
+          a.take_ws(sort_keys_temp_bytes<uint64_t>(2 * n, kEdgeKeyBits)),
+          a.take_ws(sort_pairs_temp_bytes<uint32_t, int>(n, 32)),
+          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, 64)),
+          a.take_ws(scan_temp_bytes<int>(n)), a.take_ws(scan_temp_bytes<int>(V)), a.take_ws(scan_temp_bytes<int>(F))};
+}
+
+int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, DecimBuffers& b) {
+  Arena a(ws, ws_bytes);
+  b = carve_decim(a, F, V);
+  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
+  return 0;
+}
+
+int launch_points(const float* other, int64_t V, int64_t Vn, const int32_t* parents, const int8_t* place, float* out,
+                  hipStream_t s) {
+  if (Vn == 0) return 0;
+  decim_points_kernel<<<cdiv(Vn, kT), kT, 0, s>>>(other, (int)V, (int)Vn, parents, place, out);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_decim_ws_bytes(int64_t F, int64_t V) {
+  if (sizes_ok("geobi_decim_ws_bytes", F > V ? F : V, 0) != 0 || (F < V ? F : V) < 0) return 0;
+  return carve_bytes([&](Arena& a) { carve_decim(a, F, V); });
+}
+
+int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_max_cost, float max_cost,
+                     int64_t budget, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(counts);
+  GEOBI_REQUIRE(use_max_cost == 0 || max_cost >= 0.0f, "decim_plan: max_cost = %g (not negative, not NaN)", (double)max_cost);
+  hipStream_t s = as_stream(stream);
+  if (F == 0) {                                   // nothing to collapse: V' = V, F' = 0
+    GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * kCounts, s));
+    decim_no_faces_kernel<<<1, 1, 0, s>>>((int)V, counts);
+    GEOBI_LAUNCH_OK();
+    return 0;
+  }
+  DecimBuffers b;
+  GEOBI_TRY(carve_checked("decim_plan", F, V, ws, ws_bytes, b));
+  const int n = (int)(3 * F), n_pairs = 2 * n;
+  const int k_budget = budget < 0 ? -1 : (int)(budget < F ? budget : F);
+  size_t tb;
+  StageTimer timer(stage_ms, s);
+  GEOBI_TRY(timer.mark());
+  // ---- tables
+  GEOBI_HIP(hipMemsetAsync(b.counts, 0, sizeof(int) * kDevCounts, s));
+  if (V > 0) {
+    GEOBI_HIP(hipMemsetAsync(b.locked, 0, sizeof(int) * (size_t)V, s));
+    GEOBI_HIP(hipMemsetAsync(b.blocked, 0, sizeof(int) * (size_t)V, s));
+    GEOBI_HIP(hipMemsetAsync(b.role, 0xff, sizeof(int) * (size_t)V, s));       // kPlain
+    GEOBI_HIP(hipMemsetAsync(b.partner, 0xff, sizeof(int) * (size_t)V, s));
+  }
+  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, nullptr, (int)F, (int)V, b.k_in, b.v_in);
+  GEOBI_LAUNCH_OK();
+  decim_corners_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, (int)V, b.c_in, b.fkeep, b.counts);
+  GEOBI_LAUNCH_OK();
+  tb = b.edge_sort.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(b.edge_sort.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)n, 0u, kEdgeKeyBits, s,
+                                      false));
+  tb = b.key_sort.bytes;
+  GEOBI_HIP(rocprim::radix_sort_keys(b.key_sort.p, tb, b.c_in, b.c_out, (size_t)n, 0u, kEdgeKeyBits, s, false));
+  decim_heads_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.p_in, b.locked, b.counts);
+  GEOBI_LAUNCH_OK();
+  tb = b.pair_sort.bytes;
+  GEOBI_HIP(rocprim::radix_sort_keys(b.pair_sort.p, tb, b.p_in, b.p_out, (size_t)n_pairs, 0u, kEdgeKeyBits, s, false));
+  GEOBI_TRY(timer.mark());
+  // ---- values and rank
+  if (V > 0) {
+    decim_quadrics_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.c_out, n, b.locked, b.Q, b.counts);
+    GEOBI_LAUNCH_OK();
+  }
+  decim_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, faces, b.c_out, b.p_out, n_pairs, b.locked, b.Q,
+                                                    use_max_cost, (double)max_cost, b.cost_key, b.hash_in, b.code,
+                                                    b.idx_in, b.counts);
+  GEOBI_LAUNCH_OK();
+  tb = b.hash_sort.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(b.hash_sort.p, tb, b.hash_in, b.hash_out, b.idx_in, b.idx_mid, (size_t)n, 0u, 32u, s,
+                                      false));
+  decim_gather_cost_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.cost_key, b.idx_mid, n, b.cost_in);
+  GEOBI_LAUNCH_OK();
+  tb = b.cost_sort.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(b.cost_sort.p, tb, b.cost_in, b.cost_out, b.idx_mid, b.order, (size_t)n, 0u, 64u, s,
+                                      false));
+  decim_rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.cost_out, b.order, n, b.rank, b.state);
+  GEOBI_LAUNCH_OK();
+  GEOBI_TRY(timer.mark());
+  // ---- selection
+  for (int sweep = 0; sweep < GEOBI_DECIM_SWEEPS && V > 0; ++sweep) {
+    GEOBI_HIP(hipMemsetAsync(b.m1, 0x7f, sizeof(int) * (size_t)V, s));         // kNone
+    decim_m1_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.state, b.rank, b.m1);
+    GEOBI_LAUNCH_OK();
+    decim_m2_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.m1, (int)V, b.p_out, n_pairs, b.m2);
+    GEOBI_LAUNCH_OK();
+    decim_select_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.rank, b.m2, b.p_out, n_pairs, b.state, b.blocked,
+                                                  b.counts + kSweepBase + sweep);
+    GEOBI_LAUNCH_OK();
+    decim_die_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.blocked, b.state);
+    GEOBI_LAUNCH_OK();
+  }
+  // ---- budget, roles, scans
+  decim_selected_in_rank_order_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.order, b.state, n, b.flag);
+  GEOBI_LAUNCH_OK();
+  tb = b.slot_scan.bytes;
+  GEOBI_HIP(rocprim::exclusive_scan(b.slot_scan.p, tb, b.flag, b.pos, 0, (size_t)n, rocprim::plus<int>(), s, false));
+  decim_collapse_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.v_out, n, b.order, b.flag, b.pos, b.code, (int)F, k_budget,
+                                                  b.role, b.partner, b.fkeep, b.counts);
+  GEOBI_LAUNCH_OK();
+  if (V > 0) {
+    decim_keep_vertices_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.role, (int)V, b.keepv);
+    GEOBI_LAUNCH_OK();
+    tb = b.vertex_scan.bytes;
+    GEOBI_HIP(rocprim::exclusive_scan(b.vertex_scan.p, tb, b.keepv, b.vrow, 0, (size_t)V, rocprim::plus<int>(), s, false));
+  }
+  tb = b.face_scan.bytes;
+  GEOBI_HIP(rocprim::exclusive_scan(b.face_scan.p, tb, b.fkeep, b.frow, 0, (size_t)F, rocprim::plus<int>(), s, false));
+  decim_totals_kernel<<<1, 1, 0, s>>>(b.keepv, b.vrow, (int)V, b.fkeep, b.frow, (int)F, b.counts);
+  GEOBI_LAUNCH_OK();
+  GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kCounts, hipMemcpyDeviceToDevice, s));
+  GEOBI_TRY(timer.mark());
+  return timer.finish();
+}
+
+int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int64_t Vn, int64_t Fn,
+                     float* points_out, int32_t* faces_out, int32_t* face_map, int32_t* vertex_map,
+                     int32_t* vertex_parents, int8_t* place, const void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_SIZES(Vn > Fn ? Vn : Fn, 0);
+  GEOBI_SIZES(Vn < Fn ? Vn : Fn, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(points_out); GEOBI_NOTNULL(faces_out);
+  GEOBI_NOTNULL(face_map); GEOBI_NOTNULL(vertex_map); GEOBI_NOTNULL(vertex_parents); GEOBI_NOTNULL(place);
+  GEOBI_REQUIRE(Vn <= V && Fn <= F && 2 * (V - Vn) <= F - Fn,
+                "decim_emit: V' = %lld, F' = %lld are not what a plan of V = %lld, F = %lld can give", (long long)Vn,
+                (long long)Fn, (long long)V, (long long)F);
+  hipStream_t s = as_stream(stream);
+  if (F == 0) {
+    if (V > 0) {
+      decim_identity_kernel<<<cdiv(V, kT), kT, 0, s>>>((int)V, vertex_map, vertex_parents, place);
+      GEOBI_LAUNCH_OK();
+    }
+    return launch_points(points, V, Vn, vertex_parents, place, points_out, s);
+  }
+  DecimBuffers b;
+  GEOBI_TRY(carve_checked("decim_emit", F, V, const_cast<void*>(ws), ws_bytes, b));
+  if (V > 0) {
+    decim_vertices_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.role, b.partner, b.vrow, (int)V, (int)Vn, vertex_map, vertex_parents,
+                                                    place);
+    GEOBI_LAUNCH_OK();
+    decim_faces_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, (int)V, b.fkeep, b.frow, b.role, b.partner, b.vrow, (int)Fn,
+                                                 faces_out, face_map);
+    GEOBI_LAUNCH_OK();
+  }
+  return launch_points(points, V, Vn, vertex_parents, place, points_out, s);
+}
+
+int geobi_decim_points(const float* other, int64_t V, int64_t Vn, const int32_t* vertex_parents, const int8_t* place,
+                       float* out, void* stream) {
+  GEOBI_SIZES(V > Vn ? V : Vn, 0);
+  GEOBI_SIZES(V < Vn ? V : Vn, 0);
+  GEOBI_NOTNULL(other); GEOBI_NOTNULL(vertex_parents); GEOBI_NOTNULL(place); GEOBI_NOTNULL(out);
+  GEOBI_REQUIRE(Vn <= V, "decim_points: V' = %lld rows from V = %lld", (long long)Vn, (long long)V);
+  return launch_points(other, V, Vn, vertex_parents, place, out, as_stream(stream));
+}
+
+}  // extern "C"

@@ -12,8 +12,8 @@
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
  *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
  *     (reads its undecided counts through it), geobi_topo_orient / _components / _report (read the changed flags of
- *     their rounds through it), geobi_subdiv_plan with stage_ms (waits for its own end; without it the plan is only
- *     enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
+ *     their rounds through it), geobi_subdiv_plan and geobi_decim_plan with stage_ms (wait for their own end; without
+ *     it the plan is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -817,6 +817,76 @@ int geobi_subdiv_emit(const int32_t* faces, const float* points, int64_t F, int6
                       const void* ws, size_t ws_bytes, void* stream);
 int geobi_subdiv_points(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int64_t Vn,
                         float* points_out, const void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- mesh simplification (quadric edge collapse) ----
+ * Makes a triangle mesh coarser, the inverse of geobi_subdiv_*; no counterpart in the reference.  The
+ * topology is integer-exact, every float step is fp64 from the float32 inputs in ONE stated order (no contraction, no float
+ * atomics; sqrt and / are the correctly rounded ones), nothing depends on launch geometry: tests/decim_model.py restates
+ * these rules sequentially and reproduces every output bit.  faces [F, 3] int32 index [0, V), points [V, 3] float32 finite;
+ * V, F <= GEOBI_MAX_NODES.  One ROUND is a plan and an emit and takes (points, faces) to a smaller mesh:
+ *   1 edge table         that of geobi_topo_* / geobi_subdiv_*: a face is INCLUDED when its three corners differ; keys
+ *                        lo << 24 | hi in the slots 3f + k, one stable 48-bit sort, a run is an EDGE, n_e its claimant count,
+ *                        edge ids ascend with (lo, hi).  A face that is not included is dropped by the round and counted.
+ *   2 locked vertices    a vertex with an incident edge of n_e != 2 (boundary or complex) is LOCKED: its point survives the
+ *                        round with its bits unchanged (in its own row, or in the row of `lo` when it is the `hi` of a
+ *                        collapsed edge).  A vertex no included face refers to keeps its row.  The NEIGHBOURS of a vertex are
+ *                        the other ends of its edges (of any n_e) in ascending id, its valence their number.
+ *   3 vertex quadrics    memoryless.  Included face (a, b, c), all in fp64: u = b - a, w = c - a, n = u x w (nx = uy * wz -
+ *                        uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx), s = (nx * nx + ny * ny) + nz * nz.  s == 0:
+ *                        the face adds nothing and takes no part in the flip test.  Else l = sqrt(s), d = -((nx * ax + ny *
+ *                        ay) + nz * az), p = (nx, ny, nz, d), K_ij = (p_i * p_j) / l in the order 00 01 02 03 11 12 13 22 23
+ *                        33.  Q_v starts from +0.0 and adds K entrywise over the included faces at v in ascending face id.
+ *   4 candidates         an edge with n_e == 2 whose ends are not both locked.  Q = Q_lo + Q_hi entrywise.  Placements: code
+ *                        0 the point of lo, 1 the point of hi, 2 0.5f * lo + 0.5f * hi in float32; with lo locked only code
+ *                        0, with hi locked only code 1.  The cost of a placement (x, y, z), taken to fp64:
+ *                          diag = ((Q00 * x) * x + (Q11 * y) * y) + (Q22 * z) * z
+ *                          off  = ((Q01 * x) * y + (Q02 * x) * z) + (Q12 * y) * z
+ *                          lin  = (Q03 * x + Q13 * y) + Q23 * z
+ *                          cost = (diag + 2.0 * off) + (2.0 * lin + Q33)
+ *                        The placement of least cost is taken, a tie goes to the lower code (a later code wins only with a
+ *                        strictly smaller cost).  A cost that is not finite, or with use_max_cost a cost > (double)max_cost,
+ *                        makes the edge no candidate.
+ *   5 validity           on the round's input alone.  LINK: the neighbour lists of lo and hi share exactly two vertices.
+ *                        VALENCE: both shared vertices have valence >= 4.  FLIP: every included face with s != 0 at lo or at
+ *                        hi that does not hold both is recomputed with that corner at the placement (n' as n above, from the
+ *                        face's own corner order); (nx * nx' + ny * ny') + nz * nz' must be > 0.
+ *   6 rank               the valid candidates in ascending (cost, hash, edge id): the cost as the uint64 of its bits made
+ *                        orderable (negative: all bits flipped, else the sign bit set), hash = (uint32)(((uint64)(lo << 24 |
+ *                        hi) * 0x9E3779B97F4A7C15) >> 32).  The rank of a candidate is its position in that order.
+ *   7 selection          GEOBI_DECIM_SWEEPS sweeps; every valid candidate starts LIVE, no vertex BLOCKED.  Per sweep: m1[v] =
+ *                        the least rank of a live candidate at v; m2[v] = the least m1 over v and its neighbours; a live
+ *                        candidate is SELECTED iff min(m2[lo], m2[hi]) is its own rank.  Then the ends of the sweep's
+ *                        selected edges and all their neighbours are blocked, and a candidate that was selected or has a
+ *                        blocked end is no longer live.  The ends of two selected edges are never in each other's closed
+ *                        rings, so no face, quadric or neighbour list that one collapse changes is read by the test of another.
+ *   8 budget             budget >= 0 is the face count to stop at: k = max(0, ceil((F_included - budget) / 2)) and only the
+ *                        first k selected edges in rank order COLLAPSE; budget < 0: all of them.
+ *   9 emit               hi merges into lo; the row of lo takes the placement.  The surviving rows keep their order
+ *                        (vertex_map [V]: input row -> output row, that of lo for a merged hi); vertex_parents [V', 2] = (v, v)
+ *                        or (lo, hi), place [V'] int8 = the code (0 for a row that merged nothing).  The two claimants of
+ *                        every collapsed edge and the faces that are not included go, the others keep their order and
+ *                        winding with their corners taken through vertex_map; face_map [F'] = the input face.
+ *   geobi_decim_plan     leaves the plan in `ws`; counts (device int32 [8]): [0] edges, [1] locked vertices, [2] valid
+ *                        candidates, [3] collapses, [4] V', [5] F', [6] faces not included, [7] sweeps that selected an edge.
+ *                        Nothing of the round is written yet.  F == 0 is valid (V' = V, F' = 0, no workspace needed).
+ *                        stage_ms (HOST float [3], normally NULL) is for measurement: the milliseconds of the tables (slots,
+ *                        corner keys, three sorts), of quadrics + candidates + rank, and of selection + budget + scans; the
+ *                        call then waits for its own end.
+ *   geobi_decim_emit     over the workspace of a plan of the same faces, points, F, V with the V' and F' read from its
+ *                        counts.  Vn, Fn are checked against what a plan of F, V can give (V - F / 2 <= Vn <= V, Fn <= F,
+ *                        F - Fn >= 2 (V - Vn)) before anything is written, and no row beyond them is ever written.
+ *   geobi_decim_points   out [Vn, 3]: the placements of a round replayed on another array other [V, 3] from its
+ *                        vertex_parents and place alone (code 0: other[a], 1: other[b], 2: 0.5f * other[a] + 0.5f *
+ *                        other[b]); parents outside [0, V) leave their row unwritten.  No workspace.                      */
+#define GEOBI_DECIM_SWEEPS 3
+size_t geobi_decim_ws_bytes(int64_t F, int64_t V);
+int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_max_cost, float max_cost,
+                     int64_t budget, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int64_t Vn, int64_t Fn,
+                     float* points_out, int32_t* faces_out, int32_t* face_map, int32_t* vertex_map,
+                     int32_t* vertex_parents, int8_t* place, const void* ws, size_t ws_bytes, void* stream);
+int geobi_decim_points(const float* other, int64_t V, int64_t Vn, const int32_t* vertex_parents, const int8_t* place,
+                       float* out, void* stream);
 
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
