@@ -17,6 +17,8 @@
   python -m geobi_gnn_amd subdivide --data_dir DIR [--out_dir DIR/subdivided] [--levels 1] [--scheme midpoint|loop]
   python -m geobi_gnn_amd subdivide --data_dir DIR (--max_edge L | --max_edge_diag R) [--max_rounds 16]
   python -m geobi_gnn_amd decimate --data_dir DIR [--out_dir DIR/decimated] (--ratio R | --faces N) [--max_cost C] [--max_rounds 256]
+  python -m geobi_gnn_amd remesh --data_dir DIR [--out_dir DIR/remeshed] [--target_edge L | --target_edge_diag R] [--iterations 5]
+                                 [--feature_angle 40] [--relax_lambda 0.5] [--max_rounds 64]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -579,6 +581,58 @@ def decimate(opt):
     return 1 if failed or not files else 0
 
 
+def _remesh_line(r, V, F, drift, out_file):
+    return ("V: %7d -> %7d,  F: %7d -> %7d,  in [low, high]: %5.1f%% -> %5.1f%%,  valence dev: %.3f -> %.3f,  "
+            "drift mean: %.3e,  max: %.3e,  '%s'"
+            % (V, r.points.shape[0], F, r.faces.shape[0], 100.0 * r.before['share'], 100.0 * r.after['share'],
+               r.before['valence_dev'], r.after['valence_dev'], drift[0], drift[1], os.path.basename(out_file)))
+
+
+def remesh(opt):
+    """Remesh every mesh of a folder on the device (meshremesh), with the folders of `decimate`: DIR/original/NAME.obj ->
+    OUT/original/NAME.obj if DIR/original exists, else DIR/*.obj -> OUT/NAME.obj.  Relaxation is no replayable map, so the
+    files of DIR/noisy are NOT carried along."""
+    import torch
+    from . import mesheval, meshin, meshio, meshremesh
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'remeshed')
+    original_dir = os.path.join(opt.data_dir, 'original')
+    paired = os.path.isdir(original_dir)
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
+    out_original = os.path.join(out_dir, 'original') if paired else out_dir
+    os.makedirs(out_original, exist_ok=True)
+    mode = ('target edge %g' % opt.target_edge if opt.target_edge is not None else
+            'target edge %g of the diagonal' % opt.target_edge_diag if opt.target_edge_diag is not None else
+            'target edge = the mean edge')
+    print('\nRemesh, %s, %d iterations, %d files ...\n' % (mode, opt.iterations, len(files)), flush=True)
+    if paired and os.path.isdir(os.path.join(opt.data_dir, 'noisy')):
+        print('noisy/ is not carried along: the relaxed vertices have no counterpart in a paired file.  Make new pairs '
+              'with `noise` on the output folder.\n', flush=True)
+    failed = 0
+    for path in files:
+        try:
+            points, faces = meshio.read_obj(path)
+            r = meshremesh.remesh(points, faces, target_edge=opt.target_edge, target_edge_diag=opt.target_edge_diag,
+                                  iterations=opt.iterations, feature_angle=opt.feature_angle, relax_lambda=opt.relax_lambda,
+                                  max_rounds=opt.max_rounds, device=dev)
+            out_file = os.path.join(out_original, os.path.basename(path))
+            meshio.write_obj(out_file, r.points.cpu().numpy(), r.faces.cpu().numpy())
+            drift = (0.0, 0.0)
+            if r.points.shape[0] and faces.shape[0]:         # the new vertices against the INPUT surface
+                with torch.cuda.device(dev):
+                    d = mesheval.point_to_mesh(r.points, *meshin.device_mesh(points, faces, dev))[0]
+                drift = (float(d.double().mean()), float(d.max()))
+            print(_remesh_line(r, points.shape[0], faces.shape[0], drift, out_file), flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d files skipped' % failed, file=sys.stderr)
+    return 1 if failed or not files else 0
+
+
 def _weld_tol_arg(text):
     v = float(text)
     if not (v >= 0.0 and v < float('inf')):
@@ -625,6 +679,20 @@ def _count_arg(text):
     v = int(text)
     if v < 0:
         raise argparse.ArgumentTypeError('a whole number, not negative, not %r' % text)
+    return v
+
+
+def _feature_angle_arg(text):
+    v = float(text)
+    if not (0.0 <= v <= 90.0 or v == 180.0):
+        raise argparse.ArgumentTypeError('degrees in [0, 90], or 180 for no feature edges, not %r' % text)
+    return v
+
+
+def _unit_arg(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError('a number in [0, 1], not %r' % text)
     return v
 
 
@@ -776,6 +844,22 @@ def build_parser():
     k.add_argument('--max_rounds', type=_at_least_one_arg, default=256, help='rounds at most')
     k.add_argument('--gpu', type=int, default=-1)
     k.set_defaults(fn=decimate)
+    r = sub.add_parser('remesh', help='make every mesh regular on the device: split long edges, collapse short ones, flip '
+                                      'towards valence 6, relax tangentially')
+    r.add_argument('--data_dir', type=str, required=True, help='holds original/, or the OBJ files themselves')
+    r.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/remeshed')
+    edge = r.add_mutually_exclusive_group()
+    edge.add_argument('--target_edge', type=_positive_arg, default=None, metavar='L',
+                      help='the edge length to aim at (default: the mean edge length of each mesh)')
+    edge.add_argument('--target_edge_diag', type=_positive_arg, default=None, metavar='R',
+                      help="--target_edge as R times the diagonal of the mesh's bounding box")
+    r.add_argument('--iterations', type=_count_arg, default=5, help='split / collapse / flip / relax iterations')
+    r.add_argument('--feature_angle', type=_feature_angle_arg, default=40.0, metavar='DEG',
+                   help='edges whose faces meet at more than DEG degrees (0 .. 90) keep their vertices; 180: none')
+    r.add_argument('--relax_lambda', type=_unit_arg, default=0.5, help='the step of the relaxation, in [0, 1]')
+    r.add_argument('--max_rounds', type=_at_least_one_arg, default=64, help='rounds at most in each inner loop')
+    r.add_argument('--gpu', type=int, default=-1)
+    r.set_defaults(fn=remesh)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)

@@ -16,8 +16,14 @@
 //   emit     one lane per vertex, per face and per output row
 // Every index is bounded: corners are below V (face_included), slots below 3F, vertices and faces taken out of a key were
 // put into it from such a corner or face, output rows are checked against the sizes the caller read from the counts.
+//
+// geobi_decim_plan_short is the same round with another candidate kernel: the cost is the squared length
+// of an edge below `low`, the placement follows the locks, and no neighbour may end up farther than `high`.
+#include <float.h>
+
 #include "common.h"
 #include "edge_table.h"
+#include "mesh_rings.h"
 #include "rocprim_temp.h"
 #include "stage_timer.h"
 #include "../../include/geobi_hip.h"
@@ -37,58 +43,12 @@ constexpr uint64_t kNoCost = ~0ull;                 // sorts last; the orderable
 enum State { kLive = 1, kSelected = 2 };
 enum Role { kPlain = -1, kMergedAway = 3 };         // 0, 1, 2: the `lo` of a collapsed edge, its placement code
 
-struct P3 { double x, y, z; };
-
-__device__ __forceinline__ P3 point_of(const float* __restrict__ points, int v) {
-  return {(double)points[3 * (size_t)v], (double)points[3 * (size_t)v + 1], (double)points[3 * (size_t)v + 2]};
-}
-
-// n = (b - a) x (c - a), every component two products and one subtraction; -> s = (nx nx + ny ny) + nz nz
-__device__ __forceinline__ double normal_of(const P3& a, const P3& b, const P3& c, P3& n) {
-#pragma clang fp contract(off)
-  const double ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z;
-  const double wx = c.x - a.x, wy = c.y - a.y, wz = c.z - a.z;
-  n.x = uy * wz - uz * wy;
-  n.y = uz * wx - ux * wz;
-  n.z = ux * wy - uy * wx;
-  return (n.x * n.x + n.y * n.y) + n.z * n.z;
-}
-
 __device__ __forceinline__ double cost_of(const double* q, const P3& p) {
 #pragma clang fp contract(off)
   const double diag = ((q[0] * p.x) * p.x + (q[4] * p.y) * p.y) + (q[7] * p.z) * p.z;
   const double off = ((q[1] * p.x) * p.y + (q[2] * p.x) * p.z) + (q[5] * p.y) * p.z;
   const double lin = (q[3] * p.x + q[6] * p.y) + q[8] * p.z;
   return (diag + 2.0 * off) + (2.0 * lin + q[9]);
-}
-
-__device__ __forceinline__ float midpoint(float a, float b) {
-#pragma clang fp contract(off)
-  return 0.5f * a + 0.5f * b;
-}
-
-// the first position of a sorted list that is not below x
-__device__ __forceinline__ int lower_bound(const uint64_t* __restrict__ a, int n, uint64_t x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-// a corner key v << 24 | f or a directed pair src << 24 | dst: the owner (2^24 - 1 for kNoEdge: never a vertex) and the
-// other field as an index (edge_table.h: index_from_key)
-__device__ __forceinline__ int owner_of(uint64_t key) { return (int)(key >> 24); }
-__device__ __forceinline__ int item_of(uint64_t key) { return index_from_key((int)(key & 0xffffffull)); }
-
-struct Run { bool head, two, three; };
-__device__ __forceinline__ Run run_at(const uint64_t* __restrict__ keys, int n, int i) {
-  const uint64_t key = keys[i];
-  Run r;
-  r.head = key != kNoEdge && (i == 0 || keys[i - 1] != key);
-  r.two = i + 1 < n && keys[i + 1] == key;
-  r.three = r.two && i + 2 < n && keys[i + 2] == key;
-  return r;
 }
 
 // ---- tables
@@ -164,24 +124,6 @@ __global__ void decim_quadrics_kernel(const float* __restrict__ points, const in
   count_lanes(is_locked, counts + kLocked);
 }
 
-// the faces at v other than those that hold both ends keep the side of their normal when v moves to `at`
-__device__ __forceinline__ bool no_flip(const float* __restrict__ points, const int* __restrict__ fv,
-                                        const uint64_t* __restrict__ corners, int n, int v, int other, const P3& at) {
-#pragma clang fp contract(off)
-  bool ok = true;
-  for (int j = lower_bound(corners, n, (uint64_t)v << 24); j < n && owner_of(corners[j]) == v; ++j) {
-    const int f = item_of(corners[j]);
-    const int c0 = fv[3 * (size_t)f], c1 = fv[3 * (size_t)f + 1], c2 = fv[3 * (size_t)f + 2];
-    if (c0 == other || c1 == other || c2 == other) continue;
-    const P3 a = point_of(points, c0), b = point_of(points, c1), c = point_of(points, c2);
-    P3 was, now;
-    if (normal_of(a, b, c, was) == 0.0) continue;
-    normal_of(c0 == v ? at : a, c1 == v ? at : b, c2 == v ? at : c, now);
-    if (!((was.x * now.x + was.y * now.y) + was.z * now.z > 0.0)) ok = false;
-  }
-  return ok;
-}
-
 // per sorted position: the head of an edge with two claimants whose ends are not both locked takes its placement and runs
 // the tests; cost_key = the orderable cost of a valid candidate (else kNoCost), hash, code, idx = the position itself
 __global__ void decim_candidates_kernel(const uint64_t* __restrict__ keys, int n, const float* __restrict__ points,
@@ -213,30 +155,80 @@ __global__ void decim_candidates_kernel(const uint64_t* __restrict__ keys, int n
         if (value < cost) { cost = value; code = c; }
       }
       valid = isfinite(cost) && !(use_max_cost != 0 && cost > max_cost);
-      if (valid) {                                  // link and valence: one merge walk over the two neighbour lists
-        int a = lower_bound(pairs, n_pairs, (uint64_t)lo << 24), b = lower_bound(pairs, n_pairs, (uint64_t)hi << 24);
-        int shared = 0;
-        while (a < n_pairs && b < n_pairs && owner_of(pairs[a]) == lo && owner_of(pairs[b]) == hi) {
-          const int da = item_of(pairs[a]), db = item_of(pairs[b]);
-          if (da == db) {
-            ++shared;
-            const int w = lower_bound(pairs, n_pairs, (uint64_t)da << 24);
-            if (!(w + 3 < n_pairs && owner_of(pairs[w + 3]) == da)) valid = false;     // valence below 4
-            ++a; ++b;
-          } else if (da < db) {
-            ++a;
-          } else {
-            ++b;
-          }
-        }
-        if (shared != 2) valid = false;
-      }
+      if (valid) valid = link_and_valence(pairs, n_pairs, lo, hi);
       if (valid) valid = no_flip(points, fv, corners, n, lo, hi, place[code]);
       if (valid) valid = no_flip(points, fv, corners, n, hi, lo, place[code]);
       if (valid) {
         const uint64_t bits = (uint64_t)__double_as_longlong(cost);
         ck = (bits >> 63) != 0 ? ~bits : bits | (1ull << 63);
       }
+    }
+    cost_key[i] = ck;
+    hash[i] = valid ? (uint32_t)((keys[i] * 0x9E3779B97F4A7C15ull) >> 32) : 0xffffffffu;
+    code_out[i] = code;
+    idx[i] = i;
+  }
+  count_lanes(valid, counts + kValid);
+}
+
+// ---- the short-edge collapse of 4p: the caller's lock flags join the unit's own; the locked vertices are counted here
+// (no quadrics are summed)
+__global__ void decim_join_lock_kernel(const int* __restrict__ lock, int V, int* __restrict__ locked,
+                                       int* __restrict__ counts) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  bool is_locked = false;
+  if (v < V) {
+    is_locked = locked[v] != 0 || (lock != nullptr && lock[v] != 0);
+    locked[v] = is_locked ? 1 : 0;
+  }
+  count_lanes(is_locked, counts + kLocked);
+}
+
+// no neighbour of v other than lo and hi lies farther than `high` from the placement (squared lengths, ascending id)
+__device__ __forceinline__ bool within_high(const float* __restrict__ points, const uint64_t* __restrict__ pairs,
+                                            int n_pairs, int v, int lo, int hi, const P3& at, double high2) {
+#pragma clang fp contract(off)
+  bool ok = true;
+  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j) {
+    const int w = item_of(pairs[j]);
+    if (w == lo || w == hi) continue;
+    const P3 p = point_of(points, w);
+    const double dx = p.x - at.x, dy = p.y - at.y, dz = p.z - at.z;
+    if ((dx * dx + dy * dy) + dz * dz > high2) ok = false;
+  }
+  return ok;
+}
+
+// the candidate kernel of geobi_decim_plan_short: the cost is the squared length, the placement is decided by the locks
+__global__ void decim_short_candidates_kernel(const uint64_t* __restrict__ keys, int n, const float* __restrict__ points,
+                                              const int* __restrict__ fv, const uint64_t* __restrict__ corners,
+                                              const uint64_t* __restrict__ pairs, int n_pairs,
+                                              const int* __restrict__ locked, double low2, double high2,
+                                              uint64_t* __restrict__ cost_key, uint32_t* __restrict__ hash,
+                                              int* __restrict__ code_out, int* __restrict__ idx, int* __restrict__ counts) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool valid = false;
+  if (i < n) {
+    const Run r = run_at(keys, n, i);
+    uint64_t ck = kNoCost;
+    int code = 0;
+    const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);      // meaningful at a head
+    if (r.head && r.two && !r.three && !(locked[lo] != 0 && locked[hi] != 0)) {
+      const float* pl = points + 3 * (size_t)lo;
+      const float* ph = points + 3 * (size_t)hi;
+      const double dx = (double)ph[0] - (double)pl[0], dy = (double)ph[1] - (double)pl[1], dz = (double)ph[2] - (double)pl[2];
+      const double len2 = (dx * dx + dy * dy) + dz * dz;
+      code = locked[lo] != 0 ? 0 : (locked[hi] != 0 ? 1 : 2);
+      const P3 at = code == 0 ? point_of(points, lo) : code == 1 ? point_of(points, hi) :
+                    P3{(double)midpoint(pl[0], ph[0]), (double)midpoint(pl[1], ph[1]), (double)midpoint(pl[2], ph[2])};
+      valid = len2 < low2;
+      if (valid) valid = within_high(points, pairs, n_pairs, lo, lo, hi, at, high2);
+      if (valid) valid = within_high(points, pairs, n_pairs, hi, lo, hi, at, high2);
+      if (valid) valid = link_and_valence(pairs, n_pairs, lo, hi);
+      if (valid) valid = no_flip(points, fv, corners, n, lo, hi, at);
+      if (valid) valid = no_flip(points, fv, corners, n, hi, lo, at);
+      if (valid) ck = (uint64_t)__double_as_longlong(len2) | (1ull << 63);          // len2 >= 0: orderable as in 4o
     }
     cost_key[i] = ck;
     hash[i] = valid ? (uint32_t)((keys[i] * 0x9E3779B97F4A7C15ull) >> 32) : 0xffffffffu;
@@ -273,24 +265,6 @@ __global__ void decim_m1_kernel(const uint64_t* __restrict__ keys, int n, const 
   if (i >= n || (state[i] & kLive) == 0) return;
   atomicMin(m1 + edge_key_lo(keys[i]), rank[i]);
   atomicMin(m1 + edge_key_hi(keys[i]), rank[i]);
-}
-
-__global__ void decim_m2_kernel(const int* __restrict__ m1, int V, const uint64_t* __restrict__ pairs, int n_pairs,
-                                int* __restrict__ m2) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  int m = m1[v];
-  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j) {
-    const int w = m1[item_of(pairs[j])];
-    m = w < m ? w : m;
-  }
-  m2[v] = m;
-}
-
-__device__ __forceinline__ void block_ring(const uint64_t* __restrict__ pairs, int n_pairs, int v, int* __restrict__ blocked) {
-  blocked[v] = 1;
-  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j)
-    blocked[item_of(pairs[j])] = 1;
 }
 
 // a live candidate whose rank is the least of the closed rings of both ends is selected and blocks those rings
@@ -483,26 +457,12 @@ int launch_points(const float* other, int64_t V, int64_t Vn, const int32_t* pare
   return 0;
 }
 
-}  // namespace
-
-}  // namespace geobi
-
-using namespace geobi;
-
-extern "C" {
-
-size_t geobi_decim_ws_bytes(int64_t F, int64_t V) {
-  if (sizes_ok("geobi_decim_ws_bytes", F > V ? F : V, 0) != 0 || (F < V ? F : V) < 0) return 0;
-  return carve_bytes([&](Arena& a) { carve_decim(a, F, V); });
-}
-
-int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_max_cost, float max_cost,
-                     int64_t budget, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
-  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(counts);
-  GEOBI_REQUIRE(use_max_cost == 0 || max_cost >= 0.0f, "decim_plan: max_cost = %g (not negative, not NaN)", (double)max_cost);
-  hipStream_t s = as_stream(stream);
+// one plan: the quadric costs of 4o, or with `sh` the squared lengths of the short-edge collapse of 4p; every kernel but
+// the candidate kernel (and the quadric sums it needs) is shared
+struct ShortEdges { const int* lock; float low, high; };
+int plan_round(const char* what, const int32_t* faces, const float* points, int64_t F, int64_t V, int use_max_cost,
+               float max_cost, int64_t budget, const ShortEdges* sh, int32_t* counts, float* stage_ms, void* ws,
+               size_t ws_bytes, hipStream_t s) {
   if (F == 0) {                                   // nothing to collapse: V' = V, F' = 0
     GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * kCounts, s));
     decim_no_faces_kernel<<<1, 1, 0, s>>>((int)V, counts);
@@ -510,7 +470,7 @@ int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64
     return 0;
   }
   DecimBuffers b;
-  GEOBI_TRY(carve_checked("decim_plan", F, V, ws, ws_bytes, b));
+  GEOBI_TRY(carve_checked(what, F, V, ws, ws_bytes, b));
   const int n = (int)(3 * F), n_pairs = 2 * n;
   const int k_budget = budget < 0 ? -1 : (int)(budget < F ? budget : F);
   size_t tb;
@@ -539,14 +499,26 @@ int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64
   GEOBI_HIP(rocprim::radix_sort_keys(b.pair_sort.p, tb, b.p_in, b.p_out, (size_t)n_pairs, 0u, kEdgeKeyBits, s, false));
   GEOBI_TRY(timer.mark());
   // ---- values and rank
-  if (V > 0) {
-    decim_quadrics_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.c_out, n, b.locked, b.Q, b.counts);
+  if (sh != nullptr) {
+    if (V > 0) {
+      decim_join_lock_kernel<<<cdiv(V, kT), kT, 0, s>>>(sh->lock, (int)V, b.locked, b.counts);
+      GEOBI_LAUNCH_OK();
+    }
+    decim_short_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, faces, b.c_out, b.p_out, n_pairs, b.locked,
+                                                            (double)sh->low * (double)sh->low,
+                                                            (double)sh->high * (double)sh->high, b.cost_key, b.hash_in,
+                                                            b.code, b.idx_in, b.counts);
+    GEOBI_LAUNCH_OK();
+  } else {
+    if (V > 0) {
+      decim_quadrics_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.c_out, n, b.locked, b.Q, b.counts);
+      GEOBI_LAUNCH_OK();
+    }
+    decim_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, faces, b.c_out, b.p_out, n_pairs, b.locked, b.Q,
+                                                      use_max_cost, (double)max_cost, b.cost_key, b.hash_in, b.code,
+                                                      b.idx_in, b.counts);
     GEOBI_LAUNCH_OK();
   }
-  decim_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, faces, b.c_out, b.p_out, n_pairs, b.locked, b.Q,
-                                                    use_max_cost, (double)max_cost, b.cost_key, b.hash_in, b.code,
-                                                    b.idx_in, b.counts);
-  GEOBI_LAUNCH_OK();
   tb = b.hash_sort.bytes;
   GEOBI_HIP(rocprim::radix_sort_pairs(b.hash_sort.p, tb, b.hash_in, b.hash_out, b.idx_in, b.idx_mid, (size_t)n, 0u, 32u, s,
                                       false));
@@ -563,7 +535,7 @@ int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64
     GEOBI_HIP(hipMemsetAsync(b.m1, 0x7f, sizeof(int) * (size_t)V, s));         // kNone
     decim_m1_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.state, b.rank, b.m1);
     GEOBI_LAUNCH_OK();
-    decim_m2_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.m1, (int)V, b.p_out, n_pairs, b.m2);
+    ring_min_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.m1, (int)V, b.p_out, n_pairs, b.m2);
     GEOBI_LAUNCH_OK();
     decim_select_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.rank, b.m2, b.p_out, n_pairs, b.state, b.blocked,
                                                   b.counts + kSweepBase + sweep);
@@ -592,6 +564,41 @@ int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64
   GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kCounts, hipMemcpyDeviceToDevice, s));
   GEOBI_TRY(timer.mark());
   return timer.finish();
+}
+
+}  // namespace
+
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+size_t geobi_decim_ws_bytes(int64_t F, int64_t V) {
+  if (sizes_ok("geobi_decim_ws_bytes", F > V ? F : V, 0) != 0 || (F < V ? F : V) < 0) return 0;
+  return carve_bytes([&](Arena& a) { carve_decim(a, F, V); });
+}
+
+int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_max_cost, float max_cost,
+                     int64_t budget, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(counts);
+  GEOBI_REQUIRE(use_max_cost == 0 || max_cost >= 0.0f, "decim_plan: max_cost = %g (not negative, not NaN)", (double)max_cost);
+  return plan_round("decim_plan", faces, points, F, V, use_max_cost, max_cost, budget, nullptr, counts, stage_ms, ws, ws_bytes,
+                    as_stream(stream));
+}
+
+int geobi_decim_plan_short(const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V, float low,
+                           float high, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(F > V ? F : V, 0);
+  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(counts);
+  GEOBI_REQUIRE(low > 0.0f && high >= low && high <= FLT_MAX,
+                "decim_plan_short: low = %g, high = %g (0 < low <= high, finite)", (double)low, (double)high);
+  const ShortEdges sh = {lock, low, high};
+  return plan_round("decim_plan_short", faces, points, F, V, 0, 0.0f, -1, &sh, counts, stage_ms, ws, ws_bytes,
+                    as_stream(stream));
 }
 
 int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int64_t Vn, int64_t Fn,

@@ -1,5 +1,5 @@
 // Device events at the stage borders of one call, for the measurement tools (tools/bench_topo.py, tools/bench_subdiv.py,
-// tools/bench_decim.py).
+// tools/bench_decim.py, tools/bench_remesh.py).
 #pragma once
 #include "common.h"
 

@@ -1,0 +1,318 @@
+"""Isotropic remeshing on the MI355X: make a mesh REGULAR -- edge lengths around one target length
+``L`` and valences near 6 -- by the loop of Botsch and Kobbelt.  One iteration splits the edges longer than ``high = 4/3 L``
+(``meshsubdiv.subdivide(max_edge=high)``), collapses the edges shorter than ``low = 0.8 L`` in rounds of independent
+collapses (the rounds of ``meshdecim`` ranked by length), flips edges towards the target valence in rounds of independent
+flips, and relaxes every free vertex once towards the mean of its neighbours inside its tangent plane.
+
+Vertices on a boundary, a complex edge or a feature edge (dihedral angle above ``feature_angle``) are locked: they keep
+their points, so boundaries and feature lines only get denser.  The relaxed vertices are NOT projected back onto the input
+surface, and relaxation is no replayable map: a paired point array cannot be carried along (use ``meshnoise`` on the
+result).
+
+The rules are stated in include/geobi_hip.h (geobi_remesh_lock, geobi_decim_plan_short, geobi_flip_*, geobi_relax); the
+topology is integer-exact and the result reproducible bit for bit (tests/remesh_model.py).  No CPU fallback.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import meshdecim, meshin, meshsubdiv
+
+MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h
+LOCK_KEYS = ('edges', 'boundary_vertices', 'sharp_edges', 'sharp_vertices')
+FLIP_KEYS = ('edges', 'candidates', 'valid', 'flips', 'sweeps_selected')
+RELAX_KEYS = ('moved', 'refused', 'reverted', 'turned')
+ITERATION_KEYS = ('splits', 'split_passes', 'collapses', 'collapse_rounds', 'flips', 'flip_rounds', 'moved', 'refused',
+                  'reverted', 'turned')
+
+
+class Remeshed(object):
+    """points [V', 3] float32 and faces [F', 3] int32 on the device; low, high: the float32 band; per_iteration: one dict of
+    ITERATION_KEYS per iteration; before, after: the statistics of input and output (``mesh_stats``)."""
+
+    def __init__(self, points, faces, low, high, per_iteration, before, after):
+        self.points, self.faces, self.low, self.high = points, faces, low, high
+        self.per_iteration, self.before, self.after = per_iteration, before, after
+
+
+def _whole(value):
+    return not isinstance(value, bool) and isinstance(value, (int, np.integer))
+
+
+def _number(name, value, what):
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('remesh: %s = %r (%s)' % (name, value, what))
+    if not math.isfinite(value):
+        raise ValueError('remesh: %s = %r (%s)' % (name, value, what))
+    return value
+
+
+def cos2(feature_angle):
+    """-> (use_sharp, c2): the fp64 cos^2 of the feature angle in degrees; 180 switches the sharp test off"""
+    if feature_angle == 180.0:
+        return 0, 0.0
+    c = math.cos(math.radians(feature_angle))
+    return 1, c * c
+
+
+def band(target_edge):
+    """-> (low, high) as the float32 values the device compares with: float32(0.8 * L) and float32(4.0 * L / 3.0), the
+    products and the quotient in fp64"""
+    edge = float(target_edge)
+    with np.errstate(over='ignore'):
+        return float(np.float32(0.8 * edge)), float(np.float32(4.0 * edge / 3.0))
+
+
+def check_band(low, high, what='remesh'):
+    low, high = _number('low', low, 'a positive length'), _number('high', high, 'a length, at least low')
+    with np.errstate(over='ignore'):
+        low, high = float(np.float32(low)), float(np.float32(high))
+    if not (0.0 < low <= high and math.isfinite(high)):
+        raise ValueError('%s: low = %r, high = %r (0 < low <= high, finite as float32)' % (what, low, high))
+    return low, high
+
+
+def check_args(target_edge=None, target_edge_diag=None, iterations=5, feature_angle=40.0, relax_lambda=0.5, max_rounds=64):
+    """ValueError for what ``remesh`` does not take; -> (target_edge or None, target_edge_diag or None, feature_angle,
+    relax_lambda) as Python floats."""
+    if not _whole(iterations) or iterations < 0:
+        raise ValueError('remesh: iterations = %r (a whole number, not negative)' % (iterations,))
+    if not _whole(max_rounds) or max_rounds < 1:
+        raise ValueError('remesh: max_rounds = %r (a whole number, at least 1)' % (max_rounds,))
+    if target_edge is not None and target_edge_diag is not None:
+        raise ValueError('remesh: target_edge and target_edge_diag exclude each other')
+    for name, value in (('target_edge', target_edge), ('target_edge_diag', target_edge_diag)):
+        if value is not None and not _number(name, value, 'a positive length') > 0.0:
+            raise ValueError('remesh: %s = %r (a positive length)' % (name, value))
+    feature_angle = _number('feature_angle', feature_angle, 'degrees in [0, 90], or 180 for no feature edges')
+    if not (0.0 <= feature_angle <= 90.0 or feature_angle == 180.0):
+        raise ValueError('remesh: feature_angle = %r (degrees in [0, 90], or 180 for no feature edges)' % (feature_angle,))
+    relax_lambda = _number('relax_lambda', relax_lambda, 'in [0, 1]')
+    if not 0.0 <= relax_lambda <= 1.0:
+        raise ValueError('remesh: relax_lambda = %r (in [0, 1])' % (relax_lambda,))
+    return (None if target_edge is None else float(target_edge), None if target_edge_diag is None else float(target_edge_diag),
+            feature_angle, relax_lambda)
+
+
+def bbox_diagonal(points):
+    """the diagonal of the bounding box of points [V, 3], in fp64 on the host (0 without points): the value of
+    ``subdivide --max_edge_diag``"""
+    p = np.asarray(torch.as_tensor(points).detach().cpu().numpy() if torch.is_tensor(points) else points,
+                   dtype=np.float64).reshape(-1, 3)
+    return float(np.sqrt(((p.max(axis=0) - p.min(axis=0)) ** 2).sum())) if p.shape[0] else 0.0
+
+
+def _mesh(points, faces, device, what):
+    pts, fv = meshin.device_mesh(points, faces, device, what='%s: faces' % what, error=ValueError)
+    if max(pts.shape[0], fv.shape[0]) > MAX_NODES:
+        raise ValueError('%s: %d vertices and %d faces, beyond GEOBI_MAX_NODES = %d' % (what, pts.shape[0], fv.shape[0], MAX_NODES))
+    if pts.shape[0] > 0 and not bool(torch.isfinite(pts).all()):
+        raise ValueError('%s: non-finite point coordinates' % what)
+    return pts, fv
+
+
+def _workspace(fv, pts):
+    return L.workspace(L.size_query('geobi_remesh_ws_bytes', fv.shape[0], pts.shape[0]), fv.device)
+
+
+def _lock(fv, pts, use_sharp, c2):
+    F, V = fv.shape[0], pts.shape[0]
+    lock = torch.zeros(V, dtype=torch.int32, device=fv.device)
+    counts = torch.zeros(4, dtype=torch.int32, device=fv.device)
+    if F == 0:                                      # no edge: no flag (and no pointer to hand over)
+        return lock, counts
+    ws = _workspace(fv, pts)
+    L.call('geobi_remesh_lock', L.ptr(fv), L.ptr(pts), F, V, use_sharp, c2, L.ptr(lock), L.ptr(counts), L.ptr(ws), ws.numel(),
+           L.stream())
+    return lock, counts
+
+
+def _plan_short(fv, pts, lock, low, high, stage_ms=None):
+    """geobi_decim_plan_short on a device mesh -> (workspace, the eight counts of meshdecim); one wait"""
+    F, V = fv.shape[0], pts.shape[0]
+    ws = L.workspace(L.size_query('geobi_decim_ws_bytes', F, V), fv.device)
+    counts = torch.zeros(8, dtype=torch.int32, device=fv.device)
+    L.call('geobi_decim_plan_short', L.ptr(fv), L.ptr(pts), L.ptr(lock), F, V, low, high, L.ptr(counts), stage_ms, L.ptr(ws),
+           ws.numel(), L.stream())
+    return ws, dict(zip(meshdecim.COUNT_KEYS, L.read_i32(counts, 8)))
+
+
+def _flip_plan(fv, pts, lock, use_sharp, c2, stage_ms=None):
+    F, V = fv.shape[0], pts.shape[0]
+    ws = _workspace(fv, pts)
+    counts = torch.zeros(5, dtype=torch.int32, device=fv.device)
+    L.call('geobi_flip_plan', L.ptr(fv), L.ptr(pts), L.ptr(lock), F, V, use_sharp, c2, L.ptr(counts), stage_ms, L.ptr(ws),
+           ws.numel(), L.stream())
+    return ws, dict(zip(FLIP_KEYS, L.read_i32(counts, 5)))
+
+
+def _flip_emit(fv, V, ws):
+    out = torch.empty_like(fv)
+    L.call('geobi_flip_emit', L.ptr(fv), fv.shape[0], V, L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
+    return out
+
+
+def _relax(fv, pts, lock, relax_lambda, stage_ms=None):
+    F, V = fv.shape[0], pts.shape[0]
+    ws = _workspace(fv, pts)
+    out = torch.empty_like(pts)
+    counts = torch.zeros(4, dtype=torch.int32, device=fv.device)
+    L.call('geobi_relax', L.ptr(fv), L.ptr(pts), L.ptr(lock), F, V, relax_lambda, L.ptr(out), L.ptr(counts), stage_ms, L.ptr(ws),
+           ws.numel(), L.stream())
+    return out, dict(zip(RELAX_KEYS, L.read_i32(counts, 4)))
+
+
+# ---------------------------------------------------------------------------------------------- the single steps
+def lock_flags(points, faces, feature_angle=40.0, device=None):
+    """-> (lock [V] int32 on the device, counts): bit 0 for a vertex on a boundary or complex edge, bit 1 for a vertex on
+    an edge whose faces meet at more than ``feature_angle`` degrees (180: no such edge)."""
+    feature_angle = check_args(feature_angle=feature_angle)[2]
+    pts, fv = _mesh(points, faces, device, 'lock_flags')
+    with torch.cuda.device(pts.device):
+        lock, counts = _lock(fv, pts, *cos2(feature_angle))
+        return lock, dict(zip(LOCK_KEYS, L.read_i32(counts, 4)))
+
+
+def _as_lock(lock, V, dev):
+    if lock is None:
+        return None
+    lock = meshin.to_device(lock, dev, torch.int32)
+    if lock.dim() != 1 or lock.shape[0] != V:
+        raise ValueError('lock %s for %d vertices' % (tuple(lock.shape), V))
+    return lock
+
+
+def collapse_short(points, faces, low, high, lock=None, device=None):
+    """ONE round of short-edge collapses -> (points', faces', counts of ``meshdecim``): the edges shorter than ``low`` whose
+    collapse makes no edge longer than ``high``; a vertex with a lock entry other than 0 keeps its point."""
+    low, high = check_band(low, high, 'collapse_short')
+    pts, fv = _mesh(points, faces, device, 'collapse_short')
+    lock = _as_lock(lock, pts.shape[0], pts.device)
+    with torch.cuda.device(pts.device):
+        if fv.shape[0] == 0:
+            return pts, fv, dict(dict.fromkeys(meshdecim.COUNT_KEYS, 0), V=pts.shape[0])
+        ws, c = _plan_short(fv, pts, lock, low, high)
+        if c['collapses'] == 0 and c['not_included'] == 0:
+            return pts, fv, c
+        out = meshdecim._emit(fv, pts, c['V'], c['F'], ws)
+        return out[0], out[1], c
+
+
+def flip_edges(points, faces, lock=None, feature_angle=40.0, device=None):
+    """ONE round of edge flips towards valence 6 (4 on a boundary) -> (faces', counts).  lock: the flags of ``lock_flags``
+    (computed here when None)."""
+    feature_angle = check_args(feature_angle=feature_angle)[2]
+    pts, fv = _mesh(points, faces, device, 'flip_edges')
+    use_sharp, c2 = cos2(feature_angle)
+    with torch.cuda.device(pts.device):
+        if fv.shape[0] == 0:
+            return fv, dict.fromkeys(FLIP_KEYS, 0)
+        lock = _as_lock(lock, pts.shape[0], pts.device) if lock is not None else _lock(fv, pts, use_sharp, c2)[0]
+        ws, c = _flip_plan(fv, pts, lock, use_sharp, c2)
+        return (_flip_emit(fv, pts.shape[0], ws) if c['flips'] else fv), c
+
+
+def relax(points, faces, lock=None, relax_lambda=0.5, feature_angle=40.0, device=None):
+    """ONE tangential relaxation -> (points', counts).  lock: the flags of ``lock_flags`` (computed here when None)."""
+    _, _, feature_angle, relax_lambda = check_args(feature_angle=feature_angle, relax_lambda=relax_lambda)
+    pts, fv = _mesh(points, faces, device, 'relax')
+    with torch.cuda.device(pts.device):
+        if fv.shape[0] == 0:
+            return pts, dict.fromkeys(RELAX_KEYS, 0)
+        lock = _as_lock(lock, pts.shape[0], pts.device) if lock is not None else _lock(fv, pts, *cos2(feature_angle))[0]
+        return _relax(fv, pts, lock, relax_lambda)
+
+
+def mesh_stats(points, faces, low, high, device=None):
+    """The regularity of a mesh: edges, edge_min / edge_mean / edge_max (fp64), inside and share (the edges with low <=
+    length <= high), valence_hist (valence 3 .. 11 and 12+), valence_dev (the mean |valence - target| over the vertices
+    with an edge, target 4 on a boundary or complex edge, else 6)."""
+    pts, fv = _mesh(points, faces, device, 'mesh_stats')
+    F, V, dev = fv.shape[0], pts.shape[0], pts.device
+    with torch.cuda.device(dev):
+        lens = torch.full((3 * F,), -1.0, dtype=torch.float64, device=dev)
+        valence = torch.zeros(V, dtype=torch.int32, device=dev)
+        if F > 0:
+            ws = _workspace(fv, pts)
+            L.call('geobi_remesh_stats', L.ptr(fv), L.ptr(pts), F, V, L.ptr(lens), L.ptr(valence), L.ptr(ws), ws.numel(),
+                   L.stream())
+        lock = _lock(fv, pts, 0, 0.0)[0]
+        lens = lens[lens >= 0.0]
+        E = int(lens.shape[0])
+        valence = valence.long()
+        used = valence > 0
+        target = torch.where((lock & 1) != 0, 4, 6)
+        hist = torch.bincount(valence.clamp(max=12), minlength=13)[3:].tolist()
+        inside = int(((lens >= low) & (lens <= high)).sum()) if E else 0
+        return {'edges': E, 'edge_min': float(lens.min()) if E else 0.0, 'edge_mean': float(lens.mean()) if E else 0.0,
+                'edge_max': float(lens.max()) if E else 0.0, 'inside': inside, 'share': inside / E if E else 0.0,
+                'valence_hist': [int(x) for x in hist],
+                'valence_dev': float((valence - target).abs()[used].double().mean()) if bool(used.any()) else 0.0}
+
+
+# ---------------------------------------------------------------------------------------------- the whole call
+def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5, feature_angle=40.0, relax_lambda=0.5,
+           max_rounds=64, device=None):
+    """(points [V, 3], faces [F, 3]) -> Remeshed.  The target edge length L is ``target_edge``, or ``target_edge_diag`` times
+    the diagonal of the bounding box, or by default the mean edge length of the input (``meshnoise.MeshGeometry``).  Every
+    iteration runs: splits of the edges above high = 4/3 L to exhaustion, rounds of short-edge collapses (below low = 0.8
+    L) until a round collapses nothing, rounds of flips until a round flips nothing, one relaxation.  ValueError: shapes
+    other than [V, 3] and [F, 3], a face index outside [0, V), non-finite points, arguments outside their range;
+    GeobiError: ``max_rounds`` rounds did not end one of the three inner loops."""
+    target_edge, target_edge_diag, feature_angle, relax_lambda = check_args(target_edge, target_edge_diag, iterations,
+                                                                            feature_angle, relax_lambda, max_rounds)
+    pts, fv = _mesh(points, faces, device, 'remesh')
+    dev = pts.device
+    use_sharp, c2 = cos2(feature_angle)
+    with torch.cuda.device(dev):
+        if target_edge is None and target_edge_diag is not None:
+            target_edge = target_edge_diag * bbox_diagonal(pts)
+        elif target_edge is None:
+            from . import meshnoise
+            target_edge = meshnoise.MeshGeometry(pts, fv, dev).mean_edge if fv.shape[0] > 0 else 1.0
+        low, high = band(target_edge)
+        if not (0.0 < low <= high and math.isfinite(high)):
+            raise ValueError('remesh: the target edge length %r gives the band [%r, %r]' % (target_edge, low, high))
+        before = mesh_stats(pts, fv, low, high, dev)
+        per_iteration = []
+        for _ in range(iterations):
+            c = dict.fromkeys(ITERATION_KEYS, 0)
+            refined = meshsubdiv.subdivide(pts, fv, max_edge=high, max_rounds=max_rounds, device=dev)
+            pts, fv = refined.points, refined.faces
+            c['splits'], c['split_passes'] = refined.counts['split'], refined.counts['passes']
+            lock = None                             # recomputed whenever the mesh has changed
+            while fv.shape[0] > 0:
+                lock = _lock(fv, pts, use_sharp, c2)[0]
+                ws, r = _plan_short(fv, pts, lock, low, high)
+                if r['collapses'] == 0 and r['not_included'] == 0:
+                    break
+                if c['collapse_rounds'] == max_rounds:
+                    raise L.GeobiError('remesh: edges below low = %g still collapse after max_rounds = %d rounds'
+                                       % (low, max_rounds))
+                pts, fv = meshdecim._emit(fv, pts, r['V'], r['F'], ws)[:2]
+                lock = None
+                c['collapse_rounds'] += 1
+                c['collapses'] += r['collapses']
+                if r['collapses'] == 0:
+                    break
+            while fv.shape[0] > 0:
+                lock = lock if lock is not None else _lock(fv, pts, use_sharp, c2)[0]
+                ws, r = _flip_plan(fv, pts, lock, use_sharp, c2)
+                if r['flips'] == 0:
+                    break
+                if c['flip_rounds'] == max_rounds:
+                    raise L.GeobiError('remesh: edges still flip after max_rounds = %d rounds' % max_rounds)
+                fv, lock = _flip_emit(fv, pts.shape[0], ws), None
+                c['flip_rounds'] += 1
+                c['flips'] += r['flips']
+            if fv.shape[0] > 0:
+                lock = lock if lock is not None else _lock(fv, pts, use_sharp, c2)[0]
+                pts, r = _relax(fv, pts, lock, relax_lambda)
+                c.update(r)
+            per_iteration.append(c)
+        after = mesh_stats(pts, fv, low, high, dev)
+    return Remeshed(pts, fv, np.float32(low), np.float32(high), per_iteration, before, after)

@@ -12,8 +12,8 @@
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
  *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
  *     (reads its undecided counts through it), geobi_topo_orient / _components / _report (read the changed flags of
- *     their rounds through it), geobi_subdiv_plan and geobi_decim_plan with stage_ms (wait for their own end; without
- *     it the plan is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
+ *     their rounds through it), geobi_subdiv_plan, geobi_decim_plan, geobi_decim_plan_short, geobi_flip_plan and geobi_relax
+ *     with stage_ms (wait for their own end; without it the call is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -887,6 +887,79 @@ int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64
                      int32_t* vertex_parents, int8_t* place, const void* ws, size_t ws_bytes, void* stream);
 int geobi_decim_points(const float* other, int64_t V, int64_t Vn, const int32_t* vertex_parents, const int8_t* place,
                        float* out, void* stream);
+
+/* ---------------------------------------------------------------- isotropic remeshing (split, collapse, flip, relax) ----
+ * Makes a triangle mesh REGULAR: edge lengths inside [low, high] around a target length and valences near
+ * 6, by the loop of Botsch and Kobbelt; no counterpart in the reference.  The split step is geobi_subdiv_* with max_edge =
+ * high; the entry points below are the other three steps and the lock flags they share.  As in 4n / 4o the topology is
+ * integer-exact, every float step is fp64 from the float32 inputs in ONE stated order (no contraction, no float atomics;
+ * sqrt and / are the correctly rounded ones), nothing depends on launch geometry: tests/remesh_model.py restates these rules
+ * sequentially and reproduces every output bit.  faces [F, 3] int32 index [0, V), points [V, 3] float32 finite; V, F <=
+ * GEOBI_MAX_NODES.  The edge table, INCLUDED faces, n_e, edge ids, NEIGHBOURS (ascending id) and valence are those of
+ * geobi_decim_* (rules 1 and 2 there); the normal n of a face (p, q, r) and s = |n|^2 are those of its rule 3, from the
+ * corners in the order given; (u . w) = (ux * wx + uy * wy) + uz * wz.  len2 of an edge is that of geobi_subdiv_*: d = hi -
+ * lo in fp64 from the float32 coordinates, (dx * dx + dy * dy) + dz * dz.
+ *   LOCK FLAGS   geobi_remesh_lock: lock [V] int32.  Bit 0: the vertex has an edge with n_e != 2 (boundary or complex).  Bit
+ *                1: it has a SHARP edge.  An edge is sharp when n_e == 2 and, with n0, n1 the normals of its claimants in
+ *                ascending slot order, each from its face's own row, s0 != 0 and s1 != 0 and dot = (n0 . n1) is not > 0 or
+ *                dot * dot < c2 * (s0 * s1).  c2 is the fp64 cos^2 of the feature angle, formed by the caller; use_sharp = 0
+ *                (a feature angle of 180 degrees) makes no edge sharp.  counts (device int32 [4]): edges, vertices with bit
+ *                0, sharp edges, vertices with bit 1.
+ *   SHORT-EDGE COLLAPSE   geobi_decim_plan_short: one round of geobi_decim_* with another rule 4; rules 1, 2, 5 (link,
+ *                valence, flip), 6, 7, 9, the counts, geobi_decim_emit and geobi_decim_points are unchanged, there is no
+ *                budget and no quadric.  A vertex is LOCKED by rule 2 or when its entry of `lock` (may be NULL) is not 0.
+ *                Candidate: n_e == 2, the ends not both locked, len2 < (double)low * (double)low.  Placement: code 0 when lo
+ *                is locked, else code 1 when hi is locked, else code 2.  HIGH test, before the tests of rule 5: for every
+ *                neighbour w of lo and then of hi, other than lo and hi, d = w - placement in fp64; (dx * dx + dy * dy) + dz *
+ *                dz > (double)high * (double)high refuses the edge.  The cost of rule 6 is len2.  0 < low <= high, finite.
+ *   FLIPS        geobi_flip_plan / geobi_flip_emit, one ROUND.  The TARGET valence of a vertex is 4 with lock bit 0, else 6.
+ *     candidate  an edge (a, b) = (lo, hi) with n_e == 2 whose claimants walk it in opposite directions (the direction bits
+ *                of the slots differ) and which is not sharp (as above, with the use_sharp and c2 given).  c is the third
+ *                corner of the face that walks lo -> hi, d that of the other; c != d.  gain = before - after, before the sum
+ *                of |valence - target| over a, b, c, d, after the same with the valences of a, b one lower and of c, d one
+ *                higher.  Only gain > 0 is a candidate.
+ *     validity   on the round's input: the edge (c, d) does not exist; a and b have valence >= 4 (>= 3 afterwards); with
+ *                n0 = n(a, b, c), n1 = n(b, a, d) the old and m0 = n(a, d, c), m1 = n(b, c, d) the new normals, (n0 . m0),
+ *                (n0 . m1), (n1 . m0), (n1 . m1) and (m0 . m1) are all > 0.
+ *     rank       the valid candidates in ascending (16 - gain, hash, edge id), the hash that of geobi_decim_* rule 6.
+ *     selection  GEOBI_FLIP_SWEEPS sweeps of rule 7 of geobi_decim_* over the FOUR quad vertices: m1[v] = the least rank of
+ *                a live candidate with v among a, b, c, d; m2[v] = the least m1 over v and its neighbours; a live candidate
+ *                is SELECTED iff the least m2 of its four vertices is its own rank.  Then the four vertices of the sweep's
+ *                selected candidates and all their neighbours are blocked, and a candidate that was selected or has a blocked
+ *                quad vertex is no longer live.  No quad vertex of a selected flip lies in the closed ring of a quad vertex
+ *                of another: two flips share no face, create different diagonals and change no valence the other counted.
+ *     emit       faces_out [F, 3]: the row of the face that walked lo -> hi becomes (a, d, c), the row of the other (b, c,
+ *                d); every other row is copied.  V, F, the points and the row order stay.
+ *     counts     (device int32 [5]) edges, candidates (gain > 0), valid, flips, sweeps that selected.  stage_ms (HOST float
+ *                [3], normally NULL): tables, candidates + rank, selection; the call then waits for its own end.
+ *   RELAXATION   geobi_relax, Jacobi: reads points, writes points_out.  A vertex with a lock entry != 0 or valence < 3
+ *                keeps its bits.  Else g_k = (the fp64 sum, from +0.0, of the neighbours' coordinate k in ascending id) /
+ *                (double)valence; n = the componentwise fp64 sum, from +0.0, of the normals of its included faces in
+ *                ascending face id, each from the face's own row; s = (n . n); s == 0: the vertex stays.  d = g - p, q = (n .
+ *                d) / s, t_k = d_k - n_k * q, p'_k = (float)(p_k + lambda * t_k), lambda a double in [0, 1].  A p' equal
+ *                to p in all three float32 values stays and is not counted; a p' that is not finite, or that fails the
+ *                FLIP test of geobi_decim_* rule 5 over ALL included faces at the vertex with the other corners at their OLD positions, is REFUSED;
+ *                every other vertex MOVES.  Then every included face with s != 0 whose normal from all three NEW positions
+ *                has (n_old . n_new) not > 0 puts its moved vertices back to their old bits (REVERTED, no cascade), and the
+ *                faces for which that still holds afterwards are counted (TURNED) and left.  counts (device int32 [4]):
+ *                moved (before the revert), refused, reverted, turned.  stage_ms (HOST float [2]): tables, the four launches.
+ *   geobi_remesh_stats   for reports: edge_len (device fp64 [3F]) = sqrt(len2) of every edge at the sorted position of its
+ *                head, -1 elsewhere; valence [V].  Written for F, V > 0.
+ * One workspace size serves all five entry points of this unit; F == 0 is valid everywhere (nothing flips, nothing moves). */
+#define GEOBI_FLIP_SWEEPS 3
+size_t geobi_remesh_ws_bytes(int64_t F, int64_t V);
+int geobi_remesh_lock(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_sharp, double c2,
+                      int32_t* lock, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+int geobi_decim_plan_short(const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V, float low,
+                           float high, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_flip_plan(const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V, int use_sharp,
+                    double c2, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_flip_emit(const int32_t* faces, int64_t F, int64_t V, int32_t* faces_out, const void* ws, size_t ws_bytes,
+                    void* stream);
+int geobi_relax(const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V, double lambda,
+                float* points_out, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_remesh_stats(const int32_t* faces, const float* points, int64_t F, int64_t V, void* edge_len, int32_t* valence,
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
