@@ -8,7 +8,8 @@
 //            (rocPRIM), run heads flagged, group numbers by a scan of the flags, every member takes its run's head --
 //            the LOWEST index of the run, because the sort is stable
 //   faces    corners through canon, degenerate faces marked, the 3F half-edges (a << 24 | b) sorted stably with their
-//            slot 3f + k as value: a run lists the claimants of one half-edge in ascending face order.  Kept / dropped is
+//            slot 3f + k as value (the buffers and the sort of edge_table.h; the slots are filled here, DIRECTED): a run
+//            lists the claimants of one half-edge in ascending face order.  Kept / dropped is
 //            resolved in JACOBI rounds over ping-pong state: an undecided face walks the EARLIER claimants of its three
 //            runs in the previous round's state -- one kept: dropped; all dropped: kept; else still undecided.  The lowest
 //            undecided face is decided in every round, so the loop ends; the states a round reads are the previous
@@ -16,7 +17,7 @@
 //   compact  used flags by plain stores of one value, two exclusive scans, gathers
 // The only floating-point operation is the division of the grid key.
 #include "common.h"
-#include "rocprim_temp.h"
+#include "edge_table.h"
 #include "../../include/geobi_hip.h"
 
 namespace geobi {
@@ -221,13 +222,11 @@ WeldBuffers carve_weld(Arena& a, int64_t V) {
 }
 
 struct FaceBuffers {
-  uint64_t *k_in, *k_out;
-  int *v_in, *v_out, *pos, *state_b, *counters;
-  SubWs sort_temp;
+  MeshTables t;                      // the edge table alone, here over DIRECTED half-edges: face_remap_kernel fills it
+  int *pos, *state_b, *counters;
 };
 FaceBuffers carve_faces(Arena& a, int64_t F) {
-  return {a.take<uint64_t>(3 * F), a.take<uint64_t>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F),
-          a.take<int>(F), a.take<int>(1 + kBatch), a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(3 * F, kEdgeKeyBits))};
+  return {carve_tables<false, false>(a, F), a.take<int>(3 * F), a.take<int>(F), a.take<int>(1 + kBatch)};
 }
 
 struct CompactBuffers {
@@ -264,9 +263,8 @@ int geobi_clean_weld(const float* points, int64_t V, int mode, float weld_tol, i
     GEOBI_LAUNCH_OK();
     return 0;
   }
-  Arena a(ws, ws_bytes);
-  const WeldBuffers w = carve_weld(a, V);
-  GEOBI_WS_CHECK("clean_weld", a, ws, ws_bytes);
+  WeldBuffers w;
+  GEOBI_TRY(carve_checked("clean_weld", ws, ws_bytes, w, [&](Arena& a) { return carve_weld(a, V); }));
   GEOBI_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), s));
   weld_keys_kernel<<<blocks, kT, 0, s>>>(points, n, mode, weld_tol, w.kx, w.ky, w.kz, w.idx, w.bad);
   GEOBI_LAUNCH_OK();
@@ -303,18 +301,15 @@ int geobi_clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int
   hipStream_t s = as_stream(stream);
   *rounds = 0;
   if (F == 0) return 0;
-  Arena a(ws, ws_bytes);
-  const FaceBuffers b = carve_faces(a, F);
-  GEOBI_WS_CHECK("clean_faces", a, ws, ws_bytes);
+  FaceBuffers b;
+  GEOBI_TRY(carve_checked("clean_faces", ws, ws_bytes, b, [&](Arena& a) { return carve_faces(a, F); }));
   const int n = (int)F, blocks = cdiv(F, kT);
   GEOBI_HIP(hipMemsetAsync(b.counters, 0, sizeof(int), s));
-  face_remap_kernel<<<blocks, kT, 0, s>>>(faces, canon, n, (int)V, manifold, faces_canon, state, b.k_in, b.v_in, b.counters);
+  face_remap_kernel<<<blocks, kT, 0, s>>>(faces, canon, n, (int)V, manifold, faces_canon, state, b.t.k_in, b.t.v_in, b.counters);
   GEOBI_LAUNCH_OK();
   if (!manifold) return 0;
-  size_t tb = b.sort_temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
-                                      s, false));
-  slot_position_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.v_out, 3 * n, b.pos);
+  GEOBI_TRY(sort_edge_table(b.t, F, s));
+  slot_position_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.t.v_out, 3 * n, b.pos);
   GEOBI_LAUNCH_OK();
   int* cur = state;
   int* other = b.state_b;
@@ -325,7 +320,7 @@ int geobi_clean_faces(const int32_t* faces, const int32_t* canon, int64_t F, int
     const int batch = left < want ? left : want;
     GEOBI_HIP(hipMemsetAsync(b.counters + 1, 0, sizeof(int) * batch, s));
     for (int r = 0; r < batch; ++r) {
-      face_round_kernel<<<blocks, kT, 0, s>>>(b.k_out, b.v_out, b.pos, cur, other, n, b.counters + 1 + r);
+      face_round_kernel<<<blocks, kT, 0, s>>>(b.t.k_out, b.t.v_out, b.pos, cur, other, n, b.counters + 1 + r);
       GEOBI_LAUNCH_OK();
       int* t = cur; cur = other; other = t;
     }
@@ -357,9 +352,8 @@ int geobi_clean_compact(const float* points, const int32_t* faces_canon, const i
   GEOBI_NOTNULL(points_out); GEOBI_NOTNULL(faces_out);
   GEOBI_NOTNULL(vertex_map); GEOBI_NOTNULL(vertex_src); GEOBI_NOTNULL(face_map); GEOBI_NOTNULL(counts);
   hipStream_t s = as_stream(stream);
-  Arena a(ws, ws_bytes);
-  const CompactBuffers c = carve_compact(a, V, F);
-  GEOBI_WS_CHECK("clean_compact", a, ws, ws_bytes);
+  CompactBuffers c;
+  GEOBI_TRY(carve_checked("clean_compact", ws, ws_bytes, c, [&](Arena& a) { return carve_compact(a, V, F); }));
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 5, s));
   GEOBI_HIP(hipMemsetAsync(c.used, 0, sizeof(int) * (size_t)(V + 1), s));
   compact_mark_kernel<<<cdiv(F + 1, kT), kT, 0, s>>>(faces_canon, state, (int)F, (int)V, c.keep, c.used, counts);

@@ -43,6 +43,10 @@ int sizes_ok(const char* fn, int64_t nodes, int64_t edges);      // capi.hip
     if ((p) == nullptr) return ::geobi::set_error("%s: %s is NULL", __func__, #p); \
   } while (0)
 #define GEOBI_SIZES(nodes, edges) GEOBI_TRY(::geobi::sizes_ok(__func__, (int64_t)(nodes), (int64_t)(edges)))
+// the face and vertex counts of a mesh: the larger within the limit, the smaller not negative
+#define GEOBI_MESH_SIZES(F, V)             \
+  GEOBI_SIZES((F) > (V) ? (F) : (V), 0);   \
+  GEOBI_SIZES((F) < (V) ? (F) : (V), 0)
 static inline hipStream_t as_stream(void* stream) { return (hipStream_t)stream; }
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
@@ -128,6 +132,14 @@ static inline size_t carve_bytes(Carve&& carve) {
 #define GEOBI_WS_CHECK(fn, a, ws, ws_bytes)                                                                        \
   GEOBI_REQUIRE((a).ok() && (ws) != nullptr, "%s: workspace too small (%zu bytes given, %zu needed)", fn, \
                 (size_t)(ws_bytes), (a).off)
+// the launcher's half of the rule: b = carve(arena over the caller's memory), checked under the launcher's name
+template <typename Buffers, typename Carve>
+static inline int carve_checked(const char* what, void* ws, size_t ws_bytes, Buffers& b, Carve&& carve) {
+  Arena a(ws, ws_bytes);
+  b = carve(a);
+  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
+  return 0;
+}
 
 // ---- mesh repair and topology (clean.hip, topo.hip): the state of a face, and the 48-bit key a << 24 | b of a
 // half-edge (clean.hip: directed a -> b; topo.hip: undirected, a < b) -- vertex indices stay below 2^24

@@ -4,14 +4,15 @@
 //
 // The topology is integer-exact and independent of launch geometry; every float step is fp64 in one stated order
 // (contraction off throughout, __dsqrt_rn / __ddiv_rn, no float atomics):
-//   tables   the slots and keys of topo.hip (edge_table.h) sorted stably on 48 bits: a run is an edge, and an edge is
-//            known by the sorted position of its head, which orders the edges as their ids do.  Two more 48-bit sorts: the
-//            corner keys v << 24 | f (the included faces at a vertex in ascending id) and the directed pairs src << 24 |
-//            dst of the run heads (the neighbours of a vertex in ascending id); both one binary search away
+//   tables   the edge table of edge_table.h: a run is an edge, and an edge is known by the sorted position of its head,
+//            which orders the edges as their ids do; the corner keys and the directed pairs of mesh_tables.h (the included
+//            faces and the neighbours of a vertex in ascending id, both one binary search away).  The corner kernel also
+//            writes the keep flags, the heads kernel the lock flags
 //   values   one lane per vertex sums its quadric over its corner run; one lane per edge head picks the placement and
 //            runs the link, valence and flip tests; two stable sorts (hash, then cost) rank the valid candidates
-//   select   GEOBI_DECIM_SWEEPS sweeps of: atomicMin of the ranks into m1 (nobody reads m1 in that launch), m2 per vertex,
-//            select + block (writes `blocked`, reads m2), die (reads `blocked`)
+//   select   GEOBI_DECIM_SWEEPS sweeps of mesh_select.h over the two ends of an edge: atomicMin of the ranks into m1
+//            (nobody reads m1 in that launch), m2 per vertex, select + block (writes `blocked`, reads m2), die (reads
+//            `blocked`)
 //   budget   the selected flags in rank order, scanned; roles of the vertices, keep flags of vertices and faces, scanned
 //   emit     one lane per vertex, per face and per output row
 // Every index is bounded: corners are below V (face_included), slots below 3F, vertices and faces taken out of a key were
@@ -22,9 +23,8 @@
 #include <float.h>
 
 #include "common.h"
-#include "edge_table.h"
-#include "mesh_rings.h"
-#include "rocprim_temp.h"
+#include "mesh_select.h"
+#include "mesh_tables.h"
 #include "stage_timer.h"
 #include "../../include/geobi_hip.h"
 
@@ -36,11 +36,8 @@ namespace {
 
 constexpr int kT = 256;
 enum Count { kEdges = 0, kLocked = 1, kValid = 2, kCollapses = 3, kVOut = 4, kFOut = 5, kNotIncluded = 6,
-             kSweepsSelected = 7, kCounts = 8, kSweepBase = 8, kDevCounts = 16 };   // [8 ..]: selected per sweep
-static_assert(kSweepBase + GEOBI_DECIM_SWEEPS <= kDevCounts, "one counter per sweep");
-constexpr int kNone = 0x7f7f7f7f;                   // no rank: what a memset of 0x7f leaves, above every position
-constexpr uint64_t kNoCost = ~0ull;                 // sorts last; the orderable form of no finite cost
-enum State { kLive = 1, kSelected = 2 };
+             kSweepsSelected = 7, kCounts = 8 };
+static_assert(kCounts <= kSweepBase && kSweepBase + GEOBI_DECIM_SWEEPS <= kDevCounts, "one counter per sweep");
 enum Role { kPlain = -1, kMergedAway = 3 };         // 0, 1, 2: the `lo` of a collapsed edge, its placement code
 
 __device__ __forceinline__ double cost_of(const double* q, const P3& p) {
@@ -49,44 +46,6 @@ __device__ __forceinline__ double cost_of(const double* q, const P3& p) {
   const double off = ((q[1] * p.x) * p.y + (q[2] * p.x) * p.z) + (q[5] * p.y) * p.z;
   const double lin = (q[3] * p.x + q[6] * p.y) + q[8] * p.z;
   return (diag + 2.0 * off) + (2.0 * lin + q[9]);
-}
-
-// ---- tables
-// corner keys of every face, its keep flag (= included so far), the count of the faces that are not included
-__global__ void decim_corners_kernel(const int* __restrict__ fv, int F, int V, uint64_t* __restrict__ corners,
-                                     int* __restrict__ fkeep, int* __restrict__ counts) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  bool out = false;
-  if (f < F) {
-    int c[3];
-    const bool inc = face_included(fv, nullptr, f, V, c[0], c[1], c[2]);
-    for (int k = 0; k < 3; ++k) corners[3 * (size_t)f + k] = inc ? edge_key(c[k], f) : kNoEdge;
-    fkeep[f] = inc ? 1 : 0;
-    out = !inc;
-  }
-  count_lanes(out, counts + kNotIncluded);
-}
-
-// per sorted position: the two directed pairs of an edge head, the locked flags of the ends of an edge with n_e != 2
-// (every writer stores the same 1), the count of the edges
-__global__ void decim_heads_kernel(const uint64_t* __restrict__ keys, int n, uint64_t* __restrict__ pairs,
-                                   int* __restrict__ locked, int* __restrict__ counts) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool head = false;
-  if (i < n) {
-    const Run r = run_at(keys, n, i);
-    head = r.head;
-    uint64_t forth = kNoEdge, back = kNoEdge;
-    if (head) {
-      const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);
-      forth = keys[i];
-      back = edge_key(hi, lo);
-      if (!r.two || r.three) { locked[lo] = 1; locked[hi] = 1; }
-    }
-    pairs[2 * (size_t)i] = forth;
-    pairs[2 * (size_t)i + 1] = back;
-  }
-  count_lanes(head, counts + kEdges);
 }
 
 // ---- values
@@ -125,7 +84,7 @@ __global__ void decim_quadrics_kernel(const float* __restrict__ points, const in
 }
 
 // per sorted position: the head of an edge with two claimants whose ends are not both locked takes its placement and runs
-// the tests; cost_key = the orderable cost of a valid candidate (else kNoCost), hash, code, idx = the position itself
+// the tests; cost_key = the orderable cost of a valid candidate (else kNoCandidate), hash, code, idx = the position itself
 __global__ void decim_candidates_kernel(const uint64_t* __restrict__ keys, int n, const float* __restrict__ points,
                                         const int* __restrict__ fv, const uint64_t* __restrict__ corners,
                                         const uint64_t* __restrict__ pairs, int n_pairs, const int* __restrict__ locked,
@@ -137,7 +96,7 @@ __global__ void decim_candidates_kernel(const uint64_t* __restrict__ keys, int n
   bool valid = false;
   if (i < n) {
     const Run r = run_at(keys, n, i);
-    uint64_t ck = kNoCost;
+    uint64_t ck = kNoCandidate;
     int code = 0;
     const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);      // meaningful at a head
     if (r.head && r.two && !r.three && !(locked[lo] != 0 && locked[hi] != 0)) {
@@ -211,14 +170,13 @@ __global__ void decim_short_candidates_kernel(const uint64_t* __restrict__ keys,
   bool valid = false;
   if (i < n) {
     const Run r = run_at(keys, n, i);
-    uint64_t ck = kNoCost;
+    uint64_t ck = kNoCandidate;
     int code = 0;
     const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);      // meaningful at a head
     if (r.head && r.two && !r.three && !(locked[lo] != 0 && locked[hi] != 0)) {
       const float* pl = points + 3 * (size_t)lo;
       const float* ph = points + 3 * (size_t)hi;
-      const double dx = (double)ph[0] - (double)pl[0], dy = (double)ph[1] - (double)pl[1], dz = (double)ph[2] - (double)pl[2];
-      const double len2 = (dx * dx + dy * dy) + dz * dz;
+      const double len2 = edge_len2(points, lo, hi);
       code = locked[lo] != 0 ? 0 : (locked[hi] != 0 ? 1 : 2);
       const P3 at = code == 0 ? point_of(points, lo) : code == 1 ? point_of(points, hi) :
                     P3{(double)midpoint(pl[0], ph[0]), (double)midpoint(pl[1], ph[1]), (double)midpoint(pl[2], ph[2])};
@@ -243,55 +201,16 @@ __global__ void decim_gather_cost_kernel(const uint64_t* __restrict__ cost_key, 
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const int i = idx[j];
-  out[j] = (unsigned)i < (unsigned)n ? cost_key[i] : kNoCost;
+  out[j] = (unsigned)i < (unsigned)n ? cost_key[i] : kNoCandidate;
 }
 
-// order[j] = the position of the edge of rank j: rank and state per position
-__global__ void decim_rank_kernel(const uint64_t* __restrict__ sorted_cost, const int* __restrict__ order, int n,
-                                  int* __restrict__ rank, int* __restrict__ state) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const int i = order[j];
-  if ((unsigned)i >= (unsigned)n) return;
-  const bool valid = sorted_cost[j] != kNoCost;
-  rank[i] = valid ? j : kNone;
-  state[i] = valid ? kLive : 0;
-}
-
-// ---- selection
-__global__ void decim_m1_kernel(const uint64_t* __restrict__ keys, int n, const int* __restrict__ state,
-                                const int* __restrict__ rank, int* __restrict__ m1) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (state[i] & kLive) == 0) return;
-  atomicMin(m1 + edge_key_lo(keys[i]), rank[i]);
-  atomicMin(m1 + edge_key_hi(keys[i]), rank[i]);
-}
-
-// a live candidate whose rank is the least of the closed rings of both ends is selected and blocks those rings
-__global__ void decim_select_kernel(const uint64_t* __restrict__ keys, int n, const int* __restrict__ rank,
-                                    const int* __restrict__ m2, const uint64_t* __restrict__ pairs, int n_pairs,
-                                    int* __restrict__ state, int* __restrict__ blocked, int* __restrict__ selected_count) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool selected = false;
-  if (i < n && (state[i] & kLive) != 0) {
-    const int lo = edge_key_lo(keys[i]), hi = edge_key_hi(keys[i]);
-    const int a = m2[lo], b = m2[hi];
-    selected = (a < b ? a : b) == rank[i];
-    if (selected) {
-      state[i] |= kSelected;
-      block_ring(pairs, n_pairs, lo, blocked);
-      block_ring(pairs, n_pairs, hi, blocked);
-    }
-  }
-  count_lanes(selected, selected_count);
-}
-
-__global__ void decim_die_kernel(const uint64_t* __restrict__ keys, int n, const int* __restrict__ blocked,
-                                 int* __restrict__ state) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (state[i] & kLive) == 0) return;
-  if (blocked[edge_key_lo(keys[i])] != 0 || blocked[edge_key_hi(keys[i])] != 0) state[i] &= ~kLive;
-}
+// ---- selection (mesh_select.h): the footprint of a collapse is the two ends of its edge; nothing else is recorded
+struct EdgeEnds {
+  static constexpr int kSize = 2;
+  const uint64_t* keys;
+  __device__ void footprint(int i, int* v) const { v[0] = edge_key_lo(keys[i]); v[1] = edge_key_hi(keys[i]); }
+  __device__ void record(int) const {}
+};
 
 // ---- budget
 __global__ void decim_selected_in_rank_order_kernel(const int* __restrict__ order, const int* __restrict__ state, int n,
@@ -412,8 +331,7 @@ struct DecimBuffers {
   // the state of a plan, read by emit
   int *role, *partner, *vrow, *fkeep, *frow, *counts;
   // scratch of the plan: the three tables
-  uint64_t *k_in, *k_out, *c_in, *c_out, *p_in, *p_out;
-  int *v_in, *v_out;
+  MeshTables t;
   // per vertex
   double* Q;
   int *locked, *blocked, *m1, *m2, *keepv;
@@ -421,32 +339,21 @@ struct DecimBuffers {
   uint64_t *cost_key, *cost_in, *cost_out;
   uint32_t *hash_in, *hash_out;
   int *idx_in, *idx_mid, *order, *code, *rank, *state, *flag, *pos;
-  SubWs edge_sort, key_sort, pair_sort, hash_sort, cost_sort, slot_scan, vertex_scan, face_scan;
+  SubWs hash_sort, cost_sort, slot_scan, vertex_scan, face_scan;
 };
 DecimBuffers carve_decim(Arena& a, int64_t F, int64_t V) {
   const int64_t n = 3 * F;
   return {a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(F), a.take<int>(F), a.take<int>(kDevCounts),
-          a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(2 * n),
-          a.take<uint64_t>(2 * n), a.take<int>(n), a.take<int>(n),
+          carve_tables<true, true>(a, F),
           a.take<double>(10 * V),
           a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V),
           a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n),
           a.take<uint32_t>(n), a.take<uint32_t>(n),
           a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n),
           a.take<int>(n),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, kEdgeKeyBits)),
-          a.take_ws(sort_keys_temp_bytes<uint64_t>(n, kEdgeKeyBits)),
-          a.take_ws(sort_keys_temp_bytes<uint64_t>(2 * n, kEdgeKeyBits)),
           a.take_ws(sort_pairs_temp_bytes<uint32_t, int>(n, 32)),
           a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, 64)),
           a.take_ws(scan_temp_bytes<int>(n)), a.take_ws(scan_temp_bytes<int>(V)), a.take_ws(scan_temp_bytes<int>(F))};
-}
-
-int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, DecimBuffers& b) {
-  Arena a(ws, ws_bytes);
-  b = carve_decim(a, F, V);
-  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
-  return 0;
 }
 
 int launch_points(const float* other, int64_t V, int64_t Vn, const int32_t* parents, const int8_t* place, float* out,
@@ -470,7 +377,8 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
     return 0;
   }
   DecimBuffers b;
-  GEOBI_TRY(carve_checked(what, F, V, ws, ws_bytes, b));
+  GEOBI_TRY(carve_checked(what, ws, ws_bytes, b, [&](Arena& a) { return carve_decim(a, F, V); }));
+  const MeshTables& t = b.t;
   const int n = (int)(3 * F), n_pairs = 2 * n;
   const int k_budget = budget < 0 ? -1 : (int)(budget < F ? budget : F);
   size_t tb;
@@ -484,19 +392,9 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
     GEOBI_HIP(hipMemsetAsync(b.role, 0xff, sizeof(int) * (size_t)V, s));       // kPlain
     GEOBI_HIP(hipMemsetAsync(b.partner, 0xff, sizeof(int) * (size_t)V, s));
   }
-  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, nullptr, (int)F, (int)V, b.k_in, b.v_in);
-  GEOBI_LAUNCH_OK();
-  decim_corners_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, (int)V, b.c_in, b.fkeep, b.counts);
-  GEOBI_LAUNCH_OK();
-  tb = b.edge_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.edge_sort.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)n, 0u, kEdgeKeyBits, s,
-                                      false));
-  tb = b.key_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_keys(b.key_sort.p, tb, b.c_in, b.c_out, (size_t)n, 0u, kEdgeKeyBits, s, false));
-  decim_heads_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.p_in, b.locked, b.counts);
-  GEOBI_LAUNCH_OK();
-  tb = b.pair_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_keys(b.pair_sort.p, tb, b.p_in, b.p_out, (size_t)n_pairs, 0u, kEdgeKeyBits, s, false));
+  GEOBI_TRY(build_edge_table(t, faces, nullptr, F, V, s));
+  GEOBI_TRY(build_corner_table(t, faces, F, V, b.fkeep, b.counts + kNotIncluded, s));
+  GEOBI_TRY(build_pair_table(t, F, b.locked, b.counts + kEdges, s));
   GEOBI_TRY(timer.mark());
   // ---- values and rank
   if (sh != nullptr) {
@@ -504,17 +402,17 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
       decim_join_lock_kernel<<<cdiv(V, kT), kT, 0, s>>>(sh->lock, (int)V, b.locked, b.counts);
       GEOBI_LAUNCH_OK();
     }
-    decim_short_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, faces, b.c_out, b.p_out, n_pairs, b.locked,
+    decim_short_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(t.k_out, n, points, faces, t.c_out, t.p_out, n_pairs, b.locked,
                                                             (double)sh->low * (double)sh->low,
                                                             (double)sh->high * (double)sh->high, b.cost_key, b.hash_in,
                                                             b.code, b.idx_in, b.counts);
     GEOBI_LAUNCH_OK();
   } else {
     if (V > 0) {
-      decim_quadrics_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.c_out, n, b.locked, b.Q, b.counts);
+      decim_quadrics_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, t.c_out, n, b.locked, b.Q, b.counts);
       GEOBI_LAUNCH_OK();
     }
-    decim_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, faces, b.c_out, b.p_out, n_pairs, b.locked, b.Q,
+    decim_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(t.k_out, n, points, faces, t.c_out, t.p_out, n_pairs, b.locked, b.Q,
                                                       use_max_cost, (double)max_cost, b.cost_key, b.hash_in, b.code,
                                                       b.idx_in, b.counts);
     GEOBI_LAUNCH_OK();
@@ -527,28 +425,18 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
   tb = b.cost_sort.bytes;
   GEOBI_HIP(rocprim::radix_sort_pairs(b.cost_sort.p, tb, b.cost_in, b.cost_out, b.idx_mid, b.order, (size_t)n, 0u, 64u, s,
                                       false));
-  decim_rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.cost_out, b.order, n, b.rank, b.state);
+  rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.cost_out, b.order, n, b.rank, b.state);
   GEOBI_LAUNCH_OK();
   GEOBI_TRY(timer.mark());
   // ---- selection
-  for (int sweep = 0; sweep < GEOBI_DECIM_SWEEPS && V > 0; ++sweep) {
-    GEOBI_HIP(hipMemsetAsync(b.m1, 0x7f, sizeof(int) * (size_t)V, s));         // kNone
-    decim_m1_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.state, b.rank, b.m1);
-    GEOBI_LAUNCH_OK();
-    ring_min_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.m1, (int)V, b.p_out, n_pairs, b.m2);
-    GEOBI_LAUNCH_OK();
-    decim_select_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.rank, b.m2, b.p_out, n_pairs, b.state, b.blocked,
-                                                  b.counts + kSweepBase + sweep);
-    GEOBI_LAUNCH_OK();
-    decim_die_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.blocked, b.state);
-    GEOBI_LAUNCH_OK();
-  }
+  GEOBI_TRY(run_select_sweeps(EdgeEnds{t.k_out}, GEOBI_DECIM_SWEEPS, n, V, t.p_out, n_pairs, b.rank, b.state, b.m1, b.m2,
+                              b.blocked, b.counts + kSweepBase, s));
   // ---- budget, roles, scans
   decim_selected_in_rank_order_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.order, b.state, n, b.flag);
   GEOBI_LAUNCH_OK();
   tb = b.slot_scan.bytes;
   GEOBI_HIP(rocprim::exclusive_scan(b.slot_scan.p, tb, b.flag, b.pos, 0, (size_t)n, rocprim::plus<int>(), s, false));
-  decim_collapse_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.v_out, n, b.order, b.flag, b.pos, b.code, (int)F, k_budget,
+  decim_collapse_kernel<<<cdiv(n, kT), kT, 0, s>>>(t.k_out, t.v_out, n, b.order, b.flag, b.pos, b.code, (int)F, k_budget,
                                                   b.role, b.partner, b.fkeep, b.counts);
   GEOBI_LAUNCH_OK();
   if (V > 0) {
@@ -581,8 +469,7 @@ size_t geobi_decim_ws_bytes(int64_t F, int64_t V) {
 
 int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_max_cost, float max_cost,
                      int64_t budget, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_MESH_SIZES(F, V);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(counts);
   GEOBI_REQUIRE(use_max_cost == 0 || max_cost >= 0.0f, "decim_plan: max_cost = %g (not negative, not NaN)", (double)max_cost);
   return plan_round("decim_plan", faces, points, F, V, use_max_cost, max_cost, budget, nullptr, counts, stage_ms, ws, ws_bytes,
@@ -591,8 +478,7 @@ int geobi_decim_plan(const int32_t* faces, const float* points, int64_t F, int64
 
 int geobi_decim_plan_short(const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V, float low,
                            float high, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_MESH_SIZES(F, V);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(counts);
   GEOBI_REQUIRE(low > 0.0f && high >= low && high <= FLT_MAX,
                 "decim_plan_short: low = %g, high = %g (0 < low <= high, finite)", (double)low, (double)high);
@@ -604,10 +490,8 @@ int geobi_decim_plan_short(const int32_t* faces, const float* points, const int3
 int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int64_t Vn, int64_t Fn,
                      float* points_out, int32_t* faces_out, int32_t* face_map, int32_t* vertex_map,
                      int32_t* vertex_parents, int8_t* place, const void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
-  GEOBI_SIZES(Vn > Fn ? Vn : Fn, 0);
-  GEOBI_SIZES(Vn < Fn ? Vn : Fn, 0);
+  GEOBI_MESH_SIZES(F, V);
+  GEOBI_MESH_SIZES(Vn, Fn);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(points_out); GEOBI_NOTNULL(faces_out);
   GEOBI_NOTNULL(face_map); GEOBI_NOTNULL(vertex_map); GEOBI_NOTNULL(vertex_parents); GEOBI_NOTNULL(place);
   GEOBI_REQUIRE(Vn <= V && Fn <= F && 2 * (V - Vn) <= F - Fn,
@@ -622,7 +506,7 @@ int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64
     return launch_points(points, V, Vn, vertex_parents, place, points_out, s);
   }
   DecimBuffers b;
-  GEOBI_TRY(carve_checked("decim_emit", F, V, const_cast<void*>(ws), ws_bytes, b));
+  GEOBI_TRY(carve_checked("decim_emit", const_cast<void*>(ws), ws_bytes, b, [&](Arena& a) { return carve_decim(a, F, V); }));
   if (V > 0) {
     decim_vertices_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.role, b.partner, b.vrow, (int)V, (int)Vn, vertex_map, vertex_parents,
                                                     place);
@@ -636,8 +520,7 @@ int geobi_decim_emit(const int32_t* faces, const float* points, int64_t F, int64
 
 int geobi_decim_points(const float* other, int64_t V, int64_t Vn, const int32_t* vertex_parents, const int8_t* place,
                        float* out, void* stream) {
-  GEOBI_SIZES(V > Vn ? V : Vn, 0);
-  GEOBI_SIZES(V < Vn ? V : Vn, 0);
+  GEOBI_MESH_SIZES(V, Vn);
   GEOBI_NOTNULL(other); GEOBI_NOTNULL(vertex_parents); GEOBI_NOTNULL(place); GEOBI_NOTNULL(out);
   GEOBI_REQUIRE(Vn <= V, "decim_points: V' = %lld rows from V = %lld", (long long)Vn, (long long)V);
   return launch_points(other, V, Vn, vertex_parents, place, out, as_stream(stream));

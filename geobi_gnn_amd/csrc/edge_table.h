@@ -1,8 +1,11 @@
-// The slots of the undirected edge table, shared by topo.hip and subdiv.hip (4n): which faces are
-// included, which key a slot gets.  Sorting the slots stably on kEdgeKeyBits bits makes a run of equal keys one edge, its
-// length the number of claimants, the claimants in ascending slot order and the run heads ascend with (lo, hi).
+// The undirected edge table of the mesh tools, shared by topo.hip, clean.hip, subdiv.hip, decim.hip and
+// remesh.hip: which faces are included, which key a slot gets, how a run of the sorted table is read, how an index comes out
+// of a key -- and MeshTables, the buffers of the table (and of the two tables mesh_tables.h derives from it) with their carve
+// and the one sort.  Sorting the slots stably on kEdgeKeyBits bits makes a run of equal keys one edge, its length the number
+// of claimants, the claimants in ascending slot order and the run heads ascend with (lo, hi).
 #pragma once
 #include "common.h"
+#include "rocprim_temp.h"
 
 namespace geobi {
 
@@ -41,5 +44,57 @@ __device__ __forceinline__ int index_from_key(int v) {
 }
 __device__ __forceinline__ int edge_key_lo(uint64_t key) { return index_from_key((int)(key >> 24 & 0xffffffull)); }
 __device__ __forceinline__ int edge_key_hi(uint64_t key) { return index_from_key((int)(key & 0xffffffull)); }
+
+// what sorted position i is in its run: the head of an edge, followed by a second and a third claimant
+struct Run { bool head, two, three; };
+__device__ __forceinline__ Run run_at(const uint64_t* __restrict__ keys, int n, int i) {
+  const uint64_t key = keys[i];
+  Run r;
+  r.head = key != kNoEdge && (i == 0 || keys[i - 1] != key);
+  r.two = i + 1 < n && keys[i + 1] == key;
+  r.three = r.two && i + 2 < n && keys[i + 2] == key;
+  return r;
+}
+
+// ---- the buffers of the three sorted 48-bit tables: the edges always, the directed pairs and the corner keys
+// (mesh_tables.h) where the unit asks for them.  A unit embeds MeshTables in its own buffers.
+constexpr int kTableThreads = 256;
+struct MeshTables {
+  uint64_t *k_in, *k_out;          // [3F] edge keys before and after the sort
+  int *v_in, *v_out;               // [3F] their values
+  uint64_t *p_in, *p_out;          // [6F] directed pairs, NULL when not asked for
+  uint64_t *c_in, *c_out;          // [3F] corner keys, NULL when not asked for
+  SubWs edge_sort, pair_sort, corner_sort;
+};
+// the carve of the tables a unit asks for: the takes run in the order written, as in a unit's own braced list
+template <bool kPairs, bool kCorners>
+static inline MeshTables carve_tables(Arena& a, int64_t F) {
+  const int64_t n = 3 * F;
+  MeshTables t = {a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<int>(n), a.take<int>(n)};
+  t.edge_sort = a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, kEdgeKeyBits));
+  if constexpr (kPairs) {
+    t.p_in = a.take<uint64_t>(2 * n); t.p_out = a.take<uint64_t>(2 * n);
+    t.pair_sort = a.take_ws(sort_keys_temp_bytes<uint64_t>(2 * n, kEdgeKeyBits));
+  }
+  if constexpr (kCorners) {
+    t.c_in = a.take<uint64_t>(n); t.c_out = a.take<uint64_t>(n);
+    t.corner_sort = a.take_ws(sort_keys_temp_bytes<uint64_t>(n, kEdgeKeyBits));
+  }
+  return t;
+}
+
+// the build steps of the edge table (F > 0; they enqueue on s).  k_in / v_in -> k_out / v_out: the one sort
+static inline int sort_edge_table(const MeshTables& t, int64_t F, hipStream_t s) {
+  size_t tb = t.edge_sort.bytes;
+  GEOBI_HIP(rocprim::radix_sort_pairs(t.edge_sort.p, tb, t.k_in, t.k_out, t.v_in, t.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
+                                      s, false));
+  return 0;
+}
+static inline int build_edge_table(const MeshTables& t, const int32_t* faces, const int32_t* state, int64_t F, int64_t V,
+                                   hipStream_t s) {
+  edge_slots_kernel<<<cdiv(F, kTableThreads), kTableThreads, 0, s>>>(faces, state, (int)F, (int)V, t.k_in, t.v_in);
+  GEOBI_LAUNCH_OK();
+  return sort_edge_table(t, F, s);
+}
 
 }  // namespace geobi

@@ -1,7 +1,7 @@
-// What decim.hip and remesh.hip (4p) share on the device: fp64 points and face normals in the one stated
-// order, the float32 midpoint, and the walks over the three sorted 48-bit tables -- the edge runs, the corner keys
-// v << 24 | f (the included faces at a vertex in ascending id) and the directed pairs src << 24 | dst (the neighbours of a
-// vertex in ascending id).  Every index taken out of a key passes through index_from_key (edge_table.h).
+// What subdiv.hip, decim.hip (4o) and remesh.hip (4p) share on the device: fp64 points, squared edge
+// lengths and face normals in the one stated order, the float32 midpoint, and the walks over the sorted corner and pair
+// tables of mesh_tables.h (the included faces at a vertex, the neighbours of a vertex, both in ascending id).  Every index
+// taken out of a key passes through index_from_key (edge_table.h).  The ranked selection over these walks is mesh_select.h.
 #pragma once
 #include "common.h"
 #include "edge_table.h"
@@ -14,6 +14,14 @@ struct P3 { double x, y, z; };
 
 __device__ __forceinline__ P3 point_of(const float* __restrict__ points, int v) {
   return {(double)points[3 * (size_t)v], (double)points[3 * (size_t)v + 1], (double)points[3 * (size_t)v + 2]};
+}
+
+// fp64 squared length of the edge lo - hi from its float32 ends: hi - lo per axis, (dx dx + dy dy) + dz dz
+__device__ __forceinline__ double edge_len2(const float* __restrict__ points, int lo, int hi) {
+#pragma clang fp contract(off)
+  const P3 a = point_of(points, lo), b = point_of(points, hi);
+  const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+  return (dx * dx + dy * dy) + dz * dz;
 }
 
 // n = (b - a) x (c - a), every component two products and one subtraction; -> s = (nx nx + ny ny) + nz nz
@@ -50,16 +58,6 @@ __device__ __forceinline__ int lower_bound(const uint64_t* __restrict__ a, int n
 // other field as an index (edge_table.h: index_from_key)
 __device__ __forceinline__ int owner_of(uint64_t key) { return (int)(key >> 24); }
 __device__ __forceinline__ int item_of(uint64_t key) { return index_from_key((int)(key & 0xffffffull)); }
-
-struct Run { bool head, two, three; };
-__device__ __forceinline__ Run run_at(const uint64_t* __restrict__ keys, int n, int i) {
-  const uint64_t key = keys[i];
-  Run r;
-  r.head = key != kNoEdge && (i == 0 || keys[i - 1] != key);
-  r.two = i + 1 < n && keys[i + 1] == key;
-  r.three = r.two && i + 2 < n && keys[i + 2] == key;
-  return r;
-}
 
 // the faces at v other than those that hold `other` (none for other < 0) keep the side of their normal when v moves to `at`
 __device__ __forceinline__ bool no_flip(const float* __restrict__ points, const int* __restrict__ fv,
@@ -99,25 +97,6 @@ __device__ __forceinline__ bool link_and_valence(const uint64_t* __restrict__ pa
     }
   }
   return valid && shared == 2;
-}
-
-__device__ __forceinline__ void block_ring(const uint64_t* __restrict__ pairs, int n_pairs, int v, int* __restrict__ blocked) {
-  blocked[v] = 1;
-  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j)
-    blocked[item_of(pairs[j])] = 1;
-}
-
-// m2[v] = the least m1 over the closed ring of v (the m2 step of the selection sweeps of 4o and 4p)
-static __global__ void ring_min_kernel(const int* __restrict__ m1, int V, const uint64_t* __restrict__ pairs, int n_pairs,
-                                       int* __restrict__ m2) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  int m = m1[v];
-  for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j) {
-    const int w = m1[item_of(pairs[j])];
-    m = w < m ? w : m;
-  }
-  m2[v] = m;
 }
 
 }  // namespace geobi

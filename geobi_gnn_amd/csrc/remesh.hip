@@ -5,21 +5,21 @@
 //
 // The topology is integer-exact and independent of launch geometry; every float step is fp64 in one stated order
 // (contraction off throughout, __ddiv_rn / __dsqrt_rn, no float atomics):
-//   tables   those of decim.hip: the edge slots sorted stably on 48 bits (a run is an edge, known by the sorted position of
-//            its head), the directed pairs of the run heads (the neighbours of a vertex in ascending id, its valence their
+//   tables   those of edge_table.h and mesh_tables.h: the edge table (a run is an edge, known by the sorted position of its
+//            head), the directed pairs of the run heads (the neighbours of a vertex in ascending id, its valence their
 //            number, "does the edge c - d exist" one binary search), for the relaxation also the corner keys
 //   lock     one lane per sorted position: integer atomicOr of the bits into the flags (nobody reads them in that launch)
 //   flips    one lane per edge head finds the quad, the gain and the validity; ONE stable 64-bit sort of (16 - gain) << 32 |
-//            hash ranks the valid candidates (ties keep the position, which orders as the edge ids do); the sweeps of 4o over
-//            the four quad vertices; a selected lane notes its position at its two faces; emit is one lane per face
+//            hash ranks the valid candidates (ties keep the position, which orders as the edge ids do); the sweeps of
+//            mesh_select.h over the four quad vertices; a selected lane notes its position at its two faces; emit is one
+//            lane per face
 //   relax    one lane per vertex proposes and tests its move against the old positions, one lane per face marks the
 //            vertices of a face that turned, one lane per vertex takes them back, one lane per face counts what is left
 // Every index is bounded: corners are below V (face_included), slots below 3F, vertices and faces taken out of a key were
 // put into it from such a corner or face, positions noted at a face are checked against 3F before they are used.
 #include "common.h"
-#include "edge_table.h"
-#include "mesh_rings.h"
-#include "rocprim_temp.h"
+#include "mesh_select.h"
+#include "mesh_tables.h"
 #include "stage_timer.h"
 #include "../../include/geobi_hip.h"
 
@@ -31,41 +31,10 @@ namespace {
 
 constexpr int kT = 256;
 enum LockCount { kLockEdges = 0, kLockBoundary = 1, kLockSharpEdges = 2, kLockSharp = 3, kLockCounts = 4 };
-enum FlipCount { kFlipEdges = 0, kFlipCandidates = 1, kFlipValid = 2, kFlips = 3, kFlipSweeps = 4, kFlipCounts = 5,
-                 kSweepBase = 8 };                   // [8 ..]: selected per sweep
+enum FlipCount { kFlipEdges = 0, kFlipCandidates = 1, kFlipValid = 2, kFlips = 3, kFlipSweeps = 4, kFlipCounts = 5 };
 enum RelaxCount { kMoved = 0, kRefused = 1, kReverted = 2, kTurned = 3, kRelaxCounts = 4 };
-constexpr int kDevCounts = 16, kSpareCount = 15;     // [15]: the edge count of a call that does not report it
-static_assert(kSweepBase + GEOBI_FLIP_SWEEPS <= kDevCounts, "one counter per sweep");
-constexpr int kNone = 0x7f7f7f7f;                   // no rank: what a memset of 0x7f leaves, above every position
-constexpr uint64_t kNoKey = ~0ull;                  // sorts last: no valid candidate
-enum State { kLive = 1, kSelected = 2 };
-
-// ---- tables
-// per sorted position: the two directed pairs of an edge head (kNoEdge elsewhere), the count of the edges
-__global__ void remesh_heads_kernel(const uint64_t* __restrict__ keys, int n, uint64_t* __restrict__ pairs,
-                                    int* __restrict__ edge_count) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool head = false;
-  if (i < n) {
-    head = run_at(keys, n, i).head;
-    uint64_t forth = kNoEdge, back = kNoEdge;
-    if (head) {
-      forth = keys[i];
-      back = edge_key(edge_key_hi(keys[i]), edge_key_lo(keys[i]));
-    }
-    pairs[2 * (size_t)i] = forth;
-    pairs[2 * (size_t)i + 1] = back;
-  }
-  count_lanes(head, edge_count);
-}
-
-__global__ void remesh_corners_kernel(const int* __restrict__ fv, int F, int V, uint64_t* __restrict__ corners) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  int c[3];
-  const bool inc = face_included(fv, nullptr, f, V, c[0], c[1], c[2]);
-  for (int k = 0; k < 3; ++k) corners[3 * (size_t)f + k] = inc ? edge_key(c[k], f) : kNoEdge;
-}
+constexpr int kSpareCount = kDevCounts - 1;          // the edge count of a call that does not report it
+static_assert(kFlipCounts <= kSweepBase && kSweepBase + GEOBI_FLIP_SWEEPS <= kSpareCount, "one counter per sweep");
 
 __device__ __forceinline__ int valence_of(const uint64_t* __restrict__ pairs, int n_pairs, int v) {
   return lower_bound(pairs, n_pairs, (uint64_t)(v + 1) << 24) - lower_bound(pairs, n_pairs, (uint64_t)v << 24);
@@ -131,7 +100,8 @@ __device__ __forceinline__ int deviation(int valence, int lock_bits) {
 }
 
 // per sorted position: the head of an edge with two claimants that walk it in opposite directions and that is not sharp
-// finds its quad (a, b, c, d), its gain and its validity; key = (16 - gain) << 32 | hash of a valid candidate, else kNoKey
+// finds its quad (a, b, c, d), its gain and its validity; key = (16 - gain) << 32 | hash of a valid candidate, else
+// kNoCandidate
 __global__ void flip_candidates_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ vals, int n,
                                        const float* __restrict__ points, const int* __restrict__ fv, int F, int V,
                                        const uint64_t* __restrict__ pairs, int n_pairs, const int* __restrict__ lock,
@@ -142,7 +112,7 @@ __global__ void flip_candidates_kernel(const uint64_t* __restrict__ keys, const 
   bool candidate = false, valid = false;
   if (i < n) {
     const Run r = run_at(keys, n, i);
-    uint64_t key = kNoKey;
+    uint64_t key = kNoCandidate;
     int c = 0, d = 0;
     if (r.head && r.two && !r.three && ((vals[i] ^ vals[i + 1]) & 1) != 0) {
       const int a = edge_key_lo(keys[i]), b = edge_key_hi(keys[i]);
@@ -189,68 +159,24 @@ __global__ void flip_candidates_kernel(const uint64_t* __restrict__ keys, const 
   count_lanes(valid, counts + kFlipValid);
 }
 
-// order[j] = the position of the edge of rank j: rank and state per position
-__global__ void flip_rank_kernel(const uint64_t* __restrict__ sorted_key, const int* __restrict__ order, int n,
-                                 int* __restrict__ rank, int* __restrict__ state) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const int i = order[j];
-  if ((unsigned)i >= (unsigned)n) return;
-  const bool valid = sorted_key[j] != kNoKey;
-  rank[i] = valid ? j : kNone;
-  state[i] = valid ? kLive : 0;
-}
-
-// the quad of a live candidate at position i, every vertex below V
-struct Quad { int v[4]; };
-__device__ __forceinline__ Quad quad_at(const uint64_t* __restrict__ keys, const int* __restrict__ qc,
-                                        const int* __restrict__ qd, int i, int V) {
-  Quad q = {{edge_key_lo(keys[i]), edge_key_hi(keys[i]), index_from_key(qc[i]), index_from_key(qd[i])}};
-  for (int k = 0; k < 4; ++k)
-    if ((unsigned)q.v[k] >= (unsigned)V) q.v[k] = 0;               // never: a live candidate passed the range test
-  return q;
-}
-
-__global__ void flip_m1_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ qc, const int* __restrict__ qd,
-                               int n, int V, const int* __restrict__ state, const int* __restrict__ rank,
-                               int* __restrict__ m1) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (state[i] & kLive) == 0) return;
-  const Quad q = quad_at(keys, qc, qd, i, V);
-  for (int k = 0; k < 4; ++k) atomicMin(m1 + q.v[k], rank[i]);
-}
-
-// a live candidate whose rank is the least of the closed rings of its four vertices is selected, blocks those rings and
+// ---- selection (mesh_select.h): the footprint of a flip is its quad (a, b, c, d), every vertex below V; a selected flip
 // notes its position at its two faces
-__global__ void flip_select_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ vals,
-                                   const int* __restrict__ qc, const int* __restrict__ qd, int n, int F, int V,
-                                   const int* __restrict__ rank, const int* __restrict__ m2,
-                                   const uint64_t* __restrict__ pairs, int n_pairs, int* __restrict__ state,
-                                   int* __restrict__ blocked, int* __restrict__ fedge, int* __restrict__ selected_count) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool selected = false;
-  if (i + 1 < n && (state[i] & kLive) != 0) {
-    const Quad q = quad_at(keys, qc, qd, i, V);
-    int least = m2[q.v[0]];
-    for (int k = 1; k < 4; ++k) least = m2[q.v[k]] < least ? m2[q.v[k]] : least;
-    selected = least == rank[i];
-    if (selected) {
-      state[i] |= kSelected;
-      for (int k = 0; k < 4; ++k) block_ring(pairs, n_pairs, q.v[k], blocked);
-      fedge[face_of_slot_value(vals[i], F)] = i;
-      fedge[face_of_slot_value(vals[i + 1], F)] = i;
-    }
+struct FlipQuad {
+  static constexpr int kSize = 4;
+  const uint64_t* keys;
+  const int *vals, *qc, *qd;
+  int F, V;
+  int* fedge;
+  __device__ void footprint(int i, int* v) const {
+    v[0] = edge_key_lo(keys[i]); v[1] = edge_key_hi(keys[i]); v[2] = index_from_key(qc[i]); v[3] = index_from_key(qd[i]);
+    for (int k = 0; k < 4; ++k)
+      if ((unsigned)v[k] >= (unsigned)V) v[k] = 0;                 // never: a live candidate passed the range test
   }
-  count_lanes(selected, selected_count);
-}
-
-__global__ void flip_die_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ qc, const int* __restrict__ qd,
-                                int n, int V, const int* __restrict__ blocked, int* __restrict__ state) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (state[i] & kLive) == 0) return;
-  const Quad q = quad_at(keys, qc, qd, i, V);
-  if (blocked[q.v[0]] != 0 || blocked[q.v[1]] != 0 || blocked[q.v[2]] != 0 || blocked[q.v[3]] != 0) state[i] &= ~kLive;
-}
+  __device__ void record(int i) const {
+    fedge[face_of_slot_value(vals[i], F)] = i;
+    fedge[face_of_slot_value(vals[i + 1], F)] = i;
+  }
+};
 
 __global__ void flip_totals_kernel(int* __restrict__ counts) {
   int flips = 0, sweeps = 0;
@@ -376,9 +302,7 @@ __global__ void remesh_lengths_kernel(const uint64_t* __restrict__ keys, int n, 
   if (i >= n) return;
   double len = -1.0;
   if (run_at(keys, n, i).head) {
-    const P3 a = point_of(points, edge_key_lo(keys[i])), b = point_of(points, edge_key_hi(keys[i]));
-    const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-    len = __dsqrt_rn((dx * dx + dy * dy) + dz * dz);
+    len = __dsqrt_rn(edge_len2(points, edge_key_lo(keys[i]), edge_key_hi(keys[i])));
   }
   edge_len[i] = len;
 }
@@ -390,9 +314,7 @@ __global__ void remesh_valence_kernel(const uint64_t* __restrict__ pairs, int n_
 
 struct RemeshBuffers {
   int* counts;
-  // the three tables
-  uint64_t *k_in, *k_out, *c_in, *c_out, *p_in, *p_out;
-  int *v_in, *v_out;
+  MeshTables t;                    // the three tables
   // per vertex
   int *m1, *m2, *blocked, *moved, *revert;
   // per sorted position
@@ -400,52 +322,31 @@ struct RemeshBuffers {
   int *idx_in, *order, *rank, *state, *qc, *qd;
   // per face
   int* fedge;
-  SubWs edge_sort, key_sort, pair_sort, rank_sort;
+  SubWs rank_sort;
 };
 RemeshBuffers carve_remesh(Arena& a, int64_t F, int64_t V) {
   const int64_t n = 3 * F;
   return {a.take<int>(kDevCounts),
-          a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<uint64_t>(2 * n),
-          a.take<uint64_t>(2 * n), a.take<int>(n), a.take<int>(n),
+          carve_tables<true, true>(a, F),
           a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V),
           a.take<uint64_t>(n), a.take<uint64_t>(n),
           a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n),
           a.take<int>(F),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, kEdgeKeyBits)),
-          a.take_ws(sort_keys_temp_bytes<uint64_t>(n, kEdgeKeyBits)),
-          a.take_ws(sort_keys_temp_bytes<uint64_t>(2 * n, kEdgeKeyBits)),
           a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, 64))};
 }
 
-int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, RemeshBuffers& b) {
-  Arena a(ws, ws_bytes);
-  b = carve_remesh(a, F, V);
-  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
-  return 0;
+int remesh_buffers(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, RemeshBuffers& b) {
+  return carve_checked(what, ws, ws_bytes, b, [&](Arena& a) { return carve_remesh(a, F, V); });
 }
 
 // the sorted edge slots, the sorted directed pairs and (with_corners) the sorted corner keys of F > 0 faces; the edge count
 // goes to b.counts[edge_count_at]
 int build_tables(const RemeshBuffers& b, const int32_t* faces, int64_t F, int64_t V, bool with_corners, int edge_count_at,
                  hipStream_t s) {
-  const int n = (int)(3 * F);
-  size_t tb;
   GEOBI_HIP(hipMemsetAsync(b.counts, 0, sizeof(int) * kDevCounts, s));
-  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, nullptr, (int)F, (int)V, b.k_in, b.v_in);
-  GEOBI_LAUNCH_OK();
-  tb = b.edge_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.edge_sort.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)n, 0u, kEdgeKeyBits, s,
-                                      false));
-  remesh_heads_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.p_in, b.counts + edge_count_at);
-  GEOBI_LAUNCH_OK();
-  tb = b.pair_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_keys(b.pair_sort.p, tb, b.p_in, b.p_out, (size_t)(2 * n), 0u, kEdgeKeyBits, s, false));
-  if (with_corners) {
-    remesh_corners_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, (int)V, b.c_in);
-    GEOBI_LAUNCH_OK();
-    tb = b.key_sort.bytes;
-    GEOBI_HIP(rocprim::radix_sort_keys(b.key_sort.p, tb, b.c_in, b.c_out, (size_t)n, 0u, kEdgeKeyBits, s, false));
-  }
+  GEOBI_TRY(build_edge_table(b.t, faces, nullptr, F, V, s));
+  GEOBI_TRY(build_pair_table(b.t, F, nullptr, b.counts + edge_count_at, s));
+  if (with_corners) GEOBI_TRY(build_corner_table(b.t, faces, F, V, nullptr, nullptr, s));
   return 0;
 }
 
@@ -454,10 +355,6 @@ int build_tables(const RemeshBuffers& b, const int32_t* faces, int64_t F, int64_
 }  // namespace geobi
 
 using namespace geobi;
-
-#define GEOBI_MESH_SIZES(F, V)     \
-  GEOBI_SIZES(F > V ? F : V, 0);   \
-  GEOBI_SIZES(F < V ? F : V, 0)
 
 extern "C" {
 
@@ -476,10 +373,10 @@ int geobi_remesh_lock(const int32_t* faces, const float* points, int64_t F, int6
   if (V > 0) GEOBI_HIP(hipMemsetAsync(lock, 0, sizeof(int) * (size_t)V, s));
   if (F == 0 || V == 0) return 0;
   RemeshBuffers b;
-  GEOBI_TRY(carve_checked("remesh_lock", F, V, ws, ws_bytes, b));
+  GEOBI_TRY(remesh_buffers("remesh_lock", F, V, ws, ws_bytes, b));
   const int n = (int)(3 * F);
   GEOBI_TRY(build_tables(b, faces, F, V, false, 0, s));
-  remesh_lock_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.v_out, n, points, faces, (int)F, use_sharp, c2, lock, b.counts);
+  remesh_lock_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, n, points, faces, (int)F, use_sharp, c2, lock, b.counts);
   GEOBI_LAUNCH_OK();
   remesh_lock_counts_kernel<<<cdiv(V, kT), kT, 0, s>>>(lock, (int)V, b.counts);
   GEOBI_LAUNCH_OK();
@@ -498,7 +395,7 @@ int geobi_flip_plan(const int32_t* faces, const float* points, const int32_t* lo
     return 0;
   }
   RemeshBuffers b;
-  GEOBI_TRY(carve_checked("flip_plan", F, V, ws, ws_bytes, b));
+  GEOBI_TRY(remesh_buffers("flip_plan", F, V, ws, ws_bytes, b));
   const int n = (int)(3 * F), n_pairs = 2 * n;
   size_t tb;
   StageTimer timer(stage_ms, s);
@@ -508,28 +405,18 @@ int geobi_flip_plan(const int32_t* faces, const float* points, const int32_t* lo
   GEOBI_HIP(hipMemsetAsync(b.fedge, 0xff, sizeof(int) * (size_t)F, s));
   GEOBI_TRY(timer.mark());
   // ---- candidates and rank
-  flip_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.v_out, n, points, faces, (int)F, (int)V, b.p_out, n_pairs,
+  flip_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, n, points, faces, (int)F, (int)V, b.t.p_out, n_pairs,
                                                    lock, use_sharp, c2, b.key_in, b.idx_in, b.qc, b.qd, b.counts);
   GEOBI_LAUNCH_OK();
   tb = b.rank_sort.bytes;
   GEOBI_HIP(rocprim::radix_sort_pairs(b.rank_sort.p, tb, b.key_in, b.key_out, b.idx_in, b.order, (size_t)n, 0u, 64u, s,
                                       false));
-  flip_rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.key_out, b.order, n, b.rank, b.state);
+  rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.key_out, b.order, n, b.rank, b.state);
   GEOBI_LAUNCH_OK();
   GEOBI_TRY(timer.mark());
   // ---- selection
-  for (int sweep = 0; sweep < GEOBI_FLIP_SWEEPS; ++sweep) {
-    GEOBI_HIP(hipMemsetAsync(b.m1, 0x7f, sizeof(int) * (size_t)V, s));         // kNone
-    flip_m1_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.qc, b.qd, n, (int)V, b.state, b.rank, b.m1);
-    GEOBI_LAUNCH_OK();
-    ring_min_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.m1, (int)V, b.p_out, n_pairs, b.m2);
-    GEOBI_LAUNCH_OK();
-    flip_select_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.v_out, b.qc, b.qd, n, (int)F, (int)V, b.rank, b.m2, b.p_out,
-                                                 n_pairs, b.state, b.blocked, b.fedge, b.counts + kSweepBase + sweep);
-    GEOBI_LAUNCH_OK();
-    flip_die_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.qc, b.qd, n, (int)V, b.blocked, b.state);
-    GEOBI_LAUNCH_OK();
-  }
+  GEOBI_TRY(run_select_sweeps(FlipQuad{b.t.k_out, b.t.v_out, b.qc, b.qd, (int)F, (int)V, b.fedge}, GEOBI_FLIP_SWEEPS, n, V,
+                              b.t.p_out, n_pairs, b.rank, b.state, b.m1, b.m2, b.blocked, b.counts + kSweepBase, s));
   flip_totals_kernel<<<1, 1, 0, s>>>(b.counts);
   GEOBI_LAUNCH_OK();
   GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kFlipCounts, hipMemcpyDeviceToDevice, s));
@@ -548,8 +435,8 @@ int geobi_flip_emit(const int32_t* faces, int64_t F, int64_t V, int32_t* faces_o
     return 0;
   }
   RemeshBuffers b;
-  GEOBI_TRY(carve_checked("flip_emit", F, V, const_cast<void*>(ws), ws_bytes, b));
-  flip_faces_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, b.k_out, b.v_out, b.qc, b.qd, (int)(3 * F), b.fedge, faces_out);
+  GEOBI_TRY(remesh_buffers("flip_emit", F, V, const_cast<void*>(ws), ws_bytes, b));
+  flip_faces_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, b.t.k_out, b.t.v_out, b.qc, b.qd, (int)(3 * F), b.fedge, faces_out);
   GEOBI_LAUNCH_OK();
   return 0;
 }
@@ -566,14 +453,14 @@ int geobi_relax(const int32_t* faces, const float* points, const int32_t* lock, 
     return 0;
   }
   RemeshBuffers b;
-  GEOBI_TRY(carve_checked("relax", F, V, ws, ws_bytes, b));
+  GEOBI_TRY(remesh_buffers("relax", F, V, ws, ws_bytes, b));
   const int n = (int)(3 * F), n_pairs = 2 * n;
   StageTimer timer(stage_ms, s);
   GEOBI_TRY(timer.mark());
   GEOBI_TRY(build_tables(b, faces, F, V, true, kSpareCount, s));
   GEOBI_HIP(hipMemsetAsync(b.revert, 0, sizeof(int) * (size_t)V, s));
   GEOBI_TRY(timer.mark());
-  relax_move_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.c_out, n, b.p_out, n_pairs, lock, lambda, points_out,
+  relax_move_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.t.c_out, n, b.t.p_out, n_pairs, lock, lambda, points_out,
                                               b.moved, b.counts);
   GEOBI_LAUNCH_OK();
   relax_turned_kernel<<<cdiv(F, kT), kT, 0, s>>>(points, points_out, faces, (int)F, (int)V, b.revert, nullptr);
@@ -595,12 +482,12 @@ int geobi_remesh_stats(const int32_t* faces, const float* points, int64_t F, int
   if (V > 0) GEOBI_HIP(hipMemsetAsync(valence, 0, sizeof(int) * (size_t)V, s));
   if (F == 0 || V == 0) return 0;
   RemeshBuffers b;
-  GEOBI_TRY(carve_checked("remesh_stats", F, V, ws, ws_bytes, b));
+  GEOBI_TRY(remesh_buffers("remesh_stats", F, V, ws, ws_bytes, b));
   const int n = (int)(3 * F);
   GEOBI_TRY(build_tables(b, faces, F, V, false, 0, s));
-  remesh_lengths_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, (double*)edge_len);
+  remesh_lengths_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, n, points, (double*)edge_len);
   GEOBI_LAUNCH_OK();
-  remesh_valence_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.p_out, 2 * n, (int)V, valence);
+  remesh_valence_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.t.p_out, 2 * n, (int)V, valence);
   GEOBI_LAUNCH_OK();
   return 0;
 }

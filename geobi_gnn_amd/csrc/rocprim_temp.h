@@ -1,5 +1,5 @@
-// Temporary-storage sizes of the rocPRIM calls of graph.hip, pool.hip, clean.hip, topo.hip and sample.hip, for
-// Arena::take_ws.  Kept out of common.h: only these five units compile rocPRIM.
+// Temporary-storage sizes of the rocPRIM calls of graph.hip, pool.hip, sample.hip and the mesh tools (through
+// edge_table.h), for Arena::take_ws.  Kept out of common.h: only these units compile rocPRIM.
 // 0: the size query failed (it asks the device for its properties, so it fails on a host without one); take_ws then
 // fails the carve and the enclosing *_ws_bytes answers 0.  A query that succeeds answers at least 16.
 #pragma once

@@ -4,9 +4,9 @@
 //
 // The topology is integer-exact and independent of launch geometry; positions go through one stated sequence of
 // roundings (contraction off throughout), no float atomics:
-//   table    the slots and keys of topo.hip (edge_table.h), sorted stably on 48 bits: a run is an edge, the run heads
-//            ascend with (lo, hi) -- the sorted position of a head orders the edges as their ids do, so the rank of a
-//            split edge among the split edges is the exclusive scan of the split flags of the heads
+//   table    the edge table of edge_table.h (slots and sort called one by one: a timer mark lies between): a run is an
+//            edge, the run heads ascend with (lo, hi) -- the sorted position of a head orders the edges as their ids do, so
+//            the rank of a split edge among the split edges is the exclusive scan of the split flags of the heads
 //   plan     per sorted position: head / boundary / complex / split (counted with count_lanes); scan of the split flags;
 //            per slot the rank of its edge's midpoint (or -1); per face 1 + its split edges children, scanned; V', F'.
 //            Loop only: every edge head lists its two DIRECTED pairs (src << 24 | dst) << 1 | sharp, sorted on 49 bits --
@@ -16,7 +16,7 @@
 // (checked against the sizes the caller read from the plan's counts).
 #include "common.h"
 #include "edge_table.h"
-#include "rocprim_temp.h"
+#include "mesh_rings.h"
 #include "stage_timer.h"
 #include "../../include/geobi_hip.h"
 
@@ -28,15 +28,6 @@ constexpr int kT = 256;
 enum Count { kEdges = 0, kSplit = 1, kBoundary = 2, kComplex = 3, kVOut = 4, kFOut = 5, kHasLoop = 6, kCounts = 8 };
 constexpr unsigned kPairBits = kEdgeKeyBits + 1;               // a directed pair: (src << 24 | dst) << 1 | sharp
 constexpr uint64_t kNoPair = (1ull << kPairBits) - 1;          // sorts last; its src field is 2^24 - 1, never a vertex
-
-// fp64 squared length of the edge lo - hi from its float32 ends: (dx * dx + dy * dy) + dz * dz, every operation rounded
-__device__ __forceinline__ double edge_len2(const float* __restrict__ points, int lo, int hi) {
-#pragma clang fp contract(off)
-  const double dx = (double)points[3 * (size_t)hi] - (double)points[3 * (size_t)lo];
-  const double dy = (double)points[3 * (size_t)hi + 1] - (double)points[3 * (size_t)lo + 1];
-  const double dz = (double)points[3 * (size_t)hi + 2] - (double)points[3 * (size_t)lo + 2];
-  return (dx * dx + dy * dy) + dz * dz;
-}
 
 // uniform: every edge; adaptive: strictly longer than L
 __device__ __forceinline__ bool edge_is_split(const float* __restrict__ points, uint64_t key, int adaptive, double L2) {
@@ -179,12 +170,6 @@ __global__ void subdiv_new_parents_kernel(const uint64_t* __restrict__ keys, int
   parents[2 * (size_t)row + 1] = edge_key_hi(keys[i]);
 }
 
-// the midpoint expression: 0.5f * a + 0.5f * b in float32
-__device__ __forceinline__ float midpoint(float a, float b) {
-#pragma clang fp contract(off)
-  return 0.5f * a + 0.5f * b;
-}
-
 // the rows V .. V' - 1: one lane per sorted position, the heads of split edges write.  Loop: an edge with exactly two
 // claimants takes 3/8 (lo + hi) + 1/8 (c + d) in fp64, c and d the opposite corners of its two claimants
 __global__ void subdiv_new_points_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ vals, int n,
@@ -269,29 +254,26 @@ __global__ void subdiv_loop_even_kernel(const float* __restrict__ points, int V,
 }
 
 struct SubdivBuffers {
-  // the state of a plan, read by emit and points
-  uint64_t* k_out;
-  int *v_out, *split, *rank, *slot_mid, *first_child, *counts;
-  uint64_t* p_out;
+  // the state of a plan, read by emit and points: the sorted edge table (t.k_out, t.v_out) and
+  MeshTables t;
+  int *split, *rank, *slot_mid, *first_child, *counts;
+  uint64_t* p_out;                 // Loop: the sorted 49-bit pairs (not the pair table of mesh_tables.h)
   // scratch of the plan
-  uint64_t *k_in, *p_in;
-  int *v_in, *children;
-  SubWs sort_temp, pair_sort_temp, slot_scan_temp, face_scan_temp;
+  uint64_t* p_in;
+  int* children;
+  SubWs pair_sort_temp, slot_scan_temp, face_scan_temp;
 };
 SubdivBuffers carve_subdiv(Arena& a, int64_t F) {
-  return {a.take<uint64_t>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F),
-          a.take<int>(F), a.take<int>(kCounts), a.take<uint64_t>(6 * F),
-          a.take<uint64_t>(3 * F), a.take<uint64_t>(6 * F), a.take<int>(3 * F), a.take<int>(F),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(3 * F, kEdgeKeyBits)),
+  return {carve_tables<false, false>(a, F),
+          a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(F), a.take<int>(kCounts),
+          a.take<uint64_t>(6 * F),
+          a.take<uint64_t>(6 * F), a.take<int>(F),
           a.take_ws(sort_keys_temp_bytes<uint64_t>(6 * F, kPairBits)),
           a.take_ws(scan_temp_bytes<int>(3 * F)), a.take_ws(scan_temp_bytes<int>(F))};
 }
 
-int carve_checked(const char* what, int64_t F, void* ws, size_t ws_bytes, SubdivBuffers& b) {
-  Arena a(ws, ws_bytes);
-  b = carve_subdiv(a, F);
-  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
-  return 0;
+int subdiv_buffers(const char* what, int64_t F, void* ws, size_t ws_bytes, SubdivBuffers& b) {
+  return carve_checked(what, ws, ws_bytes, b, [&](Arena& a) { return carve_subdiv(a, F); });
 }
 
 // the rows of points_out [Vn, 3] from points [V, 3] over the plan in b
@@ -304,7 +286,7 @@ int launch_points(const int32_t* faces, const float* points, int64_t F, int64_t 
       subdiv_copy_points_kernel<<<cdiv(3 * V, kT), kT, 0, s>>>(points, (int)(3 * V), points_out);
     GEOBI_LAUNCH_OK();
   }
-  subdiv_new_points_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.k_out, b.v_out, (int)(3 * F), faces, b.split, b.rank, points,
+  subdiv_new_points_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, (int)(3 * F), faces, b.split, b.rank, points,
                                                          (int)V, (int)Vn, loop, points_out);
   GEOBI_LAUNCH_OK();
   return 0;
@@ -325,8 +307,7 @@ size_t geobi_subdiv_ws_bytes(int64_t F, int64_t V) {
 
 int geobi_subdiv_plan(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int adaptive,
                       float max_edge, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_MESH_SIZES(F, V);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(counts);
   GEOBI_REQUIRE(!(loop != 0 && adaptive != 0), "subdiv_plan: the Loop scheme has no max_edge mode");
   if (adaptive != 0) {
@@ -341,24 +322,22 @@ int geobi_subdiv_plan(const int32_t* faces, const float* points, int64_t F, int6
     return 0;
   }
   SubdivBuffers b;
-  GEOBI_TRY(carve_checked("subdiv_plan", F, ws, ws_bytes, b));
+  GEOBI_TRY(subdiv_buffers("subdiv_plan", F, ws, ws_bytes, b));
   const int n = (int)(3 * F);
   const double L2 = (double)max_edge * (double)max_edge;
   StageTimer timer(stage_ms, s);
   GEOBI_TRY(timer.mark());
-  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, nullptr, (int)F, (int)V, b.k_in, b.v_in);
+  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, nullptr, (int)F, (int)V, b.t.k_in, b.t.v_in);
   GEOBI_LAUNCH_OK();
   GEOBI_TRY(timer.mark());
-  size_t tb = b.sort_temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)n, 0u, kEdgeKeyBits, s,
-                                      false));
+  GEOBI_TRY(sort_edge_table(b.t, F, s));
   GEOBI_TRY(timer.mark());
   GEOBI_HIP(hipMemsetAsync(b.counts, 0, sizeof(int) * kCounts, s));
-  subdiv_flags_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, points, adaptive, L2, b.split, b.counts);
+  subdiv_flags_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, n, points, adaptive, L2, b.split, b.counts);
   GEOBI_LAUNCH_OK();
-  tb = b.slot_scan_temp.bytes;
+  size_t tb = b.slot_scan_temp.bytes;
   GEOBI_HIP(rocprim::exclusive_scan(b.slot_scan_temp.p, tb, b.split, b.rank, 0, (size_t)n, rocprim::plus<int>(), s, false));
-  subdiv_slot_mid_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, b.v_out, n, points, adaptive, L2, b.split, b.rank, b.slot_mid);
+  subdiv_slot_mid_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, n, points, adaptive, L2, b.split, b.rank, b.slot_mid);
   GEOBI_LAUNCH_OK();
   subdiv_child_count_kernel<<<cdiv(F, kT), kT, 0, s>>>(b.slot_mid, (int)F, b.children);
   GEOBI_LAUNCH_OK();
@@ -368,7 +347,7 @@ int geobi_subdiv_plan(const int32_t* faces, const float* points, int64_t F, int6
   subdiv_totals_kernel<<<1, 1, 0, s>>>(b.children, b.first_child, (int)F, (int)V, loop != 0 ? 1 : 0, b.counts);
   GEOBI_LAUNCH_OK();
   if (loop != 0) {
-    subdiv_pairs_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.k_out, n, b.p_in);
+    subdiv_pairs_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, n, b.p_in);
     GEOBI_LAUNCH_OK();
     tb = b.pair_sort_temp.bytes;
     GEOBI_HIP(rocprim::radix_sort_keys(b.pair_sort_temp.p, tb, b.p_in, b.p_out, (size_t)(2 * n), 0u, kPairBits, s, false));
@@ -381,8 +360,7 @@ int geobi_subdiv_plan(const int32_t* faces, const float* points, int64_t F, int6
 int geobi_subdiv_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int64_t Vn, int64_t Fn,
                       int32_t* faces_out, int32_t* face_parent, int32_t* vertex_parents, float* points_out,
                       const void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_MESH_SIZES(F, V);
   GEOBI_SIZES(Vn > Fn ? Vn : Fn, 0);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(faces_out); GEOBI_NOTNULL(face_parent);
   GEOBI_NOTNULL(vertex_parents); GEOBI_NOTNULL(points_out);
@@ -399,11 +377,11 @@ int geobi_subdiv_emit(const int32_t* faces, const float* points, int64_t F, int6
     return 0;
   }
   SubdivBuffers b;
-  GEOBI_TRY(carve_checked("subdiv_emit", F, const_cast<void*>(ws), ws_bytes, b));
+  GEOBI_TRY(subdiv_buffers("subdiv_emit", F, const_cast<void*>(ws), ws_bytes, b));
   subdiv_faces_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, (int)F, (int)V, points, b.slot_mid, b.first_child, (int)Fn, faces_out,
                                                  face_parent);
   GEOBI_LAUNCH_OK();
-  subdiv_new_parents_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.k_out, (int)(3 * F), b.split, b.rank, (int)V, (int)Vn,
+  subdiv_new_parents_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.t.k_out, (int)(3 * F), b.split, b.rank, (int)V, (int)Vn,
                                                           vertex_parents);
   GEOBI_LAUNCH_OK();
   return launch_points(faces, points, F, V, loop, Vn, b, points_out, s);
@@ -411,8 +389,7 @@ int geobi_subdiv_emit(const int32_t* faces, const float* points, int64_t F, int6
 
 int geobi_subdiv_points(const int32_t* faces, const float* points, int64_t F, int64_t V, int loop, int64_t Vn,
                         float* points_out, const void* ws, size_t ws_bytes, void* stream) {
-  GEOBI_SIZES(F > V ? F : V, 0);
-  GEOBI_SIZES(F < V ? F : V, 0);
+  GEOBI_MESH_SIZES(F, V);
   GEOBI_SIZES(Vn, 0);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(points_out);
   GEOBI_REQUIRE(Vn >= V && Vn - V <= 3 * F, "subdiv_points: V' = %lld is not what a plan of V = %lld, F = %lld can give",
@@ -423,7 +400,7 @@ int geobi_subdiv_points(const int32_t* faces, const float* points, int64_t F, in
     return 0;
   }
   SubdivBuffers b;
-  GEOBI_TRY(carve_checked("subdiv_points", F, const_cast<void*>(ws), ws_bytes, b));
+  GEOBI_TRY(subdiv_buffers("subdiv_points", F, const_cast<void*>(ws), ws_bytes, b));
   return launch_points(faces, points, F, V, loop, Vn, b, points_out, s);
 }
 

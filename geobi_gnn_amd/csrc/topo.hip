@@ -2,7 +2,8 @@
 // stage between "weld / drop bad faces" (clean.hip) and "build graphs".
 //
 // Everything is integer-exact and independent of launch geometry; there is no floating point in this file:
-//   table    every included face (state 1, three different corners) lists its three UNDIRECTED edges lo << 24 | hi in the
+//   table    the edge table of edge_table.h, which subdiv.hip, decim.hip and remesh.hip build through the same code: every
+//            included face (state 1, three different corners) lists its three UNDIRECTED edges lo << 24 | hi in the
 //            slots 3f + k, sorted stably (48 bits, rocPRIM) with slot << 1 | direction bit as value: a run lists the
 //            claimants of one edge in ascending slot order.  One pass over the sorted table writes, per slot, the
 //            orientation link (runs of exactly two with different opposite corners; odd when the direction bits are equal)
@@ -17,7 +18,6 @@
 // Every value used as an index is a face index below F: keys only ever hold 2 * face + bit, links hold slot / 3.
 #include "common.h"
 #include "edge_table.h"
-#include "rocprim_temp.h"
 #include "stage_timer.h"
 #include "../../include/geobi_hip.h"
 
@@ -223,25 +223,18 @@ __global__ void topo_components_out_kernel(const int* __restrict__ fv, const int
 }
 
 struct TopoBuffers {
-  uint64_t *k_in, *k_out;
-  int *v_in, *v_out, *olink, *clink, *per_label, *used, *flags;    // per_label: bad marks, then component sizes
+  MeshTables t;                                                    // the edge table alone
+  int *olink, *clink, *per_label, *used, *flags;                   // per_label: bad marks, then component sizes
   uint32_t *key, *next;
-  SubWs sort_temp;
 };
 TopoBuffers carve_topo(Arena& a, int64_t F, int64_t V) {
-  return {a.take<uint64_t>(3 * F), a.take<uint64_t>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F),
-          a.take<int>(6 * F), a.take<int>(F), a.take<int>(V), a.take<int>(kBatch), a.take<uint32_t>(F), a.take<uint32_t>(F),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(3 * F, kEdgeKeyBits))};
+  return {carve_tables<false, false>(a, F), a.take<int>(3 * F), a.take<int>(6 * F), a.take<int>(F), a.take<int>(V),
+          a.take<int>(kBatch), a.take<uint32_t>(F), a.take<uint32_t>(F)};
 }
 
 int build_table(const int32_t* faces, const int32_t* state, int64_t F, int64_t V, const TopoBuffers& b, hipStream_t s) {
-  const int n = (int)F;
-  edge_slots_kernel<<<cdiv(F, kT), kT, 0, s>>>(faces, state, n, (int)V, b.k_in, b.v_in);
-  GEOBI_LAUNCH_OK();
-  size_t tb = b.sort_temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.sort_temp.p, tb, b.k_in, b.k_out, b.v_in, b.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
-                                      s, false));
-  topo_links_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.k_out, b.v_out, faces, 3 * n, b.olink, b.clink);
+  GEOBI_TRY(build_edge_table(b.t, faces, state, F, V, s));
+  topo_links_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, faces, (int)(3 * F), b.olink, b.clink);
   GEOBI_LAUNCH_OK();
   return 0;
 }
@@ -275,11 +268,8 @@ int run_rounds(const char* what, const int* links, int L, int64_t F, int max_rou
   }
 }
 
-int carve_checked(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, TopoBuffers& b) {
-  Arena a(ws, ws_bytes);
-  b = carve_topo(a, F, V);
-  GEOBI_WS_CHECK(what, a, ws, ws_bytes);
-  return 0;
+int topo_buffers(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, TopoBuffers& b) {
+  return carve_checked(what, ws, ws_bytes, b, [&](Arena& a) { return carve_topo(a, F, V); });
 }
 
 }  // namespace
@@ -307,7 +297,7 @@ int geobi_topo_orient(const int32_t* faces, const int32_t* state, int64_t F, int
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 3, s));
   if (F == 0) return 0;
   TopoBuffers b;
-  GEOBI_TRY(carve_checked("topo_orient", F, 0, ws, ws_bytes, b));
+  GEOBI_TRY(topo_buffers("topo_orient", F, 0, ws, ws_bytes, b));
   StageTimer timer(stage_ms, s);
   GEOBI_TRY(timer.mark());
   GEOBI_TRY(build_table(faces, state, F, V, b, s));
@@ -336,7 +326,7 @@ int geobi_topo_components(const int32_t* faces, const int32_t* state, int64_t F,
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 3, s));
   if (F == 0) return 0;
   TopoBuffers b;
-  GEOBI_TRY(carve_checked("topo_components", F, 0, ws, ws_bytes, b));
+  GEOBI_TRY(topo_buffers("topo_components", F, 0, ws, ws_bytes, b));
   StageTimer timer(stage_ms, s);
   GEOBI_TRY(timer.mark());
   GEOBI_TRY(build_table(faces, state, F, V, b, s));
@@ -363,10 +353,10 @@ int geobi_topo_report(const int32_t* faces, const int32_t* state, int64_t F, int
   GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * 16, s));
   if (F == 0) return 0;
   TopoBuffers b;
-  GEOBI_TRY(carve_checked("topo_report", F, V, ws, ws_bytes, b));
+  GEOBI_TRY(topo_buffers("topo_report", F, V, ws, ws_bytes, b));
   const int blocks = cdiv(F, kT);
   GEOBI_TRY(build_table(faces, state, F, V, b, s));
-  topo_edge_report_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.k_out, b.v_out, 3 * (int)F, counts);
+  topo_edge_report_kernel<<<cdiv(3 * F, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, 3 * (int)F, counts);
   GEOBI_LAUNCH_OK();
   if (V > 0) GEOBI_HIP(hipMemsetAsync(b.used, 0, sizeof(int) * (size_t)V, s));
   topo_mark_used_kernel<<<blocks, kT, 0, s>>>(faces, state, (int)F, (int)V, b.used, counts);

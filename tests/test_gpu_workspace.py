@@ -14,7 +14,8 @@ Short        request k of a case gets its first nbytes - 512 bytes (the requests
              512 bytes, or nothing at all.  For those the assertion is the opposite one: the call succeeds, with the same
              bits and whole sentinels.
 
-Shapes: an icosphere of subdivision 2 (162 vertices, 320 faces); node, edge, row and segment counts of 63, 64 and 65
+Shapes: the icosphere of meshgen.icosphere(2) (42 vertices, 80 faces), for subdivide, decimate and the remeshing steps with its
+vertices jittered by a fixed seed, so that edges are short and long and (after the collapses) valences flip; node, edge, row and segment counts of 63, 64 and 65
 (4 n crosses a 256-byte line between 64 and 65); 2^18 + 1 for relabel, match_coarsen, vertex_faces and segment_csr,
 whose scan or sort temporary comes from rocPRIM above 2^18; 33 parts (two launches of 32) for the part tables; FeaSt at
 (6, 32) and (128, 128) with 65 nodes; the heads at the fused width (32, 1024) and at (8, 2048), 65 rows; row_loss also at
@@ -145,6 +146,54 @@ def case_topo(dev):
     V = pts.shape[0]
     return [meshtopo.orient_faces(faces, V, device=dev), meshtopo.face_components(faces, V, min_component=3, device=dev),
             meshtopo.mesh_report(pts, faces, device=dev)]
+
+
+def _jittered_sphere(dev):
+    """the sphere with every vertex moved by a fixed normal draw of sigma 0.05, a tenth of an edge: some edges fall below
+    0.8 of the mean and some lie above it -> points, faces, the mean edge length"""
+    from geobi_gnn_amd import meshgen
+    pts, faces = meshgen.icosphere(2)
+    pts = (np.asarray(pts, np.float64) + 0.05 * np.random.RandomState(7).standard_normal(pts.shape)).astype(np.float32)
+    f = np.asarray(faces, np.int64)
+    edges = np.unique(np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1), axis=0)
+    mean_edge = float(np.linalg.norm(pts[edges[:, 0]].astype(np.float64) - pts[edges[:, 1]], axis=1).mean())
+    return _t(pts, dev, torch.float32), _t(faces, dev, torch.int64), mean_edge
+
+
+def case_subdiv(dev):
+    """one pass of each form (for max_edge: its rounds), and the stored plans replayed by ``apply``"""
+    from geobi_gnn_amd import meshsubdiv
+    pts, faces, mean_edge = _jittered_sphere(dev)
+    out = []
+    for kwargs in ({'scheme': 'midpoint'}, {'scheme': 'loop'}, {'max_edge': mean_edge}):
+        r = meshsubdiv.subdivide(pts, faces, levels=1, device=dev, **kwargs)
+        assert r.counts['split'] > 0
+        out += [r.points, r.faces, r.face_parent, r.vertex_parents, r.counts, meshsubdiv.apply(r, pts)]
+    return out
+
+
+def case_decim(dev):
+    """one round: the budget of F - 2 faces is one collapse"""
+    from geobi_gnn_amd import meshdecim
+    pts, faces, _ = _jittered_sphere(dev)
+    r = meshdecim.decimate(pts, faces, target_faces=faces.shape[0] - 2, device=dev)
+    assert r.counts['rounds'] == 1 and r.counts['collapses'] == 1
+    return [r.points, r.faces, r.face_map, r.vertex_map, r.counts, meshdecim.apply(r, pts)]
+
+
+def case_remesh(dev):
+    """every single step once, each on the result of the one before: the collapsed mesh has the valences that flip"""
+    from geobi_gnn_amd import meshremesh
+    pts, faces, mean_edge = _jittered_sphere(dev)
+    low, high = meshremesh.band(mean_edge)
+    lock, lock_counts = meshremesh.lock_flags(pts, faces, device=dev)
+    pts, faces, collapse_counts = meshremesh.collapse_short(pts, faces, low, high, lock=lock, device=dev)
+    faces, flip_counts = meshremesh.flip_edges(pts, faces, device=dev)
+    assert collapse_counts['collapses'] > 0 and flip_counts['flips'] > 0
+    pts, relax_counts = meshremesh.relax(pts, faces, device=dev)
+    assert relax_counts['moved'] > 0
+    return [lock, lock_counts, collapse_counts, flip_counts, relax_counts, pts, faces,
+            meshremesh.mesh_stats(pts, faces, low, high, device=dev)]
 
 
 def case_meshprep(dev):
@@ -321,7 +370,7 @@ def case_row_loss(dev):
     return [ops.row_loss(_rand(dev, n, n, 3), _rand(dev, n + 1, n, 3), 0) for n in COUNTS + (65 * 1024 + 1,)]
 
 
-CASES = {f.__name__[5:]: f for f in (case_clean, case_topo, case_meshprep, case_submesh, case_mesheval, case_parts,
+CASES = {f.__name__[5:]: f for f in (case_clean, case_topo, case_subdiv, case_decim, case_remesh, case_meshprep, case_submesh, case_mesheval, case_parts,
                                      case_filters, case_vertex_update, case_graph, case_pool, case_pool_big,
                                      case_feast_small, case_feast_wide, case_head_fused, case_head_unfused, case_row_loss)}
 
