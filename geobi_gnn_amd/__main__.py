@@ -19,6 +19,7 @@
   python -m geobi_gnn_amd decimate --data_dir DIR [--out_dir DIR/decimated] (--ratio R | --faces N) [--max_cost C] [--max_rounds 256]
   python -m geobi_gnn_amd remesh --data_dir DIR [--out_dir DIR/remeshed] [--target_edge L | --target_edge_diag R] [--iterations 5]
                                  [--feature_angle 40] [--relax_lambda 0.5] [--max_rounds 64]
+  python -m geobi_gnn_amd fill --data_dir DIR [--out_dir DIR/filled] [--max_hole_edges N] [--gpu -1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
 present, every original/NAME.obj is paired with its noisy/NAME_n*.obj and the two angular errors are printed per file
@@ -50,7 +51,10 @@ surface -- what a CAD target of a few large triangles needs.  `subdivide` (meshs
 with DIR/original present the refinement is planned on original/NAME.obj and applied to every noisy/NAME_n*.obj of equal
 size, which keeps the pairs in correspondence.  `decimate` (meshdecim.py) is its inverse: rounds of quadric edge collapses
 until `--faces N` or `--ratio R` times the faces are left (`--max_cost C`: no collapse dearer than C), boundaries kept at
-full resolution, with the same folders and the same pairing of noisy files.  All device work runs in this one process.
+full resolution, with the same folders and the same pairing of noisy files.  `fill` (meshfill.py) closes the holes of every
+mesh: each closed boundary loop (`--max_hole_edges N`: of at most N edges, which leaves an open border open) gets one new
+vertex at the mean of its rim and a fan of faces, with the same folders; a noisy file gets its original's fill with every
+new vertex at the mean of its own rim.  All device work runs in this one process.
 """
 import argparse
 import glob
@@ -483,6 +487,64 @@ def subdivide(opt):
     return 1 if failed or not files else 0
 
 
+def _fill_line(filled, out_file):
+    c = filled.counts
+    line = ("V: %7d -> %7d,  F: %7d -> %7d,  boundary: %d,  loops: %d,  filled: %d,  skipped: %d,  blocked: %d,  chain: %d,  '%s'"
+            % (filled.V, filled.points.shape[0], filled.F, filled.faces.shape[0], c['boundary_edges'], c['loops'],
+               c['filled_loops'], c['skipped_loops'], c['blocked_vertices'], c['chain_edges'], os.path.basename(out_file)))
+    return line + (',  run clean --orient first' if c['blocked_vertices'] or c['chain_edges'] else '')
+
+
+def fill(opt):
+    """Close the holes of every mesh of a folder on the device (meshfill), with the folders of `subdivide`: with
+    DIR/original, original/NAME.obj -> OUT/original/NAME.obj and the same fill on every noisy/NAME_n*.obj of the same size
+    -> OUT/noisy/; else DIR/*.obj -> OUT/NAME.obj."""
+    from . import meshfill, meshio
+    from ._lib import GeobiError
+    dev = _device(opt.gpu)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'filled')
+    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
+    paired = os.path.isdir(original_dir)
+    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
+    out_original = os.path.join(out_dir, 'original') if paired else out_dir
+    os.makedirs(out_original, exist_ok=True)
+    if paired:
+        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
+    print('\nFill, %s, %d files ...\n' % ('loops of at most %d edges' % opt.max_hole_edges if opt.max_hole_edges else
+                                          'every loop', len(files)), flush=True)
+    failed = 0
+    for path in files:
+        name = os.path.basename(path)[:-4]
+        try:
+            points, faces = meshio.read_obj(path)
+            filled = meshfill.fill_holes(points, faces, max_hole_edges=opt.max_hole_edges, device=dev)
+            faces_out = filled.faces.cpu().numpy()
+            out_file = os.path.join(out_original, name + '.obj')
+            meshio.write_obj(out_file, filled.points.cpu().numpy(), faces_out)
+            print(_fill_line(filled, out_file), flush=True)
+            if not paired:
+                continue
+            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
+                try:
+                    n_points, n_faces = meshio.read_obj(noisy)
+                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
+                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
+                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
+                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
+                    meshio.write_obj(out_file, meshfill.apply(filled, n_points).cpu().numpy(), faces_out)
+                    print(_fill_line(filled, out_file), flush=True)
+                except (ValueError, OSError) as e:
+                    failed += 1
+                    print('skipped: %s' % e, file=sys.stderr, flush=True)
+        except (ValueError, OSError, GeobiError) as e:
+            failed += 1
+            print('skipped: %s' % e, file=sys.stderr, flush=True)
+    print('\n--- end ---')
+    if failed:
+        print('%d files skipped' % failed, file=sys.stderr)
+    return 1 if failed or not files else 0
+
+
 INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 'complex_edges', 'inconsistent_edges',
              'components', 'orient_components', 'nonorientable', 'would_flip', 'euler')
 
@@ -860,6 +922,14 @@ def build_parser():
     r.add_argument('--max_rounds', type=_at_least_one_arg, default=64, help='rounds at most in each inner loop')
     r.add_argument('--gpu', type=int, default=-1)
     r.set_defaults(fn=remesh)
+    h = sub.add_parser('fill', help='close the holes of every mesh on the device: one new vertex and a fan of faces per '
+                                    'closed boundary loop')
+    h.add_argument('--data_dir', type=str, required=True, help='holds original/ (and noisy/), or the OBJ files themselves')
+    h.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/filled')
+    h.add_argument('--max_hole_edges', type=_count_arg, default=0, metavar='N',
+                   help='fill only the loops of at most N edges (0, the default: every loop)')
+    h.add_argument('--gpu', type=int, default=-1)
+    h.set_defaults(fn=fill)
     t = sub.add_parser('train', help='train on <data_dir>/train, evaluate on <data_dir>/test, keep the best model')
     from .trainer import add_train_flags
     add_train_flags(t)

@@ -1,5 +1,5 @@
-// The undirected edge table of the mesh tools, shared by topo.hip, clean.hip, subdiv.hip, decim.hip and
-// remesh.hip: which faces are included, which key a slot gets, how a run of the sorted table is read, how an index comes out
+// The undirected edge table of the mesh tools, shared by topo.hip, clean.hip, subdiv.hip, decim.hip,
+// remesh.hip and fill.hip: which faces are included, which key a slot gets, how a run of the sorted table is read, how an index comes out
 // of a key -- and MeshTables, the buffers of the table (and of the two tables mesh_tables.h derives from it) with their carve
 // and the one sort.  Sorting the slots stably on kEdgeKeyBits bits makes a run of equal keys one edge, its length the number
 // of claimants, the claimants in ascending slot order and the run heads ascend with (lo, hi).

@@ -1,5 +1,5 @@
 // Device events at the stage borders of one call, for the measurement tools (tools/bench_topo.py, tools/bench_subdiv.py,
-// tools/bench_decim.py, tools/bench_remesh.py).
+// tools/bench_decim.py, tools/bench_remesh.py, tools/bench_fill.py).
 #pragma once
 #include "common.h"
 
@@ -9,7 +9,8 @@ namespace geobi {
 struct StageTimer {
   float* out;
   hipStream_t s;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  static constexpr int kMaxMarks = 5;          // four stages at the most (fill.hip)
+  hipEvent_t ev[kMaxMarks] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int n = 0;
   StageTimer(float* out_ms, hipStream_t stream) : out(out_ms), s(stream) {}
   ~StageTimer() {
@@ -17,7 +18,7 @@ struct StageTimer {
       if (e != nullptr) (void)hipEventDestroy(e);
   }
   int mark() {
-    if (out == nullptr || n >= 4) return 0;
+    if (out == nullptr || n >= kMaxMarks) return 0;
     GEOBI_HIP(hipEventCreate(&ev[n]));
     GEOBI_HIP(hipEventRecord(ev[n], s));
     ++n;

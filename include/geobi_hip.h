@@ -12,8 +12,8 @@
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
  *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
  *     (reads its undecided counts through it), geobi_topo_orient / _components / _report (read the changed flags of
- *     their rounds through it), geobi_subdiv_plan, geobi_decim_plan, geobi_decim_plan_short, geobi_flip_plan and geobi_relax
- *     with stage_ms (wait for their own end; without it the call is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
+ *     their rounds through it), geobi_subdiv_plan, geobi_decim_plan, geobi_decim_plan_short, geobi_flip_plan, geobi_relax and
+ *     geobi_fill_plan with stage_ms (wait for their own end; without it the call is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -960,6 +960,64 @@ int geobi_relax(const int32_t* faces, const float* points, const int32_t* lock, 
                 float* points_out, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
 int geobi_remesh_stats(const int32_t* faces, const float* points, int64_t F, int64_t V, void* edge_len, int32_t* valence,
                        void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- hole filling (boundary loops, fan fill) ----
+ * Closes the holes of a triangle mesh; no counterpart in the reference.  The topology is integer-exact, a
+ * new position goes through ONE stated order of fp64 additions (no float atomics), nothing depends on launch geometry:
+ * tests/fill_model.py restates these rules in plain Python and reproduces every output bit.  faces [F, 3] int32 index
+ * [0, V) (range-check them first), points [V, 3] float32 finite; V, F <= GEOBI_MAX_NODES.
+ *   boundary slots       the edge table of geobi_topo_* / geobi_subdiv_* (the same code): a face is INCLUDED when its three
+ *                        corners differ; slot s = 3f + k of an included face joins its corners k and k + 1 (mod 3); a run
+ *                        of equal keys is one edge.  s is a BOUNDARY SLOT when its run has exactly one claimant.  The hole
+ *                        walks it against the face: from(s) = corner k + 1, to(s) = corner k.  B = the boundary slots.
+ *   simple vertices      out[v] = the boundary slots with from = v, in[v] = those with to = v.  v is SIMPLE iff out[v] ==
+ *                        in[v] == 1; every other vertex with out[v] + in[v] > 0 is BLOCKED (a bow-tie where two fans meet,
+ *                        a rim whose faces disagree in winding, the rim of a face next to a complex edge).
+ *   successor            next(s) = the one boundary slot with from == to(s) if to(s) is simple, else none.  A simple vertex
+ *                        has one incoming slot, so the slot graph is disjoint simple paths and simple cycles and nothing
+ *                        runs into a cycle from outside.  s is ON A LOOP iff following next from s returns to s; otherwise
+ *                        it is a CHAIN slot and is never filled.
+ *   loops                the LEADER of a loop is its lowest slot; rank(s) = the steps from the leader to s; len = the slots
+ *                        of the loop (3 or more by construction); the loops are numbered 0 .. L - 1 in ascending leader.
+ *   selection            loop i is SELECTED iff max_hole_edges == 0 or len_i <= max_hole_edges.  The j-th selected loop, in
+ *                        loop order, gets vertex V + j; its slot s gets face row F + off_j + rank(s) with the corners
+ *                        (from(s), to(s), V + j), off = the exclusive scan of len over the selected loops.  The old rows
+ *                        of points and faces are copied unchanged, faces that are not included and unreferenced vertices
+ *                        too.  Every filled edge then has two claimants that walk it in opposite directions, and the spoke
+ *                        edges are new because their far end is a new vertex: a fill never creates a complex or an
+ *                        inconsistent edge.  V' = V + selected, F' = F + the sum of the selected len.
+ *   position             of a new vertex, per coordinate: partial[l], l = 0 .. 63, starts at +0.0 and adds in fp64 the
+ *                        coordinate of from(s) for the ranks r == l (mod 64) in ascending r; total starts at +0.0 and adds
+ *                        partial[0 .. 63] in ascending l; the position is (float)(total / (double)len): one division and
+ *                        one rounding.
+ *   geobi_fill_plan      max_hole_edges >= 0.  Leaves the plan in `ws` and writes (each may be NULL) slot_loop [3F]: the
+ *                        loop number of a slot, -1 for a slot that is no boundary slot, -2 for a chain slot; slot_rank [3F]:
+ *                        rank(s), -1 off the loops; loop_leader [F] and loop_len [F]: their first L rows (L <= B / 3 <= F),
+ *                        the rows beyond them are unspecified.  counts (device int32 [16]): [0] boundary edges B, [1] blocked vertices,
+ *                        [2] chain edges, [3] loops L, [4] longest loop, [5] filled (selected) loops, [6] skipped loops,
+ *                        [7] new faces, [8] V', [9] F'.  Nothing of the fill is written yet: the caller reads the counts
+ *                        (geobi_read_i32) and sizes the outputs.  The loops come from two pointer doublings over
+ *                        the B boundary slots (labels: the lowest slot reachable, a slot without successor poisons its
+ *                        path; ranks: the distance to the leader), each of ceil(log2(max(3F, 2))) rounds -- a bound on
+ *                        log2 B that the host knows without a read-back.  F == 0 is valid (V' = V, F' = 0, no workspace
+ *                        needed).  stage_ms (HOST float [4], normally NULL) is for measurement: the milliseconds of the
+ *                        edge table, of the flags / counts / successors, of the two doublings, and of the loop tables, and
+ *                        the call then waits for its own end.
+ *   geobi_fill_emit      over the workspace of a plan of the same faces, F, V, with the V' and F' read from its counts (both
+ *                        checked against GEOBI_MAX_NODES before anything is written; a row beyond them is never written):
+ *                        faces_out [F', 3], points_out [V', 3], new_vertex_loop [V' - V], new_face_loop [F' - F] (the loop
+ *                        number of every new row).
+ *   geobi_fill_points    points_out [V', 3] alone for another point array [V, 3] over the same stored plan: the old rows
+ *                        copied, every centre taken from its own rim in that array.                                  */
+size_t geobi_fill_ws_bytes(int64_t F, int64_t V);
+int geobi_fill_plan(const int32_t* faces, int64_t F, int64_t V, int max_hole_edges, int32_t* slot_loop,
+                    int32_t* slot_rank, int32_t* loop_leader, int32_t* loop_len, int32_t* counts, float* stage_ms,
+                    void* ws, size_t ws_bytes, void* stream);
+int geobi_fill_emit(const int32_t* faces, const float* points, int64_t F, int64_t V, int64_t Vn, int64_t Fn,
+                    int32_t* faces_out, float* points_out, int32_t* new_vertex_loop, int32_t* new_face_loop,
+                    const void* ws, size_t ws_bytes, void* stream);
+int geobi_fill_points(const float* points, int64_t F, int64_t V, int64_t Vn, float* points_out, const void* ws,
+                      size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
