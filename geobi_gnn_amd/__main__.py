@@ -57,12 +57,13 @@ vertex at the mean of its rim and a fan of faces, with the same folders; a noisy
 new vertex at the mean of its own rim.  All device work runs in this one process.
 """
 import argparse
-import glob
 import os
 import sys
 import time
 
 import numpy as np
+
+from . import folders
 
 
 BNF_N_ITER = 20          # vertex-update sweeps of --method bnf / gnf when --n_iter is not given (filters.bilateral_denoise's default)
@@ -81,13 +82,9 @@ def _denoise_list(data_dir, noisy_dir=''):
     if not in DIR/noisy (`train` hands over the test meshes it drew itself)."""
     original_dir, noisy_dir = os.path.join(data_dir, 'original'), noisy_dir or os.path.join(data_dir, 'noisy')
     if os.path.isdir(original_dir) and os.path.isdir(noisy_dir):
-        jobs = []
-        for gt in sorted(glob.glob(os.path.join(glob.escape(original_dir), '*.obj'))):
-            stem = os.path.basename(gt)[:-4]
-            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(stem) + '_n*.obj'))):
-                jobs.append((noisy, gt))
-        return jobs
-    return [(f, None) for f in sorted(glob.glob(os.path.join(glob.escape(data_dir), '*.obj')))]
+        return [(noisy, gt) for gt in folders.obj_files(original_dir)
+                for noisy in folders.noisy_of(noisy_dir, folders.stem_of(gt))]
+    return [(f, None) for f in folders.obj_files(data_dir)]
 
 
 def _device(gpu):
@@ -215,9 +212,9 @@ def align_list(data_dir, target_dir):
     """[(source file, target file)] in sorted order: mesheval.pair_files' pairing, every target_dir/NAME.obj with every
     data_dir/NAME_*.obj, and with data_dir/NAME.obj where the stem has no NAME_*.obj."""
     jobs = []
-    for target in sorted(glob.glob(os.path.join(glob.escape(target_dir), '*.obj'))):
-        stem = os.path.basename(target)[:-4]
-        found = sorted(glob.glob(os.path.join(glob.escape(data_dir), glob.escape(stem) + '_*.obj')))
+    for target in folders.obj_files(target_dir):
+        stem = folders.stem_of(target)
+        found = folders.variants_of(data_dir, stem)
         same = os.path.join(data_dir, stem + '.obj')
         if not found and os.path.isfile(same):
             found = [same]
@@ -229,47 +226,39 @@ def align(opt):
     """Every source mesh of --data_dir aligned to its target of --target_dir by rigid ICP on the device (mesheval.align),
     written to --out_dir with aligned vertices and its own faces."""
     from . import mesheval, meshio, meshnoise
-    from ._lib import GeobiError
     dev = _device(opt.gpu)
     jobs = align_list(opt.data_dir, opt.target_dir)
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'aligned')
     os.makedirs(out_dir, exist_ok=True)
     print('\nAlign, scale %s, reflections %s, max_iter %d, rmse_thr %g, %d files ...\n'
           % ('on' if opt.scale else 'off', 'on' if opt.reflect else 'off', opt.max_iter, opt.rmse_thr, len(jobs)), flush=True)
-    failed = 0
-    for source, target in jobs:
+
+    def one(job, skip):
+        source, target = job
         t0 = time.time()
-        try:
-            points, faces = meshio.read_obj(source)
-            t_points, t_faces = meshio.read_obj(target)
-            if points.shape[0] == 0 or t_points.shape[0] == 0:
-                raise ValueError('%s or its target %s has no vertices' % (source, target))
-            sampling = {}
-            if opt.samples:         # the target's surface joins its vertices: the stream is the target's name
-                sampling = {'target_faces': t_faces, 'samples': opt.samples, 'seed': opt.seed,
-                            'stream_id': meshnoise.stream_of(os.path.basename(target)[:-4])}
-            res = mesheval.align(points, t_points, device=dev, estimate_scale=opt.scale, allow_reflection=opt.reflect,
-                                 max_iterations=opt.max_iter, relative_rmse_thr=opt.rmse_thr, **sampling)
-            out_file = os.path.join(out_dir, os.path.basename(source))
-            meshio.write_obj(out_file, res.xt.cpu().numpy(), faces)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-            continue
+        points, faces = meshio.read_obj(source)
+        t_points, t_faces = meshio.read_obj(target)
+        if points.shape[0] == 0 or t_points.shape[0] == 0:
+            raise ValueError('%s or its target %s has no vertices' % (source, target))
+        sampling = {}
+        if opt.samples:         # the target's surface joins its vertices: the stream is the target's name
+            sampling = {'target_faces': t_faces, 'samples': opt.samples, 'seed': opt.seed,
+                        'stream_id': meshnoise.stream_of(folders.stem_of(target))}
+        res = mesheval.align(points, t_points, device=dev, estimate_scale=opt.scale, allow_reflection=opt.reflect,
+                             max_iterations=opt.max_iter, relative_rmse_thr=opt.rmse_thr, **sampling)
+        out_file = os.path.join(out_dir, os.path.basename(source))
+        meshio.write_obj(out_file, res.xt.cpu().numpy(), faces)
         info = mesheval.align_info(res)
         print("iterations: %3d,  converged: %s,  rmse: %.6e,  scale: %.6f,  angle: %10.6f,  shift: %.6f,  time: %7.4f s,  '%s'"
               % (info['icp_iterations'], 'yes' if info['icp_converged'] else 'no', info['icp_rmse'], info['icp_scale'],
                  info['icp_angle'], info['icp_shift'], time.time() - t0, os.path.basename(out_file)), flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d of %d files skipped' % (failed, len(jobs)), file=sys.stderr)
-    return 1 if failed or not jobs else 0
+
+    return folders.walk(jobs, one)
 
 
 def noise(opt):
     """original/NAME.obj -> noisy/NAME_n<k>.obj for every level k = 1.., drawn on the device (meshnoise)."""
     from . import meshio, meshnoise
-    from ._lib import GeobiError
     from .dataset import read_original
     dev = _device(opt.gpu)
     try:
@@ -277,71 +266,56 @@ def noise(opt):
     except ValueError as e:
         print('noise: %s' % e, file=sys.stderr)
         return 1
-    originals = sorted(glob.glob(os.path.join(glob.escape(os.path.join(opt.data_dir, 'original')), '*.obj')))
+    originals = folders.obj_files(os.path.join(opt.data_dir, 'original'))
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'noisy')
     os.makedirs(out_dir, exist_ok=True)
     print('\nNoise %s / %s, levels %s, seed %d, %d files ...\n'
           % (options.kind, options.direction, ','.join('%g' % v for v in options.levels), options.seed, len(originals)),
           flush=True)
-    failed = 0
-    for original in originals:
-        name = os.path.basename(original)[:-4]
-        try:
-            points, faces = read_original(original)
-            geom = meshnoise.MeshGeometry(points, faces, dev)
-            for k, level in enumerate(options.levels, 1):
-                noisy = geom.draw(level, options.kind, options.direction, options.fraction, options.seed,
-                                  meshnoise.stream_of(name), k)
-                out_file = os.path.join(out_dir, meshnoise.noisy_name(name, k) + '.obj')
-                meshio.write_obj(out_file, noisy.cpu().numpy(), faces)
-                print("V: %7d,  F: %7d,  L: %.6g,  sigma: %.6g,  '%s'"
-                      % (points.shape[0], faces.shape[0], geom.mean_edge, geom.sigma(level), os.path.basename(out_file)),
-                      flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d of %d files skipped' % (failed, len(originals)), file=sys.stderr)
-    return 1 if failed or not originals else 0
+
+    def one(original, skip):
+        name = folders.stem_of(original)
+        points, faces = read_original(original)
+        geom = meshnoise.MeshGeometry(points, faces, dev)
+        for k, level in enumerate(options.levels, 1):
+            noisy = geom.draw(level, options.kind, options.direction, options.fraction, options.seed,
+                              meshnoise.stream_of(name), k)
+            out_file = os.path.join(out_dir, meshnoise.noisy_name(name, k) + '.obj')
+            meshio.write_obj(out_file, noisy.cpu().numpy(), faces)
+            print("V: %7d,  F: %7d,  L: %.6g,  sigma: %.6g,  '%s'"
+                  % (points.shape[0], faces.shape[0], geom.mean_edge, geom.sigma(level), os.path.basename(out_file)),
+                  flush=True)
+
+    return folders.walk(originals, one)
 
 
 def sample(opt):
     """Every DIR/original/*.obj, or else DIR/*.obj -> OUT/NAME.obj: --n points drawn by area on its surface (meshsample),
     `v` lines only, with --normals a `vn` line per point (the normal of the point's face)."""
     from . import meshin, meshio, meshnoise, meshsample
-    from ._lib import GeobiError
     dev = _device(opt.gpu)
-    original_dir = os.path.join(opt.data_dir, 'original')
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if os.path.isdir(original_dir) else opt.data_dir), '*.obj')))
+    files = folders.originals(opt.data_dir)[0]
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'samples')
     os.makedirs(out_dir, exist_ok=True)
     print('\nSample, n %d, seed %d, normals %s, %d files ...\n' % (opt.n, opt.seed, 'on' if opt.normals else 'off', len(files)),
           flush=True)
-    failed = 0
-    for path in files:
-        name = os.path.basename(path)[:-4]
-        try:
-            points, faces = meshio.read_obj(path)
-            if faces.shape[0] == 0:
-                raise ValueError('%s: no faces' % path)
-            p, fv = meshin.device_mesh(points, faces, dev)
-            weights = meshsample.surface_weights(p, fv, check=False)
-            area, zero = meshsample.surface_info(weights)
-            drawn = meshsample.sample_surface(p, fv, opt.n, seed=opt.seed, stream_id=meshnoise.stream_of(name), weights=weights,
-                                              check=False)
-            normals = meshsample.sample_normals(p, fv, drawn).cpu().numpy() if opt.normals else None
-            out_file = os.path.join(out_dir, name + '.obj')
-            meshio.write_obj(out_file, drawn.points.cpu().numpy(), np.zeros((0, 3), dtype=np.int32), normals=normals)
-            print("V: %7d,  F: %7d,  area: %.6g,  zero_faces: %d,  samples: %d,  '%s'"
-                  % (points.shape[0], faces.shape[0], area, zero, opt.n, os.path.basename(out_file)), flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d of %d files skipped' % (failed, len(files)), file=sys.stderr)
-    return 1 if failed or not files else 0
+
+    def one(path, skip):
+        points, faces = meshio.read_obj(path)
+        if faces.shape[0] == 0:
+            raise ValueError('%s: no faces' % path)
+        p, fv = meshin.device_mesh(points, faces, dev)
+        weights = meshsample.surface_weights(p, fv, check=False)
+        area, zero = meshsample.surface_info(weights)
+        drawn = meshsample.sample_surface(p, fv, opt.n, seed=opt.seed, stream_id=meshnoise.stream_of(folders.stem_of(path)),
+                                          weights=weights, check=False)
+        normals = meshsample.sample_normals(p, fv, drawn).cpu().numpy() if opt.normals else None
+        out_file = os.path.join(out_dir, os.path.basename(path))
+        meshio.write_obj(out_file, drawn.points.cpu().numpy(), np.zeros((0, 3), dtype=np.int32), normals=normals)
+        print("V: %7d,  F: %7d,  area: %.6g,  zero_faces: %d,  samples: %d,  '%s'"
+              % (points.shape[0], faces.shape[0], area, zero, opt.n, os.path.basename(out_file)), flush=True)
+
+    return folders.walk(files, one)
 
 
 def _weld_tol(opt):
@@ -351,6 +325,11 @@ def _weld_tol(opt):
 def _topo_args(opt):
     """--orient / --min_component as clean_mesh takes them (neither is in the options without its flag)"""
     return {'orient': getattr(opt, 'orient', False), 'min_component': getattr(opt, 'min_component', 0)}
+
+
+def _host_mesh(result):
+    """what a mesh tool made, as the arrays write_obj takes"""
+    return result.points.cpu().numpy(), result.faces.cpu().numpy()
 
 
 def _clean_line(cleaned, V, F, out_file):
@@ -367,55 +346,22 @@ def _clean_line(cleaned, V, F, out_file):
 def clean(opt):
     """Repair every mesh of a folder on the device (meshclean): with DIR/original, original/NAME.obj -> OUT/original/NAME.obj
     and the same maps on every noisy/NAME_n*.obj of the same size -> OUT/noisy/; else DIR/*.obj -> OUT/NAME.obj."""
-    from . import meshclean, meshio
-    from ._lib import GeobiError
+    from . import meshclean
     dev = _device(opt.gpu)
-    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'clean')
-    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
-    paired = os.path.isdir(original_dir)
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
-    out_original = os.path.join(out_dir, 'original') if paired else out_dir
-    os.makedirs(out_original, exist_ok=True)
-    if paired:
-        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
     weld_tol = _weld_tol(opt)
-    print('\nClean, weld %s, half-edge rule %s, %d files ...\n'
-          % ('off' if weld_tol is None else ('exact' if weld_tol == 0 else 'grid %g' % weld_tol),
-             'off' if opt.no_manifold else 'on', len(files)), flush=True)
-    failed = 0
-    for path in files:
-        name = os.path.basename(path)[:-4]
-        try:
-            points, faces = meshio.read_obj(path)
-            cleaned = meshclean.clean_mesh(points, faces, weld_tol=weld_tol, manifold=not opt.no_manifold, device=dev,
-                                           **_topo_args(opt))
-            if cleaned.faces.shape[0] == 0:
-                raise ValueError('%s: no faces left after cleaning' % path)
-            faces_out = cleaned.faces.cpu().numpy()
-            out_file = os.path.join(out_original, name + '.obj')
-            meshio.write_obj(out_file, cleaned.points.cpu().numpy(), faces_out)
-            print(_clean_line(cleaned, points.shape[0], faces.shape[0], out_file), flush=True)
-            if not paired:
-                continue
-            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
-                try:
-                    n_points, n_faces = meshio.read_obj(noisy)
-                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
-                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
-                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
-                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
-                    meshio.write_obj(out_file, meshclean.apply(cleaned, n_points), faces_out)
-                    print(_clean_line(cleaned, points.shape[0], faces.shape[0], out_file), flush=True)
-                except (ValueError, OSError) as e:
-                    failed += 1
-                    print('skipped: %s' % e, file=sys.stderr, flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d files skipped' % failed, file=sys.stderr)
-    return 1 if failed or not files else 0
+
+    def plan(points, faces, path):
+        cleaned = meshclean.clean_mesh(points, faces, weld_tol=weld_tol, manifold=not opt.no_manifold, device=dev,
+                                       **_topo_args(opt))
+        if cleaned.faces.shape[0] == 0:
+            raise ValueError('%s: no faces left after cleaning' % path)
+        return cleaned
+
+    title = 'Clean, weld %s, half-edge rule %s' % (
+        'off' if weld_tol is None else ('exact' if weld_tol == 0 else 'grid %g' % weld_tol), 'off' if opt.no_manifold else 'on')
+    # the maps index a numpy array as it is: a paired array never goes to the device
+    return folders.paired_walk(opt.data_dir, opt.out_dir or os.path.join(opt.data_dir, 'clean'), title, plan, _host_mesh,
+                               _clean_line, meshclean.apply)
 
 
 def _subdivide_line(refined, V, F, out_file):
@@ -425,72 +371,31 @@ def _subdivide_line(refined, V, F, out_file):
                c['complex_edges'], c['passes'], os.path.basename(out_file)))
 
 
-def bbox_diagonal(points):
-    """the diagonal of the bounding box of points [V, 3], in fp64 on the host (0 without points)"""
-    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
-    return float(np.sqrt(((p.max(axis=0) - p.min(axis=0)) ** 2).sum())) if p.shape[0] else 0.0
-
-
 def subdivide(opt):
     """Refine every mesh of a folder on the device (meshsubdiv), with the folders of `clean`: with DIR/original,
     original/NAME.obj -> OUT/original/NAME.obj and the same plan on every noisy/NAME_n*.obj of the same size -> OUT/noisy/;
     else DIR/*.obj -> OUT/NAME.obj."""
-    from . import meshio, meshsubdiv
-    from ._lib import GeobiError
+    from . import meshin, meshsubdiv
     dev = _device(opt.gpu)
-    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'subdivided')
-    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
-    paired = os.path.isdir(original_dir)
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
-    out_original = os.path.join(out_dir, 'original') if paired else out_dir
-    os.makedirs(out_original, exist_ok=True)
-    if paired:
-        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
+
+    def plan(points, faces, path):
+        max_edge = opt.max_edge
+        if opt.max_edge_diag is not None:
+            max_edge = opt.max_edge_diag * meshin.bbox_diagonal(points)
+        return meshsubdiv.subdivide(points, faces, levels=opt.levels, scheme=opt.scheme, max_edge=max_edge,
+                                    max_rounds=opt.max_rounds, device=dev)
+
     mode = ('max_edge %g' % opt.max_edge if opt.max_edge is not None else
             'max_edge %g of the diagonal' % opt.max_edge_diag if opt.max_edge_diag is not None else
             '%s, levels %d' % (opt.scheme, opt.levels))
-    print('\nSubdivide, %s, %d files ...\n' % (mode, len(files)), flush=True)
-    failed = 0
-    for path in files:
-        name = os.path.basename(path)[:-4]
-        try:
-            points, faces = meshio.read_obj(path)
-            max_edge = opt.max_edge
-            if opt.max_edge_diag is not None:
-                max_edge = opt.max_edge_diag * bbox_diagonal(points)
-            refined = meshsubdiv.subdivide(points, faces, levels=opt.levels, scheme=opt.scheme, max_edge=max_edge,
-                                           max_rounds=opt.max_rounds, device=dev)
-            faces_out = refined.faces.cpu().numpy()
-            out_file = os.path.join(out_original, name + '.obj')
-            meshio.write_obj(out_file, refined.points.cpu().numpy(), faces_out)
-            print(_subdivide_line(refined, points.shape[0], faces.shape[0], out_file), flush=True)
-            if not paired:
-                continue
-            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
-                try:
-                    n_points, n_faces = meshio.read_obj(noisy)
-                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
-                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
-                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
-                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
-                    meshio.write_obj(out_file, meshsubdiv.apply(refined, n_points).cpu().numpy(), faces_out)
-                    print(_subdivide_line(refined, points.shape[0], faces.shape[0], out_file), flush=True)
-                except (ValueError, OSError) as e:
-                    failed += 1
-                    print('skipped: %s' % e, file=sys.stderr, flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d files skipped' % failed, file=sys.stderr)
-    return 1 if failed or not files else 0
+    return folders.paired_walk(opt.data_dir, opt.out_dir or os.path.join(opt.data_dir, 'subdivided'), 'Subdivide, ' + mode,
+                               plan, _host_mesh, _subdivide_line, lambda r, p: meshsubdiv.apply(r, p).cpu().numpy())
 
 
-def _fill_line(filled, out_file):
+def _fill_line(filled, V, F, out_file):
     c = filled.counts
     line = ("V: %7d -> %7d,  F: %7d -> %7d,  boundary: %d,  loops: %d,  filled: %d,  skipped: %d,  blocked: %d,  chain: %d,  '%s'"
-            % (filled.V, filled.points.shape[0], filled.F, filled.faces.shape[0], c['boundary_edges'], c['loops'],
+            % (V, filled.points.shape[0], F, filled.faces.shape[0], c['boundary_edges'], c['loops'],
                c['filled_loops'], c['skipped_loops'], c['blocked_vertices'], c['chain_edges'], os.path.basename(out_file)))
     return line + (',  run clean --orient first' if c['blocked_vertices'] or c['chain_edges'] else '')
 
@@ -499,50 +404,15 @@ def fill(opt):
     """Close the holes of every mesh of a folder on the device (meshfill), with the folders of `subdivide`: with
     DIR/original, original/NAME.obj -> OUT/original/NAME.obj and the same fill on every noisy/NAME_n*.obj of the same size
     -> OUT/noisy/; else DIR/*.obj -> OUT/NAME.obj."""
-    from . import meshfill, meshio
-    from ._lib import GeobiError
+    from . import meshfill
     dev = _device(opt.gpu)
-    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'filled')
-    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
-    paired = os.path.isdir(original_dir)
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
-    out_original = os.path.join(out_dir, 'original') if paired else out_dir
-    os.makedirs(out_original, exist_ok=True)
-    if paired:
-        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
-    print('\nFill, %s, %d files ...\n' % ('loops of at most %d edges' % opt.max_hole_edges if opt.max_hole_edges else
-                                          'every loop', len(files)), flush=True)
-    failed = 0
-    for path in files:
-        name = os.path.basename(path)[:-4]
-        try:
-            points, faces = meshio.read_obj(path)
-            filled = meshfill.fill_holes(points, faces, max_hole_edges=opt.max_hole_edges, device=dev)
-            faces_out = filled.faces.cpu().numpy()
-            out_file = os.path.join(out_original, name + '.obj')
-            meshio.write_obj(out_file, filled.points.cpu().numpy(), faces_out)
-            print(_fill_line(filled, out_file), flush=True)
-            if not paired:
-                continue
-            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
-                try:
-                    n_points, n_faces = meshio.read_obj(noisy)
-                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
-                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
-                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
-                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
-                    meshio.write_obj(out_file, meshfill.apply(filled, n_points).cpu().numpy(), faces_out)
-                    print(_fill_line(filled, out_file), flush=True)
-                except (ValueError, OSError) as e:
-                    failed += 1
-                    print('skipped: %s' % e, file=sys.stderr, flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d files skipped' % failed, file=sys.stderr)
-    return 1 if failed or not files else 0
+
+    def plan(points, faces, path):
+        return meshfill.fill_holes(points, faces, max_hole_edges=opt.max_hole_edges, device=dev)
+
+    title = 'Fill, %s' % ('loops of at most %d edges' % opt.max_hole_edges if opt.max_hole_edges else 'every loop')
+    return folders.paired_walk(opt.data_dir, opt.out_dir or os.path.join(opt.data_dir, 'filled'), title,
+                               plan, _host_mesh, _fill_line, lambda r, p: meshfill.apply(r, p).cpu().numpy())
 
 
 INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 'complex_edges', 'inconsistent_edges',
@@ -552,28 +422,20 @@ INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 
 def info(opt):
     """One meshtopo.mesh_report line per DIR/original/*.obj if that folder exists, else per DIR/*.obj."""
     from . import meshio, meshtopo
-    from ._lib import GeobiError
     dev = _device(opt.gpu)
-    original_dir = os.path.join(opt.data_dir, 'original')
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if os.path.isdir(original_dir) else opt.data_dir), '*.obj')))
+    files = folders.originals(opt.data_dir)[0]
     weld_tol = _weld_tol(opt)
     print('\nInfo, weld %s, %d files ...\n'
           % ('off' if weld_tol is None else ('exact' if weld_tol == 0 else 'grid %g' % weld_tol), len(files)), flush=True)
-    failed = 0
-    for path in files:
-        try:
-            points, faces = meshio.read_obj(path)
-            r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev)
-            print("V: %7d,  F: %7d,  %s,  closed: %s,  '%s'"
-                  % (points.shape[0], faces.shape[0], ',  '.join('%s: %d' % (k, r[k]) for k in INFO_KEYS),
-                     'yes' if r['closed'] else 'no', os.path.basename(path)), flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d of %d files skipped' % (failed, len(files)), file=sys.stderr)
-    return 1 if failed or not files else 0
+
+    def one(path, skip):
+        points, faces = meshio.read_obj(path)
+        r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev)
+        print("V: %7d,  F: %7d,  %s,  closed: %s,  '%s'"
+              % (points.shape[0], faces.shape[0], ',  '.join('%s: %d' % (k, r[k]) for k in INFO_KEYS),
+                 'yes' if r['closed'] else 'no', os.path.basename(path)), flush=True)
+
+    return folders.walk(files, one)
 
 
 def train(opt):
@@ -594,53 +456,18 @@ def decimate(opt):
     """Simplify every mesh of a folder on the device (meshdecim), with the folders of `subdivide`: with DIR/original,
     original/NAME.obj -> OUT/original/NAME.obj and the same collapses on every noisy/NAME_n*.obj of the same size ->
     OUT/noisy/; else DIR/*.obj -> OUT/NAME.obj."""
-    from . import meshdecim, meshio
-    from ._lib import GeobiError
+    from . import meshdecim
     dev = _device(opt.gpu)
-    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'decimated')
-    original_dir, noisy_dir = os.path.join(opt.data_dir, 'original'), os.path.join(opt.data_dir, 'noisy')
-    paired = os.path.isdir(original_dir)
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
-    out_original = os.path.join(out_dir, 'original') if paired else out_dir
-    os.makedirs(out_original, exist_ok=True)
-    if paired:
-        os.makedirs(os.path.join(out_dir, 'noisy'), exist_ok=True)
+
+    def plan(points, faces, path):
+        return meshdecim.decimate(points, faces, target_faces=opt.faces, ratio=opt.ratio, max_cost=opt.max_cost,
+                                  max_rounds=opt.max_rounds, device=dev)
+
     mode = ('to %d faces' % opt.faces if opt.faces is not None else 'to %g of the faces' % opt.ratio)
     if opt.max_cost is not None:
         mode += ', max_cost %g' % opt.max_cost
-    print('\nDecimate, %s, %d files ...\n' % (mode, len(files)), flush=True)
-    failed = 0
-    for path in files:
-        name = os.path.basename(path)[:-4]
-        try:
-            points, faces = meshio.read_obj(path)
-            decimated = meshdecim.decimate(points, faces, target_faces=opt.faces, ratio=opt.ratio, max_cost=opt.max_cost,
-                                           max_rounds=opt.max_rounds, device=dev)
-            faces_out = decimated.faces.cpu().numpy()
-            out_file = os.path.join(out_original, name + '.obj')
-            meshio.write_obj(out_file, decimated.points.cpu().numpy(), faces_out)
-            print(_decimate_line(decimated, points.shape[0], faces.shape[0], out_file), flush=True)
-            if not paired:
-                continue
-            for noisy in sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj'))):
-                try:
-                    n_points, n_faces = meshio.read_obj(noisy)
-                    if n_points.shape != points.shape or n_faces.shape != faces.shape:
-                        raise ValueError('%s (V = %d, F = %d) and its original %s (V = %d, F = %d) differ in size'
-                                         % (noisy, n_points.shape[0], n_faces.shape[0], path, points.shape[0], faces.shape[0]))
-                    out_file = os.path.join(out_dir, 'noisy', os.path.basename(noisy))
-                    meshio.write_obj(out_file, meshdecim.apply(decimated, n_points).cpu().numpy(), faces_out)
-                    print(_decimate_line(decimated, points.shape[0], faces.shape[0], out_file), flush=True)
-                except (ValueError, OSError) as e:
-                    failed += 1
-                    print('skipped: %s' % e, file=sys.stderr, flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d files skipped' % failed, file=sys.stderr)
-    return 1 if failed or not files else 0
+    return folders.paired_walk(opt.data_dir, opt.out_dir or os.path.join(opt.data_dir, 'decimated'), 'Decimate, ' + mode,
+                               plan, _host_mesh, _decimate_line, lambda r, p: meshdecim.apply(r, p).cpu().numpy())
 
 
 def _remesh_line(r, V, F, drift, out_file):
@@ -656,12 +483,9 @@ def remesh(opt):
     files of DIR/noisy are NOT carried along."""
     import torch
     from . import mesheval, meshin, meshio, meshremesh
-    from ._lib import GeobiError
     dev = _device(opt.gpu)
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'remeshed')
-    original_dir = os.path.join(opt.data_dir, 'original')
-    paired = os.path.isdir(original_dir)
-    files = sorted(glob.glob(os.path.join(glob.escape(original_dir if paired else opt.data_dir), '*.obj')))
+    files, paired = folders.originals(opt.data_dir)
     out_original = os.path.join(out_dir, 'original') if paired else out_dir
     os.makedirs(out_original, exist_ok=True)
     mode = ('target edge %g' % opt.target_edge if opt.target_edge is not None else
@@ -671,28 +495,22 @@ def remesh(opt):
     if paired and os.path.isdir(os.path.join(opt.data_dir, 'noisy')):
         print('noisy/ is not carried along: the relaxed vertices have no counterpart in a paired file.  Make new pairs '
               'with `noise` on the output folder.\n', flush=True)
-    failed = 0
-    for path in files:
-        try:
-            points, faces = meshio.read_obj(path)
-            r = meshremesh.remesh(points, faces, target_edge=opt.target_edge, target_edge_diag=opt.target_edge_diag,
-                                  iterations=opt.iterations, feature_angle=opt.feature_angle, relax_lambda=opt.relax_lambda,
-                                  max_rounds=opt.max_rounds, device=dev)
-            out_file = os.path.join(out_original, os.path.basename(path))
-            meshio.write_obj(out_file, r.points.cpu().numpy(), r.faces.cpu().numpy())
-            drift = (0.0, 0.0)
-            if r.points.shape[0] and faces.shape[0]:         # the new vertices against the INPUT surface
-                with torch.cuda.device(dev):
-                    d = mesheval.point_to_mesh(r.points, *meshin.device_mesh(points, faces, dev))[0]
-                drift = (float(d.double().mean()), float(d.max()))
-            print(_remesh_line(r, points.shape[0], faces.shape[0], drift, out_file), flush=True)
-        except (ValueError, OSError, GeobiError) as e:
-            failed += 1
-            print('skipped: %s' % e, file=sys.stderr, flush=True)
-    print('\n--- end ---')
-    if failed:
-        print('%d files skipped' % failed, file=sys.stderr)
-    return 1 if failed or not files else 0
+
+    def one(path, skip):
+        points, faces = meshio.read_obj(path)
+        r = meshremesh.remesh(points, faces, target_edge=opt.target_edge, target_edge_diag=opt.target_edge_diag,
+                              iterations=opt.iterations, feature_angle=opt.feature_angle, relax_lambda=opt.relax_lambda,
+                              max_rounds=opt.max_rounds, device=dev)
+        out_file = os.path.join(out_original, os.path.basename(path))
+        meshio.write_obj(out_file, *_host_mesh(r))
+        drift = (0.0, 0.0)
+        if r.points.shape[0] and faces.shape[0]:         # the new vertices against the INPUT surface
+            with torch.cuda.device(dev):
+                d = mesheval.point_to_mesh(r.points, *meshin.device_mesh(points, faces, dev))[0]
+            drift = (float(d.double().mean()), float(d.max()))
+        print(_remesh_line(r, points.shape[0], faces.shape[0], drift, out_file), flush=True)
+
+    return folders.walk(files, one, of_total=False)
 
 
 def _weld_tol_arg(text):
@@ -710,8 +528,9 @@ def _min_component_arg(text):
 
 
 def _samples_arg(text):
+    from .meshin import MAX_NODES
     v = int(text)
-    if not 0 <= v <= (1 << 24) - 1:
+    if not 0 <= v <= MAX_NODES:
         raise argparse.ArgumentTypeError('a number of samples is between 0 and 16 777 215, not %r' % text)
     return v
 

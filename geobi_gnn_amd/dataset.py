@@ -18,14 +18,13 @@ patches of at most ``filter_patch_count`` faces are dropped.  Preprocessing runs
 (meshprep.build_dual_data); the samples stay there with everything that depends on one mesh built once, so a training
 step's batch is data.union_batch_graphs over resident pairs -- which always copies: nothing downstream writes a sample.
 """
-import glob
 import os
 import sys
 
 import torch
 
 from . import _lib as L
-from . import meshio, meshnoise, meshprep, patches
+from . import folders, meshio, meshnoise, meshprep, patches
 from .data import load_processed, save_processed
 
 PROCESSED_FOLDER = 'processed_data'
@@ -39,7 +38,7 @@ def _originals(root, split, data_list_txt):
         with open(os.path.join(root, data_list_txt)) as fh:
             names = [ln.strip() for ln in fh if ln.strip()]
     else:
-        names = [os.path.basename(f)[:-4] for f in sorted(glob.glob(os.path.join(glob.escape(original_dir), '*.obj')))]
+        names = [folders.stem_of(f) for f in folders.obj_files(original_dir)]
     found = []
     for name in names:
         original = os.path.join(original_dir, name + '.obj')
@@ -67,7 +66,7 @@ def file_pairs(root, split, data_list_txt=None):
     noisy_dir = os.path.join(root, split, 'noisy')
     pairs = []
     for name, original in _originals(root, split, data_list_txt):
-        noisy = sorted(glob.glob(os.path.join(glob.escape(noisy_dir), glob.escape(name) + '_n*.obj')))
+        noisy = folders.noisy_of(noisy_dir, name)
         if not noisy:
             print('skipped: %s has no noisy file %s' % (name, os.path.join(noisy_dir, name + '_n*.obj')), file=sys.stderr,
                   flush=True)

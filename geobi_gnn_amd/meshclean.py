@@ -142,11 +142,9 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
     if int(min_component) < 0:
         raise ValueError('clean_mesh: min_component = %r (0 or more)' % (min_component,))
     # the face table is range-checked as it came in (an int64 id must not wrap into range), BEFORE any kernel walks it
-    pts, fv = meshin.device_mesh(meshin.as_tensor(points).reshape(-1, 3), meshin.as_tensor(faces).reshape(-1, 3), dev,
-                                 what='clean_mesh: faces', error=ValueError)
+    pts, fv = meshin.finite_mesh(meshin.as_tensor(points).reshape(-1, 3), meshin.as_tensor(faces).reshape(-1, 3), dev,
+                                 'clean_mesh')
     V, F = pts.shape[0], fv.shape[0]
-    if V > 0 and not bool(torch.isfinite(pts).all()):
-        raise ValueError('clean_mesh: non-finite point coordinates')
     with torch.cuda.device(dev):
         canon, wcounts = weld(pts, weld_tol)
         groups, bad = L.read_i32(wcounts)

@@ -18,7 +18,6 @@ import torch
 from . import _lib as L
 from . import meshin
 
-MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h
 COUNT_KEYS = ('edges', 'locked', 'valid', 'collapses', 'V', 'F', 'not_included', 'sweeps_selected')
 
 
@@ -41,20 +40,16 @@ class Decimated(object):
         self.counts, self.passes = counts, passes
 
 
-def _whole(value):
-    return not isinstance(value, bool) and isinstance(value, (int, np.integer))
-
-
 def check_args(target_faces=None, ratio=None, max_cost=None, max_rounds=256):
     """ValueError for what ``decimate`` does not take; -> (target_faces or None, ratio or None, max_cost as the float32 the
     device compares with or None)."""
-    if not _whole(max_rounds) or max_rounds < 1:
+    if not meshin.whole(max_rounds) or max_rounds < 1:
         raise ValueError('decimate: max_rounds = %r (a whole number, at least 1)' % (max_rounds,))
     if target_faces is not None and ratio is not None:
         raise ValueError('decimate: target_faces and ratio exclude each other')
     if target_faces is None and ratio is None and max_cost is None:
         raise ValueError('decimate: one of target_faces, ratio or max_cost must say when to stop')
-    if target_faces is not None and (not _whole(target_faces) or target_faces < 0):
+    if target_faces is not None and (not meshin.whole(target_faces) or target_faces < 0):
         raise ValueError('decimate: target_faces = %r (a whole number, not negative)' % (target_faces,))
     if ratio is not None:
         try:
@@ -112,10 +107,8 @@ def decimate(points, faces, target_faces=None, ratio=None, max_cost=None, max_ro
     [F, 3], a face index outside [0, V), non-finite points, arguments outside their range, not exactly one of target_faces /
     ratio / max_cost-alone; GeobiError: ``max_rounds`` rounds were not enough."""
     target_faces, ratio, max_cost = check_args(target_faces, ratio, max_cost, max_rounds)
-    pts, fv = meshin.device_mesh(points, faces, device, what='decimate: faces', error=ValueError)
+    pts, fv = meshin.finite_mesh(points, faces, device, 'decimate')
     dev, V, F = pts.device, pts.shape[0], fv.shape[0]
-    if V > 0 and not bool(torch.isfinite(pts).all()):
-        raise ValueError('decimate: non-finite point coordinates')
     target = stop_target(F, target_faces, ratio)
     passes, first, included = [], None, F
     with torch.cuda.device(dev):
@@ -147,12 +140,9 @@ def apply(decimated, other_points):
     """Another point array of the INPUT's size [V, 3] (the paired noisy points) -> [V', 3] float32 on the device: the
     same merges and the same placements, round by round.  ``apply(decimated, the input points)`` is bit-equal to
     ``decimated.points``."""
-    other = meshin.as_tensor(other_points)
-    V = decimated.passes[0].V if decimated.passes else decimated.points.shape[0]
-    if other.dim() != 2 or other.shape[1] != 3 or other.shape[0] != V:
-        raise ValueError('apply: points %s for a decimation of %d vertices' % (tuple(other.shape), V))
     dev = decimated.points.device
-    pts = meshin.to_device(other, dev, torch.float32)
+    pts = meshin.paired_points(other_points, decimated.passes[0].V if decimated.passes else decimated.points.shape[0], dev,
+                               'a decimation of')
     with torch.cuda.device(dev):
         for p in decimated.passes:
             out = torch.empty((p.Vn, 3), dtype=torch.float32, device=dev)

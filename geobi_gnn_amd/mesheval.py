@@ -6,13 +6,12 @@ CPU threads (code/my_hausdorff.py) and keeps the point-to-surface form commented
 are all-pairs HIP kernels here (csrc/dist.hip: geobi_nearest_point, geobi_nearest_triangle); sums and maxima are
 reduced in fp64 on the device (geobi_dist_summary), and one read brings a pair's numbers to the host.
 """
-import glob
 import os
 
 import torch
 
 from . import _lib as L
-from . import meshin, meshio, meshnoise, meshprep, network, ops
+from . import folders, meshin, meshio, meshnoise, meshprep, network, ops
 from .data_util import computer_face_normal, face_centroids
 
 
@@ -265,12 +264,8 @@ def sampled_totals(rows):
 def pair_files(dir_result, dir_original):
     """The reference's pairing (code/data_util.py:563-567), sorted: every dir_original/NAME.obj with every
     dir_result/NAME_*.obj -> [(result file, original file)]."""
-    pairs = []
-    for name in sorted(glob.glob(os.path.join(glob.escape(dir_original), '*.obj'))):
-        stem = os.path.basename(name)[:-4]
-        for name_r in sorted(glob.glob(os.path.join(glob.escape(dir_result), glob.escape(stem) + '_*.obj'))):
-            pairs.append((name_r, name))
-    return pairs
+    return [(name_r, name) for name in folders.obj_files(dir_original)
+            for name_r in folders.variants_of(dir_result, folders.stem_of(name))]
 
 
 _FILE_FMT = '{0:<{1}}  {2:>7}  {3:.6f}  {4:9.6f}  {5:>7}  {6:9.6f}  {7:.6f}  {8:9.6f}  {9:.6f}  {10:9.6f}\n'

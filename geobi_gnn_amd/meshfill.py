@@ -8,13 +8,12 @@ every new face gets and the order of the sum behind every new position -- are st
 runs through a blocked vertex (a bow-tie, faces wound against each other) is a chain and stays open: ``clean --orient``
 first.  No CPU fallback.
 """
-import numpy as np
 import torch
 
 from . import _lib as L
 from . import meshin
 
-MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h
+MAX_NODES = meshin.MAX_NODES
 COUNT_KEYS = ('boundary_edges', 'blocked_vertices', 'chain_edges', 'loops', 'longest_loop', 'filled_loops', 'skipped_loops',
               'new_faces')
 
@@ -42,7 +41,7 @@ class Filled(object):
 
 def check_args(max_hole_edges=0):
     """ValueError for what ``fill_holes`` does not take"""
-    if isinstance(max_hole_edges, bool) or not isinstance(max_hole_edges, (int, np.integer)) or max_hole_edges < 0:
+    if not meshin.whole(max_hole_edges) or max_hole_edges < 0:
         raise ValueError('fill: max_hole_edges = %r (a whole number; 0 fills every loop)' % (max_hole_edges,))
     return min(int(max_hole_edges), 2 ** 31 - 1)      # the C int of the entry point; no loop is that long
 
@@ -86,7 +85,7 @@ def _emit(fv, pts, Vn, Fn, ws):
 def boundary_loops(faces, V, device=None):
     """faces [F, 3] of a mesh of V vertices -> Loops.  ValueError: a shape other than [F, 3], V outside [0,
     GEOBI_MAX_NODES], a face index outside [0, V)."""
-    if isinstance(V, bool) or not isinstance(V, (int, np.integer)) or not 0 <= V <= MAX_NODES:
+    if not meshin.whole(V) or not 0 <= V <= MAX_NODES:
         raise ValueError('boundary_loops: V = %r (a vertex count, at most GEOBI_MAX_NODES = %d)' % (V, MAX_NODES))
     fv = meshin.as_tensor(faces)
     if fv.dim() != 2 or fv.shape[1] != 3:
@@ -104,10 +103,8 @@ def fill_holes(points, faces, max_hole_edges=0, device=None):
     non-finite points, a max_hole_edges that is no whole number >= 0; GeobiError: an output beyond GEOBI_MAX_NODES rows
     (nothing is written)."""
     max_hole_edges = check_args(max_hole_edges)
-    pts, fv = meshin.device_mesh(points, faces, device, what='fill: faces', error=ValueError)
+    pts, fv = meshin.finite_mesh(points, faces, device, 'fill')
     dev, V, F = pts.device, pts.shape[0], fv.shape[0]
-    if V > 0 and not bool(torch.isfinite(pts).all()):
-        raise ValueError('fill: non-finite point coordinates')
     with torch.cuda.device(dev):
         ws, loops, c = _plan(fv, V, max_hole_edges)
         Vn, Fn = c[8], c[9]
@@ -122,11 +119,8 @@ def apply(filled, other_points):
     """Another point array of the INPUT's size [V, 3] (the paired noisy points) -> [V', 3] float32 on the device: the old
     rows as they are, every new vertex at the mean of ITS rim in that array, over the stored plan.  ``apply(filled, the
     input points)`` is bit-equal to ``filled.points``."""
-    other = meshin.as_tensor(other_points)
-    if other.dim() != 2 or other.shape[1] != 3 or other.shape[0] != filled.V:
-        raise ValueError('apply: points %s for a fill of %d vertices' % (tuple(other.shape), filled.V))
     dev = filled.points.device
-    pts = meshin.to_device(other, dev, torch.float32)
+    pts = meshin.paired_points(other_points, filled.V, dev, 'a fill of')
     Vn = filled.points.shape[0]
     out = torch.empty((Vn, 3), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):

@@ -4,11 +4,28 @@ through here (filters, meshprep, meshclean, mesheval, meshnoise, patches, data_u
 
 The range check reads the table as it arrives -- where it lives, in its own dtype -- because the conversion to int32
 wraps: the int64 id 2**32 + 1 becomes 1 and would pass a check made afterwards.
+
+What the mesh tools' wrappers share beyond that is here too: the library's row limit, the test for a whole number, the
+intake that also refuses non-finite points (``finite_mesh``), the paired array of an ``apply`` (``paired_points``).
 """
 import numpy as np
 import torch
 
 from . import _lib as L
+
+MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h (tests/test_folders_host.py compares the two)
+
+
+def whole(value):
+    """whether value is a whole number: a Python or numpy integer, no bool"""
+    return not isinstance(value, bool) and isinstance(value, (int, np.integer))
+
+
+def bbox_diagonal(points):
+    """the diagonal of the bounding box of points [V, 3] (an array or a tensor), in fp64 on the host (0 without points):
+    the value of ``subdivide --max_edge_diag`` and ``remesh --target_edge_diag``"""
+    p = np.asarray(points.detach().cpu().numpy() if torch.is_tensor(points) else points, dtype=np.float64).reshape(-1, 3)
+    return float(np.sqrt(((p.max(axis=0) - p.min(axis=0)) ** 2).sum())) if p.shape[0] else 0.0
 
 
 def as_tensor(a):
@@ -63,3 +80,21 @@ def device_mesh(points, faces, device=None, check=True, what='faces', error=L.Ge
     if check:
         check_faces(fv, pts.shape[0], what, error)
     return to_device(pts, dev, torch.float32), to_device(fv, dev, torch.int32)
+
+
+def finite_mesh(points, faces, device, what):
+    """``device_mesh`` for a mesh tool named `what`: a face index outside [0, V) and a non-finite coordinate are
+    ValueErrors that name the tool."""
+    pts, fv = device_mesh(points, faces, device, what='%s: faces' % what, error=ValueError)
+    if pts.shape[0] > 0 and not bool(torch.isfinite(pts).all()):
+        raise ValueError('%s: non-finite point coordinates' % what)
+    return pts, fv
+
+
+def paired_points(other, V, device, what):
+    """The paired point array of an ``apply`` -> fp32 [V, 3] on the device; ValueError unless it has the V rows of the
+    tool's input (`what`: 'a refinement of', ...)."""
+    other = as_tensor(other)
+    if other.dim() != 2 or other.shape[1] != 3 or other.shape[0] != V:
+        raise ValueError('apply: points %s for %s %d vertices' % (tuple(other.shape), what, V))
+    return to_device(other, device, torch.float32)

@@ -20,7 +20,8 @@ import torch
 from . import _lib as L
 from . import meshdecim, meshin, meshsubdiv
 
-MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h
+MAX_NODES = meshin.MAX_NODES
+bbox_diagonal = meshin.bbox_diagonal
 LOCK_KEYS = ('edges', 'boundary_vertices', 'sharp_edges', 'sharp_vertices')
 FLIP_KEYS = ('edges', 'candidates', 'valid', 'flips', 'sweeps_selected')
 RELAX_KEYS = ('moved', 'refused', 'reverted', 'turned')
@@ -35,10 +36,6 @@ class Remeshed(object):
     def __init__(self, points, faces, low, high, per_iteration, before, after):
         self.points, self.faces, self.low, self.high = points, faces, low, high
         self.per_iteration, self.before, self.after = per_iteration, before, after
-
-
-def _whole(value):
-    return not isinstance(value, bool) and isinstance(value, (int, np.integer))
 
 
 def _number(name, value, what):
@@ -79,9 +76,9 @@ def check_band(low, high, what='remesh'):
 def check_args(target_edge=None, target_edge_diag=None, iterations=5, feature_angle=40.0, relax_lambda=0.5, max_rounds=64):
     """ValueError for what ``remesh`` does not take; -> (target_edge or None, target_edge_diag or None, feature_angle,
     relax_lambda) as Python floats."""
-    if not _whole(iterations) or iterations < 0:
+    if not meshin.whole(iterations) or iterations < 0:
         raise ValueError('remesh: iterations = %r (a whole number, not negative)' % (iterations,))
-    if not _whole(max_rounds) or max_rounds < 1:
+    if not meshin.whole(max_rounds) or max_rounds < 1:
         raise ValueError('remesh: max_rounds = %r (a whole number, at least 1)' % (max_rounds,))
     if target_edge is not None and target_edge_diag is not None:
         raise ValueError('remesh: target_edge and target_edge_diag exclude each other')
@@ -98,20 +95,10 @@ def check_args(target_edge=None, target_edge_diag=None, iterations=5, feature_an
             feature_angle, relax_lambda)
 
 
-def bbox_diagonal(points):
-    """the diagonal of the bounding box of points [V, 3], in fp64 on the host (0 without points): the value of
-    ``subdivide --max_edge_diag``"""
-    p = np.asarray(torch.as_tensor(points).detach().cpu().numpy() if torch.is_tensor(points) else points,
-                   dtype=np.float64).reshape(-1, 3)
-    return float(np.sqrt(((p.max(axis=0) - p.min(axis=0)) ** 2).sum())) if p.shape[0] else 0.0
-
-
 def _mesh(points, faces, device, what):
-    pts, fv = meshin.device_mesh(points, faces, device, what='%s: faces' % what, error=ValueError)
+    pts, fv = meshin.finite_mesh(points, faces, device, what)
     if max(pts.shape[0], fv.shape[0]) > MAX_NODES:
         raise ValueError('%s: %d vertices and %d faces, beyond GEOBI_MAX_NODES = %d' % (what, pts.shape[0], fv.shape[0], MAX_NODES))
-    if pts.shape[0] > 0 and not bool(torch.isfinite(pts).all()):
-        raise ValueError('%s: non-finite point coordinates' % what)
     return pts, fv
 
 

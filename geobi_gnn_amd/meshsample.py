@@ -86,8 +86,8 @@ def sample_surface(points, faces, n, *, seed, stream_id=0, draw=0, first=0, weig
     n, first = int(n), int(first)
     if n < 0 or first < 0:
         raise ValueError('sample_surface: n = %d, first = %d (neither may be negative)' % (n, first))
-    if first + n > L_MAX_NODES:
-        raise ValueError('sample_surface: first + n = %d exceeds %d rows per draw' % (first + n, L_MAX_NODES))
+    if first + n > meshin.MAX_NODES:
+        raise ValueError('sample_surface: first + n = %d exceeds %d rows per draw' % (first + n, meshin.MAX_NODES))
     if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream_id) < 2 ** 32 or not 0 <= int(draw) < 2 ** 32:
         raise ValueError('sample_surface: seed is 64 bits, stream_id and draw are 32 bits, none negative')
     F, dev = fv.shape[0], p.device
@@ -106,9 +106,6 @@ def sample_surface(points, faces, n, *, seed, stream_id=0, draw=0, first=0, weig
     L.call('geobi_sample_surface', L.ptr(p), L.ptr(fv), L.ptr(cum), F, p.shape[0], n, first, int(seed), int(stream_id),
            int(draw), L.ptr(out.points), L.ptr(out.face), L.ptr(out.bary), L.stream())
     return out
-
-
-L_MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h
 
 
 # ------------------------------------------------------------------------------- every mesh of a union batch in one call
@@ -158,9 +155,9 @@ def sample_surface_parts(points, faces, fptr, n, *, seed, stream_ids, draw=0, fi
     n, first = int(n), int(first)
     if n < 0 or first < 0:
         raise ValueError('sample_surface_parts: n = %d, first = %d (neither may be negative)' % (n, first))
-    if first + n > L_MAX_NODES or P * n > L_MAX_NODES:
-        raise ValueError('sample_surface_parts: first + n = %d, P * n = %d: above %d rows per draw' % (first + n, P * n,
-                                                                                                      L_MAX_NODES))
+    if first + n > meshin.MAX_NODES or P * n > meshin.MAX_NODES:
+        raise ValueError('sample_surface_parts: first + n = %d, P * n = %d: above %d rows per draw'
+                         % (first + n, P * n, meshin.MAX_NODES))
     sid = [int(s) for s in (stream_ids.tolist() if torch.is_tensor(stream_ids) else stream_ids)]
     if len(sid) != P:
         raise ValueError('sample_surface_parts: %d stream ids for %d parts' % (len(sid), P))

@@ -22,7 +22,7 @@ from . import _lib as L
 from . import meshin
 
 SCHEMES = ('midpoint', 'loop')
-MAX_NODES = (1 << 24) - 1          # GEOBI_MAX_NODES of include/geobi_hip.h
+MAX_NODES = meshin.MAX_NODES
 COUNT_KEYS = ('edges', 'split', 'boundary_edges', 'complex_edges')
 
 
@@ -49,9 +49,9 @@ def check_args(levels=1, scheme='midpoint', max_edge=None, max_rounds=16):
     """ValueError for what ``subdivide`` does not take; -> max_edge as the float32 the device compares with (or None)."""
     if scheme not in SCHEMES:
         raise ValueError('subdivide: scheme = %r (one of %s)' % (scheme, ', '.join(SCHEMES)))
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
+    if not meshin.whole(levels) or levels < 1:
         raise ValueError('subdivide: levels = %r (a whole number, at least 1)' % (levels,))
-    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1:
+    if not meshin.whole(max_rounds) or max_rounds < 1:
         raise ValueError('subdivide: max_rounds = %r (a whole number, at least 1)' % (max_rounds,))
     if max_edge is None:
         return None
@@ -96,10 +96,8 @@ def subdivide(points, faces, levels=1, scheme='midpoint', max_edge=None, max_rou
     GeobiError: more than ``max_rounds`` rounds, or a pass whose output would exceed GEOBI_MAX_NODES rows (nothing of that
     pass is written)."""
     max_edge = check_args(levels, scheme, max_edge, max_rounds)
-    pts, fv = meshin.device_mesh(points, faces, device, what='subdivide: faces', error=ValueError)
+    pts, fv = meshin.finite_mesh(points, faces, device, 'subdivide')
     dev, V, F = pts.device, pts.shape[0], fv.shape[0]
-    if V > 0 and not bool(torch.isfinite(pts).all()):
-        raise ValueError('subdivide: non-finite point coordinates')
     loop = scheme == 'loop'
     counts = dict.fromkeys(COUNT_KEYS + ('passes',), 0)
     passes = []
@@ -133,12 +131,9 @@ def apply(refined, other_points):
     """Another point array of the INPUT's size [V, 3] (the paired noisy points) -> [V', 3] float32 on the device: the
     same splits and the same masks, pass by pass, over the stored plans.  ``apply(refined, the input points)`` is
     bit-equal to ``refined.points``."""
-    other = meshin.as_tensor(other_points)
-    V = refined.passes[0].V if refined.passes else refined.points.shape[0]
-    if other.dim() != 2 or other.shape[1] != 3 or other.shape[0] != V:
-        raise ValueError('apply: points %s for a refinement of %d vertices' % (tuple(other.shape), V))
     dev = refined.points.device
-    pts = meshin.to_device(other, dev, torch.float32)
+    pts = meshin.paired_points(other_points, refined.passes[0].V if refined.passes else refined.points.shape[0], dev,
+                               'a refinement of')
     with torch.cuda.device(dev):
         for p in refined.passes:
             out = torch.empty((p.Vn, 3), dtype=torch.float32, device=dev)

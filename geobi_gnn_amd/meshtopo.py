@@ -121,11 +121,9 @@ def mesh_report(points, faces, weld_tol=0.0, max_rounds=256, device=None):
     _check_rounds('mesh_report', max_rounds)
     dev = meshin.default_device(device)
     meshclean.check_weld_tol('mesh_report', weld_tol)
-    pts, fv = meshin.device_mesh(meshin.as_tensor(points).reshape(-1, 3), meshin.as_tensor(faces).reshape(-1, 3), dev,
-                                 what='mesh_report: faces', error=ValueError)
+    pts, fv = meshin.finite_mesh(meshin.as_tensor(points).reshape(-1, 3), meshin.as_tensor(faces).reshape(-1, 3), dev,
+                                 'mesh_report')
     V, F = pts.shape[0], fv.shape[0]
-    if V > 0 and not bool(torch.isfinite(pts).all()):
-        raise ValueError('mesh_report: non-finite point coordinates')
     with torch.cuda.device(dev):
         canon, wcounts = meshclean.weld(pts, weld_tol)
         _, bad = L.read_i32(wcounts)

@@ -12,6 +12,7 @@ import torch
 from torch.optim import lr_scheduler
 
 from . import network
+from .meshin import MAX_NODES
 from .parallel import reduce_sums
 
 LR_SCHEDULES = ('step', 'multi_step', 'exp', 'auto', 'lmd')
@@ -28,7 +29,7 @@ def non_negative_float(text):
 def loss_samples_arg(text):
     """argparse type of --loss_samples: the sample counts the `sample` command takes, without its 0 (no loss from nothing)."""
     value = int(text)
-    if not 1 <= value <= (1 << 24) - 1:
+    if not 1 <= value <= MAX_NODES:
         raise argparse.ArgumentTypeError('a number of samples is between 1 and 16 777 215, not %r' % text)
     return value
 
