@@ -18,7 +18,8 @@
   python -m geobi_gnn_amd subdivide --data_dir DIR (--max_edge L | --max_edge_diag R) [--max_rounds 16]
   python -m geobi_gnn_amd decimate --data_dir DIR [--out_dir DIR/decimated] (--ratio R | --faces N) [--max_cost C] [--max_rounds 256]
   python -m geobi_gnn_amd remesh --data_dir DIR [--out_dir DIR/remeshed] [--target_edge L | --target_edge_diag R] [--iterations 5]
-                                 [--feature_angle 40] [--relax_lambda 0.5] [--max_rounds 64]
+                                 [--feature_angle 40] [--relax_lambda 0.5] [--max_rounds 64] [--project]
+  python -m geobi_gnn_amd project --data_dir DIR --target_dir DIR2 [--out_dir DIR/projected] [--max_dist D | --max_dist_diag R]
   python -m geobi_gnn_amd fill --data_dir DIR [--out_dir DIR/filled] [--max_hole_edges N] [--gpu -1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
@@ -54,7 +55,13 @@ until `--faces N` or `--ratio R` times the faces are left (`--max_cost C`: no co
 full resolution, with the same folders and the same pairing of noisy files.  `fill` (meshfill.py) closes the holes of every
 mesh: each closed boundary loop (`--max_hole_edges N`: of at most N edges, which leaves an open border open) gets one new
 vertex at the mean of its rim and a fan of faces, with the same folders; a noisy file gets its original's fill with every
-new vertex at the mean of its own rim.  All device work runs in this one process.
+new vertex at the mean of its own rim.  `remesh --project` (meshproject.py) ends every iteration by moving the relaxed
+vertices back to their closest points on the input surface, so the result does not drift off it, and every output vertex
+keeps a (face, barycentric) address on the input: with DIR/noisy present its files are carried along through that map.
+`project` moves the vertices of every DIR/NAME_*.obj -- or DIR/NAME.obj -- to their closest points on the surface of
+DIR2/NAME.obj (the pairing of `align`) and writes it with its own faces; `--max_dist D` / `--max_dist_diag R` (R times the
+diagonal of the target's bounding box) leaves the vertices that are farther away where they are.  All device work runs in
+this one process.
 """
 import argparse
 import os
@@ -480,37 +487,80 @@ def _remesh_line(r, V, F, drift, out_file):
 def remesh(opt):
     """Remesh every mesh of a folder on the device (meshremesh), with the folders of `decimate`: DIR/original/NAME.obj ->
     OUT/original/NAME.obj if DIR/original exists, else DIR/*.obj -> OUT/NAME.obj.  Relaxation is no replayable map, so the
-    files of DIR/noisy are NOT carried along."""
+    files of DIR/noisy are NOT carried along -- unless --project is given: then every iteration ends on the input surface,
+    every output vertex has an address on it, and with DIR/noisy present every noisy/NAME_n*.obj of equal size is written to
+    OUT/noisy through that map (the paired walk of `decimate`)."""
     import torch
     from . import mesheval, meshin, meshio, meshremesh
     dev = _device(opt.gpu)
     out_dir = opt.out_dir or os.path.join(opt.data_dir, 'remeshed')
-    files, paired = folders.originals(opt.data_dir)
-    out_original = os.path.join(out_dir, 'original') if paired else out_dir
-    os.makedirs(out_original, exist_ok=True)
     mode = ('target edge %g' % opt.target_edge if opt.target_edge is not None else
             'target edge %g of the diagonal' % opt.target_edge_diag if opt.target_edge_diag is not None else
             'target edge = the mean edge')
-    print('\nRemesh, %s, %d iterations, %d files ...\n' % (mode, opt.iterations, len(files)), flush=True)
-    if paired and os.path.isdir(os.path.join(opt.data_dir, 'noisy')):
-        print('noisy/ is not carried along: the relaxed vertices have no counterpart in a paired file.  Make new pairs '
-              'with `noise` on the output folder.\n', flush=True)
 
-    def one(path, skip):
-        points, faces = meshio.read_obj(path)
+    def run(points, faces):
+        """-> (Remeshed, (mean, max) of the drift)"""
         r = meshremesh.remesh(points, faces, target_edge=opt.target_edge, target_edge_diag=opt.target_edge_diag,
                               iterations=opt.iterations, feature_angle=opt.feature_angle, relax_lambda=opt.relax_lambda,
-                              max_rounds=opt.max_rounds, device=dev)
-        out_file = os.path.join(out_original, os.path.basename(path))
-        meshio.write_obj(out_file, *_host_mesh(r))
+                              max_rounds=opt.max_rounds, device=dev, project=opt.project)
         drift = (0.0, 0.0)
         if r.points.shape[0] and faces.shape[0]:         # the new vertices against the INPUT surface
             with torch.cuda.device(dev):
                 d = mesheval.point_to_mesh(r.points, *meshin.device_mesh(points, faces, dev))[0]
             drift = (float(d.double().mean()), float(d.max()))
+        return r, drift
+
+    if opt.project and os.path.isdir(os.path.join(opt.data_dir, 'original')) and os.path.isdir(os.path.join(opt.data_dir, 'noisy')):
+        return folders.paired_walk(opt.data_dir, out_dir, 'Remesh, %s, %d iterations, projected' % (mode, opt.iterations),
+                                   lambda points, faces, path: run(points, faces), lambda rd: _host_mesh(rd[0]),
+                                   lambda rd, V, F, out_file: _remesh_line(rd[0], V, F, rd[1], out_file),
+                                   lambda rd, p: meshremesh.apply(rd[0], p).cpu().numpy())
+    files, paired = folders.originals(opt.data_dir)
+    out_original = os.path.join(out_dir, 'original') if paired else out_dir
+    os.makedirs(out_original, exist_ok=True)
+    print('\nRemesh, %s, %d iterations%s, %d files ...\n' % (mode, opt.iterations, ', projected' if opt.project else '',
+                                                            len(files)), flush=True)
+    if paired and not opt.project and os.path.isdir(os.path.join(opt.data_dir, 'noisy')):
+        print('noisy/ is not carried along: the relaxed vertices have no counterpart in a paired file.  Make new pairs '
+              'with `noise` on the output folder.\n', flush=True)
+
+    def one(path, skip):
+        points, faces = meshio.read_obj(path)
+        r, drift = run(points, faces)
+        out_file = os.path.join(out_original, os.path.basename(path))
+        meshio.write_obj(out_file, *_host_mesh(r))
         print(_remesh_line(r, points.shape[0], faces.shape[0], drift, out_file), flush=True)
 
     return folders.walk(files, one, of_total=False)
+
+
+def project(opt):
+    """The vertices of every source mesh of --data_dir moved to their closest points on the surface of its target of
+    --target_dir (meshproject.project; the pairing of `align`), written to --out_dir with its own faces."""
+    from . import meshin, meshio, meshproject
+    dev = _device(opt.gpu)
+    jobs = align_list(opt.data_dir, opt.target_dir)
+    out_dir = opt.out_dir or os.path.join(opt.data_dir, 'projected')
+    os.makedirs(out_dir, exist_ok=True)
+    mode = ('max_dist %g' % opt.max_dist if opt.max_dist is not None else
+            'max_dist %g of the diagonal' % opt.max_dist_diag if opt.max_dist_diag is not None else 'no max_dist')
+    print('\nProject, %s, %d files ...\n' % (mode, len(jobs)), flush=True)
+
+    def one(job, skip):
+        source, target = job
+        points, faces = meshio.read_obj(source)
+        t_points, t_faces = meshio.read_obj(target)
+        if points.shape[0] == 0:
+            raise ValueError('%s has no vertices' % source)
+        max_dist = opt.max_dist_diag * meshin.bbox_diagonal(t_points) if opt.max_dist_diag is not None else opt.max_dist
+        out, kept, c = meshproject.project(points, t_points, t_faces, max_dist=max_dist, device=dev)
+        out_file = os.path.join(out_dir, os.path.basename(source))
+        meshio.write_obj(out_file, out.cpu().numpy(), faces)
+        moved = (out - c.points.new_tensor(points)).double().norm(dim=1)
+        print("V: %7d,  kept: %7d,  moved mean: %.6e,  max: %.6e,  '%s'"
+              % (points.shape[0], kept, float(moved.mean()), float(moved.max()), os.path.basename(out_file)), flush=True)
+
+    return folders.walk(jobs, one)
 
 
 def _weld_tol_arg(text):
@@ -739,8 +789,23 @@ def build_parser():
                    help='edges whose faces meet at more than DEG degrees (0 .. 90) keep their vertices; 180: none')
     r.add_argument('--relax_lambda', type=_unit_arg, default=0.5, help='the step of the relaxation, in [0, 1]')
     r.add_argument('--max_rounds', type=_at_least_one_arg, default=64, help='rounds at most in each inner loop')
+    r.add_argument('--project', action='store_true',
+                   help='end every iteration by moving the relaxed vertices to their closest points on the input surface; '
+                        'with <data_dir>/noisy present its files are carried along to <out_dir>/noisy')
     r.add_argument('--gpu', type=int, default=-1)
     r.set_defaults(fn=remesh)
+    j = sub.add_parser('project', help='move the vertices of every mesh of a folder to their closest points on the surface '
+                                       'of its target and write it with its own faces')
+    j.add_argument('--data_dir', type=str, required=True, help='the meshes to move: NAME_*.obj, or NAME.obj')
+    j.add_argument('--target_dir', type=str, required=True, help='holds the targets NAME.obj')
+    j.add_argument('--out_dir', type=str, default='', help='default: <data_dir>/projected')
+    far = j.add_mutually_exclusive_group()
+    far.add_argument('--max_dist', type=_not_negative_arg, default=None, metavar='D',
+                     help='a vertex farther than D from the surface stays where it is')
+    far.add_argument('--max_dist_diag', type=_not_negative_arg, default=None, metavar='R',
+                     help="--max_dist as R times the diagonal of the target's bounding box")
+    j.add_argument('--gpu', type=int, default=-1)
+    j.set_defaults(fn=project)
     h = sub.add_parser('fill', help='close the holes of every mesh on the device: one new vertex and a fan of faces per '
                                     'closed boundary loop')
     h.add_argument('--data_dir', type=str, required=True, help='holds original/ (and noisy/), or the OBJ files themselves')

@@ -1,7 +1,8 @@
 // Isotropic remeshing on the device: the lock flags, the edge flips towards the target valence and
 // the tangential relaxation of the split / collapse / flip / relax loop.  The split step is subdiv.hip (max_edge), the
 // short-edge collapse is geobi_decim_plan_short of decim.hip.  The rules are stated in include/geobi_hip.h (geobi_remesh_*,
-// geobi_flip_*, geobi_relax); tests/remesh_model.py restates them sequentially and every output is compared bit for bit.
+// geobi_flip_*, geobi_relax, geobi_move_to); tests/remesh_model.py restates them sequentially (tests/project_model.py:
+// geobi_move_to, the step back onto the input surface of DESIGN.md 4r) and every output is compared bit for bit.
 //
 // The topology is integer-exact and independent of launch geometry; every float step is fp64 in one stated order
 // (contraction off throughout, __ddiv_rn / __dsqrt_rn, no float atomics):
@@ -14,7 +15,8 @@
 //            mesh_select.h over the four quad vertices; a selected lane notes its position at its two faces; emit is one
 //            lane per face
 //   relax    one lane per vertex proposes and tests its move against the old positions, one lane per face marks the
-//            vertices of a face that turned, one lane per vertex takes them back, one lane per face counts what is left
+//            vertices of a face that turned, one lane per vertex takes them back, one lane per face counts what is left;
+//            move_to is the same text with the proposal read from an array
 // Every index is bounded: corners are below V (face_included), slots below 3F, vertices and faces taken out of a key were
 // put into it from such a corner or face, positions noted at a face are checked against 3F before they are used.
 #include "common.h"
@@ -211,48 +213,72 @@ __device__ __forceinline__ void copy_point(const float* __restrict__ from, float
   for (int k = 0; k < 3; ++k) to[3 * (size_t)v + k] = from[3 * (size_t)v + k];
 }
 
+// the proposals of a free vertex v, each from the old positions: -> whether there is one, and `to`
+// geobi_relax: towards the mean of the neighbours inside the tangent plane (none for valence < 3 or a normal sum of zero)
+struct TangentialProposal {
+  double lambda;
+  __device__ bool operator()(const float* __restrict__ points, const int* __restrict__ fv, const uint64_t* __restrict__ corners,
+                             int n, const uint64_t* __restrict__ pairs, int n_pairs, int v, float* to) const {
+#pragma clang fp contract(off)
+    double gx = 0.0, gy = 0.0, gz = 0.0;
+    int valence = 0;
+    for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j) {
+      const P3 w = point_of(points, item_of(pairs[j]));
+      gx = gx + w.x; gy = gy + w.y; gz = gz + w.z;
+      ++valence;
+    }
+    P3 nrm = {0.0, 0.0, 0.0};
+    for (int j = lower_bound(corners, n, (uint64_t)v << 24); j < n && owner_of(corners[j]) == v; ++j) {
+      P3 nf;
+      face_normal(points, fv, item_of(corners[j]), nf);
+      nrm.x = nrm.x + nf.x; nrm.y = nrm.y + nf.y; nrm.z = nrm.z + nf.z;
+    }
+    const double s = dot_of(nrm, nrm);
+    if (valence < 3 || s == 0.0) return false;
+    const P3 p = point_of(points, v);
+    const double count = (double)valence;
+    const P3 d = {__ddiv_rn(gx, count) - p.x, __ddiv_rn(gy, count) - p.y, __ddiv_rn(gz, count) - p.z};
+    const double q = __ddiv_rn(dot_of(nrm, d), s);
+    to[0] = (float)(p.x + lambda * (d.x - nrm.x * q));
+    to[1] = (float)(p.y + lambda * (d.y - nrm.y * q));
+    to[2] = (float)(p.z + lambda * (d.z - nrm.z * q));
+    return true;
+  }
+};
+
+// geobi_move_to: the given position (none for valence < 3)
+struct TargetProposal {
+  const float* target;
+  __device__ bool operator()(const float* __restrict__, const int* __restrict__, const uint64_t* __restrict__, int,
+                             const uint64_t* __restrict__ pairs, int n_pairs, int v, float* to) const {
+    if (valence_of(pairs, n_pairs, v) < 3) return false;
+    for (int k = 0; k < 3; ++k) to[k] = target[3 * (size_t)v + k];
+    return true;
+  }
+};
+
 // one lane per vertex: the proposal from the old positions, the refusal test against the old positions
+template <typename Proposal>
 __global__ void relax_move_kernel(const float* __restrict__ points, const int* __restrict__ fv, int V,
                                   const uint64_t* __restrict__ corners, int n, const uint64_t* __restrict__ pairs,
-                                  int n_pairs, const int* __restrict__ lock, double lambda, float* __restrict__ out,
+                                  int n_pairs, const int* __restrict__ lock, Proposal proposal, float* __restrict__ out,
                                   int* __restrict__ moved, int* __restrict__ counts) {
 #pragma clang fp contract(off)
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   bool moves = false, refused = false;
   if (v < V) {
     float now[3] = {points[3 * (size_t)v], points[3 * (size_t)v + 1], points[3 * (size_t)v + 2]};
-    if (lock[v] == 0) {
-      double gx = 0.0, gy = 0.0, gz = 0.0;
-      int valence = 0;
-      for (int j = lower_bound(pairs, n_pairs, (uint64_t)v << 24); j < n_pairs && owner_of(pairs[j]) == v; ++j) {
-        const P3 w = point_of(points, item_of(pairs[j]));
-        gx = gx + w.x; gy = gy + w.y; gz = gz + w.z;
-        ++valence;
-      }
-      P3 nrm = {0.0, 0.0, 0.0};
-      for (int j = lower_bound(corners, n, (uint64_t)v << 24); j < n && owner_of(corners[j]) == v; ++j) {
-        P3 nf;
-        face_normal(points, fv, item_of(corners[j]), nf);
-        nrm.x = nrm.x + nf.x; nrm.y = nrm.y + nf.y; nrm.z = nrm.z + nf.z;
-      }
-      const double s = dot_of(nrm, nrm);
-      if (valence >= 3 && s != 0.0) {
-        const P3 p = point_of(points, v);
-        const double count = (double)valence;
-        const P3 d = {__ddiv_rn(gx, count) - p.x, __ddiv_rn(gy, count) - p.y, __ddiv_rn(gz, count) - p.z};
-        const double q = __ddiv_rn(dot_of(nrm, d), s);
-        const float to[3] = {(float)(p.x + lambda * (d.x - nrm.x * q)), (float)(p.y + lambda * (d.y - nrm.y * q)),
-                             (float)(p.z + lambda * (d.z - nrm.z * q))};
-        if (!(isfinite(to[0]) && isfinite(to[1]) && isfinite(to[2]))) {
+    float to[3];
+    if (lock[v] == 0 && proposal(points, fv, corners, n, pairs, n_pairs, v, to)) {
+      if (!(isfinite(to[0]) && isfinite(to[1]) && isfinite(to[2]))) {
+        refused = true;
+      } else if (to[0] != now[0] || to[1] != now[1] || to[2] != now[2]) {
+        const P3 at = {(double)to[0], (double)to[1], (double)to[2]};
+        if (no_flip(points, fv, corners, n, v, -1, at)) {
+          moves = true;
+          for (int k = 0; k < 3; ++k) now[k] = to[k];
+        } else {
           refused = true;
-        } else if (to[0] != now[0] || to[1] != now[1] || to[2] != now[2]) {
-          const P3 at = {(double)to[0], (double)to[1], (double)to[2]};
-          if (no_flip(points, fv, corners, n, v, -1, at)) {
-            moves = true;
-            for (int k = 0; k < 3; ++k) now[k] = to[k];
-          } else {
-            refused = true;
-          }
         }
       }
     }
@@ -348,6 +374,38 @@ int build_tables(const RemeshBuffers& b, const int32_t* faces, int64_t F, int64_
   GEOBI_TRY(build_pair_table(b.t, F, nullptr, b.counts + edge_count_at, s));
   if (with_corners) GEOBI_TRY(build_corner_table(b.t, faces, F, V, nullptr, nullptr, s));
   return 0;
+}
+
+// the protocol geobi_relax and geobi_move_to share: one lane per vertex proposes and tests, turned / revert / turned
+template <typename Proposal>
+int guarded_move(const char* what, const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V,
+                 const Proposal& proposal, float* points_out, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes,
+                 hipStream_t s) {
+  if (F == 0 || V == 0) {
+    GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * kRelaxCounts, s));
+    if (V > 0) GEOBI_HIP(hipMemcpyAsync(points_out, points, sizeof(float) * 3 * (size_t)V, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  RemeshBuffers b;
+  GEOBI_TRY(remesh_buffers(what, F, V, ws, ws_bytes, b));
+  const int n = (int)(3 * F), n_pairs = 2 * n;
+  StageTimer timer(stage_ms, s);
+  GEOBI_TRY(timer.mark());
+  GEOBI_TRY(build_tables(b, faces, F, V, true, kSpareCount, s));
+  GEOBI_HIP(hipMemsetAsync(b.revert, 0, sizeof(int) * (size_t)V, s));
+  GEOBI_TRY(timer.mark());
+  relax_move_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.t.c_out, n, b.t.p_out, n_pairs, lock, proposal, points_out,
+                                              b.moved, b.counts);
+  GEOBI_LAUNCH_OK();
+  relax_turned_kernel<<<cdiv(F, kT), kT, 0, s>>>(points, points_out, faces, (int)F, (int)V, b.revert, nullptr);
+  GEOBI_LAUNCH_OK();
+  relax_revert_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, (int)V, b.moved, b.revert, points_out, b.counts);
+  GEOBI_LAUNCH_OK();
+  relax_turned_kernel<<<cdiv(F, kT), kT, 0, s>>>(points, points_out, faces, (int)F, (int)V, nullptr, b.counts + kTurned);
+  GEOBI_LAUNCH_OK();
+  GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kRelaxCounts, hipMemcpyDeviceToDevice, s));
+  GEOBI_TRY(timer.mark());
+  return timer.finish();
 }
 
 }  // namespace
@@ -446,32 +504,17 @@ int geobi_relax(const int32_t* faces, const float* points, const int32_t* lock, 
   GEOBI_MESH_SIZES(F, V);
   GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(lock); GEOBI_NOTNULL(points_out); GEOBI_NOTNULL(counts);
   GEOBI_REQUIRE(lambda >= 0.0 && lambda <= 1.0, "relax: lambda = %g (in [0, 1])", lambda);
-  hipStream_t s = as_stream(stream);
-  if (F == 0 || V == 0) {
-    GEOBI_HIP(hipMemsetAsync(counts, 0, sizeof(int) * kRelaxCounts, s));
-    if (V > 0) GEOBI_HIP(hipMemcpyAsync(points_out, points, sizeof(float) * 3 * (size_t)V, hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  RemeshBuffers b;
-  GEOBI_TRY(remesh_buffers("relax", F, V, ws, ws_bytes, b));
-  const int n = (int)(3 * F), n_pairs = 2 * n;
-  StageTimer timer(stage_ms, s);
-  GEOBI_TRY(timer.mark());
-  GEOBI_TRY(build_tables(b, faces, F, V, true, kSpareCount, s));
-  GEOBI_HIP(hipMemsetAsync(b.revert, 0, sizeof(int) * (size_t)V, s));
-  GEOBI_TRY(timer.mark());
-  relax_move_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, faces, (int)V, b.t.c_out, n, b.t.p_out, n_pairs, lock, lambda, points_out,
-                                              b.moved, b.counts);
-  GEOBI_LAUNCH_OK();
-  relax_turned_kernel<<<cdiv(F, kT), kT, 0, s>>>(points, points_out, faces, (int)F, (int)V, b.revert, nullptr);
-  GEOBI_LAUNCH_OK();
-  relax_revert_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, (int)V, b.moved, b.revert, points_out, b.counts);
-  GEOBI_LAUNCH_OK();
-  relax_turned_kernel<<<cdiv(F, kT), kT, 0, s>>>(points, points_out, faces, (int)F, (int)V, nullptr, b.counts + kTurned);
-  GEOBI_LAUNCH_OK();
-  GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kRelaxCounts, hipMemcpyDeviceToDevice, s));
-  GEOBI_TRY(timer.mark());
-  return timer.finish();
+  return guarded_move("relax", faces, points, lock, F, V, TangentialProposal{lambda}, points_out, counts, stage_ms, ws, ws_bytes,
+                      as_stream(stream));
+}
+
+int geobi_move_to(const int32_t* faces, const float* points, const float* target, const int32_t* lock, int64_t F, int64_t V,
+                  float* points_out, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_MESH_SIZES(F, V);
+  GEOBI_NOTNULL(faces); GEOBI_NOTNULL(points); GEOBI_NOTNULL(target); GEOBI_NOTNULL(lock); GEOBI_NOTNULL(points_out);
+  GEOBI_NOTNULL(counts);
+  return guarded_move("move_to", faces, points, lock, F, V, TargetProposal{target}, points_out, counts, stage_ms, ws, ws_bytes,
+                      as_stream(stream));
 }
 
 int geobi_remesh_stats(const int32_t* faces, const float* points, int64_t F, int64_t V, void* edge_len, int32_t* valence,

@@ -11,7 +11,9 @@ Order.  Files in sorted order; in the paired walk every original is followed by 
 printed line per written file, flushed.
 
 Output folders.  The paired walk writes OUT/original and OUT/noisy when DIR/original exists -- OUT/noisy is made even when
-DIR/noisy is absent -- and OUT alone otherwise.  `remesh` carries no noisy files along and makes no OUT/noisy.
+DIR/noisy is absent -- and OUT alone otherwise.  `remesh` carries no noisy files along and makes no OUT/noisy; `remesh
+--project` with DIR/original and DIR/noisy present is a paired walk like the others.  `project` pairs as `align` does and
+writes OUT alone.
 
 Skips.  ``walk`` catches ValueError, OSError and GeobiError around the work of one file, prints ``skipped: ...`` on stderr
 and counts one file, however much of it was done (`noise`: a failure part-way through the levels is one file).  In the
@@ -20,8 +22,8 @@ the next noisy file; this inner handler catches ValueError and OSError only, so 
 stem through the outer handler and counts once (what the inner handler counted before stays counted).
 
 Trailer.  ``\\n--- end ---`` on stdout, then on stderr, if anything was skipped, ``N files skipped`` (of_total=False:
-`clean`, `subdivide`, `decimate`, `fill`, `remesh`) or ``N of M files skipped`` (`info`, `sample`, `noise`, `align`).  The
-return value is 1 if anything was skipped or there was no file at all, else 0.
+`clean`, `subdivide`, `decimate`, `fill`, `remesh`) or ``N of M files skipped`` (`info`, `sample`, `noise`, `align`,
+`project`).  The return value is 1 if anything was skipped or there was no file at all, else 0.
 """
 import glob
 import os

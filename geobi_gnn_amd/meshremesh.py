@@ -5,12 +5,18 @@ collapses (the rounds of ``meshdecim`` ranked by length), flips edges towards th
 flips, and relaxes every free vertex once towards the mean of its neighbours inside its tangent plane.
 
 Vertices on a boundary, a complex edge or a feature edge (dihedral angle above ``feature_angle``) are locked: they keep
-their points, so boundaries and feature lines only get denser.  The relaxed vertices are NOT projected back onto the input
-surface, and relaxation is no replayable map: a paired point array cannot be carried along (use ``meshnoise`` on the
-result).
+their points, so boundaries and feature lines only get denser.  By default the relaxed vertices are NOT projected back onto
+the input surface, and relaxation is no replayable map: a paired point array cannot be carried along (use ``meshnoise`` on
+the result).
 
-The rules are stated in include/geobi_hip.h (geobi_remesh_lock, geobi_decim_plan_short, geobi_flip_*, geobi_relax); the
-topology is integer-exact and the result reproducible bit for bit (tests/remesh_model.py).  No CPU fallback.
+``project=True`` adds the fifth step of the loop: after every relaxation the free vertices move to
+their closest points on the INPUT surface (``meshproject``), under the guard of the relaxation (``move_to``).  Every output
+vertex then carries a (face, barycentric) address on the input, ``Remeshed.source_face`` / ``source_bary``, and ``apply``
+evaluates that map on a paired array of the input's vertices: ``noisy/`` can be carried along.
+
+The rules are stated in include/geobi_hip.h (geobi_remesh_lock, geobi_decim_plan_short, geobi_flip_*, geobi_relax,
+geobi_move_to); the topology is integer-exact and the result reproducible bit for bit (tests/remesh_model.py,
+tests/project_model.py).  No CPU fallback.
 """
 import math
 
@@ -27,15 +33,21 @@ FLIP_KEYS = ('edges', 'candidates', 'valid', 'flips', 'sweeps_selected')
 RELAX_KEYS = ('moved', 'refused', 'reverted', 'turned')
 ITERATION_KEYS = ('splits', 'split_passes', 'collapses', 'collapse_rounds', 'flips', 'flip_rounds', 'moved', 'refused',
                   'reverted', 'turned')
+PROJECT_KEYS = ('projected', 'project_refused', 'project_reverted', 'project_turned')    # with project=True, beside them
 
 
 class Remeshed(object):
     """points [V', 3] float32 and faces [F', 3] int32 on the device; low, high: the float32 band; per_iteration: one dict of
-    ITERATION_KEYS per iteration; before, after: the statistics of input and output (``mesh_stats``)."""
+    ITERATION_KEYS per iteration (with project=True also PROJECT_KEYS); before, after: the statistics of input and output
+    (``mesh_stats``).  With project=True, source_face [V'] int32 and source_bary [V', 3] float32 on the device: the closest
+    point of every output vertex on the input surface, as a face of input_faces [F, 3] and the weights of its corners
+    (``apply``); else None."""
 
-    def __init__(self, points, faces, low, high, per_iteration, before, after):
+    def __init__(self, points, faces, low, high, per_iteration, before, after, source_face=None, source_bary=None,
+                 input_faces=None, input_V=None):
         self.points, self.faces, self.low, self.high = points, faces, low, high
         self.per_iteration, self.before, self.after = per_iteration, before, after
+        self.source_face, self.source_bary, self.input_faces, self.input_V = source_face, source_bary, input_faces, input_V
 
 
 def _number(name, value, what):
@@ -143,6 +155,16 @@ def _flip_emit(fv, V, ws):
     return out
 
 
+def _move_to(fv, pts, target, lock, stage_ms=None):
+    F, V = fv.shape[0], pts.shape[0]
+    ws = _workspace(fv, pts)
+    out = torch.empty_like(pts)
+    counts = torch.zeros(4, dtype=torch.int32, device=fv.device)
+    L.call('geobi_move_to', L.ptr(fv), L.ptr(pts), L.ptr(target), L.ptr(lock), F, V, L.ptr(out), L.ptr(counts), stage_ms,
+           L.ptr(ws), ws.numel(), L.stream())
+    return out, dict(zip(RELAX_KEYS, L.read_i32(counts, 4)))
+
+
 def _relax(fv, pts, lock, relax_lambda, stage_ms=None):
     F, V = fv.shape[0], pts.shape[0]
     ws = _workspace(fv, pts)
@@ -214,6 +236,24 @@ def relax(points, faces, lock=None, relax_lambda=0.5, feature_angle=40.0, device
         return _relax(fv, pts, lock, relax_lambda)
 
 
+def move_to(points, faces, target, lock=None, feature_angle=40.0, device=None):
+    """ONE guarded move of every free vertex to its row of ``target`` [V, 3] -> (points', counts of ``relax``): the
+    protocol of the relaxation -- locked vertices and those of valence < 3 stay, a move that would turn a face at the vertex
+    is refused, the moved vertices of a face that turned all the same go back -- with the given positions as proposals.
+    lock: the flags of ``lock_flags`` (computed here when None).  A target row that is not finite is refused."""
+    feature_angle = check_args(feature_angle=feature_angle)[2]
+    pts, fv = _mesh(points, faces, device, 'move_to')
+    target = meshin.as_tensor(target)
+    if target.dim() != 2 or target.shape[1] != 3 or target.shape[0] != pts.shape[0]:
+        raise ValueError('move_to: target %s for %d vertices' % (tuple(target.shape), pts.shape[0]))
+    target = meshin.to_device(target, pts.device, torch.float32)
+    with torch.cuda.device(pts.device):
+        if fv.shape[0] == 0:
+            return pts, dict.fromkeys(RELAX_KEYS, 0)
+        lock = _as_lock(lock, pts.shape[0], pts.device) if lock is not None else _lock(fv, pts, *cos2(feature_angle))[0]
+        return _move_to(fv, pts, target, lock)
+
+
 def mesh_stats(points, faces, low, high, device=None):
     """The regularity of a mesh: edges, edge_min / edge_mean / edge_max (fp64), inside and share (the edges with low <=
     length <= high), valence_hist (valence 3 .. 11 and 12+), valence_dev (the mean |valence - target| over the vertices
@@ -243,17 +283,27 @@ def mesh_stats(points, faces, low, high, device=None):
 
 # ---------------------------------------------------------------------------------------------- the whole call
 def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5, feature_angle=40.0, relax_lambda=0.5,
-           max_rounds=64, device=None):
+           max_rounds=64, device=None, project=False):
     """(points [V, 3], faces [F, 3]) -> Remeshed.  The target edge length L is ``target_edge``, or ``target_edge_diag`` times
     the diagonal of the bounding box, or by default the mean edge length of the input (``meshnoise.MeshGeometry``).  Every
     iteration runs: splits of the edges above high = 4/3 L to exhaustion, rounds of short-edge collapses (below low = 0.8
-    L) until a round collapses nothing, rounds of flips until a round flips nothing, one relaxation.  ValueError: shapes
+    L) until a round collapses nothing, rounds of flips until a round flips nothing, one relaxation.  project=True: every
+    iteration ends with the closest points of the relaxed vertices on the INPUT mesh (``meshproject``) and one ``move_to``
+    from the relaxed positions to them under the lock flags the relaxation used (counts: PROJECT_KEYS); after the last
+    iteration the closest points of ALL output vertices on the input, locked ones included, fill ``source_face`` /
+    ``source_bary`` -- a map only, no point moves (``iterations=0``: the one-hot map of the input onto itself).  Without
+    project the launches and the dicts are what they were.  ValueError: project for an input without faces, shapes
     other than [V, 3] and [F, 3], a face index outside [0, V), non-finite points, arguments outside their range;
     GeobiError: ``max_rounds`` rounds did not end one of the three inner loops."""
     target_edge, target_edge_diag, feature_angle, relax_lambda = check_args(target_edge, target_edge_diag, iterations,
                                                                             feature_angle, relax_lambda, max_rounds)
     pts, fv = _mesh(points, faces, device, 'remesh')
     dev = pts.device
+    if project and fv.shape[0] == 0:
+        raise ValueError('remesh: project = True needs a surface to project onto, the input has no faces')
+    if project:
+        from . import meshproject
+        in_pts, in_fv = pts, fv
     use_sharp, c2 = cos2(feature_angle)
     with torch.cuda.device(dev):
         if target_edge is None and target_edge_diag is not None:
@@ -300,6 +350,27 @@ def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5,
                 lock = lock if lock is not None else _lock(fv, pts, use_sharp, c2)[0]
                 pts, r = _relax(fv, pts, lock, relax_lambda)
                 c.update(r)
+            if project:
+                c.update(dict.fromkeys(PROJECT_KEYS, 0))
+                if fv.shape[0] > 0:
+                    pts, r = _move_to(fv, pts, meshproject._closest(pts, in_pts, in_fv).points, lock)
+                    c.update(zip(PROJECT_KEYS, (r[k] for k in RELAX_KEYS)))
             per_iteration.append(c)
         after = mesh_stats(pts, fv, low, high, dev)
+        source = meshproject._closest(pts, in_pts, in_fv) if project else None
+    if project:
+        return Remeshed(pts, fv, np.float32(low), np.float32(high), per_iteration, before, after, source.face, source.bary,
+                        in_fv, in_pts.shape[0])
     return Remeshed(pts, fv, np.float32(low), np.float32(high), per_iteration, before, after)
+
+
+def apply(remeshed, other_points):
+    """The output vertices of a ``remesh(project=True)`` on a paired array of the INPUT's vertices (other_points [V, 3],
+    the noisy copy of the input): ``ops.bary_points(other_points, input faces, source_face, source_bary)`` -> float32
+    [V', 3] on the device.  ValueError for a result without the map (project=False) or another V."""
+    if remeshed.source_face is None:
+        raise ValueError('apply: this result carries no map onto its input (remesh(project=True) makes one)')
+    from . import ops
+    other = meshin.paired_points(other_points, remeshed.input_V, remeshed.source_face.device, 'a remeshing of')
+    with torch.cuda.device(other.device):
+        return ops.bary_points(other, remeshed.input_faces, remeshed.source_face, remeshed.source_bary)

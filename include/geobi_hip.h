@@ -12,8 +12,8 @@
  *     with the matching *_ws_bytes function, which is a pure host computation + rocPRIM size query).
  *     Documented exceptions (plus one helper): geobi_read_i32 (the size read-back: waits for `stream`), geobi_clean_faces
  *     (reads its undecided counts through it), geobi_topo_orient / _components / _report (read the changed flags of
- *     their rounds through it), geobi_subdiv_plan, geobi_decim_plan, geobi_decim_plan_short, geobi_flip_plan, geobi_relax and
- *     geobi_fill_plan with stage_ms (wait for their own end; without it the call is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
+ *     their rounds through it), geobi_subdiv_plan, geobi_decim_plan, geobi_decim_plan_short, geobi_flip_plan, geobi_relax,
+ *     geobi_move_to and geobi_fill_plan with stage_ms (wait for their own end; without it the call is only enqueued and the caller reads its counts through geobi_read_i32, once per pass), the whole-network
  *     entry points geobi_net_forward / geobi_net_forward_train / geobi_net_train_groups (four reads of pooling sizes
  *     per pass, through mapped host memory) -- and, for its own purpose, geobi_host_mailbox (hands out mapped HOST memory)
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*)
@@ -943,9 +943,18 @@ int geobi_decim_points(const float* other, int64_t V, int64_t Vn, const int32_t*
  *                has (n_old . n_new) not > 0 puts its moved vertices back to their old bits (REVERTED, no cascade), and the
  *                faces for which that still holds afterwards are counted (TURNED) and left.  counts (device int32 [4]):
  *                moved (before the revert), refused, reverted, turned.  stage_ms (HOST float [2]): tables, the four launches.
+ *   MOVE TO      geobi_move_to: the protocol of geobi_relax with the proposal p' = target[v] (target [V, 3] float32, read
+ *                as it is) in place of the tangential formula, and the same text on the device for everything else.  A
+ *                vertex with a lock entry != 0 or valence < 3 keeps its bits (a vertex whose normal sum s is 0 is proposed
+ *                like any other: the proposal needs no normal).  A p' equal to p in all three float32 values stays and is
+ *                not counted; a p' that is not finite, or that fails the FLIP test as above, is REFUSED; every other vertex
+ *                MOVES; the turned / revert / turned launches and the four counts are those of geobi_relax.  stage_ms
+ *                (HOST float [2]) as there.  This is step five of the loop: the relaxed vertices go back to the input
+ *                surface (target = the closest points of geobi_closest_on_faces) under the guard of the relaxation.
  *   geobi_remesh_stats   for reports: edge_len (device fp64 [3F]) = sqrt(len2) of every edge at the sorted position of its
  *                head, -1 elsewhere; valence [V].  Written for F, V > 0.
- * One workspace size serves all five entry points of this unit; F == 0 is valid everywhere (nothing flips, nothing moves). */
+ * One workspace size serves all six entry points of this unit; F == 0 is valid everywhere (nothing flips, nothing moves:
+ * geobi_relax and geobi_move_to copy the points and zero the counts). */
 #define GEOBI_FLIP_SWEEPS 3
 size_t geobi_remesh_ws_bytes(int64_t F, int64_t V);
 int geobi_remesh_lock(const int32_t* faces, const float* points, int64_t F, int64_t V, int use_sharp, double c2,
@@ -958,8 +967,46 @@ int geobi_flip_emit(const int32_t* faces, int64_t F, int64_t V, int32_t* faces_o
                     void* stream);
 int geobi_relax(const int32_t* faces, const float* points, const int32_t* lock, int64_t F, int64_t V, double lambda,
                 float* points_out, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
+int geobi_move_to(const int32_t* faces, const float* points, const float* target, const int32_t* lock, int64_t F, int64_t V,
+                  float* points_out, int32_t* counts, float* stage_ms, void* ws, size_t ws_bytes, void* stream);
 int geobi_remesh_stats(const int32_t* faces, const float* points, int64_t F, int64_t V, void* edge_len, int32_t* valence,
                        void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- closest points on given faces (projection) ----
+ * WHERE on a surface the nearest point lies; no counterpart in the reference, whose commented-out p2m gives
+ * distances only.  geobi_nearest_triangle stays the search (all pairs, fp32) and keeps its bits; this is the step after it:
+ * q [Q, 3] float32, verts [V, 3] float32, fv [F, 3] int32, face [Q] int32 as geobi_nearest_triangle returned it ->
+ * bary [Q, 3] float32, point [Q, 3] float32, dist [Q] float32.  One lane per query; as in 4n - 4q every float step is fp64
+ * from the float32 inputs in ONE stated order (no contraction; / and sqrt are the correctly rounded ones), nothing depends
+ * on launch geometry: tests/project_model.py restates these rules in plain Python and reproduces every output bit.
+ *   corners      (a, b, c) = verts[fv[face[i]]] in the face row's own order, the ids clamped into [0, V) as in
+ *                geobi_bary_points.  (u . w) = (ux * wx + uy * wy) + uz * wz.  p = q[i].
+ *   region test  Ericson, Real-Time Collision Detection 5.1.5, in its priority order.  ab = b - a, ac = c - a, ap = p - a,
+ *                bp = p - b, cp = p - c, every difference per coordinate in fp64; d1 = (ab . ap), d2 = (ac . ap), d3 = (ab .
+ *                bp), d4 = (ac . bp), d5 = (ab . cp), d6 = (ac . cp): all six from ap, bp, cp directly, never from
+ *                differences of d1 and d2, so a query that EQUALS a corner has three zero dot products and lands exactly
+ *                in that corner's region.  vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4.  The
+ *                first rule that holds decides (v, w):
+ *                  1  d1 <= 0 and d2 <= 0                         corner a   (0, 0)
+ *                  2  d3 >= 0 and d4 <= d3                        corner b   (1, 0)
+ *                  3  vc <= 0 and d1 >= 0 and d3 <= 0             edge ab    (d1 / (d1 - d3), 0)
+ *                  4  d6 >= 0 and d5 <= d6                        corner c   (0, 1)
+ *                  5  vb <= 0 and d2 >= 0 and d6 <= 0             edge ac    (0, d2 / (d2 - d6))
+ *                  6  va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0   edge bc    (1 - t, t), t = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+ *                  7  otherwise                                   inside     (vb / den, vc / den), den = (va + vb) + vc
+ *                A quotient whose denominator is 0, or that is NaN, is the weight 0 (in rule 6: t = 0).  Finally v = min(max(
+ *                v, 0), 1) and w = min(max(w, 0), 1 - v): a triangle without area (two or three equal corners, collinear
+ *                corners) still answers with a finite point of the closed triangle -- a point OF it, not always its nearest.
+ *   outputs      bary = ((float)((1 - v) - w), (float)v, (float)w).  point = the formula of geobi_bary_points on those
+ *                three float32 weights, per coordinate fmaf(b2, c, fmaf(b1, b, b0 * a)) in float32: geobi_bary_points(verts,
+ *                fv, face, bary) returns point bit for bit, and on another vertex array of the same V the counterpart of
+ *                the projected point.  dist = (float)sqrt((ex * ex + ey * ey) + ez * ez), e_k = p_k - ((a_k + v * ab_k) + w *
+ *                ac_k), in fp64 with the clamped v and w.
+ *   exceptions   face[i] outside [0, F): zeros in all three outputs, as geobi_bary_points.  A query with a coordinate that
+ *                is not finite: dist = +inf, bary = (1, 0, 0), point = that formula on (1, 0, 0), which is a.
+ * Q, V, F >= 1 and <= GEOBI_MAX_NODES.  No workspace.                                                                      */
+int geobi_closest_on_faces(const float* q, const float* verts, const int32_t* fv, const int32_t* face, int64_t Q, int64_t V,
+                           int64_t F, float* bary, float* point, float* dist, void* stream);
 
 /* ---------------------------------------------------------------- hole filling (boundary loops, fan fill) ----
  * Closes the holes of a triangle mesh; no counterpart in the reference.  The topology is integer-exact, a
