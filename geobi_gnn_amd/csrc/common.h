@@ -344,8 +344,12 @@ static inline size_t gemm_nn_fixed_ws_bytes(int64_t M, int N, int slices) {
   size_t b = (size_t)slices * M * N * sizeof(float);
   return (slices > 1 && b <= ((size_t)256 << 20)) ? align_up(b) + 256 : 256;
 }
+// What a gemm_nn call decided on the host (the launch follows it; geobi_debug_gemm_nn reports it).  shape: the tile shape
+// by its GEOBI_NN_CFG number, 0 = nothing was launched; slices > 1: split-K through ep.ws and the reduce kernel.
+struct NnPlan { int fast = 0, shape = 0, wm = 0, wn = 0, tm = 0, tn = 0, bk = 0, slices = 0, k_chunk = 0, wide = 0; };
+// cfg != 0: this call's tile shape, as GEOBI_NN_CFG of that value forces it for the process; ran: the plan that ran
 int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N, int K,
-            const GemmEpilogue& ep, hipStream_t s);
+            const GemmEpilogue& ep, hipStream_t s, int cfg = 0, NnPlan* ran = nullptr);
 size_t gemm_tn_ws_bytes(int I, int J, int64_t M);
 size_t gemm_tn_ws_bytes_any_width(int I, int J, int64_t M);   // max over column widths 1..J
 enum TnOut { TN_PLAIN = 0, TN_LIN_UNPACK = 1, TN_DU_DC = 2, TN_RPRIME = 3 };
@@ -366,10 +370,15 @@ struct TnOutput {
 // I, J: logical output sizes INCLUDING an implicit ones row / column when ones_row / ones_col >= 0, or the column-sums
 // row (sum_row == I - 1: the sums of B's columns over the M rows, formed on the VALU beside the MFMAs; TnOutput.extra_row
 // routes it).
+// What a gemm_tn call decided on the host: the kernel instance <ti, tj, u, va> (va: the vector-A kernel), its grid
+// (tiles_i x tiles_j output tiles, blocks_y blocks of four node slices of m_per_slice rows each = blocks_y slabs) and the
+// extra bias blocks of the reduce kernel.  All zero: nothing was launched.
+struct TnPlan {
+  int ti = 0, tj = 0, va = 0, u = 0, tiles_i = 0, tiles_j = 0, slices = 0, blocks_y = 0, bias_blocks = 0;
+  int64_t m_per_slice = 0;
+};
 int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, int ones_row, int ones_col,
-            const TnOutput& o, void* ws, size_t ws_bytes, hipStream_t s, int sum_row = -1);
-size_t colsum_ws_bytes(int64_t M, int J);
-int colsum(const float* A, int lda, int64_t M, int J, float* out, void* ws, size_t ws_bytes, hipStream_t s);
+            const TnOutput& o, void* ws, size_t ws_bytes, hipStream_t s, int sum_row = -1, TnPlan* ran = nullptr);
 
 // feast.hip
 int exp_le0_probe(const float* x, float* y, int64_t n, hipStream_t s);

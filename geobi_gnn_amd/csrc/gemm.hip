@@ -7,7 +7,6 @@
 //   gemm_tn : C[I,J] = sum_m A[m,I] * B[m,J]   (weight gradients; the reduction runs over the
 //             node dimension, split across workgroups into partial slabs that a second kernel
 //             adds in a fixed order -> deterministic, no float atomics).
-//   colsum  : column sums (bias / c gradients), same two-stage scheme.
 #include "common.h"
 
 #include <algorithm>
@@ -582,45 +581,9 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
   tn_emit(o, idx / J, idx % J, I, J, s);
 }
 
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ A, int lda, int64_t M, int J,
-                                                             int64_t rows_per_block, float* __restrict__ partial) {
-  // block (bx, by) sums rows [bx*rpb, (bx+1)*rpb) of the column block by*cols .. ; the 256 threads
-  // form a (rows_par x cols) grid so narrow matrices (J = 9..32) still use the whole block.
-  __shared__ float red[256];
-  const int cols = J < 256 ? J : 256;
-  const int rows_par = 256 / cols;
-  const int rr = threadIdx.x / cols, jc = threadIdx.x % cols;
-  const int j = blockIdx.y * 256 + jc;
-  int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > M) r1 = M;
-  float s = 0.f;
-  if (rr < rows_par && j < J)
-    for (int64_t r = r0 + rr; r < r1; r += rows_par) s += A[r * lda + j];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (rr == 0 && j < J) {
-    float t = 0.f;
-    for (int q = 0; q < rows_par; ++q) t += red[q * cols + jc];
-    partial[(size_t)blockIdx.x * J + j] = t;
-  }
-}
-
-__global__ void colsum_final_kernel(const float* __restrict__ partial, int blocks, int J, float* __restrict__ out) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= J) return;
-  float s = 0.f;
-  for (int b = 0; b < blocks; ++b) s += partial[(size_t)b * J + j];
-  out[j] = s;
-}
-
-struct TnPlan {
-  int ti, tj, va, u, tiles_i, tiles_j, slices, blocks_y;
-  int64_t m_per_slice;
-};
-
 TnPlan plan_tn(const float* A, int lda, int I, int J, int64_t M, int ones_row) {
   TnPlan p;
+  if (M < 1) M = 1;      // no rows: one block per tile writes a slab of zeros (0 rows per slice would divide by zero below)
   // per-wave tile = (32 TI) x (32 TJ): as large as the shape fills (MFMA work is padded to tiles)
   int ci = cdiv(I, 32), cj = cdiv(J, 32);
   const int Id = I - (ones_row >= 0 ? 1 : 0);
@@ -657,41 +620,33 @@ TnPlan plan_tn(const float* A, int lda, int I, int J, int64_t M, int ones_row) {
   return p;
 }
 
-}  // namespace
+// GEOBI_NN_CFG: tuning knob for tools/nn_cfg_sweep.py, one tile shape for every gemm_nn call of the process.  A call's
+// own `cfg` argument (geobi_debug_gemm_nn) goes before it.
+Knob g_nn_cfg{"GEOBI_NN_CFG", 0};
 
-int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N, int K,
-            const GemmEpilogue& ep, hipStream_t s) {
-  if (M <= 0 || N <= 0) return 0;
-  GEOBI_REQUIRE(K > 0, "gemm_nn: K must be positive");
-  prof_begin(PROF_GEMM, s, 2.0 * M * N * K, 1);          // "bytes" carries the flop count here
-  dim3 block(256);
-  const bool fast = ((lda & 3) == 0) && ((ldb & 3) == 0) && ((K & 3) == 0) && K >= 4 &&
-                    ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0 && (transB || ((N & 3) == 0 && N >= 4));
-#define GEOBI_GEMM_LAUNCH(WM, WN, TM_, TN_, BK_)                                                                    \
-  do {                                                                                                          \
-    if (fast) { GEOBI_GEMM_LAUNCH_F(WM, WN, TM_, TN_, BK_, true); } else { GEOBI_GEMM_LAUNCH_F(WM, WN, TM_, TN_, BK_, false); } \
-  } while (0)
-#define GEOBI_GEMM_LAUNCH_F(WM, WN, TM_, TN_, BK_, FAST_)                                                          \
-  do {                                                                                                          \
-    constexpr int BM_ = WM * TM_ * 32;                                                                          \
-    constexpr int BN_ = WN * TN_ * 32;                                                                          \
-    dim3 grid(cdiv(M, BM_), cdiv(N, BN_), slices);                                                              \
-    gemm_nn_kernel<WM, WN, TM_, TN_, BK_, FAST_><<<grid, block, 0, s>>>(A, lda, B, ldb, transB, C, ldc, M, N, K, \
-                                                                ep.bias,                                        \
-                                                           ep.slope, ep.C1, ep.split, ep.ldc1, k_chunk, partial,  \
-                                                           wide);                                                \
-  } while (0)
+// The tile shapes gemm_nn instantiates, by the number that GEOBI_NN_CFG / `cfg` forces them with.
+struct NnShape { int wm, wn, tm, tn, bk; };
+constexpr NnShape kNnShapes[6] = {{0, 0, 0, 0, 0}, {2, 2, 1, 1, 32}, {2, 2, 2, 1, 32}, {2, 2, 1, 1, 64},
+                                  {2, 2, 2, 2, 16}, {4, 1, 1, 1, 32}};
+
+// Everything a gemm_nn launch decides on the host: the ONE selection, which the launch below follows and which
+// geobi_debug_gemm_nn reports.
+NnPlan plan_nn(const float* A, int lda, const float* B, int ldb, int transB, const float* C, int ldc, int M, int N, int K,
+               const GemmEpilogue& ep, int cfg) {
+  NnPlan p;
+  p.fast = (((lda & 3) == 0) && ((ldb & 3) == 0) && ((K & 3) == 0) && K >= 4 &&
+            ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0 && (transB || ((N & 3) == 0 && N >= 4))) ? 1 : 0;
   // Few rows (coarse graph levels): shrink the block tile so the grid still covers the 256 CUs, and
   // split K across blockIdx.z when even the small tiles leave CUs idle.
   const int64_t big_blocks = (int64_t)cdiv(M, 128) * cdiv(N, N > 64 ? 128 : (N > 32 ? 64 : 32));
   int slices = 1, k_chunk = K;
-  float* partial = nullptr;
+  bool split_k = false;
   const int64_t blocks_small = N <= 32 ? (int64_t)cdiv(M, 128) : (int64_t)cdiv(M, 64) * cdiv(N, 64);   // tiles below
   if (ep.fixed_slices > 0) {
     if (ep.fixed_slices > 1 && ep.ws != nullptr) {
       k_chunk = ((K + ep.fixed_slices - 1) / ep.fixed_slices + 63) / 64 * 64;
       slices = (K + k_chunk - 1) / k_chunk;
-      if (slices > 1 && (size_t)slices * M * N * sizeof(float) <= ep.ws_bytes) partial = (float*)ep.ws;
+      if (slices > 1 && (size_t)slices * M * N * sizeof(float) <= ep.ws_bytes) split_k = true;
       else { slices = 1; k_chunk = K; }
     }
   } else if (big_blocks < 384 && blocks_small < 512 && K >= 256 && ep.ws != nullptr) {
@@ -702,12 +657,14 @@ int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float*
     if (slices < 1) slices = 1;
     k_chunk = ((K + slices - 1) / slices + 63) / 64 * 64;       // whole k-tiles per slice
     slices = (K + k_chunk - 1) / k_chunk;
-    if (slices > 1 && (size_t)slices * M * N * sizeof(float) <= ep.ws_bytes) partial = (float*)ep.ws;
+    if (slices > 1 && (size_t)slices * M * N * sizeof(float) <= ep.ws_bytes) split_k = true;
     else { slices = 1; k_chunk = K; }
   }
+  p.slices = slices;                     // > 1: split-K, the partial sums go through ep.ws and splitk_reduce_kernel
+  p.k_chunk = k_chunk;
   // 16-B row stores need a plain, aligned, 4-float-granular output
-  const int wide = (partial == nullptr && ep.C1 == nullptr && (ldc & 3) == 0 && (N & 3) == 0 &&
-                    (((uintptr_t)C) & 15) == 0 && (ep.bias == nullptr || (((uintptr_t)ep.bias) & 15) == 0)) ? 1 : 0;
+  p.wide = (!split_k && ep.C1 == nullptr && (ldc & 3) == 0 && (N & 3) == 0 &&
+            (((uintptr_t)C) & 15) == 0 && (ep.bias == nullptr || (((uintptr_t)ep.bias) & 15) == 0)) ? 1 : 0;
   // one-tile-per-wave shapes: 64-deep k-tiles when there is k to cover (half the barriers per MFMA and
   // twice the prefetch distance)
   const bool deep = k_chunk >= 128;
@@ -722,36 +679,54 @@ int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float*
   //                     reductions -- dz = g Wf^T -- are bound by writing the output)
   // 64-deep k-tiles from K >= 512 (half the barriers per MFMA); the k order is the same for every shape,
   // so results do not depend on the choice.
-  static Knob forced_knob{"GEOBI_NN_CFG", 0};
-  const int forced = (int)forced_knob.get();
-  if (forced) {                 // tuning knob for tools/nn_cfg_sweep.py: force one tile shape for every call
-    switch (forced) {
-      case 1: GEOBI_GEMM_LAUNCH(2, 2, 1, 1, 32); break;
-      case 2: GEOBI_GEMM_LAUNCH(2, 2, 2, 1, 32); break;
-      case 4: GEOBI_GEMM_LAUNCH(2, 2, 2, 2, 16); break;
-      case 5: GEOBI_GEMM_LAUNCH(4, 1, 1, 1, 32); break;
-      default: GEOBI_GEMM_LAUNCH(2, 2, 1, 1, 64); break;
-    }
-  } else if (N <= 32) {
-    GEOBI_GEMM_LAUNCH(4, 1, 1, 1, 32);
-  } else if (N <= 64 && M >= 98304) {
-    GEOBI_GEMM_LAUNCH(2, 2, 2, 1, 32);
-  } else if (N > 64 && K > 64 && M >= 81920) {
-    GEOBI_GEMM_LAUNCH(2, 2, 2, 2, 16);
-  } else if (deep && K >= 512) {
-    GEOBI_GEMM_LAUNCH(2, 2, 1, 1, 64);
-  } else {
-    GEOBI_GEMM_LAUNCH(2, 2, 1, 1, 32);
-  }
-#undef GEOBI_GEMM_LAUNCH
-#undef GEOBI_GEMM_LAUNCH_F
+  const int forced = cfg ? cfg : (int)g_nn_cfg.get();
+  if (forced) p.shape = (forced == 1 || forced == 2 || forced == 4 || forced == 5) ? forced : 3;   // every other value: 3
+  else if (N <= 32) p.shape = 5;
+  else if (N <= 64 && M >= 98304) p.shape = 2;
+  else if (N > 64 && K > 64 && M >= 81920) p.shape = 4;
+  else if (deep && K >= 512) p.shape = 3;
+  else p.shape = 1;
+  const NnShape& t = kNnShapes[p.shape];
+  p.wm = t.wm; p.wn = t.wn; p.tm = t.tm; p.tn = t.tn; p.bk = t.bk;
+  return p;
+}
+
+template <int SHAPE>
+void launch_nn(const NnPlan& p, const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M,
+               int N, int K, const GemmEpilogue& ep, float* partial, hipStream_t s) {
+  constexpr NnShape t = kNnShapes[SHAPE];
+  const dim3 grid(cdiv(M, t.wm * t.tm * 32), cdiv(N, t.wn * t.tn * 32), p.slices);
+  if (p.fast)
+    gemm_nn_kernel<t.wm, t.wn, t.tm, t.tn, t.bk, true><<<grid, 256, 0, s>>>(
+        A, lda, B, ldb, transB, C, ldc, M, N, K, ep.bias, ep.slope, ep.C1, ep.split, ep.ldc1, p.k_chunk, partial, p.wide);
+  else
+    gemm_nn_kernel<t.wm, t.wn, t.tm, t.tn, t.bk, false><<<grid, 256, 0, s>>>(
+        A, lda, B, ldb, transB, C, ldc, M, N, K, ep.bias, ep.slope, ep.C1, ep.split, ep.ldc1, p.k_chunk, partial, p.wide);
+}
+
+}  // namespace
+
+int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N, int K,
+            const GemmEpilogue& ep, hipStream_t s, int cfg, NnPlan* ran) {
+  if (ran) *ran = NnPlan();
+  if (M <= 0 || N <= 0) return 0;
+  GEOBI_REQUIRE(K > 0, "gemm_nn: K must be positive");
+  prof_begin(PROF_GEMM, s, 2.0 * M * N * K, 1);          // "bytes" carries the flop count here
+  const NnPlan p = plan_nn(A, lda, B, ldb, transB, C, ldc, M, N, K, ep, cfg);
+  float* partial = p.slices > 1 ? (float*)ep.ws : nullptr;
+  const int rc = dispatch_int<1, 2, 3, 4, 5>(p.shape, [&](auto shape) {
+    launch_nn<decltype(shape)::value>(p, A, lda, B, ldb, transB, C, ldc, M, N, K, ep, partial, s);
+    return 0;
+  });
+  GEOBI_REQUIRE(rc != kNoCase, "gemm_nn: no tile shape %d", p.shape);
   GEOBI_LAUNCH_OK();
   if (partial) {
-    splitk_reduce_kernel<<<cdiv((int64_t)M * N, 256), 256, 0, s>>>(partial, slices, M, N, C, ldc, ep.bias, ep.slope,
+    splitk_reduce_kernel<<<cdiv((int64_t)M * N, 256), 256, 0, s>>>(partial, p.slices, M, N, C, ldc, ep.bias, ep.slope,
                                                                   ep.C1, ep.split, ep.ldc1);
     GEOBI_LAUNCH_OK();
   }
   prof_end(PROF_GEMM, s);
+  if (ran) *ran = p;
   return 0;
 }
 
@@ -781,7 +756,8 @@ size_t gemm_tn_ws_bytes_any_width(int I, int J, int64_t M) {
 }
 
 int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, int ones_row, int ones_col,
-            const TnOutput& o, void* ws, size_t ws_bytes, hipStream_t s, int sum_row) {
+            const TnOutput& o, void* ws, size_t ws_bytes, hipStream_t s, int sum_row, TnPlan* ran) {
+  if (ran) *ran = TnPlan();
   if (I <= 0 || J <= 0) return 0;
   const bool extra = ones_row >= 0 || sum_row >= 0;
   GEOBI_REQUIRE(M >= 0 && I - extra >= 1 && J - (ones_col >= 0) >= 1, "gemm_tn: empty operand");
@@ -790,10 +766,11 @@ int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, 
   GEOBI_REQUIRE(ones_col < 0 || ones_col == J - 1, "gemm_tn: the ones column is the last column");
   // the column-sums row is not an MFMA row: tiles cover the data rows only
   const int I_mma = sum_row >= 0 ? I - 1 : I;
-  TnPlan p = plan_tn(A, lda, I_mma, J, M > 0 ? M : 1, ones_row);
+  TnPlan p = plan_tn(A, lda, I_mma, J, M, ones_row);
   Arena a(ws, ws_bytes);
   float* slabs = carve_tn(a, p, I, J);
   GEOBI_WS_CHECK("gemm_tn", a, ws, ws_bytes);
+  p.bias_blocks = (o.mode == TN_RPRIME && o.extra_row && o.C2 != nullptr) ? cdiv(o.Cout, 8) : 0;
   prof_begin(PROF_GEMM, s, 2.0 * (double)M * I_mma * J, 2);
   dim3 grid(p.tiles_i * p.tiles_j, p.blocks_y);
 #define GEOBI_TN(TI_, TJ_, U_, VA_)                                                                         \
@@ -810,36 +787,10 @@ int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, 
   }
 #undef GEOBI_TN
   GEOBI_LAUNCH_OK();
-  const int bias_blocks = (o.mode == TN_RPRIME && o.extra_row && o.C2 != nullptr) ? cdiv(o.Cout, 8) : 0;
-  tn_reduce_kernel<<<cdiv((int64_t)I * J, 64) + bias_blocks, 256, 0, s>>>(slabs, p.blocks_y, I, J, o);
+  tn_reduce_kernel<<<cdiv((int64_t)I * J, 64) + p.bias_blocks, 256, 0, s>>>(slabs, p.blocks_y, I, J, o);
   GEOBI_LAUNCH_OK();
   prof_end(PROF_GEMM, s);
-  return 0;
-}
-
-static int colsum_blocks(int64_t M) {
-  int64_t b = (M + 511) / 512;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-static float* carve_colsum(Arena& a, int64_t M, int J) { return a.take<float>((size_t)colsum_blocks(M) * J); }
-
-size_t colsum_ws_bytes(int64_t M, int J) { return carve_bytes([&](Arena& a) { carve_colsum(a, M, J); }); }
-
-int colsum(const float* A, int lda, int64_t M, int J, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (J <= 0) return 0;
-  int blocks = colsum_blocks(M);
-  Arena a(ws, ws_bytes);
-  float* partial = carve_colsum(a, M, J);
-  GEOBI_WS_CHECK("colsum", a, ws, ws_bytes);
-  int64_t rpb = (M + blocks - 1) / blocks;
-  if (rpb < 1) rpb = 1;
-  colsum_partial_kernel<<<dim3(blocks, cdiv(J, 256)), 256, 0, s>>>(A, lda, M, J, rpb, partial);
-  GEOBI_LAUNCH_OK();
-  colsum_final_kernel<<<cdiv(J, 256), 256, 0, s>>>(partial, blocks, J, out);
-  GEOBI_LAUNCH_OK();
+  if (ran) *ran = p;
   return 0;
 }
 

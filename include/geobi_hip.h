@@ -1259,6 +1259,33 @@ int geobi_debug_pool_edge_rows_onepass(const int32_t* cnew, const int32_t* segpt
                                        int64_t nbound, int64_t E_fine, const int32_t* rowinfo_in, int32_t* rowptr_c,
                                        int32_t* row_c, int32_t* col_c, float* w_c, int32_t* count, int32_t* overflow,
                                        void* ws, size_t ws_bytes, void* stream);
+/* diagnostic entries of the dense products (csrc/gemm.hip), for tests: forms that otherwise only the layers call, and a
+ * report of the path a call took.  `plan` is a HOST array of 8 values, filled from the plan the launch itself followed.
+ *   geobi_debug_gemm_nn : geobi_gemm_nn with the rest of its epilogue -- C1 / split / ldc1: columns >= split go to
+ *                         C1[row * ldc1 + col - split]; ws / ws_bytes: scratch that allows split-K (automatic for few
+ *                         blocks and K >= 256, or exactly fixed_slices > 1 slices; too small a scratch: one slice) --
+ *                         and cfg: 0 = the launcher's own tile shape, 1..5 = the shape GEOBI_NN_CFG of that value forces
+ *                         (for this call only).
+ *                         plan = (FAST kernel 0/1, shape number 1..5, tile as the digits WAVES_M WAVES_N TM TN, BK, slices,
+ *                         k_chunk, wide store 0/1, split-K reduce launched 0/1); all 0 when M or N is 0
+ *   geobi_debug_gemm_tn : C[I, J] = sum_m A[m, I] B[m, J] with the implicit last row / column (ones_row = I - 1: a row of
+ *                         ones in A^T; ones_col = J - 1: a column of ones in B; sum_row = I - 1: the column sums of B; -1:
+ *                         none) and every output map: mode 0 plain (C [I, ldc]; extra_row / extra_col: the last row /
+ *                         column goes to C2), 1 lin-unpack (rows (head, in-channel), C = lin.weight.grad [9 Cout, Cin],
+ *                         last row -> C2 = bias.grad), 2 du/dc (A = [dp | dcs] rows 0..8 and 12..20, C = du [9, ldc],
+ *                         last column -> C2 = dc [9] or NULL), 3 r' (columns [r 9 Cout | dp 12 | dcs 12]: C = lin.weight.grad
+ *                         [9 Cout, Cin] at input channel col0 + row, C3 = u.weight.grad [9, Cin] or NULL; with extra_row
+ *                         the last row holds column sums: C2 = bias.grad [Cout] or NULL, C4 = c.grad [9] or NULL);
+ *                         accumulate != 0 adds to the outputs.  Workspace of geobi_gemm_tn_ws_bytes(I, J, M) bytes.
+ *                         plan = (vector-A kernel 0/1, TI, TJ, tiles_i, tiles_j, slabs = blocks along the reduction,
+ *                         rows per wave slice, bias blocks of the reduce kernel)                                          */
+int geobi_debug_gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N,
+                        int K, const float* bias, float slope, float* C1, int split, int ldc1, void* ws, size_t ws_bytes,
+                        int fixed_slices, int cfg, int64_t* plan, void* stream);
+int geobi_debug_gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, int ones_row,
+                        int ones_col, int sum_row, int mode, float* C, int ldc, float* C2, float* C3, float* C4, int Cin,
+                        int Cout, int col0, int extra_row, int extra_col, int accumulate, void* ws, size_t ws_bytes,
+                        int64_t* plan, void* stream);
 int geobi_prof_collect(int tag, int64_t* launches, double* total_ms, double* total_bytes);
 
 #ifdef __cplusplus
