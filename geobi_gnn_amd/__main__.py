@@ -9,8 +9,8 @@
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
   python -m geobi_gnn_amd clean --data_dir DIR [--out_dir DIR/clean] [--weld_tol 0] [--no_weld] [--no_manifold]
   python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold] [--orient] [--min_component N]
-  python -m geobi_gnn_amd clean ... [--orient] [--min_component N]
-  python -m geobi_gnn_amd info --data_dir DIR [--weld_tol 0] [--no_weld] [--gpu -1]
+  python -m geobi_gnn_amd clean ... [--orient] [--min_component N] [--drop_intersecting]
+  python -m geobi_gnn_amd info --data_dir DIR [--weld_tol 0] [--no_weld] [--intersections] [--gpu -1]
   python -m geobi_gnn_amd sample --data_dir DIR [--out_dir DIR/samples] --n N [--seed 1] [--normals] [--gpu -1]
   python -m geobi_gnn_amd eval ... --free --samples N [--seed 1]
   python -m geobi_gnn_amd align ... --samples N [--seed 1]
@@ -39,7 +39,9 @@ noisy/NAME_n*.obj of equal size (welding noisy coordinates would be wrong: dupli
 winds the faces of every connected part consistently before the half-edge rule, which otherwise drops one of every two
 neighbours wound in opposite senses; `--min_component N` drops the edge-connected parts of fewer than N faces (scan debris).
 `info` prints what a file is before any of that is chosen: edges, boundary, complex and inconsistent edges, parts, whether
-it is closed and orientable.  `align` (ops.icp) brings every DIR/NAME_*.obj -- or DIR/NAME.obj where a stem has none -- into
+it is closed and orientable; `info --intersections` (meshselfx.py) also says whether the surface passes through itself:
+the pairs of faces that intersect, the faces in such a pair, the pairs folded flat onto each other.  `clean
+--drop_intersecting` drops those faces, and `fill` closes what that opens.  `align` (ops.icp) brings every DIR/NAME_*.obj -- or DIR/NAME.obj where a stem has none -- into
 the frame of DIR2/NAME.obj by rigid point-to-point ICP and writes it with its own faces; the two meshes may differ in size.
 `eval --align` does the same before it scores (AlignInfo.txt beside ErrorInfo_h.txt), `eval --free` scores pairs whose
 vertex counts or face tables differ (ErrorInfo_free.txt).  `sample` (meshsample.py) writes N points drawn uniformly by
@@ -330,8 +332,9 @@ def _weld_tol(opt):
 
 
 def _topo_args(opt):
-    """--orient / --min_component as clean_mesh takes them (neither is in the options without its flag)"""
-    return {'orient': getattr(opt, 'orient', False), 'min_component': getattr(opt, 'min_component', 0)}
+    """--orient / --min_component / --drop_intersecting as clean_mesh takes them (none is in the options without its flag)"""
+    return {'orient': getattr(opt, 'orient', False), 'min_component': getattr(opt, 'min_component', 0),
+            'drop_intersecting': getattr(opt, 'drop_intersecting', False)}
 
 
 def _host_mesh(result):
@@ -347,6 +350,8 @@ def _clean_line(cleaned, V, F, out_file):
     if t is not None:          # '-': the stage that counts it was not asked for
         line += ',  ' + ',  '.join('%s: %s' % (label, t.get(key, '-')) for label, key in (
             ('flipped', 'flipped'), ('nonorientable', 'nonorientable'), ('components', 'components'), ('small', 'faces_dropped')))
+    if 'intersecting' in c:    # only with --drop_intersecting
+        line += ',  intersecting: %d' % c['intersecting']
     return line
 
 
@@ -424,6 +429,7 @@ def fill(opt):
 
 INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 'complex_edges', 'inconsistent_edges',
              'components', 'orient_components', 'nonorientable', 'would_flip', 'euler')
+INTERSECTION_KEYS = ('intersecting_pairs', 'intersecting_faces', 'folded_pairs')      # info --intersections
 
 
 def info(opt):
@@ -437,10 +443,13 @@ def info(opt):
 
     def one(path, skip):
         points, faces = meshio.read_obj(path)
-        r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev)
-        print("V: %7d,  F: %7d,  %s,  closed: %s,  '%s'"
-              % (points.shape[0], faces.shape[0], ',  '.join('%s: %d' % (k, r[k]) for k in INFO_KEYS),
-                 'yes' if r['closed'] else 'no', os.path.basename(path)), flush=True)
+        r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev, intersections=opt.intersections)
+        line = ("V: %7d,  F: %7d,  %s,  closed: %s,  '%s'"
+                % (points.shape[0], faces.shape[0], ',  '.join('%s: %d' % (k, r[k]) for k in INFO_KEYS),
+                   'yes' if r['closed'] else 'no', os.path.basename(path)))
+        if opt.intersections:
+            line += ',  ' + ',  '.join('%s: %d' % (k, r[k]) for k in INTERSECTION_KEYS)
+        print(line, flush=True)
 
     return folders.walk(files, one)
 
@@ -657,6 +666,9 @@ def _add_clean_flags(p, given=False):
                         'rule')
     p.add_argument('--min_component', type=_min_component_arg, default=argparse.SUPPRESS, action=_StoreGiven, metavar='N',
                    help='drop the edge-connected parts of fewer than N faces')
+    p.add_argument('--drop_intersecting', action=_TrueGiven, default=argparse.SUPPRESS,
+                   help='drop the faces that intersect another face (all pairs, on the welded table); `fill` closes the '
+                        'holes this opens')
 
 
 def build_parser():
@@ -745,6 +757,9 @@ def build_parser():
     i.add_argument('--data_dir', type=str, required=True, help='holds original/, or the OBJ files themselves')
     i.add_argument('--weld_tol', type=_weld_tol_arg, default=0.0, help='as for clean: the report is computed after the weld')
     i.add_argument('--no_weld', action='store_true', help='keep every vertex apart')
+    i.add_argument('--intersections', action='store_true',
+                   help='also count the pairs of faces that intersect, the faces in such a pair and the pairs folded flat onto '
+                        'each other (all pairs of faces: F * F box tests)')
     i.add_argument('--gpu', type=int, default=-1)
     i.set_defaults(fn=info)
     u = sub.add_parser('subdivide', help='make every mesh denser on the device: midpoint or Loop passes, or split the edges '
@@ -830,7 +845,7 @@ def parse_args(argv=None):
         if opt.method in ('bnf', 'gnf') and (opt.normal_iters < 0 or not opt.sigma_r > 0 or not opt.sigma_s > 0 or opt.n_iter < 0):
             ap.error('denoise: --normal_iters and --n_iter are not negative, --sigma_r and --sigma_s positive')
         if not opt.clean:
-            for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component'):
+            for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component', 'drop_intersecting'):
                 if getattr(opt, flag + '_given', False):
                     ap.error('denoise: --%s needs --clean' % flag)
     if opt.command == 'eval' and opt.scale and not opt.align:

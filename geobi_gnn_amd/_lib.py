@@ -141,6 +141,13 @@ def read_i32(t, n=None):
     return list(buf)
 
 
+def read_i64(t, n=None):
+    """Device int64 tensor -> list of Python ints: the same read-back on its 2 n int32 halves (n <= 32)."""
+    n = t.numel() if n is None else n
+    halves = read_i32(t.view(torch.int32), 2 * n)
+    return [(halves[2 * i] & 0xffffffff) | (halves[2 * i + 1] << 32) for i in range(n)]
+
+
 _size_cache = {}
 
 

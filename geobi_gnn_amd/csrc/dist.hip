@@ -23,6 +23,7 @@
 // written out), the result is bit-identical for every S.  d2 is formed from coordinate DIFFERENCES, never
 // |q|^2 + |t|^2 - 2 q.t; one sqrt per query at the end.
 #include "common.h"
+#include "pair_slices.h"
 #include "../../include/geobi_hip.h"
 
 #include <math.h>
@@ -40,31 +41,7 @@ constexpr int kThreads = 256;
 #endif
 constexpr int kPointQpl = 4, kPointTile = GEOBI_DIST_POINT_TILE;     // LDS: float4 per target point
 constexpr int kTriQpl = 2, kTriTile = 256;          // 16 KB of LDS: four float4 per triangle
-constexpr int kTargetBlocks = 1024;                 // workgroups wanted per launch (256 CUs x 4)
-constexpr int kMaxSlices = 1024;
-
-struct Slicing { int qblocks, slices, tiles_per_slice; };
-
-// slices a launch with `qblocks` query blocks in all would like: its workgroups together should fill the chip
-int want_slices(int64_t qblocks) {
-  const int64_t want = (kTargetBlocks + qblocks - 1) / qblocks;
-  return (int)(want > kMaxSlices ? kMaxSlices : (want < 1 ? 1 : want));
-}
-
-// THE slicing rule: T targets in whole tiles, at most `want` slices, no empty slice
-Slicing slice_targets(int64_t Q, int64_t T, int qpl, int tile, int want) {
-  Slicing c;
-  c.qblocks = cdiv(Q, (int64_t)kThreads * qpl);
-  const int ntiles = cdiv(T, tile);
-  if (want > ntiles) want = ntiles;
-  c.tiles_per_slice = cdiv(ntiles, want);
-  c.slices = cdiv(ntiles, c.tiles_per_slice);
-  return c;
-}
-
-Slicing choose_slices(int64_t Q, int64_t T, int qpl, int tile) {
-  return slice_targets(Q, T, qpl, tile, want_slices(cdiv(Q, (int64_t)kThreads * qpl)));
-}
+static_assert(kThreads == kWalkThreads, "the slicing rule (pair_slices.h) counts query blocks of kWalkThreads lanes");
 
 // ---------------------------------------------------------------- the walk
 // Queries q0 .. q_end of this workgroup (QPL per lane, kThreads apart) against targets t_begin .. t_end; the partial

@@ -21,6 +21,9 @@ keeps every face.  ``clean_mesh`` applies that rule, after a weld openmesh does 
   half-edge rule the faces are wound consistently per component -- two neighbours wound in opposite senses walk their
   common edge in the same direction, and the half-edge rule alone would drop one of them; after the rule, the faces of
   every edge-connected part of fewer than m kept faces are dropped too (state 4, not counted as nonmanifold)
+* **self-intersections** (``drop_intersecting=True``; ``meshselfx``): after the half-edge rule and
+  before ``min_component`` the kept faces that intersect another kept face are dropped together (state 5, counted under
+  ``intersecting`` alone)
 
 Everything is integer-exact (geobi_clean_* in csrc/clean.hip).  No CPU fallback.
 """
@@ -36,7 +39,7 @@ from . import meshin
 class CleanResult(object):
     """points [V', 3] float32, faces [F', 3] int32 (cleaned numbering), vertex_map [V] (new index of canon[v], or -1),
     vertex_src [V'] (input index of every cleaned vertex), face_map [F'] (input index of every kept face), canon [V];
-    counts: welded, degenerate, nonmanifold, unreferenced, rounds.  With ``orient`` / ``min_component``: topology, a dict of
+    counts: welded, degenerate, nonmanifold, unreferenced, rounds (and intersecting with ``drop_intersecting``).  With ``orient`` / ``min_component``: topology, a dict of
     flipped, nonorientable, orient_components, orient_rounds (orient) and components, components_dropped, faces_dropped,
     component_rounds (min_component), else None; face_flip [F] (input numbering: 1 where the winding was reversed)."""
 
@@ -126,7 +129,8 @@ def check_weld_tol(what, weld_tol):
         raise ValueError('%s: weld_tol = %r is not a finite float32' % (what, weld_tol))
 
 
-def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, device=None, orient=False, min_component=0):
+def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, device=None, orient=False, min_component=0,
+               drop_intersecting=False):
     """(points [V, 3], faces [F, 3]) -> CleanResult, on the device.  ValueError: non-finite points, a face index outside
     [0, V), weld_tol < 0, max_rounds < 1, min_component < 0.  GeobiError: the library's errors -- a grid quotient outside
     int32, more than ``max_rounds`` rounds of the half-edge rule (a chain of faces that each share a directed edge with the
@@ -134,7 +138,10 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
 
     ``orient``: weld, corners through canon, consistent winding per component (meshtopo.orient_device), then the
     half-edge rule on the oriented table.  ``min_component = m > 0``: after the rule, the kept faces of every
-    edge-connected part of fewer than m faces are dropped (a face they displaced under the rule does not come back)."""
+    edge-connected part of fewer than m faces are dropped (a face they displaced under the rule does not come back).
+    ``drop_intersecting``: after the rule and before ``min_component``, every kept face that intersects another kept face
+    (``meshselfx``, DESIGN.md 4t) is dropped -- all of them together, in one pass -- and counted under ``intersecting``;
+    ``meshfill`` closes the holes this opens."""
     dev = meshin.default_device(device)
     check_weld_tol('clean_mesh', weld_tol)
     if int(max_rounds) < 1:
@@ -163,6 +170,11 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
             topology['orient_rounds'] = orient_rounds
         # canon is idempotent: on an oriented table it leaves every corner as it is
         fc, state, rounds = resolve_faces(fv, canon, V, manifold, max_rounds)
+        if drop_intersecting:
+            from . import meshselfx
+            hits, _, xcounts = meshselfx.search_device(pts, fc[:F], state[:F] if F else None)
+            # a state the compaction drops without counting it, as 4; only kept faces have hits
+            state = torch.where(hits > 0, torch.full_like(state, meshselfx.STATE_INTERSECTING), state)
         if min_component > 0:
             _, state, ccounts, topology['component_rounds'] = meshtopo.components_device(fc[:F], V, state[:F], min_component)
             tcounts.append(ccounts)
@@ -174,6 +186,11 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
             face_flip = face_flip[:F]
         if min_component > 0:
             topology['components'], topology['components_dropped'], topology['faces_dropped'] = host[-3:]
-    return CleanResult(p_out[:v_new], f_out[:f_new], vmap[:V], vsrc[:v_new], fmap[:f_new], canon[:V],
-                       {'welded': V - groups, 'degenerate': degenerate, 'nonmanifold': nonmanifold,
-                        'unreferenced': unreferenced, 'rounds': rounds}, topology, face_flip)
+        if drop_intersecting:
+            intersecting = dict(zip(meshselfx.COUNT_KEYS, L.read_i64(xcounts)))['faces_hit']
+    result = {'welded': V - groups, 'degenerate': degenerate, 'nonmanifold': nonmanifold, 'unreferenced': unreferenced,
+              'rounds': rounds}
+    if drop_intersecting:
+        result['intersecting'] = intersecting
+    return CleanResult(p_out[:v_new], f_out[:f_new], vmap[:V], vsrc[:v_new], fmap[:f_new], canon[:V], result, topology,
+                       face_flip)

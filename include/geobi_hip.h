@@ -1066,6 +1066,51 @@ int geobi_fill_emit(const int32_t* faces, const float* points, int64_t F, int64_
 int geobi_fill_points(const float* points, int64_t F, int64_t V, int64_t Vn, float* points_out, const void* ws,
                       size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- self-intersections (all pairs of faces) ----
+ * Which faces of ONE mesh pass through each other; no counterpart in the reference, which never asks.  All
+ * pairs, brute force: a float32 box test per pair, then an fp64 test in ONE stated order (no contraction) for the pairs
+ * whose boxes overlap; nothing depends on launch geometry: tests/selfx_model.py restates these rules in numpy and
+ * reproduces every output, and states the point-set definition in exact arithmetic beside them.
+ * verts [V, 3] float32, faces [F, 3] int32 in [0, V) (range-check them first; an id outside makes the face degenerate),
+ * state [F] int32 or NULL.  Adjacency is by INDEX: run it on a welded table (geobi_clean_weld, geobi_clean_faces).
+ *   included     state == NULL or state[f] == 1, the three ids distinct, and n = (b - a) x (c - a) != (0, 0, 0).  A face
+ *                that passes the state and fails one of the other two is counted as degenerate.
+ *   arithmetic   every coordinate difference is the fp64 difference of two float32 values; u x w = (uy * wz - uz * wy,
+ *                uz * wx - ux * wz, ux * wy - uy * wx); (u . w) = (ux * wx + uy * wy) + uz * wz; a decision is the sign of
+ *                the computed value.  For integer coordinates of magnitude <= 2^14 every value is exact (differences <=
+ *                2^15, products <= 2^30, cross components <= 2^31, dot products < 2^48) and so is the answer.
+ *   side(T, p)   ((t1 - t0) x (t2 - t0)) . (p - t0), the corners of T in the face row's own order.
+ *   axis(T)      of n = (t1 - t0) x (t2 - t0): 0, then 1 if |ny| > |nx|, then 2 if |nz| > the larger; a 2D point is the
+ *                other two coordinates in ascending axis order.  o2(a, b, c) = (bu - au) * (cv - av) - (bv - av) * (cu - au).
+ *   seg_tri(p, q, T)  the closed segment pq meets the closed triangle T.  dp = side(T, p), dq = side(T, q).  Both > 0 or
+ *                both < 0: no.  Both == 0 (coplanar), in 2D on axis(T): yes iff o2(t0, t1, p), o2(t1, t2, p), o2(t2, t0, p)
+ *                are all >= 0 or all <= 0, or pq meets one of the edges t0 t1, t1 t2, t2 t0: with o1 = o2(p, q, c), o2' =
+ *                o2(p, q, d), o3 = o2(c, d, p), o4 = o2(c, d, q) for the edge cd -- all four zero: yes iff the float32
+ *                boxes of pq and cd overlap (<=) in both 2D coordinates; else yes iff neither (o1, o2') nor (o3, o4) are
+ *                both > 0 or both < 0.  Otherwise, with d = q - p and u_i = t_i - p: s0 = d . (u0 x u1), s1 = d . (u1 x u2),
+ *                s2 = d . (u2 x u0); yes iff all >= 0 or all <= 0.
+ *   pair (a, b)  a < b both included, A and B their triangles, k = the number of vertex ids they share.
+ *                k = 0: no if side(A, b_i) are all > 0 or all < 0, no if side(B, a_i) are; else yes iff one of seg_tri(b0 b1,
+ *                A), (b1 b2, A), (b2 b0, A), (a0 a1, B), (a1 a2, B), (a2 a0, B).  k = 1, A's corner i and B's corner j the
+ *                shared one: seg_tri(a_{i+1} a_{i+2}, B) or seg_tri(b_{j+1} b_{j+2}, A), corners mod 3.  k = 2, pa and pb the
+ *                corners off the shared edge uv (u, v in A's cyclic order): side(A, pb) == 0 and, in 2D on axis(A),
+ *                o2(u, v, pa) and o2(u, v, pb) both > 0 or both < 0 (B folded flat onto A).  k = 3: never.
+ *                The pair is always evaluated as (lower face, higher face), whichever of the two is the query.
+ *   outputs      hits [F] int32: the number of faces a face intersects (0 for a face that is not included).  pairs
+ *                [max_pairs, 2] int32: the pairs (a < b) in ascending (a, b) order, the first max_pairs of them; the rows
+ *                beyond min(total, max_pairs) are not written; max_pairs == 0 takes pairs == NULL.  counts (device int64
+ *                [8]): [0] pairs, [1] pairs with k = 0, [2] k = 1, [3] k = 2, [4] faces with hits > 0, [5] degenerate,
+ *                [6] included, [7] box candidates: the pairs a < b, k < 3, whose boxes overlap (<=) -- what went to the
+ *                fp64 test.  The box of a face is the exact float32 min / max of its corners.
+ * F == 0 answers zeros and needs no workspace.  F, V <= GEOBI_MAX_NODES.  geobi_self_intersections_slices: the slices the
+ * target faces are cut into for F faces (the rule of geobi_nearest_slices), a pure host function; every output is the same
+ * for every slicing.                                                                                                      */
+int geobi_self_intersections_slices(int64_t F);
+size_t geobi_self_intersections_ws_bytes(int64_t F, int64_t V);
+int geobi_self_intersections(const float* verts, const int32_t* faces, const int32_t* state, int64_t V, int64_t F,
+                             int32_t* hits, int32_t* pairs, int64_t max_pairs, void* counts, void* ws, size_t ws_bytes,
+                             void* stream);
+
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
 int geobi_gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N,
