@@ -56,8 +56,12 @@ const char* geobi_last_error(void);
  * are dropped when drop_self != 0.  rowptr[N] is the number of kept edges; col / eid have E slots
  * (eid[k] = position of sorted edge k in the input COO).  Pairs with an id outside [0, N) are dropped
  * and counted in bad[0] (device int32, optional): they never reach a kernel as an index.
+ * The sort is stable: eid ascends within a run of equal pairs.  Beyond rowptr[N], col is -1 and eid lists the dropped
+ * pairs in input order, so eid as a whole is a permutation of 0 .. E-1.
  * geobi_csr_transpose: CSR of the reversed edges; pos_t[e'] = index of that edge in the input CSR,
- * inv_pos[e] = index of input edge e in the transposed CSR (either may be NULL... pos_t may not). */
+ * inv_pos[e] = index of input edge e in the transposed CSR (inv_pos may be NULL, pos_t may not).  The valid edge count is
+ * read on the device (rowptr[N], which must not exceed Ecap, the length of col / col_t / pos_t); equal edges keep their
+ * input order; col_t and pos_t are -1 in [rowptr[N], Ecap) and inv_pos is written only below rowptr[N]. */
 size_t geobi_csr_ws_bytes(int64_t E, int64_t N);
 int geobi_csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_t N, int drop_self,
                        int32_t* rowptr, int32_t* col, int32_t* eid, int32_t* bad, void* ws, size_t ws_bytes,
@@ -66,7 +70,8 @@ int geobi_csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, in
                         int32_t* col_t, int32_t* pos_t, int32_t* inv_pos, void* ws, size_t ws_bytes, void* stream);
 /* geobi_csr_reverse_index: for a (row, col)-sorted CSR, pos_rev[e] = position of the reverse of edge e
  * (or -1, with flag[0] |= 1, when it is missing; flag is zeroed first and may be NULL when the caller
- * already knows the graph is symmetric).  For a symmetric graph (every mesh graph of the
+ * already knows the graph is symmetric).  Where the reverse edge is listed several times it is the FIRST of that run, for
+ * every copy of e: on a multigraph pos_rev is no permutation.  For a symmetric graph (every mesh graph of the
  * path, and every pooled graph derived from one) the transposed CSR equals the CSR and pos_rev is the
  * edge correspondence -- no second sort. */
 int geobi_csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int32_t* col, int64_t E,

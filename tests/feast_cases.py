@@ -74,8 +74,28 @@ def ring_graph(n):
     return torch.stack([key // n, key % n], 0)
 
 
+MULTI_N, MULTI_PAIRS, MULTI_TWICE = 37, 90, 30
+
+
+@functools.lru_cache(maxsize=None)
+def _multi():
+    pairs = torch.combinations(torch.arange(MULTI_N))                                   # all 666 pairs u < v
+    pick = pairs[torch.randperm(pairs.shape[0], generator=torch.Generator().manual_seed(37))[:MULTI_PAIRS]]
+    und = torch.cat([pick, pick[:MULTI_TWICE]]).t()
+    return torch.cat([und, und.flip(0)], 1).contiguous()
+
+
+def multi_graph():
+    """The symmetric MULTIgraph a face list gives before coalescing: 90 random pairs on 37 nodes, the first 30 listed
+    twice, both directions of each (240 entries, no self loops).  On it the reverse-edge index is no permutation."""
+    return _multi().clone()
+
+
 def graph_of_name(name):
-    """'ladder', 'ladder_rev' (every edge flipped) or 'ring<n>' -> (edge_index, N, info)"""
+    """'ladder', 'ladder_rev' (every edge flipped), 'multi37' or 'ring<n>' -> (edge_index, N, info)"""
+    if name == 'multi37':
+        ei = multi_graph()
+        return ei, MULTI_N, GraphInfo(ei, MULTI_N)
     if name == 'ladder':
         return ladder_graph()
     if name == 'ladder_rev':
@@ -177,10 +197,12 @@ def run_oracle_fp32(name, Cin, Cout, slope, seed=None):
     return _oracle(name, Cin, Cout, slope, seed_of(Cin, Cout) if seed is None else seed, torch.float32)
 
 
-def run_gpu(dev, name, Cin, Cout, slope, split, fused=True, seed=None):
+def run_gpu(dev, name, Cin, Cout, slope, split, fused=True, seed=None, transpose=False):
     """The HIP path on the numbers of run_oracle(name, ...), tensors returned on the host.
     fused=True: aggregation + node transform in one kernel on 16-node tiles; fused=32: the same kernels on 32-node tiles
-    (geobi_set_tile_rows); fused=False: separate aggregation and GEMM kernels (ops.FUSED = False)."""
+    (geobi_set_tile_rows); fused=False: separate aggregation and GEMM kernels (ops.FUSED = False).
+    transpose=True (a symmetric graph): Graph.symmetric is forced to False before ensure_in(), so the in-CSR and pos_in come
+    from geobi_csr_transpose instead of geobi_csr_reverse_index."""
     import torch.cuda                                    # noqa: F401
     from geobi_gnn_amd import ops, _lib as lib
     from geobi_gnn_amd.feast_conv import FeaStConv
@@ -194,6 +216,13 @@ def run_gpu(dev, name, Cin, Cout, slope, split, fused=True, seed=None):
         conv = FeaStConv(Cin, Cout, 9).to(dev)
         conv.load_state_dict(params)
         eid = ei.to(dev)
+        if transpose:
+            from geobi_gnn_amd.graph import graph_of
+            g = graph_of(eid, n)                         # cached on eid: the layer finds this graph
+            assert g.symmetric
+            g.symmetric, g.rowptr_in, g.col_in, g.pos_in = False, None, None, None
+            g.ensure_in()
+            assert g.rowptr_in is not g.rowptr_out
         if split:
             xa = x[:, :Cin // 2].contiguous().to(dev).requires_grad_(True)
             xb = x[:, Cin // 2:].contiguous().to(dev).requires_grad_(True)
