@@ -63,8 +63,31 @@ struct BranchTape {
   Level L[3];
   ConvSave conv[8];
   PoolSave pool[2];
-  int Cin = 0;
 };
+
+// The channel plan of a branch's eight FeaSt layers (GNNModule, network.py:270-300): input width, output width, level.
+// Layer 0 reads the branch's own Cin.
+struct LayerPlan { int cin, cout, lvl; };
+constexpr LayerPlan kPlan[8] = {{0, 32, 0}, {32, 64, 1}, {64, 128, 2}, {128, 128, 2}, {128, 64, 1}, {128, 64, 1}, {64, 32, 0}, {64, 32, 0}};
+constexpr int plan_cin(int i, int Cin) { return i == 0 ? Cin : kPlan[i].cin; }
+
+// Everything the backward takes from the arena (carve_branch_bwd / carve_net_bwd below).  The training forward carves it
+// right behind its own records; the backward allocates nothing.
+struct BranchBwd {
+  // gradients of the layer outputs and inputs, named after the forward's tensors.  g_x1 and g_x0 hold a skip connection's
+  // sum while other layers run; they come last, so that a buffer carved too narrow in front of them runs into live data
+  float *g_r3, *g_up1, *g_x1b, *g_r1, *g_up2, *g_x2, *g_x2a, *g_x2p, *g_x1, *g_x1p, *g_x0;
+  float* pool_tmp[2][2];                  // mean pooling only: per pooling layer the step gradients [R1, C] and [P, C]
+  SubWs ws[8];                            // one FeaSt backward workspace per layer
+};
+struct NetBwd {
+  float *g_feat_f, *g_xf12, *corner, *g_vsum, *g_feat_v;
+  float* zeros;                           // stands in for a missing upstream gradient
+  size_t zeros_floats;
+  BranchBwd f, v;
+  SubWs ws_hf, ws_hv;                     // the two heads' workspaces
+};
+
 struct NetTape {
   geobi_net_params_t prm;
   BranchTape v, f;
@@ -72,8 +95,7 @@ struct NetTape {
   const float *x_v = nullptr, *dd = nullptr;
   const int32_t* fv = nullptr;
   float *feat_v = nullptr, *feat_f = nullptr, *raw_v = nullptr, *raw_f = nullptr, *verts = nullptr;
-  char* arena = nullptr;
-  size_t arena_bytes = 0, fwd_peak = 0;
+  NetBwd bwd{};
   int side_low = 0;                       // weight-gradient side stream at the lowest priority whatever the batch size
 };
 
@@ -315,7 +337,7 @@ int unpool_rows(Bump& b, const float* x, const int32_t* idx, int C, int64_t n, f
   return 0;
 }
 
-// GNNModule.forward (network.py:270-300): channel plan Cin -> 32 | 64 | 128, 128 | 64, 64 | 32, 32
+// GNNModule.forward (network.py:270-300): channel plan Cin -> 32 | 64 | 128, 128 | 64, 64 | 32, 32 (kPlan)
 int gnn_forward(Bump& b, const Level& L0, const float* x_in, int Cin, const geobi_gnn_params_t& p, int pool_mean,
                 float** feat, geobi_branch_out_t& bo, BranchTape* tape, hipStream_t s) {
   float *x0, *x1, *x2a, *x2, *up2, *r1, *x1b, *up1, *r3, *out;
@@ -323,16 +345,15 @@ int gnn_forward(Bump& b, const Level& L0, const float* x_in, int Cin, const geob
   Level L1s, L2s;
   // levels referenced by the saved records must outlive this call: they live in the tape when there is one
   Level& L0r = tape ? tape->L[0] : const_cast<Level&>(L0);
-  if (tape) { tape->L[0] = L0; tape->Cin = Cin; }
+  if (tape) tape->L[0] = L0;
   auto cs = [&](int i) { return tape ? &tape->conv[i] : nullptr; };
   // the packed weights of the branch's eight layers, one launch (training: every form, kept for the backward;
   // inference: the forward forms)
-  const int plan[8][2] = {{Cin, 32}, {32, 64}, {64, 128}, {128, 128}, {128, 64}, {128, 64}, {64, 32}, {64, 32}};
   float* pk[8];
   {
     FusedPackItem items[8];
     for (int i = 0; i < 8; ++i) {
-      const int ci = plan[i][0], co = plan[i][1];
+      const int ci = plan_cin(i, Cin), co = kPlan[i].cout;
       pk[i] = b.take<float>(tape ? feast_wpack_floats(ci, co) : feast_fused_fwd_pack_floats(ci, co));
       if (!b.ok) return kArenaFull;
       items[i].lin_w = p.conv[i].lin_w; items[i].u_w = p.conv[i].u_w; items[i].c = p.conv[i].c;
@@ -381,30 +402,53 @@ __global__ void add_inplace_kernel(float* __restrict__ a, const float* __restric
   if (i < n) a[i] += bsrc[i];
 }
 
+// The backward's buffers of one branch.  dx_in: the branch owes a gradient to its input (the facet branch: the geometry
+// coupling reads it; the vertex branch does not).  Each workspace is sized here and nowhere else.  Nothing is released:
+// the side stream may still read a layer's workspace (weight-gradient GEMMs, joined once at the end of the backward), so
+// scratch of consecutive layers must not alias -- the backward region is bump-only.
+BranchBwd carve_branch_bwd(Bump& b, const BranchTape& t, bool dx_in) {
+  auto g_in = [&](int i) { return b.take<float>((size_t)t.L[kPlan[i].lvl].N * kPlan[i].cin); };
+  auto g_out = [&](int i) { return b.take<float>((size_t)t.L[kPlan[i].lvl].N * kPlan[i].cout); };
+  BranchBwd w{g_out(6), g_in(6), g_out(5), g_out(4), g_in(4), g_out(3), g_out(2), g_in(2), g_out(1), g_in(1), g_out(0),
+              {}, {}};
+  for (int l = 0; l < 2 && t.pool[l].pool_mean; ++l) {
+    const PoolSave& p = t.pool[l];
+    w.pool_tmp[l][0] = b.take<float>((size_t)p.R1 * p.C);
+    w.pool_tmp[l][1] = b.take<float>((size_t)p.P * p.C);
+  }
+  for (int i = 0; i < 8; ++i) {
+    const ConvSave& c = t.conv[i];
+    const size_t bytes = feast_bwd_ws_bytes_for(c.g->N, c.g->E, c.Ca + c.Cb, c.Cb, c.Cout, i != 0 || dx_in);
+    w.ws[i] = {b.take<char>(bytes), bytes};
+  }
+  return w;
+}
+
+// Everything geobi_net_backward takes, for a recorded forward (the level sizes are known once it has run).  The zeros are
+// always set aside: the forward cannot know which upstream gradient will be missing.
+NetBwd carve_net_bwd(Bump& b, const NetTape& t) {
+  const size_t V = t.V, F = t.F, nz = (F > V ? F : V) * 3;
+  const size_t hws_f = head_bwd_ws_bytes(t.F, 32, 1024), hws_v = head_bwd_ws_bytes(t.V, 32, 1024);
+  return {b.take<float>(F * 32), b.take<float>(F * 12), b.take<float>(F * 9), b.take<float>(V * 3), b.take<float>(V * 32),
+          b.take<float>(nz), nz,
+          carve_branch_bwd(b, t.f, true), carve_branch_bwd(b, t.v, false),
+          {b.take<char>(hws_f), hws_f}, {b.take<char>(hws_v), hws_v}};
+}
+
 // Backward of one FeaStConv from its saved record; gradients w.r.t. the input halves go to dxa / dxb (nullable)
-int conv_bwd(Bump& b, const ConvSave& c, const geobi_conv_params_t& grad, const float* gout, float* dxa, float* dxb,
-             int accumulate, hipStream_t s) {
+int conv_bwd(const ConvSave& c, const geobi_conv_params_t& grad, const float* gout, float* dxa, float* dxb, int accumulate,
+             SubWs ws, hipStream_t s) {
   const Level& g = *c.g;
-  const size_t m = b.mark();
-  const size_t wsb = feast_bwd_ws_bytes_for(g.N, g.E, c.Ca + c.Cb, c.Cb, c.Cout, dxa != nullptr);
-  void* ws = b.take<char>(wsb);
-  if (!b.ok) return kArenaFull;
-  GEOBI_TRY(feast_bwd(c.xa, c.xb, c.Ca, c.Cb, g.N, g.E, g.rowptr, g.col, g.rowptr, g.col, g.pos_rev, c.p->lin_w, c.p->u_w,
-                      c.p->c, c.Cout, c.slope, c.out, gout, c.logits, nullptr, c.wf, dxa, dxb, (float*)grad.lin_w,
-                      (float*)grad.u_w, (float*)grad.c, (float*)grad.bias, accumulate, ws, wsb, s));
-  // the side stream may still read the workspace (weight-gradient GEMMs, joined once at the end of the backward):
-  // scratch of consecutive layers must not alias -> no release here; the backward region is bump-only
-  (void)m;
-  return 0;
+  return feast_bwd(c.xa, c.xb, c.Ca, c.Cb, g.N, g.E, g.rowptr, g.col, g.rowptr, g.col, g.pos_rev, c.p->lin_w, c.p->u_w,
+                   c.p->c, c.Cout, c.slope, c.out, gout, c.logits, nullptr, c.wf, dxa, dxb, (float*)grad.lin_w,
+                   (float*)grad.u_w, (float*)grad.c, (float*)grad.bias, accumulate, ws.p, ws.bytes, s);
 }
 
 // pooling backward: gradient of the pooled features [R2, C], ADDED to `acc` [P, C] (the gradient the layer input
-// already has from its skip connection)
-int pool_bwd(Bump& b, const PoolSave& p, const float* g2, float* acc, hipStream_t s) {
+// already has from its skip connection).  tmp: the layer's BranchBwd::pool_tmp
+int pool_bwd(const PoolSave& p, const float* g2, float* acc, float* const tmp[2], hipStream_t s) {
   if (!p.pool_mean) return segment_max2_bwd(g2, p.arg[1], p.unpool, p.C, p.R2, p.P, acc, 1, s);
-  float* g1 = b.take<float>((size_t)p.R1 * p.C);
-  float* g0 = b.take<float>((size_t)p.P * p.C);
-  if (!b.ok) return kArenaFull;
+  float *g1 = tmp[0], *g0 = tmp[1];
   GEOBI_TRY(segment_mean_bwd(g2, p.seg[1], p.segptr[1], p.C, p.R1, g1, s));
   GEOBI_TRY(segment_mean_bwd(g1, p.seg[0], p.segptr[0], p.C, p.P, g0, s));
   add_inplace_kernel<<<cdiv(p.P * p.C, 256), 256, 0, s>>>(acc, g0, p.P * p.C);
@@ -412,60 +456,27 @@ int pool_bwd(Bump& b, const PoolSave& p, const float* g2, float* acc, hipStream_
   return 0;
 }
 
-// GNNModule backward: g_out = gradient of the branch output [N0, 32]; dx_in (nullable) = gradient of its input
-int gnn_backward(Bump& b, const BranchTape& t, const geobi_gnn_params_t& grad, const float* g_out, float* dx_in,
+// GNNModule backward: g_out = gradient of the branch output [N0, 32]; dx_in (nullable, as the branch was carved) =
+// gradient of its input
+int gnn_backward(const BranchTape& t, const BranchBwd& w, const geobi_gnn_params_t& grad, const float* g_out, float* dx_in,
                  int accumulate, hipStream_t s) {
-  const int64_t N0 = t.L[0].N, N1 = t.L[1].N, N2 = t.L[2].N;
-  float* g_x0 = b.take<float>((size_t)N0 * 32);
-  float* g_r3 = b.take<float>((size_t)N0 * 32);
-  float* g_up1 = b.take<float>((size_t)N0 * 64);
-  float* g_x1b = b.take<float>((size_t)N1 * 64);
-  float* g_x1 = b.take<float>((size_t)N1 * 64);
-  float* g_r1 = b.take<float>((size_t)N1 * 64);
-  float* g_up2 = b.take<float>((size_t)N1 * 128);
-  float* g_x2 = b.take<float>((size_t)N2 * 128);
-  float* g_x2a = b.take<float>((size_t)N2 * 128);
-  float* g_x2p = b.take<float>((size_t)N2 * 64);
-  float* g_x1p = b.take<float>((size_t)N1 * 32);
-  if (!b.ok) return kArenaFull;
-  GEOBI_TRY(conv_bwd(b, t.conv[7], grad.conv[7], g_out, g_x0, g_r3, accumulate, s));
-  GEOBI_TRY(conv_bwd(b, t.conv[6], grad.conv[6], g_r3, g_up1, nullptr, accumulate, s));
+  const int64_t N1 = t.L[1].N, N2 = t.L[2].N;
+  GEOBI_TRY(conv_bwd(t.conv[7], grad.conv[7], g_out, w.g_x0, w.g_r3, accumulate, w.ws[7], s));
+  GEOBI_TRY(conv_bwd(t.conv[6], grad.conv[6], w.g_r3, w.g_up1, nullptr, accumulate, w.ws[6], s));
   // unpool backward: sums over the composed segments, walked through the two steps' lists (no composed list is built)
-  GEOBI_TRY(segment_sum2(g_up1, 64, t.pool[0].segptr[0], t.pool[0].members[0], t.pool[0].segptr[1], t.pool[0].members[1],
-                         N1, g_x1b, s));
-  GEOBI_TRY(conv_bwd(b, t.conv[5], grad.conv[5], g_x1b, g_x1, g_r1, accumulate, s));
-  GEOBI_TRY(conv_bwd(b, t.conv[4], grad.conv[4], g_r1, g_up2, nullptr, accumulate, s));
-  GEOBI_TRY(segment_sum2(g_up2, 128, t.pool[1].segptr[0], t.pool[1].members[0], t.pool[1].segptr[1], t.pool[1].members[1],
-                         N2, g_x2, s));
-  GEOBI_TRY(conv_bwd(b, t.conv[3], grad.conv[3], g_x2, g_x2a, nullptr, accumulate, s));
-  GEOBI_TRY(conv_bwd(b, t.conv[2], grad.conv[2], g_x2a, g_x2p, nullptr, accumulate, s));
-  GEOBI_TRY(pool_bwd(b, t.pool[1], g_x2p, g_x1, s));                  // skip (r_conv2) + pooling2 paths
-  GEOBI_TRY(conv_bwd(b, t.conv[1], grad.conv[1], g_x1, g_x1p, nullptr, accumulate, s));
-  GEOBI_TRY(pool_bwd(b, t.pool[0], g_x1p, g_x0, s));                  // skip (r_conv4) + pooling1 paths
-  GEOBI_TRY(conv_bwd(b, t.conv[0], grad.conv[0], g_x0, dx_in, nullptr, accumulate, s));
+  GEOBI_TRY(segment_sum2(w.g_up1, 64, t.pool[0].segptr[0], t.pool[0].members[0], t.pool[0].segptr[1], t.pool[0].members[1],
+                         N1, w.g_x1b, s));
+  GEOBI_TRY(conv_bwd(t.conv[5], grad.conv[5], w.g_x1b, w.g_x1, w.g_r1, accumulate, w.ws[5], s));
+  GEOBI_TRY(conv_bwd(t.conv[4], grad.conv[4], w.g_r1, w.g_up2, nullptr, accumulate, w.ws[4], s));
+  GEOBI_TRY(segment_sum2(w.g_up2, 128, t.pool[1].segptr[0], t.pool[1].members[0], t.pool[1].segptr[1], t.pool[1].members[1],
+                         N2, w.g_x2, s));
+  GEOBI_TRY(conv_bwd(t.conv[3], grad.conv[3], w.g_x2, w.g_x2a, nullptr, accumulate, w.ws[3], s));
+  GEOBI_TRY(conv_bwd(t.conv[2], grad.conv[2], w.g_x2a, w.g_x2p, nullptr, accumulate, w.ws[2], s));
+  GEOBI_TRY(pool_bwd(t.pool[1], w.g_x2p, w.g_x1, w.pool_tmp[1], s));            // skip (r_conv2) + pooling2 paths
+  GEOBI_TRY(conv_bwd(t.conv[1], grad.conv[1], w.g_x1, w.g_x1p, nullptr, accumulate, w.ws[1], s));
+  GEOBI_TRY(pool_bwd(t.pool[0], w.g_x1p, w.g_x0, w.pool_tmp[0], s));            // skip (r_conv4) + pooling1 paths
+  GEOBI_TRY(conv_bwd(t.conv[0], grad.conv[0], w.g_x0, dx_in, nullptr, accumulate, w.ws[0], s));
   return 0;
-}
-
-// Exact arena need of geobi_net_backward for a recorded forward (mirrors its allocations; the level sizes are known
-// once the forward has run, so the training forward can refuse an arena the backward would overflow)
-size_t branch_backward_bytes(const BranchTape& t) {
-  const int64_t N0 = t.L[0].N, N1 = t.L[1].N, N2 = t.L[2].N;
-  auto f = [](int64_t n) { return align_up((size_t)(n ? n : 1) * sizeof(float)); };
-  size_t b = f(N0 * 32) * 2 + f(N0 * 64) + f(N1 * 64) * 3 + f(N1 * 128) + f(N2 * 128) * 2 + f(N2 * 64) + f(N1 * 32);
-  for (int i = 0; i < 8; ++i) {
-    const ConvSave& c = t.conv[i];
-    // (the first layer may or may not owe an input gradient: without one its workspace is the larger)
-    b += align_up(feast_bwd_ws_bytes_for(c.g->N, c.g->E, c.Ca + c.Cb, c.Cb, c.Cout, i != 0));
-  }
-  for (int l = 0; l < 2; ++l) b += f(t.pool[l].R1 * t.pool[l].C) + f(t.pool[l].P * t.pool[l].C);
-  return b;
-}
-size_t net_backward_bytes(const NetTape& t) {
-  auto f = [](int64_t n) { return align_up((size_t)(n ? n : 1) * sizeof(float)); };
-  const int64_t V = t.V, F = t.F;
-  return f(F * 32) + f(F * 12) + f(F * 9) + f(V * 3) + f(V * 32) + f((F > V ? F : V) * 3) +
-         align_up(head_bwd_ws_bytes(F, 32, 1024)) + align_up(head_bwd_ws_bytes(V, 32, 1024)) + branch_backward_bytes(t.v) +
-         branch_backward_bytes(t.f) + 4096;
 }
 
 int net_forward_impl(const geobi_net_params_t* prm, const geobi_level0_t* gv, const geobi_level0_t* gf, const float* x_v,
@@ -505,6 +516,44 @@ int net_forward_impl(const geobi_net_params_t* prm, const geobi_level0_t* gv, co
   return 0;
 }
 
+// The record of a training forward: a fresh tape, the forward, the caller's own takes (`own_takes(Bump&, const NetTape&)`:
+// a mesh group's loss buffers), the backward's carve behind them.  Bump keeps counting past its capacity, so
+// out->used_bytes is the exact forward + backward need of this mesh whether or not it fits; an arena that does not hold it
+// is refused here, before anything of the backward is enqueued.  `tape` is empty on failure.
+template <typename OwnTakes>
+int record_train(const char* fn, const char* for_what, const geobi_net_params_t* prm, const geobi_level0_t* gv,
+                 const geobi_level0_t* gf, const int32_t* pos_rev_v, const int32_t* pos_rev_f, const float* x_v,
+                 const float* x_f, const int32_t* fv, const float* depth_direction, void* arena, size_t arena_bytes,
+                 geobi_net_out_t* out, std::unique_ptr<NetTape>& tape, OwnTakes&& own_takes, hipStream_t s) {
+  tape.reset(new NetTape());
+  tape->prm = *prm;
+  Bump b(arena, arena_bytes);
+  int rc = net_forward_impl(prm, gv, gf, x_v, x_f, fv, depth_direction, pos_rev_v, pos_rev_f, b, out, tape.get(), s);
+  out->used_bytes = (int64_t)b.peak;
+  if (rc == kArenaFull) set_error("%s: arena too small (%zu bytes needed so far, %zu given)", fn, b.peak, arena_bytes);
+  if (rc == 0) {
+    own_takes(b, *tape);
+    tape->bwd = carve_net_bwd(b, *tape);
+    out->used_bytes = (int64_t)b.peak;            // forward + backward: what an arena for this mesh must hold
+    if (!b.ok) {
+      set_error("%s: arena too small%s (%zu bytes needed, %zu given)", fn, for_what, b.peak, arena_bytes);
+      rc = kArenaFull;
+    }
+  }
+  if (rc != 0) tape.reset();
+  return rc;
+}
+
+// The level-0 sizes every entry point accepts; group >= 0: the wording of geobi_net_train_groups
+int check_level0(const char* fn, const geobi_level0_t* gv, const geobi_level0_t* gf, int group = -1) {
+  if (gv->N <= GEOBI_MAX_NODES && gf->N <= GEOBI_MAX_NODES && gv->E <= GEOBI_MAX_EDGES && gf->E <= GEOBI_MAX_EDGES && gv->N >= 0 &&
+      gf->N >= 0 && gv->E >= 0 && gf->E >= 0)
+    return 0;
+  if (group >= 0) return set_error("%s: group %d: level-0 sizes outside GEOBI_MAX_NODES / GEOBI_MAX_EDGES", fn, group);
+  return set_error("%s: level-0 sizes outside [0, GEOBI_MAX_NODES = %d] nodes / [0, GEOBI_MAX_EDGES = %d] edges (split the mesh into patches)",
+                   fn, GEOBI_MAX_NODES, GEOBI_MAX_EDGES);
+}
+
 }  // namespace
 
 }  // namespace geobi
@@ -527,10 +576,7 @@ extern "C" int geobi_net_forward(const geobi_net_params_t* prm, const geobi_leve
                                  void* arena, size_t arena_bytes, geobi_net_out_t* out, void* stream) {
   if (!prm || !gv || !gf || !x_v || !x_f || !fv || !arena || !out) return set_error("geobi_net_forward: null argument");
   if (prm->force_depth && !depth_direction) return set_error("geobi_net_forward: force_depth needs depth_direction");
-  if (gv->N > GEOBI_MAX_NODES || gf->N > GEOBI_MAX_NODES || gv->E > GEOBI_MAX_EDGES || gf->E > GEOBI_MAX_EDGES || gv->N < 0 ||
-      gf->N < 0 || gv->E < 0 || gf->E < 0)
-    return set_error("geobi_net_forward: level-0 sizes outside [0, GEOBI_MAX_NODES = %d] nodes / [0, GEOBI_MAX_EDGES = %d] edges (split the mesh into patches)",
-                     GEOBI_MAX_NODES, GEOBI_MAX_EDGES);
+  GEOBI_TRY(check_level0("geobi_net_forward", gv, gf));
   Bump b(arena, arena_bytes);
   int rc = net_forward_impl(prm, gv, gf, x_v, x_f, fv, depth_direction, nullptr, nullptr, b, out, nullptr, (hipStream_t)stream);
   out->used_bytes = (int64_t)b.peak;
@@ -543,12 +589,11 @@ extern "C" size_t geobi_net_train_arena_bytes(int64_t V, int64_t Ev, int64_t F, 
   // may still read it), bounded by the level-0 sizes
   auto branch = [](int64_t N, int64_t E) {
     size_t w = 0;
-    const int cin[8] = {12, 32, 64, 128, 128, 128, 64, 64}, cout[8] = {32, 64, 128, 128, 64, 64, 32, 32};
-    const int lvl[8] = {0, 1, 2, 2, 1, 1, 0, 0};
     for (int i = 0; i < 8; ++i) {
-      const int64_t n = lvl[i] == 0 ? N : (lvl[i] == 1 ? (N * 2) / 5 : N / 8);          // typical level sizes + margin
-      const int64_t e = lvl[i] == 0 ? E : (lvl[i] == 1 ? (E * 2) / 5 : E / 8);
-      w += feast_bwd_ws_bytes(n, e, cin[i], cout[i]);
+      const int lvl = kPlan[i].lvl;
+      const int64_t n = lvl == 0 ? N : (lvl == 1 ? (N * 2) / 5 : N / 8);          // typical level sizes + margin
+      const int64_t e = lvl == 0 ? E : (lvl == 1 ? (E * 2) / 5 : E / 8);
+      w += feast_bwd_ws_bytes(n, e, plan_cin(i, 12), kPlan[i].cout);         // (the wider first layer for both branches)
     }
     return w + (size_t)N * 4 * 1024;
   };
@@ -556,8 +601,9 @@ extern "C" size_t geobi_net_train_arena_bytes(int64_t V, int64_t Ev, int64_t F, 
          head_bwd_ws_bytes(F, 32, 1024) + ((size_t)64 << 20);
 }
 
-// Training forward: as geobi_net_forward, but everything the backward needs stays in the arena and a host-side
-// record of it is returned as `*handle` (release with geobi_net_release; the arena must outlive the backward).
+// Training forward: as geobi_net_forward, but everything the backward needs stays in the arena, the backward's own
+// buffers are set aside behind it (out->used_bytes: the exact forward + backward need) and a host-side record of both is
+// returned as `*handle` (release with geobi_net_release; the arena must outlive the backward).
 extern "C" int geobi_net_forward_train(const geobi_net_params_t* prm, const geobi_level0_t* gv, const geobi_level0_t* gf,
                                        const int32_t* pos_rev_v, const int32_t* pos_rev_f, const float* x_v,
                                        const float* x_f, const int32_t* fv, const float* depth_direction, void* arena,
@@ -565,33 +611,13 @@ extern "C" int geobi_net_forward_train(const geobi_net_params_t* prm, const geob
   if (!prm || !gv || !gf || !pos_rev_v || !pos_rev_f || !x_v || !x_f || !fv || !arena || !out || !handle)
     return set_error("geobi_net_forward_train: null argument");
   if (prm->force_depth && !depth_direction) return set_error("geobi_net_forward_train: force_depth needs depth_direction");
-  if (gv->N > GEOBI_MAX_NODES || gf->N > GEOBI_MAX_NODES || gv->E > GEOBI_MAX_EDGES || gf->E > GEOBI_MAX_EDGES || gv->N < 0 ||
-      gf->N < 0 || gv->E < 0 || gf->E < 0)
-    return set_error("geobi_net_forward_train: level-0 sizes outside [0, GEOBI_MAX_NODES = %d] nodes / [0, GEOBI_MAX_EDGES = %d] edges (split the mesh into patches)",
-                     GEOBI_MAX_NODES, GEOBI_MAX_EDGES);
-  NetTape* tape = new NetTape();
-  tape->prm = *prm;
-  tape->arena = (char*)arena; tape->arena_bytes = arena_bytes;
-  Bump b(arena, arena_bytes);
-  int rc = net_forward_impl(prm, gv, gf, x_v, x_f, fv, depth_direction, pos_rev_v, pos_rev_f, b, out, tape, (hipStream_t)stream);
-  out->used_bytes = (int64_t)b.peak;
-  if (rc != 0) {
-    if (rc == kArenaFull) set_error("geobi_net_forward_train: arena too small (%zu bytes needed so far, %zu given)", b.peak, arena_bytes);
-    delete tape;
-    *handle = 0;
-    return rc;
-  }
-  tape->fwd_peak = b.off;
-  const size_t need = align_up(b.off) + net_backward_bytes(*tape);
-  out->used_bytes = (int64_t)need;              // forward + backward: what an arena for this mesh must hold
-  if (need > arena_bytes) {
-    set_error("geobi_net_forward_train: arena too small for the backward (%zu bytes needed, %zu given)", need, arena_bytes);
-    delete tape;
-    *handle = 0;
-    return kArenaFull;
-  }
-  *handle = (int64_t)(intptr_t)tape;
-  return 0;
+  GEOBI_TRY(check_level0("geobi_net_forward_train", gv, gf));
+  std::unique_ptr<NetTape> tape;
+  const int rc = record_train("geobi_net_forward_train", " for the backward", prm, gv, gf, pos_rev_v, pos_rev_f, x_v, x_f, fv,
+                              depth_direction, arena, arena_bytes, out, tape, [](Bump&, const NetTape&) {},
+                              (hipStream_t)stream);
+  *handle = (int64_t)(intptr_t)tape.release();
+  return rc;
 }
 
 extern "C" int geobi_net_release(int64_t handle) {
@@ -605,45 +631,31 @@ namespace {
 // geobi_net_backward_facet_events: where the NEXT backward of this host thread marks "the facet branch's gradients are final"
 thread_local hipEvent_t g_facet_ev_main = nullptr, g_facet_ev_side = nullptr;
 
-// Backward of a recorded forward from arena offset `start` on (geobi_net_backward: right behind the forward's records;
-// a mesh group of geobi_net_train_groups: behind its loss buffers as well).
-int net_backward_impl(NetTape* t, size_t start, const float* g_verts, const float* g_normals, const geobi_net_params_t* grads,
+// Backward of a recorded forward, in the buffers the forward's record set aside (NetTape::bwd): nothing is allocated here
+int net_backward_impl(NetTape* t, const float* g_verts, const float* g_normals, const geobi_net_params_t* grads,
                       int accumulate, const int32_t* corner_segptr, const int32_t* corner_members, hipStream_t s) {
   void* stream = (void*)s;
-  Bump b(t->arena, t->arena_bytes);
-  b.off = b.peak = start;
   const geobi_net_params_t& P = t->prm;
   const geobi_net_params_t& G = *grads;
+  const NetBwd& w = t->bwd;
   const int64_t V = t->V, F = t->F;
   const int nout_v = P.force_depth ? 1 : 3;
-  float* g_feat_f = b.take<float>((size_t)F * 32);
-  float* g_xf12 = b.take<float>((size_t)F * 12);
-  float* corner = b.take<float>((size_t)F * 9);
-  float* g_vsum = b.take<float>((size_t)V * 3);
-  float* g_feat_v = b.take<float>((size_t)V * 32);
-  float* zeros = nullptr;
-  if (!g_normals || !g_verts) zeros = b.take<float>((size_t)(F > V ? F : V) * 3);
-  const size_t hws_f = head_bwd_ws_bytes(F, 32, 1024), hws_v = head_bwd_ws_bytes(V, 32, 1024);
-  void* ws_hf = b.take<char>(hws_f);
-  void* ws_hv = b.take<char>(hws_v);
   auto fail = [&](int rc) {
     (void)geobi_side_defer(0);
     (void)geobi_side_join(stream);
     side_select(0);
-    if (rc == kArenaFull) set_error("geobi_net_backward: arena too small (%zu bytes needed so far, %zu given)", b.peak, t->arena_bytes);
     return rc;
   };
-  if (!b.ok) return fail(kArenaFull);
-  if (zeros) GEOBI_HIP(hipMemsetAsync(zeros, 0, (size_t)(F > V ? F : V) * 3 * sizeof(float), s));
+  if (!g_normals || !g_verts) GEOBI_HIP(hipMemsetAsync(w.zeros, 0, w.zeros_floats * sizeof(float), s));
   // weight-gradient GEMMs of every layer run on the side stream and are joined once, at the end; from ~80 k level-0 nodes
   // on (device-bound batches) on the lowest-priority one
   side_select(V + F >= 80000 || t->side_low);
   (void)geobi_side_defer(1);
   int rc = head_bwd(t->feat_f, 32, F, P.fc_f1_w, P.fc_f1_b, 1024, P.fc_f2_w, 3, kLeak, 1, nullptr, nullptr, t->raw_f,
-                    g_normals ? g_normals : zeros, g_feat_f, (float*)G.fc_f1_w, (float*)G.fc_f1_b, (float*)G.fc_f2_w,
-                    (float*)G.fc_f2_b, accumulate, ws_hf, hws_f, s);
+                    g_normals ? g_normals : w.zeros, w.g_feat_f, (float*)G.fc_f1_w, (float*)G.fc_f1_b, (float*)G.fc_f2_w,
+                    (float*)G.fc_f2_b, accumulate, w.ws_hf.p, w.ws_hf.bytes, s);
   if (rc) return fail(rc);
-  rc = gnn_backward(b, t->f, G.gnn_f, g_feat_f, g_xf12, accumulate, s);
+  rc = gnn_backward(t->f, w.f, G.gnn_f, w.g_feat_f, w.g_xf12, accumulate, s);
   if (rc) return fail(rc);
   if (g_facet_ev_main) {
     // every gradient of gnn_f / fc_f1 / fc_f2 is enqueued by now: the main stream's share up to here, the weight-gradient
@@ -656,19 +668,19 @@ int net_backward_impl(NetTape* t, size_t start, const float* g_verts, const floa
     if (es && hipEventRecord(es, side ? side : s) != hipSuccess) return fail(set_error("geobi_net_backward: facet event"));
   }
   // geometry coupling: d[x_f | centroid | normal] -> per-corner gradients -> vertices (fixed-order segment sum)
-  rc = face_geom_bwd(t->verts, t->fv, g_xf12, F, corner, s);
+  rc = face_geom_bwd(t->verts, t->fv, w.g_xf12, F, w.corner, s);
   if (rc) return fail(rc);
-  rc = segment_sum(corner, 3, corner_segptr, corner_members, V, 0, g_vsum, s);
+  rc = segment_sum(w.corner, 3, corner_segptr, corner_members, V, 0, w.g_vsum, s);
   if (rc) return fail(rc);
   if (g_verts) {
-    add_inplace_kernel<<<cdiv(V * 3, 256), 256, 0, s>>>(g_vsum, g_verts, V * 3);
+    add_inplace_kernel<<<cdiv(V * 3, 256), 256, 0, s>>>(w.g_vsum, g_verts, V * 3);
     if (hipGetLastError() != hipSuccess) return fail(set_error("geobi_net_backward: launch failed"));
   }
-  rc = head_bwd(t->feat_v, 32, V, P.fc_v1_w, P.fc_v1_b, 1024, P.fc_v2_w, nout_v, kLeak, 0, t->dd, nullptr, t->raw_v, g_vsum,
-                g_feat_v, (float*)G.fc_v1_w, (float*)G.fc_v1_b, (float*)G.fc_v2_w, (float*)G.fc_v2_b, accumulate, ws_hv,
-                hws_v, s);
+  rc = head_bwd(t->feat_v, 32, V, P.fc_v1_w, P.fc_v1_b, 1024, P.fc_v2_w, nout_v, kLeak, 0, t->dd, nullptr, t->raw_v,
+                w.g_vsum, w.g_feat_v, (float*)G.fc_v1_w, (float*)G.fc_v1_b, (float*)G.fc_v2_w, (float*)G.fc_v2_b, accumulate,
+                w.ws_hv.p, w.ws_hv.bytes, s);
   if (rc) return fail(rc);
-  rc = gnn_backward(b, t->v, G.gnn_v, g_feat_v, nullptr, accumulate, s);
+  rc = gnn_backward(t->v, w.v, G.gnn_v, w.g_feat_v, nullptr, accumulate, s);
   if (rc) return fail(rc);
   (void)geobi_side_defer(0);
   rc = geobi_side_join(stream);
@@ -751,40 +763,29 @@ int run_group(const geobi_net_params_t* prm, geobi_train_group_t* g, int kind_v,
   hipStream_t s = (hipStream_t)g->stream;
   if (start) GEOBI_HIP(hipStreamWaitEvent(s, start, 0));
   if (g->grad_flat && g->grad_count > 0) GEOBI_HIP(hipMemsetAsync(g->grad_flat, 0, (size_t)g->grad_count * sizeof(float), s));
-  std::unique_ptr<NetTape> tape(new NetTape());
-  tape->prm = *prm;
-  tape->arena = (char*)g->arena; tape->arena_bytes = g->arena_bytes;
-  Bump b(g->arena, g->arena_bytes);
-  int rc = net_forward_impl(prm, g->gv, g->gf, g->x_v, g->x_f, g->fv, g->depth_direction, g->pos_rev_v, g->pos_rev_f, b,
-                            &g->out, tape.get(), s);
-  g->out.used_bytes = (int64_t)b.peak;
-  if (rc != 0) {
-    if (rc == kArenaFull) set_error("geobi_net_train_groups: arena too small (%zu bytes needed so far, %zu given)", b.peak, g->arena_bytes);
-    return rc;
-  }
+  // loss (network.py:364-389, dual_loss :392-396) and its gradient with respect to the two predictions: its buffers lie
+  // between the forward's records and the backward's
+  float *g_verts = nullptr, *g_normals = nullptr;
+  SubWs ws_lv{}, ws_lf{};
+  auto loss_takes = [&](Bump& b, const NetTape& t) {
+    g_verts = b.take<float>((size_t)t.V * 3);
+    g_normals = b.take<float>((size_t)t.F * 3);
+    const size_t lws_v = row_loss_ws_bytes(t.V), lws_f = row_loss_ws_bytes(t.F);
+    ws_lv = {b.take<char>(lws_v), lws_v};
+    ws_lf = {b.take<char>(lws_f), lws_f};
+  };
+  std::unique_ptr<NetTape> tape;
+  GEOBI_TRY(record_train("geobi_net_train_groups", "", prm, g->gv, g->gf, g->pos_rev_v, g->pos_rev_f, g->x_v, g->x_f, g->fv,
+                         g->depth_direction, g->arena, g->arena_bytes, &g->out, tape, loss_takes, s));
   const int64_t V = tape->V, F = tape->F;
-  // loss (network.py:364-389, dual_loss :392-396) and its gradient with respect to the two predictions
-  float* g_verts = b.take<float>((size_t)V * 3);
-  float* g_normals = b.take<float>((size_t)F * 3);
-  const size_t lws_v = row_loss_ws_bytes(V), lws_f = row_loss_ws_bytes(F);
-  void* ws_lv = b.take<char>(lws_v);
-  void* ws_lf = b.take<char>(lws_f);
-  tape->fwd_peak = b.off;
-  const size_t need = align_up(b.off) + net_backward_bytes(*tape);
-  g->out.used_bytes = (int64_t)need;
-  if (!b.ok || need > g->arena_bytes) {
-    set_error("geobi_net_train_groups: arena too small (%zu bytes needed, %zu given)", need, g->arena_bytes);
-    return kArenaFull;
-  }
   const float* verts = (const float*)((const char*)g->arena + g->out.verts_off);
   const float* normals = (const float*)((const char*)g->arena + g->out.normals_off);
   const float sv = g->w_v ? g->scale_v : g->scale_v / (float)V, sn = g->w_f ? g->scale_n : g->scale_n / (float)F;
-  GEOBI_TRY(row_loss_fwd(verts, g->y_v, g->w_v, V, kind_v, sv, g->losses, ws_lv, lws_v, s));
-  GEOBI_TRY(row_loss_fwd(normals, g->y_f, g->w_f, F, kind_n, sn, g->losses + 1, ws_lf, lws_f, s));
+  GEOBI_TRY(row_loss_fwd(verts, g->y_v, g->w_v, V, kind_v, sv, g->losses, ws_lv.p, ws_lv.bytes, s));
+  GEOBI_TRY(row_loss_fwd(normals, g->y_f, g->w_f, F, kind_n, sn, g->losses + 1, ws_lf.p, ws_lf.bytes, s));
   GEOBI_TRY(row_loss_bwd(verts, g->y_v, g->w_v, nullptr, V, kind_v, sv, g_verts, s));
   GEOBI_TRY(row_loss_bwd(normals, g->y_f, g->w_f, nullptr, F, kind_n, sn, g_normals, s));
-  GEOBI_TRY(net_backward_impl(tape.get(), tape->fwd_peak, g_verts, g_normals, &g->grads, 1, g->corner_segptr,
-                              g->corner_members, s));
+  GEOBI_TRY(net_backward_impl(tape.get(), g_verts, g_normals, &g->grads, 1, g->corner_segptr, g->corner_members, s));
   if (done) GEOBI_HIP(hipEventRecord(done, s));
   return 0;
 }
@@ -798,14 +799,13 @@ using namespace geobi;
 // Backward of a recorded forward.  g_verts [V,3] / g_normals [F,3] (either may be NULL = zero); `grads` mirrors the
 // parameter struct (same order) and receives (accumulate != 0: is added) the parameter gradients.  corner_segptr /
 // corner_members: vertex -> corner inverse lists of the face table (the geometry coupling's gradient is summed through
-// them in a fixed order).  Scratch is taken from the rest of the forward's arena.
+// them in a fixed order).  Every buffer it uses was set aside in the arena by the training forward.
 extern "C" int geobi_net_backward(int64_t handle, const float* g_verts, const float* g_normals,
                                   const geobi_net_params_t* grads, int accumulate, const int32_t* corner_segptr,
                                   const int32_t* corner_members, void* stream) {
   NetTape* t = (NetTape*)(intptr_t)handle;
   if (!t || !grads || !corner_segptr || !corner_members) return set_error("geobi_net_backward: null argument");
-  return net_backward_impl(t, t->fwd_peak, g_verts, g_normals, grads, accumulate, corner_segptr, corner_members,
-                           (hipStream_t)stream);
+  return net_backward_impl(t, g_verts, g_normals, grads, accumulate, corner_segptr, corner_members, (hipStream_t)stream);
 }
 
 extern "C" int geobi_net_backward_facet_events(void* ev_main, void* ev_side) {
@@ -844,9 +844,7 @@ extern "C" int geobi_net_train_groups(const geobi_net_params_t* prm, geobi_train
     if (!g.gv || !g.gf || !g.pos_rev_v || !g.pos_rev_f || !g.x_v || !g.x_f || !g.fv || !g.y_v || !g.y_f ||
         !g.corner_segptr || !g.corner_members || !g.arena || !g.losses || !g.stream)
       return set_error("geobi_net_train_groups: null field in group %d (a group needs its OWN stream, not the null stream)", k);
-    if (g.gv->N > GEOBI_MAX_NODES || g.gf->N > GEOBI_MAX_NODES || g.gv->E > GEOBI_MAX_EDGES || g.gf->E > GEOBI_MAX_EDGES ||
-        g.gv->N < 0 || g.gf->N < 0 || g.gv->E < 0 || g.gf->E < 0)
-      return set_error("geobi_net_train_groups: group %d: level-0 sizes outside GEOBI_MAX_NODES / GEOBI_MAX_EDGES", k);
+    GEOBI_TRY(check_level0("geobi_net_train_groups", g.gv, g.gf, k));
     if (sum_into && (!g.grad_flat || g.grad_count != sum_count))
       return set_error("geobi_net_train_groups: sum_into needs every group's grad_flat with %lld floats", (long long)sum_count);
     for (int j = 0; j < k; ++j)

@@ -289,6 +289,15 @@ def _learned_size(table, key, used_bytes):
     table[key] = max(table.get(key, 0), want)
     return table[key]
 
+
+def _grown(used_bytes, have):
+    """The arena size after a GEOBI_NET_ARENA refusal: a quarter and 64 MiB over what the library reported (the exact
+    forward + backward need when the forward's own takes fitted, the bytes so far when they did not), or twice what there
+    was if it reported no more than that."""
+    used = int(used_bytes)
+    return int(1.25 * used) + (64 << 20) if used > have else 2 * have
+
+
 class Recorded(object):
     """A training forward recorded by the library: the arena with every saved buffer, the host-side record (handle)
     and what the backward needs from the Python side.  The record is released with the object."""
@@ -347,8 +356,7 @@ def forward_train(net, data_v, data_f):
                                          ctypes.byref(out), ctypes.byref(handle), L.stream())
         if rc != 3:
             break
-        used = int(out.used_bytes)       # mid-forward overflow: bytes so far; end-of-forward check: the exact total
-        nbytes = int(1.25 * used) + (64 << 20) if used > nbytes else 2 * nbytes
+        nbytes = _grown(out.used_bytes, nbytes)
         STATS['arena_retry'] += 1
     STATS['calls'] += 1
     if rc == 2:
@@ -561,9 +569,7 @@ class TrainGroups(object):
             STATS['arena_retry'] += 1
             for k, pr in enumerate(self._prep):            # every group reports what it needs
                 if arr[k].rc == 3:
-                    used = int(arr[k].out.used_bytes)
-                    have = pr['res']['arena'].numel()
-                    self._arena(pr, grow=int(1.25 * used) + (64 << 20) if used > have else 2 * have)
+                    self._arena(pr, grow=_grown(arr[k].out.used_bytes, pr['res']['arena'].numel()))
         if rc == 2:
             STATS['fallback'] += 1
             return self._sequential()

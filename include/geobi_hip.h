@@ -1184,7 +1184,13 @@ int geobi_net_forward(const geobi_net_params_t* prm, const geobi_level0_t* gv, c
  * autograd's accumulation into .grad, code/train_dual.py:211-218).  pos_rev_*: position of each level-0 edge's reverse
  * edge (geobi_csr_reverse_index).  corner_segptr / corner_members: vertex -> corner inverse lists of the face table
  * (geobi_segment_csr over fv viewed as [3F]).  The arena must stay untouched from the forward to the end of the
- * backward; geobi_net_release frees the host-side record (after the backward, or instead of it).                  */
+ * backward; geobi_net_release frees the host-side record (after the backward, or instead of it).
+ * Arena: geobi_net_train_arena_bytes is an estimate from the level-0 sizes.  geobi_net_forward_train sets aside, behind
+ * what it keeps, every buffer the backward will use (gradients, workspaces, the zeros that stand in for a NULL g_verts /
+ * g_normals), so a successful call leaves out->used_bytes = the exact forward + backward need of this mesh, and
+ * geobi_net_backward takes nothing from the arena that the forward has not set aside: it cannot run out of it.  An arena
+ * too small is refused by the forward with GEOBI_NET_ARENA and no record: out->used_bytes is then the bytes needed so
+ * far when the forward itself ran out, the exact total when only the backward's buffers did not fit.               */
 size_t geobi_net_train_arena_bytes(int64_t V, int64_t Ev, int64_t F, int64_t Ef);
 int geobi_net_forward_train(const geobi_net_params_t* prm, const geobi_level0_t* gv, const geobi_level0_t* gf,
                             const int32_t* pos_rev_v, const int32_t* pos_rev_f, const float* x_v, const float* x_f,
