@@ -4,7 +4,7 @@
   python -m geobi_gnn_amd denoise --model net.pt --data_dir DIR [--out_dir DIR/result] [--sub_size 20000]
   python -m geobi_gnn_amd denoise --method bnf --data_dir DIR [--normal_iters 20] [--sigma_r 0.35] [--sigma_s 1.0] [--n_iter 20]
   python -m geobi_gnn_amd denoise --method gnf --data_dir DIR [the same flags]
-  python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original [--align [--scale]] [--free]
+  python -m geobi_gnn_amd eval --result_dir DIR/result --original_dir DIR/original [--align [--scale]] [--free] [--index grid]
   python -m geobi_gnn_amd align --data_dir DIR --target_dir DIR2 [--out_dir DIR/aligned] [--scale] [--reflect] [--max_iter 100]
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
   python -m geobi_gnn_amd clean --data_dir DIR [--out_dir DIR/clean] [--weld_tol 0] [--no_weld] [--no_manifold]
@@ -18,8 +18,9 @@
   python -m geobi_gnn_amd subdivide --data_dir DIR (--max_edge L | --max_edge_diag R) [--max_rounds 16]
   python -m geobi_gnn_amd decimate --data_dir DIR [--out_dir DIR/decimated] (--ratio R | --faces N) [--max_cost C] [--max_rounds 256]
   python -m geobi_gnn_amd remesh --data_dir DIR [--out_dir DIR/remeshed] [--target_edge L | --target_edge_diag R] [--iterations 5]
-                                 [--feature_angle 40] [--relax_lambda 0.5] [--max_rounds 64] [--project]
+                                 [--feature_angle 40] [--relax_lambda 0.5] [--max_rounds 64] [--project [--index grid]]
   python -m geobi_gnn_amd project --data_dir DIR --target_dir DIR2 [--out_dir DIR/projected] [--max_dist D | --max_dist_diag R]
+                                  [--index grid]
   python -m geobi_gnn_amd fill --data_dir DIR [--out_dir DIR/filled] [--max_hole_edges N] [--gpu -1]
 
 `denoise` is predict_dir of the reference (code/test_dual.py:25-150): with DIR/original and DIR/noisy
@@ -200,6 +201,11 @@ def denoise(opt):
     return 1 if failed or not jobs else 0
 
 
+def _index_of(opt):
+    """--index none|grid -> the index= keyword of the searches' callers"""
+    return None if opt.index == 'none' else opt.index
+
+
 def evaluate(opt):
     from . import mesheval
     from ._lib import GeobiError
@@ -208,7 +214,7 @@ def evaluate(opt):
     t0 = time.time()
     try:
         rows, _ = mesheval.eval_dirs(opt.result_dir, opt.original_dir, device=dev, stats=stats, align=opt.align, free=opt.free,
-                                     estimate_scale=opt.scale, samples=opt.samples, seed=opt.seed)
+                                     estimate_scale=opt.scale, samples=opt.samples, seed=opt.seed, index=_index_of(opt))
     except (ValueError, OSError, GeobiError) as e:
         print('eval failed: %s' % e, file=sys.stderr)
         return 1
@@ -511,7 +517,7 @@ def remesh(opt):
         """-> (Remeshed, (mean, max) of the drift)"""
         r = meshremesh.remesh(points, faces, target_edge=opt.target_edge, target_edge_diag=opt.target_edge_diag,
                               iterations=opt.iterations, feature_angle=opt.feature_angle, relax_lambda=opt.relax_lambda,
-                              max_rounds=opt.max_rounds, device=dev, project=opt.project)
+                              max_rounds=opt.max_rounds, device=dev, project=opt.project, index=_index_of(opt))
         drift = (0.0, 0.0)
         if r.points.shape[0] and faces.shape[0]:         # the new vertices against the INPUT surface
             with torch.cuda.device(dev):
@@ -562,7 +568,7 @@ def project(opt):
         if points.shape[0] == 0:
             raise ValueError('%s has no vertices' % source)
         max_dist = opt.max_dist_diag * meshin.bbox_diagonal(t_points) if opt.max_dist_diag is not None else opt.max_dist
-        out, kept, c = meshproject.project(points, t_points, t_faces, max_dist=max_dist, device=dev)
+        out, kept, c = meshproject.project(points, t_points, t_faces, max_dist=max_dist, device=dev, index=_index_of(opt))
         out_file = os.path.join(out_dir, os.path.basename(source))
         meshio.write_obj(out_file, out.cpu().numpy(), faces)
         moved = (out - c.points.new_tensor(points)).double().norm(dim=1)
@@ -711,6 +717,8 @@ def build_parser():
                    help='with --free: also score from N points drawn by area on each surface; writes ErrorInfo_sampled.txt '
                         '(with --align the ground truth is aligned to as its vertices plus its samples)')
     e.add_argument('--seed', type=int, default=1, help='with --samples: the seed of the draw')
+    e.add_argument('--index', type=str, choices=('none', 'grid'), default='none',
+                   help='none: the searches walk all pairs; grid: a uniform grid in front of them, the same bits (DESIGN.md 4u)')
     e.set_defaults(fn=evaluate)
     a = sub.add_parser('align', help='align every mesh of a folder to its target by rigid ICP and write it with its own faces')
     a.add_argument('--data_dir', type=str, required=True, help='the meshes to move: NAME_*.obj, or NAME.obj')
@@ -807,6 +815,8 @@ def build_parser():
     r.add_argument('--project', action='store_true',
                    help='end every iteration by moving the relaxed vertices to their closest points on the input surface; '
                         'with <data_dir>/noisy present its files are carried along to <out_dir>/noisy')
+    r.add_argument('--index', type=str, choices=('none', 'grid'), default='none',
+                   help='none: the searches walk all pairs; grid: a uniform grid in front of them, the same bits (DESIGN.md 4u)')
     r.add_argument('--gpu', type=int, default=-1)
     r.set_defaults(fn=remesh)
     j = sub.add_parser('project', help='move the vertices of every mesh of a folder to their closest points on the surface '
@@ -819,6 +829,8 @@ def build_parser():
                      help='a vertex farther than D from the surface stays where it is')
     far.add_argument('--max_dist_diag', type=_not_negative_arg, default=None, metavar='R',
                      help="--max_dist as R times the diagonal of the target's bounding box")
+    j.add_argument('--index', type=str, choices=('none', 'grid'), default='none',
+                   help='none: the searches walk all pairs; grid: a uniform grid in front of them, the same bits (DESIGN.md 4u)')
     j.add_argument('--gpu', type=int, default=-1)
     j.set_defaults(fn=project)
     h = sub.add_parser('fill', help='close the holes of every mesh on the device: one new vertex and a fan of faces per '
@@ -848,6 +860,8 @@ def parse_args(argv=None):
             for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component', 'drop_intersecting'):
                 if getattr(opt, flag + '_given', False):
                     ap.error('denoise: --%s needs --clean' % flag)
+    if opt.command == 'remesh' and opt.index != 'none' and not opt.project:
+        ap.error('remesh: --index serves the searches of --project')
     if opt.command == 'eval' and opt.scale and not opt.align:
         ap.error('eval: --scale needs --align')
     if opt.command == 'eval' and opt.samples and not opt.free:

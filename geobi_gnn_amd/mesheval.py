@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib as L
-from . import folders, meshin, meshio, meshnoise, meshprep, network, ops
+from . import folders, meshgrid, meshin, meshio, meshnoise, meshprep, network, ops
 from .data_util import computer_face_normal, face_centroids
 
 
@@ -27,13 +27,18 @@ def _nearest_ws(Q, T, dev):
     return L.workspace(L.size_query('geobi_nearest_ws_bytes', Q, T), dev)
 
 
-def nearest_point(a, b):
+def nearest_point(a, b, index=None):
     """my_hausdorff.nearest_distance(a, b): for every row of a [Q, 3] the distance to the nearest row of b [T, 3] and
-    that row's index (the lowest among equally near ones) -> (dist float32 [Q], idx int32 [Q])."""
+    that row's index (the lowest among equally near ones) -> (dist float32 [Q], idx int32 [Q]).  index: None walks all
+    pairs; 'grid' builds a meshgrid.PointGrid over b first, a PointGrid built over b before is used as it is -- the same
+    bits either way."""
+    index = meshgrid.check_index(index)
     a, b = _points(a, 'query points'), _points(b, 'target points')
     Q, T = a.shape[0], b.shape[0]
     if Q == 0 or T == 0:
         raise L.GeobiError('nearest_point: empty query or target set (Q = %d, T = %d)' % (Q, T))
+    if index is not None:
+        return meshgrid.point_grid(index, b).nearest(a)
     dist = torch.empty(Q, dtype=torch.float32, device=a.device)
     idx = torch.empty(Q, dtype=torch.int32, device=a.device)
     ws = _nearest_ws(Q, T, a.device)
@@ -41,14 +46,19 @@ def nearest_point(a, b):
     return dist, idx
 
 
-def point_to_mesh(points, verts, faces):
+def point_to_mesh(points, verts, faces, index=None):
     """Distance from every row of points [Q, 3] to the surface (verts [V, 3], faces [F, 3]): the closest point of the
-    closest triangle, interior, edge or corner -> (dist float32 [Q], face int32 [Q])."""
+    closest triangle, interior, edge or corner -> (dist float32 [Q], face int32 [Q]).  index: None walks all pairs; 'grid'
+    builds a meshgrid.TriangleGrid over the surface first, one built over it before is used as it is -- the same bits
+    either way."""
+    index = meshgrid.check_index(index)
     p, v = _points(points, 'query points'), _points(verts, 'mesh vertices')
     L.require_device(faces, 'faces')
     Q, V, F = p.shape[0], v.shape[0], faces.shape[0]
     if Q == 0 or V == 0 or F == 0 or faces.dim() != 2 or faces.shape[1] != 3:
         raise L.GeobiError('point_to_mesh: empty query set or mesh (Q = %d, V = %d, faces %s)' % (Q, V, tuple(faces.shape)))
+    if index is not None:
+        return meshgrid.triangle_grid(index, v, faces).nearest(p)
     meshin.check_faces(faces, V)                             # range-checked before a kernel walks it
     fv = faces.to(torch.int32).contiguous()
     dist = torch.empty(Q, dtype=torch.float32, device=p.device)
@@ -122,7 +132,7 @@ _ALIGN_KEYS = ('icp_rmse', 'icp_iterations', 'icp_converged')
 _align_points = align          # the scoring functions below take a flag of the same name
 
 
-def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None, align=False, estimate_scale=False):
+def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None, align=False, estimate_scale=False, index=None):
     """The numbers of one (result, ground truth) pair, code/data_util.py:584-616.  Arrays or tensors; the work runs on
     `device` (default: the tensors' device, else the current one).  gt_faces defaults to `faces` (a denoised mesh keeps its
     connectivity).  align: the result points are first brought into the ground truth's frame by rigid ICP (align();
@@ -132,7 +142,11 @@ def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None, align
       err_v (mean distance to the nearest ground-truth vertex), err_v_norm (the same over `scale`, the ground truth's
       mean edge length)                                                   -- the reference's six
       surf, surf_norm (mean distance to the ground-truth SURFACE, raw and over `scale`),
-      hausdorff (the larger of the two directed maxima of nearest-vertex distance), scale."""
+      hausdorff (the larger of the two directed maxima of nearest-vertex distance), scale.
+
+    index='grid': every search goes through a grid over its target (meshgrid), built once per target; the numbers are the
+    same bits."""
+    index = meshgrid.check_index_word(index, 'eval_pair')
     dev = meshin.default_device(device, result_points)
     pr, po = meshin.to_device(result_points, dev, torch.float32), meshin.to_device(gt_points, dev, torch.float32)
     fr = meshin.as_tensor(faces)
@@ -152,9 +166,9 @@ def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None, align
     err_face = network.loss_n(nr, no, 'L2')
     angle = network.error_n(nr, no)
     scale = mean_edge_length(po, fo)
-    d_ro, _ = nearest_point(pr, po)
-    d_or, _ = nearest_point(po, pr)
-    d_surf, _ = point_to_mesh(pr, po, fo)
+    d_ro, _ = nearest_point(pr, po, index=index)             # three targets, each searched once
+    d_or, _ = nearest_point(po, pr, index=index)
+    d_surf, _ = point_to_mesh(pr, po, fo, index=index)
     s_ro, s_or, s_surf = dist_summary(d_ro), dist_summary(d_or), dist_summary(d_surf)
     host = torch.cat([err_face.reshape(1).double(), angle.reshape(1).double(), scale.double(), s_ro, s_or, s_surf]).tolist()
     err_face, angle, scale = host[0], host[1], host[2]
@@ -167,7 +181,7 @@ def eval_pair(result_points, faces, gt_points, gt_faces=None, device=None, align
     return row
 
 
-def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, align=False, estimate_scale=False):
+def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, align=False, estimate_scale=False, index=None):
     """The numbers of a pair whose vertex counts, face tables or numbering DIFFER (another tool's output, a scan against
     its CAD model): nothing here pairs row i with row i.  align / estimate_scale as in eval_pair.  Returns a dict:
 
@@ -177,7 +191,11 @@ def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, ali
       surf (mean distance from the result's vertices to the ground-truth SURFACE), surf_back (from the ground truth's
       vertices to the result's surface), hausdorff (the larger of the two directed maxima of those distances),
       scale (the ground truth's mean edge length), surf_norm, surf_back_norm (over scale),
-      and with align: icp_rmse, icp_iterations, icp_converged."""
+      and with align: icp_rmse, icp_iterations, icp_converged.
+
+    index='grid': the searches go through one grid per surface (meshgrid), the ground truth's serving both of its
+    searches; the numbers are the same bits."""
+    index = meshgrid.check_index_word(index, 'eval_free')
     dev = meshin.default_device(device, result_points)
     pr, fr = meshin.device_mesh(result_points, result_faces, dev)
     po, fo = meshin.device_mesh(gt_points, gt_faces, dev)
@@ -189,13 +207,14 @@ def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, ali
         icp = _align_points(pr, po, dev, estimate_scale=estimate_scale)
         pr = icp.xt
     nr, no = computer_face_normal(pr, fr).contiguous(), computer_face_normal(po, fo).contiguous()
-    _, near = point_to_mesh(face_centroids(pr, fr), po, fo)
+    g_o = meshgrid.TriangleGrid(_points(po, 'mesh vertices'), fo) if index is not None else None
+    _, near = point_to_mesh(face_centroids(pr, fr), po, fo, index=g_o)
     ng = torch.empty_like(nr)
     L.call('geobi_gather_rows', L.ptr(no), L.ptr(near), 3, near.shape[0], L.ptr(ng), L.stream())
     angle = network.error_n(nr, ng)
     scale = mean_edge_length(po, fo)
-    d_ro, _ = point_to_mesh(pr, po, fo)
-    d_or, _ = point_to_mesh(po, pr, fr)
+    d_ro, _ = point_to_mesh(pr, po, fo, index=g_o)
+    d_or, _ = point_to_mesh(po, pr, fr, index=index)
     host = torch.cat([angle.reshape(1).double(), scale.double(), dist_summary(d_ro), dist_summary(d_or)]).tolist()
     scale = host[1]
     surf, back = host[2] / pr.shape[0], host[4] / po.shape[0]
@@ -208,7 +227,7 @@ def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, ali
     return row
 
 
-def eval_sampled(result_points, result_faces, gt_points, gt_faces, n_samples, seed=1, stream_id=0, device=None):
+def eval_sampled(result_points, result_faces, gt_points, gt_faces, n_samples, seed=1, stream_id=0, device=None, index=None):
     """eval_free's distances measured from points drawn by area on the two SURFACES (meshsample.sample_surface) instead of
     from their vertices: two meshes that share every vertex and differ inside their triangles are `surf = 0` to eval_free
     and not to this.  Returns a dict:
@@ -222,8 +241,10 @@ def eval_sampled(result_points, result_faces, gt_points, gt_faces, n_samples, se
       scale (the ground truth's mean edge length), surf_s_norm, surf_back_s_norm (over scale).
 
     The sums go through dist_summary; one host read brings the pair's numbers (beside the one read per sampled mesh that
-    refuses a mesh without area)."""
+    refuses a mesh without area).  index='grid': either search goes through a grid over its surface (meshgrid); the
+    numbers are the same bits."""
     from . import meshsample
+    index = meshgrid.check_index_word(index, 'eval_sampled')
     n = int(n_samples)
     if n < 1:
         raise ValueError('eval_sampled: n_samples = %d (at least one)' % n)
@@ -235,8 +256,8 @@ def eval_sampled(result_points, result_faces, gt_points, gt_faces, n_samples, se
                          % (pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]))
     sr = meshsample.sample_surface(pr, fr, n, seed=seed, stream_id=stream_id, draw=1, check=False)
     so = meshsample.sample_surface(po, fo, n, seed=seed, stream_id=stream_id, draw=0, check=False)
-    d_ro, near = point_to_mesh(sr.points, po, fo)
-    d_or, _ = point_to_mesh(so.points, pr, fr)
+    d_ro, near = point_to_mesh(sr.points, po, fo, index=index)   # two targets, each searched once
+    d_or, _ = point_to_mesh(so.points, pr, fr, index=index)
     no = computer_face_normal(po, fo).contiguous()
     ng = torch.empty((n, 3), dtype=torch.float32, device=dev)
     L.call('geobi_gather_rows', L.ptr(no), L.ptr(near), 3, n, L.ptr(ng), L.stream())
@@ -314,7 +335,7 @@ def align_line(name, width, info):
 
 
 def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, free=False, estimate_scale=False, samples=0,
-              seed=1):
+              seed=1, index=None):
     """eval_denoising_result(dir_result, dir_original): every pair of pair_files scored with eval_pair, the per-file
     and totals lines printed and written to dir_result/ErrorInfo_h.txt in the reference's format with three columns
     appended (surf, surf_norm, hausdorff).  A result whose V or F differs from its ground truth is a ValueError naming
@@ -327,8 +348,10 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
     dir_result/ErrorInfo_sampled.txt is written beside ErrorInfo_free.txt, whose bytes the flag does not change; with align
     as well, the alignment target is the ground truth's vertices followed by its draw-0 samples (align(samples=)), which
     is another alignment and so other numbers in both files.  Returns (rows, totals) -- rows carry 'file', and with
-    samples eval_sampled's keys."""
+    samples eval_sampled's keys.  index='grid': the scoring searches go through grids (eval_pair, eval_free, eval_sampled);
+    every file keeps its bytes."""
     import time
+    index = meshgrid.check_index_word(index, 'eval')
     if samples and not free:
         raise ValueError('eval: samples need the free scoring (eval_free pairs nothing by index; neither do samples)')
     pairs = pair_files(dir_result, dir_original)
@@ -352,9 +375,10 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
                                 samples=samples, seed=seed, stream_id=stream_id)
             infos.append(align_info(res))
             pr = res.xt
-        row = eval_free(pr, fr, po, fo, device=dev) if free else eval_pair(pr, fr, po, gt_faces=fo, device=dev)
+        row = (eval_free(pr, fr, po, fo, device=dev, index=index) if free
+               else eval_pair(pr, fr, po, gt_faces=fo, device=dev, index=index))
         if samples:
-            sampled = eval_sampled(pr, fr, po, fo, samples, seed=seed, stream_id=stream_id, device=dev)
+            sampled = eval_sampled(pr, fr, po, fo, samples, seed=seed, stream_id=stream_id, device=dev, index=index)
             row.update((k, sampled[k]) for k in _SAMPLED_COLUMNS)
         if align:
             row.update((k, infos[-1][k]) for k in _ALIGN_KEYS)

@@ -15,7 +15,7 @@ import math
 import torch
 
 from . import _lib as L
-from . import mesheval, meshin, ops
+from . import mesheval, meshgrid, meshin, ops
 
 MAX_NODES = meshin.MAX_NODES
 
@@ -59,24 +59,26 @@ def closest_on_faces(q, verts, fv, face):
     return bary, points, dist
 
 
-def _closest(q, v, fv):
-    """the search and the step behind it on checked device tensors -> Closest"""
-    face = mesheval.point_to_mesh(q, v, fv)[1]
+def _closest(q, v, fv, index=None):
+    """the search (index: as mesheval.point_to_mesh) and the step behind it on checked device tensors -> Closest"""
+    face = mesheval.point_to_mesh(q, v, fv, index=index)[1]
     bary, points, dist = closest_on_faces(q, v, fv, face)
     return Closest(face, bary, points, dist, fv, v.shape[0])
 
 
-def closest(points, verts, faces, device=None):
+def closest(points, verts, faces, device=None, index=None):
     """For every row of points [Q, 3] its closest point on the surface (verts [V, 3], faces [F, 3]) -> Closest.  Arrays or
     tensors; a query with a coordinate that is not finite gets dist = +inf and the first corner of its face.  ValueError:
     other shapes, no query, an empty surface, a face index outside [0, V), non-finite vertices, sizes beyond
-    GEOBI_MAX_NODES."""
+    GEOBI_MAX_NODES.  index: None searches all pairs, 'grid' through a meshgrid.TriangleGrid built here, or through one
+    built over this surface before; the same bits either way."""
+    index = meshgrid.check_index(index)
     q = check_queries(points, 'closest')                  # before the device is asked for: checked without one
     dev = meshin.default_device(device, meshin.as_tensor(verts))
     v, fv = _surface(verts, faces, dev, 'closest')
     q = meshin.to_device(q, dev, torch.float32)
     with torch.cuda.device(dev):
-        return _closest(q, v, fv)
+        return _closest(q, v, fv, index)
 
 
 def apply(closest, other_verts):
@@ -101,17 +103,18 @@ def check_max_dist(max_dist, what='project'):
     return value
 
 
-def project(points, verts, faces, max_dist=None, device=None):
+def project(points, verts, faces, max_dist=None, device=None, index=None):
     """points [Q, 3] moved to their closest points on the surface -> (projected float32 [Q, 3] on the device, kept, Closest).
     A row whose distance is above ``max_dist`` (None: no limit) keeps its coordinates -- a query that is not finite always
-    does -- and ``kept`` is the number of such rows."""
+    does -- and ``kept`` is the number of such rows.  index: as ``closest``."""
+    index = meshgrid.check_index(index)
     max_dist = check_max_dist(max_dist)
     q = check_queries(points, 'project')
     dev = meshin.default_device(device, meshin.as_tensor(verts))
     v, fv = _surface(verts, faces, dev, 'project')
     q = meshin.to_device(q, dev, torch.float32)
     with torch.cuda.device(dev):
-        c = _closest(q, v, fv)
+        c = _closest(q, v, fv, index)
         keep = ~torch.isfinite(c.dist) if max_dist is None else ~(c.dist <= max_dist)
         out = torch.where(keep[:, None], q, c.points)
         return out, int(keep.sum()), c

@@ -283,7 +283,7 @@ def mesh_stats(points, faces, low, high, device=None):
 
 # ---------------------------------------------------------------------------------------------- the whole call
 def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5, feature_angle=40.0, relax_lambda=0.5,
-           max_rounds=64, device=None, project=False):
+           max_rounds=64, device=None, project=False, index=None):
     """(points [V, 3], faces [F, 3]) -> Remeshed.  The target edge length L is ``target_edge``, or ``target_edge_diag`` times
     the diagonal of the bounding box, or by default the mean edge length of the input (``meshnoise.MeshGeometry``).  Every
     iteration runs: splits of the edges above high = 4/3 L to exhaustion, rounds of short-edge collapses (below low = 0.8
@@ -292,11 +292,18 @@ def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5,
     from the relaxed positions to them under the lock flags the relaxation used (counts: PROJECT_KEYS); after the last
     iteration the closest points of ALL output vertices on the input, locked ones included, fill ``source_face`` /
     ``source_bary`` -- a map only, no point moves (``iterations=0``: the one-hot map of the input onto itself).  Without
-    project the launches and the dicts are what they were.  ValueError: project for an input without faces, shapes
+    project the launches and the dicts are what they were.  index (with project): None searches all pairs; 'grid' builds
+    ONE meshgrid.TriangleGrid over the input surface for all these searches, one built over it before is used as it is;
+    the output is the same bits.  ValueError: project for an input without faces, shapes
     other than [V, 3] and [F, 3], a face index outside [0, V), non-finite points, arguments outside their range;
     GeobiError: ``max_rounds`` rounds did not end one of the three inner loops."""
     target_edge, target_edge_diag, feature_angle, relax_lambda = check_args(target_edge, target_edge_diag, iterations,
                                                                             feature_angle, relax_lambda, max_rounds)
+    if index is not None:
+        from . import meshgrid
+        index = meshgrid.check_index(index)
+        if not project:
+            raise ValueError('remesh: index = %r serves the searches of project = True' % (index,))
     pts, fv = _mesh(points, faces, device, 'remesh')
     dev = pts.device
     if project and fv.shape[0] == 0:
@@ -304,6 +311,9 @@ def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5,
     if project:
         from . import meshproject
         in_pts, in_fv = pts, fv
+        if index is not None:
+            with torch.cuda.device(dev):
+                index = meshgrid.triangle_grid(index, in_pts, in_fv)     # one grid over the input for all its searches
     use_sharp, c2 = cos2(feature_angle)
     with torch.cuda.device(dev):
         if target_edge is None and target_edge_diag is not None:
@@ -353,11 +363,11 @@ def remesh(points, faces, target_edge=None, target_edge_diag=None, iterations=5,
             if project:
                 c.update(dict.fromkeys(PROJECT_KEYS, 0))
                 if fv.shape[0] > 0:
-                    pts, r = _move_to(fv, pts, meshproject._closest(pts, in_pts, in_fv).points, lock)
+                    pts, r = _move_to(fv, pts, meshproject._closest(pts, in_pts, in_fv, index).points, lock)
                     c.update(zip(PROJECT_KEYS, (r[k] for k in RELAX_KEYS)))
             per_iteration.append(c)
         after = mesh_stats(pts, fv, low, high, dev)
-        source = meshproject._closest(pts, in_pts, in_fv) if project else None
+        source = meshproject._closest(pts, in_pts, in_fv, index) if project else None
     if project:
         return Remeshed(pts, fv, np.float32(low), np.float32(high), per_iteration, before, after, source.face, source.bary,
                         in_fv, in_pts.shape[0])

@@ -1013,6 +1013,64 @@ int geobi_remesh_stats(const int32_t* faces, const float* points, int64_t F, int
 int geobi_closest_on_faces(const float* q, const float* verts, const int32_t* fv, const int32_t* face, int64_t Q, int64_t V,
                            int64_t F, float* bary, float* point, float* dist, void* stream);
 
+/* ---------------------------------------------------------------- spatial grid in front of the nearest searches ----
+ * A uniform grid over the box of the FINITE targets; no counterpart in the reference.  Its answer is the
+ * answer of geobi_nearest_point / geobi_nearest_triangle on the same arrays BIT FOR BIT -- the same float32 distance and
+ * the lowest index among equally near targets -- because a pair's squared distance comes from the same text (csrc/
+ * dist_pairs.h) and the walk stops only when everything it has not visited is strictly farther than its best, by a margin
+ * that covers the rounding of the binning, of the bound and of the pair function.  A target with a coordinate that is not
+ * finite (a face with such a corner) is left out of box and bins: the all-pairs `<` never lets it win either.
+ *   desc         HOST int32 [16], written by a plan and handed back to every later call: [0..2] cells per axis nx, ny, nz;
+ *                [3..5] the box's low corner, [6..8] its high corner, [9..11] the cell edge per axis, [12] the largest
+ *                target coordinate magnitude (float32 by their bits); [13] entries: the finite points, or the (cell, face)
+ *                pairs; [14] the counting rounds a triangle plan took; [15] the finite targets.  Cell (x, y, z) has the id
+ *                (z * ny + y) * nx + x.
+ *   geobi_grid_points_plan / geobi_grid_triangles_plan   the box (two-stage min / max), then the resolution from the target
+ *                count and the box alone; cells > 0 forces that many cells on every axis with extent (<=
+ *                geobi_grid_max_cells()).  A triangle is filed in every cell its bounding box meets; while the entries
+ *                exceed geobi_grid_entry_cap() * F the resolution is halved and counted again (one cell per axis gives at
+ *                most F entries).  WAIT for `stream`: one geobi_read_i32 for the box and one per counting round, at most 9.
+ *                ws: geobi_grid_plan_ws_bytes(F) (F = 0 for points).
+ *   geobi_grid_points_build      cell_start [cells + 1], order [T]: the first cell_start[cells] rows of order are the
+ *                finite targets sorted by (cell, index) by one stable radix sort; cell c owns order[cell_start[c] ..
+ *                cell_start[c + 1]).  ws: geobi_grid_points_build_ws_bytes(T).
+ *   geobi_grid_triangles_build   cell_start [cells + 1], order [desc[13]] likewise for the (cell, face) pairs, and records
+ *                [F, 16] float32: the record of every face as the all-pairs walk stages it (a face without area as its
+ *                longest edge), in face order; the search reads records, not corners.  ws:
+ *                geobi_grid_triangles_build_ws_bytes(F).
+ *   geobi_grid_nearest_point / geobi_grid_nearest_triangle   one lane per query (sorted by cell first): Chebyshev shells
+ *                r = 0, 1, ... around the query's cell, at most max_rings of them (-1: geobi_grid_default_rings(); 0:
+ *                none).  dist / idx (idx, face may be NULL) are written for every query that finished; the others are
+ *                LEFT OVER: left [Q] holds their ids in ascending order, left_q [Q, 3] their coordinates, count (device
+ *                int32 [1]) how many.  The caller reads count (geobi_read_i32), runs geobi_nearest_point /
+ *                geobi_nearest_triangle on the first count rows of left_q and hands the answers to geobi_grid_scatter.
+ *                The budget changes the time, never a bit.  A query that is not finite answers (+inf, 0).
+ *                ws: geobi_grid_nearest_ws_bytes(Q).
+ *   geobi_grid_scatter           dist[left[k]] = dist_in[k], idx[left[k]] = idx_in[k] for k < n (idx, idx_in may be NULL).
+ * Q, T, V, F >= 1 and <= GEOBI_MAX_NODES; indices are int32.                                                            */
+int geobi_grid_default_rings(void);
+int geobi_grid_max_cells(void);
+int geobi_grid_entry_cap(void);
+size_t geobi_grid_plan_ws_bytes(int64_t F);
+int geobi_grid_points_plan(const float* t, int64_t T, int cells, int32_t* desc, void* ws, size_t ws_bytes, void* stream);
+size_t geobi_grid_points_build_ws_bytes(int64_t T);
+int geobi_grid_points_build(const float* t, int64_t T, const int32_t* desc, int32_t* cell_start, int32_t* order, void* ws,
+                            size_t ws_bytes, void* stream);
+int geobi_grid_triangles_plan(const float* verts, const int32_t* fv, int64_t V, int64_t F, int cells, int32_t* desc, void* ws,
+                              size_t ws_bytes, void* stream);
+size_t geobi_grid_triangles_build_ws_bytes(int64_t F);
+int geobi_grid_triangles_build(const float* verts, const int32_t* fv, int64_t V, int64_t F, const int32_t* desc,
+                               int32_t* cell_start, int32_t* order, float* records, void* ws, size_t ws_bytes, void* stream);
+size_t geobi_grid_nearest_ws_bytes(int64_t Q);
+int geobi_grid_nearest_point(const float* q, const float* t, int64_t Q, int64_t T, const int32_t* desc, const int32_t* cell_start,
+                             const int32_t* order, int max_rings, float* dist, int32_t* idx, int32_t* left, float* left_q,
+                             int32_t* count, void* ws, size_t ws_bytes, void* stream);
+int geobi_grid_nearest_triangle(const float* q, const float* records, int64_t Q, int64_t F, const int32_t* desc,
+                                const int32_t* cell_start, const int32_t* order, int max_rings, float* dist, int32_t* face,
+                                int32_t* left, float* left_q, int32_t* count, void* ws, size_t ws_bytes, void* stream);
+int geobi_grid_scatter(const int32_t* left, int64_t n, int64_t Q, const float* dist_in, const int32_t* idx_in, float* dist,
+                       int32_t* idx, void* stream);
+
 /* ---------------------------------------------------------------- hole filling (boundary loops, fan fill) ----
  * Closes the holes of a triangle mesh; no counterpart in the reference.  The topology is integer-exact, a
  * new position goes through ONE stated order of fp64 additions (no float atomics), nothing depends on launch geometry:
