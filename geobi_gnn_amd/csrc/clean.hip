@@ -213,12 +213,12 @@ __global__ void compact_faces_kernel(const int* __restrict__ fc, const int* __re
 struct WeldBuffers {
   uint32_t *kx, *ky, *kz, *ka, *kb;
   int *idx, *va, *vb, *flag, *rank, *head, *bad;
-  SubWs sort_temp, scan_temp;
+  PairSort<uint32_t, int> sort; IntScan scan;      // sort: one temporary, the three passes of the LSD sort
 };
 WeldBuffers carve_weld(Arena& a, int64_t V) {
   return {a.take<uint32_t>(V), a.take<uint32_t>(V), a.take<uint32_t>(V), a.take<uint32_t>(V), a.take<uint32_t>(V),
           a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(V + 1), a.take<int>(V + 1), a.take<int>(V),
-          a.take<int>(1), a.take_ws(sort_pairs_temp_bytes<uint32_t, int>(V)), a.take_ws(scan_ws_bytes(V + 1))};
+          a.take<int>(1), PairSort<uint32_t, int>::take(a, V), IntScan::take(a, V + 1)};
 }
 
 struct FaceBuffers {
@@ -231,11 +231,11 @@ FaceBuffers carve_faces(Arena& a, int64_t F) {
 
 struct CompactBuffers {
   int *used, *vrank, *keep, *frank;
-  SubWs scan_v, scan_f;
+  IntScan scan_v, scan_f;
 };
 CompactBuffers carve_compact(Arena& a, int64_t V, int64_t F) {
   return {a.take<int>(V + 1), a.take<int>(V + 1), a.take<int>(F + 1), a.take<int>(F + 1),
-          a.take_ws(scan_ws_bytes(V + 1)), a.take_ws(scan_ws_bytes(F + 1))};
+          IntScan::take(a, V + 1), IntScan::take(a, F + 1)};
 }
 
 }  // namespace
@@ -269,19 +269,16 @@ int geobi_clean_weld(const float* points, int64_t V, int mode, float weld_tol, i
   weld_keys_kernel<<<blocks, kT, 0, s>>>(points, n, mode, weld_tol, w.kx, w.ky, w.kz, w.idx, w.bad);
   GEOBI_LAUNCH_OK();
   // LSD: least significant word first; each pass is stable, so the order of the earlier passes survives among equal keys
-  size_t tb = w.sort_temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp.p, tb, w.kz, w.kb, w.idx, w.vb, (size_t)V, 0u, 32u, s, false));
+  GEOBI_TRY(w.sort.run(w.kz, w.kb, w.idx, w.vb, s));
   gather_u32_kernel<<<blocks, kT, 0, s>>>(w.ky, w.vb, n, w.ka);
   GEOBI_LAUNCH_OK();
-  tb = w.sort_temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp.p, tb, w.ka, w.kb, w.vb, w.va, (size_t)V, 0u, 32u, s, false));
+  GEOBI_TRY(w.sort.run(w.ka, w.kb, w.vb, w.va, s));
   gather_u32_kernel<<<blocks, kT, 0, s>>>(w.kx, w.va, n, w.ka);
   GEOBI_LAUNCH_OK();
-  tb = w.sort_temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(w.sort_temp.p, tb, w.ka, w.kb, w.va, w.vb, (size_t)V, 0u, 32u, s, false));
+  GEOBI_TRY(w.sort.run(w.ka, w.kb, w.va, w.vb, s));
   weld_heads_kernel<<<cdiv(V + 1, kT), kT, 0, s>>>(w.kx, w.ky, w.kz, w.vb, n, w.flag);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(w.scan_temp.p, w.scan_temp.bytes, w.flag, w.rank, V + 1, s));
+  GEOBI_TRY(w.scan.run(w.flag, w.rank, s));
   weld_head_index_kernel<<<blocks, kT, 0, s>>>(w.vb, w.flag, w.rank, n, w.head);
   GEOBI_LAUNCH_OK();
   weld_canon_kernel<<<blocks, kT, 0, s>>>(w.vb, w.flag, w.rank, w.head, n, w.bad, canon, counts);
@@ -358,8 +355,8 @@ int geobi_clean_compact(const float* points, const int32_t* faces_canon, const i
   GEOBI_HIP(hipMemsetAsync(c.used, 0, sizeof(int) * (size_t)(V + 1), s));
   compact_mark_kernel<<<cdiv(F + 1, kT), kT, 0, s>>>(faces_canon, state, (int)F, (int)V, c.keep, c.used, counts);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(c.scan_v.p, c.scan_v.bytes, c.used, c.vrank, V + 1, s));
-  GEOBI_TRY(scan_exclusive_i32(c.scan_f.p, c.scan_f.bytes, c.keep, c.frank, F + 1, s));
+  GEOBI_TRY(c.scan_v.run(c.used, c.vrank, s));
+  GEOBI_TRY(c.scan_f.run(c.keep, c.frank, s));
   if (V > 0) {
     compact_vertices_kernel<<<cdiv(V, kT), kT, 0, s>>>(points, canon, c.used, c.vrank, (int)V, points_out, vertex_map,
                                                        vertex_src, counts);

@@ -339,7 +339,8 @@ struct DecimBuffers {
   uint64_t *cost_key, *cost_in, *cost_out;
   uint32_t *hash_in, *hash_out;
   int *idx_in, *idx_mid, *order, *code, *rank, *state, *flag, *pos;
-  SubWs hash_sort, cost_sort, slot_scan, vertex_scan, face_scan;
+  PairSort<uint32_t, int> hash_sort; PairSort<uint64_t, int> cost_sort;
+  ExclusiveScan<int> slot_scan, vertex_scan, face_scan;
 };
 DecimBuffers carve_decim(Arena& a, int64_t F, int64_t V) {
   const int64_t n = 3 * F;
@@ -351,9 +352,8 @@ DecimBuffers carve_decim(Arena& a, int64_t F, int64_t V) {
           a.take<uint32_t>(n), a.take<uint32_t>(n),
           a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n),
           a.take<int>(n),
-          a.take_ws(sort_pairs_temp_bytes<uint32_t, int>(n, 32)),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, 64)),
-          a.take_ws(scan_temp_bytes<int>(n)), a.take_ws(scan_temp_bytes<int>(V)), a.take_ws(scan_temp_bytes<int>(F))};
+          PairSort<uint32_t, int>::take(a, n, 32), PairSort<uint64_t, int>::take(a, n, 64),
+          ExclusiveScan<int>::take(a, n), ExclusiveScan<int>::take(a, V), ExclusiveScan<int>::take(a, F)};
 }
 
 int launch_points(const float* other, int64_t V, int64_t Vn, const int32_t* parents, const int8_t* place, float* out,
@@ -381,7 +381,6 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
   const MeshTables& t = b.t;
   const int n = (int)(3 * F), n_pairs = 2 * n;
   const int k_budget = budget < 0 ? -1 : (int)(budget < F ? budget : F);
-  size_t tb;
   StageTimer timer(stage_ms, s);
   GEOBI_TRY(timer.mark());
   // ---- tables
@@ -417,14 +416,10 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
                                                       b.idx_in, b.counts);
     GEOBI_LAUNCH_OK();
   }
-  tb = b.hash_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.hash_sort.p, tb, b.hash_in, b.hash_out, b.idx_in, b.idx_mid, (size_t)n, 0u, 32u, s,
-                                      false));
+  GEOBI_TRY(b.hash_sort.run(b.hash_in, b.hash_out, b.idx_in, b.idx_mid, s));
   decim_gather_cost_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.cost_key, b.idx_mid, n, b.cost_in);
   GEOBI_LAUNCH_OK();
-  tb = b.cost_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.cost_sort.p, tb, b.cost_in, b.cost_out, b.idx_mid, b.order, (size_t)n, 0u, 64u, s,
-                                      false));
+  GEOBI_TRY(b.cost_sort.run(b.cost_in, b.cost_out, b.idx_mid, b.order, s));
   rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.cost_out, b.order, n, b.rank, b.state);
   GEOBI_LAUNCH_OK();
   GEOBI_TRY(timer.mark());
@@ -434,19 +429,16 @@ int plan_round(const char* what, const int32_t* faces, const float* points, int6
   // ---- budget, roles, scans
   decim_selected_in_rank_order_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.order, b.state, n, b.flag);
   GEOBI_LAUNCH_OK();
-  tb = b.slot_scan.bytes;
-  GEOBI_HIP(rocprim::exclusive_scan(b.slot_scan.p, tb, b.flag, b.pos, 0, (size_t)n, rocprim::plus<int>(), s, false));
+  GEOBI_TRY(b.slot_scan.run(b.flag, b.pos, s));
   decim_collapse_kernel<<<cdiv(n, kT), kT, 0, s>>>(t.k_out, t.v_out, n, b.order, b.flag, b.pos, b.code, (int)F, k_budget,
                                                   b.role, b.partner, b.fkeep, b.counts);
   GEOBI_LAUNCH_OK();
   if (V > 0) {
     decim_keep_vertices_kernel<<<cdiv(V, kT), kT, 0, s>>>(b.role, (int)V, b.keepv);
     GEOBI_LAUNCH_OK();
-    tb = b.vertex_scan.bytes;
-    GEOBI_HIP(rocprim::exclusive_scan(b.vertex_scan.p, tb, b.keepv, b.vrow, 0, (size_t)V, rocprim::plus<int>(), s, false));
+    GEOBI_TRY(b.vertex_scan.run(b.keepv, b.vrow, s));
   }
-  tb = b.face_scan.bytes;
-  GEOBI_HIP(rocprim::exclusive_scan(b.face_scan.p, tb, b.fkeep, b.frow, 0, (size_t)F, rocprim::plus<int>(), s, false));
+  GEOBI_TRY(b.face_scan.run(b.fkeep, b.frow, s));
   decim_totals_kernel<<<1, 1, 0, s>>>(b.keepv, b.vrow, (int)V, b.fkeep, b.frow, (int)F, b.counts);
   GEOBI_LAUNCH_OK();
   GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kCounts, hipMemcpyDeviceToDevice, s));

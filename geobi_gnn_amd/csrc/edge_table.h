@@ -1,11 +1,10 @@
 // The undirected edge table of the mesh tools, shared by topo.hip, clean.hip, subdiv.hip, decim.hip,
 // remesh.hip and fill.hip: which faces are included, which key a slot gets, how a run of the sorted table is read, how an index comes out
 // of a key -- and MeshTables, the buffers of the table (and of the two tables mesh_tables.h derives from it) with their carve
-// and the one sort.  Sorting the slots stably on kEdgeKeyBits bits makes a run of equal keys one edge, its length the number
+// and its sorts.  Sorting the slots stably on kEdgeKeyBits bits makes a run of equal keys one edge, its length the number
 // of claimants, the claimants in ascending slot order and the run heads ascend with (lo, hi).
 #pragma once
-#include "common.h"
-#include "rocprim_temp.h"
+#include "device_steps.h"
 
 namespace geobi {
 
@@ -64,31 +63,28 @@ struct MeshTables {
   int *v_in, *v_out;               // [3F] their values
   uint64_t *p_in, *p_out;          // [6F] directed pairs, NULL when not asked for
   uint64_t *c_in, *c_out;          // [3F] corner keys, NULL when not asked for
-  SubWs edge_sort, pair_sort, corner_sort;
+  PairSort<uint64_t, int> edge_sort; KeySort<uint64_t> pair_sort, corner_sort;
 };
 // the carve of the tables a unit asks for: the takes run in the order written, as in a unit's own braced list
 template <bool kPairs, bool kCorners>
 static inline MeshTables carve_tables(Arena& a, int64_t F) {
   const int64_t n = 3 * F;
   MeshTables t = {a.take<uint64_t>(n), a.take<uint64_t>(n), a.take<int>(n), a.take<int>(n)};
-  t.edge_sort = a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, kEdgeKeyBits));
+  t.edge_sort = PairSort<uint64_t, int>::take(a, n, kEdgeKeyBits);
   if constexpr (kPairs) {
     t.p_in = a.take<uint64_t>(2 * n); t.p_out = a.take<uint64_t>(2 * n);
-    t.pair_sort = a.take_ws(sort_keys_temp_bytes<uint64_t>(2 * n, kEdgeKeyBits));
+    t.pair_sort = KeySort<uint64_t>::take(a, 2 * n, kEdgeKeyBits);
   }
   if constexpr (kCorners) {
     t.c_in = a.take<uint64_t>(n); t.c_out = a.take<uint64_t>(n);
-    t.corner_sort = a.take_ws(sort_keys_temp_bytes<uint64_t>(n, kEdgeKeyBits));
+    t.corner_sort = KeySort<uint64_t>::take(a, n, kEdgeKeyBits);
   }
   return t;
 }
 
 // the build steps of the edge table (F > 0; they enqueue on s).  k_in / v_in -> k_out / v_out: the one sort
 static inline int sort_edge_table(const MeshTables& t, int64_t F, hipStream_t s) {
-  size_t tb = t.edge_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(t.edge_sort.p, tb, t.k_in, t.k_out, t.v_in, t.v_out, (size_t)(3 * F), 0u, kEdgeKeyBits,
-                                      s, false));
-  return 0;
+  return t.edge_sort.run(t.k_in, t.k_out, t.v_in, t.v_out, 3 * F, kEdgeKeyBits, s);
 }
 static inline int build_edge_table(const MeshTables& t, const int32_t* faces, const int32_t* state, int64_t F, int64_t V,
                                    hipStream_t s) {

@@ -279,7 +279,7 @@ struct FillBuffers {
   MeshTables t;
   int *bflag, *bpos, *ent_slot, *next, *lab, *lead, *loop_no, *out_cnt, *in_cnt, *out_ent, *sel_len;
   int2 *ping, *pong;
-  SubWs slot_scan_temp, loop_scan_temp;
+  ExclusiveScan<int> slot_scan, loop_scan;     // each serves two runs
 };
 FillBuffers carve_fill(Arena& a, int64_t F, int64_t V) {
   const int64_t n = 3 * F;
@@ -289,7 +289,7 @@ FillBuffers carve_fill(Arena& a, int64_t F, int64_t V) {
           a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n),
           a.take<int>(V), a.take<int>(V), a.take<int>(V), a.take<int>(F),
           a.take<int2>(n), a.take<int2>(n),
-          a.take_ws(scan_temp_bytes<int>(n)), a.take_ws(scan_temp_bytes<int>(F))};
+          ExclusiveScan<int>::take(a, n), ExclusiveScan<int>::take(a, F)};
 }
 
 int fill_buffers(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, FillBuffers& b) {
@@ -301,12 +301,6 @@ int doubling_rounds(int64_t n) {
   int r = 1;
   while (((int64_t)1 << r) < n) ++r;
   return r;
-}
-
-int scan_i32(const SubWs& temp, const int* in, int* out, int64_t n, hipStream_t s) {
-  size_t tb = temp.bytes;
-  GEOBI_HIP(rocprim::exclusive_scan(temp.p, tb, in, out, 0, (size_t)n, rocprim::plus<int>(), s, false));
-  return 0;
 }
 
 // the rows V .. Vn - 1 of points_out over the plan in b
@@ -371,7 +365,7 @@ int geobi_fill_plan(const int32_t* faces, int64_t F, int64_t V, int max_hole_edg
   }
   fill_flags_kernel<<<grid_n, kT, 0, s>>>(b.t.k_out, b.t.v_out, n, b.bflag, b.counts);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_i32(b.slot_scan_temp, b.bflag, b.bpos, n, s));
+  GEOBI_TRY(b.slot_scan.run(b.bflag, b.bpos, s));
   fill_entries_kernel<<<grid_n, kT, 0, s>>>(faces, n, (int)V, b.bflag, b.bpos, b.ent_slot, b.out_cnt, b.in_cnt, b.out_ent);
   GEOBI_LAUNCH_OK();
   if (V > 0) {
@@ -399,13 +393,13 @@ int geobi_fill_plan(const int32_t* faces, int64_t F, int64_t V, int max_hole_edg
   }
   GEOBI_TRY(timer.mark());
   // loop tables, selection, per-slot results
-  GEOBI_TRY(scan_i32(b.slot_scan_temp, b.lead, b.loop_no, n, s));
+  GEOBI_TRY(b.slot_scan.run(b.lead, b.loop_no, s));
   fill_loops_kernel<<<grid_n, kT, 0, s>>>(cur, b.lead, b.loop_no, b.ent_slot, b.next, (int)F, b.loop_leader, b.loop_len, b.counts);
   GEOBI_LAUNCH_OK();
   fill_select_kernel<<<grid_f, kT, 0, s>>>(b.loop_len, (int)F, max_hole_edges, b.counts, b.sel, b.sel_len);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_i32(b.loop_scan_temp, b.sel, b.sel_id, F, s));
-  GEOBI_TRY(scan_i32(b.loop_scan_temp, b.sel_len, b.sel_off, F, s));
+  GEOBI_TRY(b.loop_scan.run(b.sel, b.sel_id, s));
+  GEOBI_TRY(b.loop_scan.run(b.sel_len, b.sel_off, s));
   fill_totals_kernel<<<grid_f, kT, 0, s>>>(b.sel, b.sel_len, b.sel_id, b.sel_off, (int)F, (int)V, b.sel_loop, b.counts);
   GEOBI_LAUNCH_OK();
   fill_slots_kernel<<<grid_n, kT, 0, s>>>(faces, n, (int)F, b.bflag, b.bpos, b.lab, cur, b.loop_no, b.loop_len, b.sel, b.sel_off,

@@ -8,7 +8,7 @@
 // the conv kernels apply implicitly, and the pooling layer drops them first too
 // (/root/reference/code/net_util.py:163).
 #include "common.h"
-#include "rocprim_temp.h"
+#include "device_steps.h"
 #include "../../include/geobi_hip.h"
 
 #include <cstring>
@@ -112,10 +112,10 @@ __global__ void reverse_index_kernel(const int32_t* __restrict__ rowptr, const i
   }
 }
 
-struct SortBuffers { uint64_t *k_in, *k_out; int32_t *v_in, *v_out; SubWs temp; };
+struct SortBuffers { uint64_t *k_in, *k_out; int32_t *v_in, *v_out; PairSort<uint64_t, int32_t> sort; };
 SortBuffers carve_sort(Arena& a, int64_t E) {
   return {a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<int32_t>(E), a.take<int32_t>(E),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int32_t>(E))};
+          PairSort<uint64_t, int32_t>::take(a, E)};
 }
 
 }  // namespace
@@ -160,9 +160,7 @@ int geobi_csr_from_coo(const int64_t* seg, const int64_t* nbr, int64_t E, int64_
   const int bits = key_bits(N);
   make_keys_kernel<<<cdiv(E, T), T, 0, s>>>(seg, nbr, E, N, drop_self, bits, sb.k_in, sb.v_in, bad);
   GEOBI_LAUNCH_OK();
-  size_t tb = sb.temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(sb.temp.p, tb, sb.k_in, sb.k_out, sb.v_in, eid, (size_t)E, 0u, (unsigned)(2 * bits), s,
-                                      false));
+  GEOBI_TRY(sb.sort.run(sb.k_in, sb.k_out, sb.v_in, eid, E, (unsigned)(2 * bits), s));
   unpack_sorted_kernel<<<cdiv(E, T), T, 0, s>>>(sb.k_out, E, bits, col);
   GEOBI_LAUNCH_OK();
   rowptr_search_kernel<<<cdiv(N + 1, T), T, 0, s>>>(sb.k_out, E, (int)N, bits, rowptr);
@@ -191,9 +189,7 @@ int geobi_csr_transpose(const int32_t* rowptr, const int32_t* col, int64_t N, in
   const int bits = key_bits(N);
   expand_keys_kernel<<<blocks, T, 0, s>>>(rowptr, col, (int)N, Ecap, bits, sb.k_in, sb.v_in);
   GEOBI_LAUNCH_OK();
-  size_t tb = sb.temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(sb.temp.p, tb, sb.k_in, sb.k_out, sb.v_in, pos_t, (size_t)Ecap, 0u,
-                                      (unsigned)(2 * bits), s, false));
+  GEOBI_TRY(sb.sort.run(sb.k_in, sb.k_out, sb.v_in, pos_t, Ecap, (unsigned)(2 * bits), s));
   // low 32 bits of the transposed key hold the original row = the neighbour in the transposed view
   unpack_sorted_kernel<<<cdiv(Ecap, T), T, 0, s>>>(sb.k_out, Ecap, bits, col_t);
   GEOBI_LAUNCH_OK();

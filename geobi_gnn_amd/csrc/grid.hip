@@ -24,7 +24,7 @@
 // holds is clamped into [0, T) before a target row is read.
 #include "common.h"
 #include "dist_pairs.h"
-#include "rocprim_temp.h"
+#include "device_steps.h"
 #include "../../include/geobi_hip.h"
 
 #include <math.h>
@@ -408,30 +408,28 @@ struct PlanBufs { Stat* partial; long long* sums; int* out; int* cnt; };
 PlanBufs carve_plan(Arena& a, int64_t F) {
   return {a.take<Stat>(kStatBlocks), a.take<long long>(kStatBlocks), a.take<int>(16), a.take<int>((size_t)F + 1)};
 }
-struct SortBufs { int *key_in, *val_in, *key_out; SubWs temp; };
+struct SortBufs { int *key_in, *val_in, *key_out; PairSort<int, int> sort; };
 SortBufs carve_sort(Arena& a, int64_t n) {
   return {a.take<int>((size_t)n), a.take<int>((size_t)n), a.take<int>((size_t)n),
-          a.take_ws(sort_pairs_temp_bytes<int, int>(n, kKeyBits))};
+          PairSort<int, int>::take(a, n, kKeyBits)};
 }
-struct TriBufs { int *cnt, *off; SubWs scan; SortBufs sort; };
+struct TriBufs { int *cnt, *off; IntScan scan; SortBufs sort; };
 TriBufs carve_tri(Arena& a, int64_t F) {
-  return {a.take<int>((size_t)F + 1), a.take<int>((size_t)F + 1), a.take_ws(scan_ws_bytes(F + 1)), carve_sort(a, kEntryCap * F)};
+  return {a.take<int>((size_t)F + 1), a.take<int>((size_t)F + 1), IntScan::take(a, F + 1), carve_sort(a, kEntryCap * F)};
 }
-struct SearchBufs { SortBufs sort; int *qorder, *flag, *rank; SubWs scan; };
+struct SearchBufs { SortBufs sort; int *qorder, *flag, *rank; IntScan scan; };
 SearchBufs carve_search(Arena& a, int64_t Q) {
   return {carve_sort(a, Q), a.take<int>((size_t)Q), a.take<int>((size_t)Q + 1), a.take<int>((size_t)Q + 1),
-          a.take_ws(scan_ws_bytes(Q + 1))};
+          IntScan::take(a, Q + 1)};
 }
 
 // one stable sort of n (cell, index) pairs: indices that ascend going in ascend inside every cell coming out
 int sort_cells(const SortBufs& b, int64_t n, int* val_out, hipStream_t s) {
   size_t need = 0;
-  GEOBI_HIP(rocprim::radix_sort_pairs(nullptr, need, b.key_in, b.key_out, b.val_in, val_out, (size_t)n, 0u, kKeyBits, s, false));
-  GEOBI_REQUIRE(need <= b.temp.bytes, "grid: the sort of %lld entries wants %zu bytes of temporary storage, %zu reserved",
-                (long long)n, need, b.temp.bytes);
-  size_t tb = b.temp.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.temp.p, tb, b.key_in, b.key_out, b.val_in, val_out, (size_t)n, 0u, kKeyBits, s, false));
-  return 0;
+  GEOBI_TRY(b.sort.need(n, &need));
+  GEOBI_REQUIRE(need <= b.sort.temp.bytes, "grid: the sort of %lld entries wants %zu bytes of temporary storage, %zu reserved",
+                (long long)n, need, b.sort.temp.bytes);
+  return b.sort.run(b.key_in, b.key_out, b.val_in, val_out, n, kKeyBits, s);
 }
 
 // the box of the finite targets -> the first words of a descriptor, the resolution rule applied; one read-back
@@ -485,7 +483,7 @@ int search(const char* fn, const Entries& en, const float* q, int64_t Q, int64_t
   grid_search_kernel<Entries><<<blocks, kThreads, 0, s>>>(g, en, q, b.qorder, (int)Q, (int)T, cell_start, order,
                                                           max_rings < 0 ? kDefaultRings : max_rings, dist, idx, b.flag);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(b.scan.p, b.scan.bytes, b.flag, b.rank, Q + 1, s));
+  GEOBI_TRY(b.scan.run(b.flag, b.rank, s));
   compact_left_kernel<<<blocks, kThreads, 0, s>>>(b.flag, b.rank, q, (int)Q, left, left_q, count);
   GEOBI_LAUNCH_OK();
   return 0;
@@ -597,7 +595,7 @@ int geobi_grid_triangles_build(const float* verts, const int32_t* fv, int64_t V,
   face_records_kernel<<<cdiv(F, kThreads), kThreads, 0, s>>>(verts, fv, (int)V, (int)F, (float4*)records);
   face_count_kernel<<<cdiv(F + 1, kThreads), kThreads, 0, s>>>(g, verts, fv, (int)V, (int)F, b.cnt);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(b.scan.p, b.scan.bytes, b.cnt, b.off, F + 1, s));
+  GEOBI_TRY(b.scan.run(b.cnt, b.off, s));
   if (E > 0) {
     face_emit_kernel<<<cdiv(F, kThreads), kThreads, 0, s>>>(g, verts, fv, (int)V, (int)F, b.off, (int)E, b.sort.key_in, b.sort.val_in);
     GEOBI_LAUNCH_OK();

@@ -52,18 +52,14 @@ static inline int build_pair_table(const MeshTables& t, int64_t F, int* locked, 
   const int n = (int)(3 * F);
   edge_heads_kernel<<<cdiv(n, kTableThreads), kTableThreads, 0, s>>>(t.k_out, n, t.p_in, locked, edge_count);
   GEOBI_LAUNCH_OK();
-  size_t tb = t.pair_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_keys(t.pair_sort.p, tb, t.p_in, t.p_out, (size_t)(2 * n), 0u, kEdgeKeyBits, s, false));
-  return 0;
+  return t.pair_sort.run(t.p_in, t.p_out, 2 * n, kEdgeKeyBits, s);
 }
 // fkeep, not_included (or NULL): see corner_keys_kernel
 static inline int build_corner_table(const MeshTables& t, const int32_t* faces, int64_t F, int64_t V, int* fkeep,
                                      int* not_included, hipStream_t s) {
   corner_keys_kernel<<<cdiv(F, kTableThreads), kTableThreads, 0, s>>>(faces, (int)F, (int)V, t.c_in, fkeep, not_included);
   GEOBI_LAUNCH_OK();
-  size_t tb = t.corner_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_keys(t.corner_sort.p, tb, t.c_in, t.c_out, (size_t)(3 * F), 0u, kEdgeKeyBits, s, false));
-  return 0;
+  return t.corner_sort.run(t.c_in, t.c_out, 3 * F, kEdgeKeyBits, s);
 }
 
 }  // namespace geobi

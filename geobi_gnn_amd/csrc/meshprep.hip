@@ -8,6 +8,7 @@
 // Integer results are exact; the graphs come out sorted and duplicate-free by construction (each node
 // repeatedly selects the smallest not-yet-emitted neighbour of its 1-ring), no global sort.
 #include "common.h"
+#include "device_steps.h"
 #include "../../include/geobi_hip.h"
 
 namespace geobi {
@@ -250,10 +251,10 @@ __global__ void calc_weight_parts_kernel(const float* __restrict__ pos, const fl
 }
 
 // n + 1 counts, with_cursor: the fill cursors of vertex_faces (cursor[n] doubles as the bad-index counter), and the
-// temporary of the scan over the counts
-struct CountBuffers { int *cnt, *cursor; SubWs temp; };
+// scan over the counts
+struct CountBuffers { int *cnt, *cursor; IntScan scan; };
 CountBuffers carve_counts(Arena& a, int64_t n, bool with_cursor) {
-  return {a.take<int>(n + 1), with_cursor ? a.take<int>(n + 1) : nullptr, a.take_ws(scan_ws_bytes(n + 1))};
+  return {a.take<int>(n + 1), with_cursor ? a.take<int>(n + 1) : nullptr, IntScan::take(a, n + 1)};
 }
 double* carve_partials(Arena& a, size_t n_parts) { return a.take<double>(n_parts * kPartials); }
 
@@ -286,7 +287,7 @@ int geobi_vertex_faces(const int32_t* fv, int64_t F, int64_t V, int32_t* rowptr,
   const int blocks = cdiv(F3 > 0 ? F3 : 1, 256);
   vf_count_kernel<<<blocks, 256, 0, s>>>(fv, F3, (int)V, cnt, cursor + V);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, rowptr, V + 1, s));
+  GEOBI_TRY(c.scan.run(cnt, rowptr, s));
   vf_fill_kernel<<<blocks, 256, 0, s>>>(fv, F3, (int)V, rowptr, cursor, list);
   GEOBI_LAUNCH_OK();
   vf_sort_kernel<<<cdiv(V, 128), 128, 0, s>>>(rowptr, (int)V, list);
@@ -351,7 +352,7 @@ int geobi_ring_graph_count(int kind, const int32_t* fv, const int32_t* rowptr_vf
   else
     ring_graph_kernel<1, 0><<<blocks, 128, 0, s>>>(fv, rowptr_vf, list, (int)n_nodes, cnt, nullptr, nullptr);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, rowptr_g, n_nodes + 1, s));
+  GEOBI_TRY(c.scan.run(cnt, rowptr_g, s));
   return 0;
 }
 

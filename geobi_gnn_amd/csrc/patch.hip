@@ -8,6 +8,7 @@
 // slot numbers (patch_grow_kernel).  Its sequential statement lives with the test infrastructure (oracle/oracle_c.c).
 
 #include "common.h"
+#include "device_steps.h"
 #include "../../include/geobi_hip.h"
 
 namespace geobi {
@@ -434,9 +435,9 @@ __global__ __launch_bounds__(kGrowThreads) void patch_grow_kernel(
   }
 }
 
-struct SubmeshBuffers { int *first, *flag, *rank; SubWs temp; };
+struct SubmeshBuffers { int *first, *flag, *rank; IntScan scan; };
 SubmeshBuffers carve_submesh(Arena& a, int64_t n_sel, int64_t V) {
-  return {a.take<int>(V), a.take<int>(3 * n_sel + 1), a.take<int>(3 * n_sel + 1), a.take_ws(scan_ws_bytes(3 * n_sel + 1))};
+  return {a.take<int>(V), a.take<int>(3 * n_sel + 1), a.take<int>(3 * n_sel + 1), IntScan::take(a, 3 * n_sel + 1)};
 }
 
 }  // namespace
@@ -511,7 +512,7 @@ int geobi_submesh(const int32_t* fv, const int32_t* sel, int64_t n_sel, int64_t 
   GEOBI_LAUNCH_OK();
   submesh_flag_kernel<<<blocks, 256, 0, s>>>(fv, sel, n_sel, first, flag);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(b.temp.p, b.temp.bytes, flag, rank, 3 * n_sel + 1, s));
+  GEOBI_TRY(b.scan.run(flag, rank, s));
   submesh_assign_kernel<<<blocks, 256, 0, s>>>(fv, sel, n_sel, first, rank, v_idx, f_sub, count);
   GEOBI_LAUNCH_OK();
   return 0;

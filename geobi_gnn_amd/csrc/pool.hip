@@ -15,7 +15,7 @@
 // order, computed by rounds of mutual proposals.  oracle/oracle_c.c:oracle_greedy_sorted is the
 // sequential statement of the same rule.
 #include "common.h"
-#include "rocprim_temp.h"
+#include "device_steps.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -1118,9 +1118,8 @@ static hipError_t lookback_scan(const int* in, int* out, int64_t n, hipStream_t 
 }
 
 
-static hipError_t exclusive_scan_int(void* temp, size_t& tb, const int* in, int* out, int64_t n, hipStream_t s) {
+static hipError_t exclusive_scan_int(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s) {
   if (n <= kSmallScan) {
-    if (temp == nullptr) { tb = 16; return hipSuccess; }
     const bool lookback = g_scan_lookback.on();
     if (lookback && n > kOneBlockScan) {
       prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_LOOKBACK);
@@ -1134,18 +1133,17 @@ static hipError_t exclusive_scan_int(void* temp, size_t& tb, const int* in, int*
     return hipGetLastError();
   }
   prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_ROCPRIM);
-  const hipError_t e = rocprim::exclusive_scan(temp, tb, in, out, 0, (size_t)n, rocprim::plus<int>(), s, false);
+  const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, out, 0, (size_t)n, rocprim::plus<int>(), s, false);
   prof_end(PROF_POOL_FORM, s);
   return e;
 }
 
 }  // namespace
 
-size_t scan_ws_bytes(int64_t n) { return n <= kSmallScan ? 16 : scan_temp_bytes<int>(n); }
+size_t scan_ws_bytes(int64_t n) { return n <= kSmallScan ? 16 : ExclusiveScan<int>::temp_bytes(n); }
 
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s) {
-  size_t tb = temp_bytes;
-  GEOBI_HIP(exclusive_scan_int(temp, tb, in, out, n, s));
+  GEOBI_HIP(exclusive_scan_int(temp, temp_bytes, in, out, n, s));
   return 0;
 }
 
@@ -1215,15 +1213,15 @@ static void launch_match_rounds(const int32_t* rowptr, const int32_t* col, const
 
 namespace {
 struct MatchBuffers { int *prop0, *prop1; };            // the proposals, ping-pong
-struct CoarsenBuffers { MatchBuffers m; int *flag, *sz, *rank, *offs; SubWs temp_a, temp_b; };
+struct CoarsenBuffers { MatchBuffers m; int *flag, *sz, *rank, *offs; IntScan scan_a, scan_b; };
 MatchBuffers carve_match(Arena& a, int64_t N) { return {a.take<int>(N), a.take<int>(N)}; }
 CoarsenBuffers carve_match_coarsen(Arena& a, int64_t N) {
   return {carve_match(a, N), a.take<int>(N + 1), a.take<int>(N + 1), a.take<int>(N + 1), a.take<int>(N + 1),
-          a.take_ws(scan_ws_bytes(N + 1)), a.take_ws(scan_ws_bytes(N + 1))};
+          IntScan::take(a, N + 1), IntScan::take(a, N + 1)};
 }
-// n counts (or flags) and the temporary of the scan over them
-struct CountScan { int* cnt; SubWs temp; };
-CountScan carve_count_scan(Arena& a, int64_t n) { return {a.take<int>(n), a.take_ws(scan_ws_bytes(n))}; }
+// n counts (or flags) and the scan over them
+struct CountScan { int* cnt; IntScan scan; };
+CountScan carve_count_scan(Arena& a, int64_t n) { return {a.take<int>(n), IntScan::take(a, n)}; }
 }  // namespace
 
 size_t match_ws_bytes(int64_t N) { return carve_bytes([&](Arena& a) { carve_match(a, N); }); }
@@ -1289,8 +1287,8 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
     prof_end(PROF_POOL_FORM, s);
     GEOBI_LAUNCH_OK();
   } else {
-    GEOBI_TRY(scan_exclusive_i32(b.temp_a.p, b.temp_a.bytes, flag, rank, N + 1, s));
-    GEOBI_TRY(scan_exclusive_i32(b.temp_b.p, b.temp_b.bytes, sz, offs, N + 1, s));
+    GEOBI_TRY(b.scan_a.run(flag, rank, s));
+    GEOBI_TRY(b.scan_b.run(sz, offs, s));
   }
   match_lists_kernel<<<blocks, 256, 0, s>>>(state, cluster_final, rank, offs, (int)N, cnew, counters + 1, segptr,
                                             members);
@@ -1320,16 +1318,16 @@ int relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t*
     rep_flag_kernel<<<blocks, 256, 0, s>>>(cluster, (int)N, flag);
   }
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(b.flag.temp.p, b.flag.temp.bytes, flag, rank, N, s));
+  GEOBI_TRY(b.flag.scan.run(flag, rank, s));
   relabel_apply_kernel<<<blocks, 256, 0, s>>>(cluster, flag, rank, (int)N, cnew, count);
   GEOBI_LAUNCH_OK();
   return 0;
 }
 
 namespace {
-struct KeySortBuffers { uint64_t *k_in, *k_out; SubWs temp; };
+struct KeySortBuffers { uint64_t *k_in, *k_out; KeySort<uint64_t> sort; };
 KeySortBuffers carve_key_sort(Arena& a, int64_t n) {
-  return {a.take<uint64_t>(n), a.take<uint64_t>(n), a.take_ws(sort_keys_temp_bytes<uint64_t>(n))};
+  return {a.take<uint64_t>(n), a.take<uint64_t>(n), KeySort<uint64_t>::take(a, n)};
 }
 }  // namespace
 
@@ -1345,12 +1343,11 @@ int segment_csr(const int32_t* seg, int64_t n, int64_t nseg, int32_t* segptr, in
   const KeySortBuffers b = carve_key_sort(a, n);
   GEOBI_WS_CHECK("segment_csr", a, ws, ws_bytes);
   uint64_t *k_in = b.k_in, *k_out = b.k_out;
-  size_t tb = b.temp.bytes;
   const int bits = key_bits(n);                 // member index < n
   const int sbits = key_bits(nseg);
   seg_keys_kernel<<<cdiv(n, 256), 256, 0, s>>>(seg, n, bits, k_in);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(rocprim::radix_sort_keys(b.temp.p, tb, k_in, k_out, (size_t)n, 0u, (unsigned)(bits + sbits), s, false));
+  GEOBI_TRY(b.sort.run(k_in, k_out, n, (unsigned)(bits + sbits), s));
   seg_unpack_kernel<<<cdiv(n, 256), 256, 0, s>>>(k_out, n, bits, members);
   seg_ptr_kernel<<<cdiv(nseg + 1, 256), 256, 0, s>>>(k_out, n, (int)nseg, bits, segptr);
   GEOBI_LAUNCH_OK();
@@ -1369,7 +1366,7 @@ int segment_csr_pairs(const int32_t* cnew, const int32_t* raw, int64_t N, int64_
   pair_count_kernel<<<cdiv(nseg, 256), 256, 0, s>>>(cnew, raw, (int)N, (int)nseg, cnt);
   pair_mark_kernel<<<cdiv(N, 256), 256, 0, s>>>(cnew, raw, (int)N, cnt);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, segptr, nseg, s));
+  GEOBI_TRY(c.scan.run(cnt, segptr, s));
   pair_fill_kernel<<<cdiv(N, 256), 256, 0, s>>>(cnew, raw, (int)N, (int)nseg, segptr, members);
   GEOBI_LAUNCH_OK();
   return 0;
@@ -1385,7 +1382,7 @@ int segment_csr_compose(const int32_t* segptr1, const int32_t* members1, const i
   int* cnt = c.cnt;
   compose_count_kernel<<<cdiv(nseg2, 256), 256, 0, s>>>(segptr1, segptr2, members2, (int)nseg2, cnt);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(c.temp.p, c.temp.bytes, cnt, segptr12, nseg2, s));
+  GEOBI_TRY(c.scan.run(cnt, segptr12, s));
   compose_fill_kernel<<<cdiv(nseg2, 256), 256, 0, s>>>(segptr1, members1, segptr2, members2, (int)nseg2,
                                                        (int)n_fine, segptr12, members12);
   GEOBI_LAUNCH_OK();
@@ -1495,7 +1492,7 @@ int pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32_t* me
                                                      nullptr, nullptr, tcol, tw, overflow, nullptr, rowinfo,
                                                      (const int4*)rowinfo_in);
     GEOBI_LAUNCH_OK();
-    GEOBI_TRY(scan_exclusive_i32(b.cnt.temp.p, b.cnt.temp.bytes, cnt, rowptr_c, nbound + 1, s));
+    GEOBI_TRY(b.cnt.scan.run(cnt, rowptr_c, s));
     pool_edge_compact_kernel<<<cdiv(nbound * 16, 256), 256, 0, s>>>(ncount, (int)nbound, rowptr_c, rowinfo, tcol,
                                                                     w ? tw : nullptr, row_c, col_c, w_c, count,
                                                                     publish_src, publish_host, publish_seq);
@@ -1505,7 +1502,7 @@ int pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32_t* me
   pool_edge_rows_kernel<0><<<blocks, 256, 0, s>>>(cnew, segptr, members, rowptr, col, w, ncount, (int)nbound, cnt,
                                                    nullptr, nullptr, nullptr, nullptr, overflow, nullptr, rowinfo, nullptr);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(b.cnt.temp.p, b.cnt.temp.bytes, cnt, rowptr_c, nbound + 1, s));
+  GEOBI_TRY(b.cnt.scan.run(cnt, rowptr_c, s));
   pool_edge_rows_kernel<1><<<blocks, 256, 0, s>>>(cnew, segptr, members, rowptr, col, w, ncount, (int)nbound, cnt,
                                                    rowptr_c, row_c, col_c, w_c, overflow, count, rowinfo, nullptr);
   GEOBI_LAUNCH_OK();
@@ -1513,10 +1510,10 @@ int pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32_t* me
 }
 
 namespace {
-struct PoolEdgeBuffers { uint64_t *k_in, *k_out, *ukeys; int *v_in, *v_out, *rank; CountScan head; SubWs t_sort; };
+struct PoolEdgeBuffers { uint64_t *k_in, *k_out, *ukeys; int *v_in, *v_out, *rank; CountScan head; PairSort<uint64_t, int> sort; };
 PoolEdgeBuffers carve_pool_edge(Arena& a, int64_t E) {
   return {a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<int>(E), a.take<int>(E), a.take<int>(E),
-          carve_count_scan(a, E), a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(E))};
+          carve_count_scan(a, E), PairSort<uint64_t, int>::take(a, E)};
 }
 }  // namespace
 
@@ -1537,16 +1534,14 @@ int pool_edge(const int32_t* cnew, const int32_t* row, const int32_t* col, const
   GEOBI_WS_CHECK("pool_edge", a, ws, ws_bytes);
   uint64_t *k_in = b.k_in, *k_out = b.k_out, *ukeys = b.ukeys;
   int *v_in = b.v_in, *v_out = b.v_out, *head = b.head.cnt, *rank = b.rank;
-  size_t tb_sort = b.t_sort.bytes;
   int blocks = cdiv(E, 256);
   const int bits = key_bits(nmax);
   pool_edge_keys_kernel<<<blocks, 256, 0, s>>>(cnew, row, col, E, bits, k_in, v_in);
   GEOBI_LAUNCH_OK();
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.t_sort.p, tb_sort, k_in, k_out, v_in, v_out, (size_t)E, 0u, (unsigned)(2 * bits),
-                                      s, false));
+  GEOBI_TRY(b.sort.run(k_in, k_out, v_in, v_out, E, (unsigned)(2 * bits), s));
   pool_edge_heads_kernel<<<blocks, 256, 0, s>>>(k_out, E, head);
   GEOBI_LAUNCH_OK();
-  GEOBI_TRY(scan_exclusive_i32(b.head.temp.p, b.head.temp.bytes, head, rank, E, s));
+  GEOBI_TRY(b.head.scan.run(head, rank, s));
   pool_edge_emit_kernel<<<blocks, 256, 0, s>>>(k_out, v_out, head, rank, w, E, row_c, col_c, w_c, ukeys, count,
                                                bits);
   GEOBI_LAUNCH_OK();

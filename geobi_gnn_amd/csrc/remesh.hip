@@ -348,7 +348,7 @@ struct RemeshBuffers {
   int *idx_in, *order, *rank, *state, *qc, *qd;
   // per face
   int* fedge;
-  SubWs rank_sort;
+  PairSort<uint64_t, int> rank_sort;
 };
 RemeshBuffers carve_remesh(Arena& a, int64_t F, int64_t V) {
   const int64_t n = 3 * F;
@@ -358,7 +358,7 @@ RemeshBuffers carve_remesh(Arena& a, int64_t F, int64_t V) {
           a.take<uint64_t>(n), a.take<uint64_t>(n),
           a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n),
           a.take<int>(F),
-          a.take_ws(sort_pairs_temp_bytes<uint64_t, int>(n, 64))};
+          PairSort<uint64_t, int>::take(a, n, 64)};
 }
 
 int remesh_buffers(const char* what, int64_t F, int64_t V, void* ws, size_t ws_bytes, RemeshBuffers& b) {
@@ -455,7 +455,6 @@ int geobi_flip_plan(const int32_t* faces, const float* points, const int32_t* lo
   RemeshBuffers b;
   GEOBI_TRY(remesh_buffers("flip_plan", F, V, ws, ws_bytes, b));
   const int n = (int)(3 * F), n_pairs = 2 * n;
-  size_t tb;
   StageTimer timer(stage_ms, s);
   GEOBI_TRY(timer.mark());
   GEOBI_TRY(build_tables(b, faces, F, V, false, 0, s));
@@ -466,9 +465,7 @@ int geobi_flip_plan(const int32_t* faces, const float* points, const int32_t* lo
   flip_candidates_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, n, points, faces, (int)F, (int)V, b.t.p_out, n_pairs,
                                                    lock, use_sharp, c2, b.key_in, b.idx_in, b.qc, b.qd, b.counts);
   GEOBI_LAUNCH_OK();
-  tb = b.rank_sort.bytes;
-  GEOBI_HIP(rocprim::radix_sort_pairs(b.rank_sort.p, tb, b.key_in, b.key_out, b.idx_in, b.order, (size_t)n, 0u, 64u, s,
-                                      false));
+  GEOBI_TRY(b.rank_sort.run(b.key_in, b.key_out, b.idx_in, b.order, s));
   rank_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.key_out, b.order, n, b.rank, b.state);
   GEOBI_LAUNCH_OK();
   GEOBI_TRY(timer.mark());

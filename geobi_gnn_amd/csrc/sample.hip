@@ -33,7 +33,7 @@
 #include "common.h"
 #include "../../include/geobi_hip.h"
 #include "philox.h"
-#include "rocprim_temp.h"
+#include "device_steps.h"
 
 #include <math.h>
 
@@ -251,21 +251,21 @@ __global__ __launch_bounds__(kThreads) void sample_surface_parts_kernel(
 
 struct WeightBuffers {
   double *d, *partial;
-  SubWs scan;
+  InclusiveScan<long long> scan;
 };
 WeightBuffers carve_weights(Arena& a, int64_t F) {
-  return {a.take<double>(F), a.take<double>(kMaxBlocks), a.take_ws(inclusive_scan_temp_bytes<long long>(F))};
+  return {a.take<double>(F), a.take<double>(kMaxBlocks), InclusiveScan<long long>::take(a, F)};
 }
 
 struct WeightPartsBuffers {
   double *d, *partial;
   long long* scan;
-  SubWs temp;
+  InclusiveScan<long long> scan_step;
 };
 // partial: one maximum per workgroup, at most F / kThreads + P of them
 WeightPartsBuffers carve_weights_parts(Arena& a, int64_t F, int P) {
   return {a.take<double>(F), a.take<double>(F / kThreads + P), a.take<long long>(F),
-          a.take_ws(inclusive_scan_temp_bytes<long long>(F))};
+          InclusiveScan<long long>::take(a, F)};
 }
 
 // the face pointer of a union batch: parts_check, and it starts at row 0
@@ -308,10 +308,7 @@ int geobi_sample_weights(const float* points, const int32_t* fv, int64_t F, int6
   GEOBI_LAUNCH_OK();
   face_weight_kernel<<<blocks, kThreads, 0, s>>>(w.d, (int)F, exponent, (long long*)weight);
   GEOBI_LAUNCH_OK();
-  size_t tb = w.scan.bytes;
-  GEOBI_HIP(rocprim::inclusive_scan(w.scan.p, tb, (long long*)weight, (long long*)cum, (size_t)F, rocprim::plus<long long>(), s,
-                                    false));
-  return 0;
+  return w.scan.run((long long*)weight, (long long*)cum, s);
 }
 
 int geobi_sample_surface(const float* points, const int32_t* fv, const void* cum, int64_t F, int64_t V, int64_t N,
@@ -369,8 +366,7 @@ int geobi_sample_weights_parts(const float* points, const int32_t* fv, const int
     GEOBI_LAUNCH_OK();
     used += blocks;
   }
-  size_t tb = w.temp.bytes;
-  GEOBI_HIP(rocprim::inclusive_scan(w.temp.p, tb, (long long*)weight, w.scan, (size_t)F, rocprim::plus<long long>(), s, false));
+  GEOBI_TRY(w.scan_step.run((long long*)weight, w.scan, s));
   for (int base = 0; base < P; base += kMaxParts) {
     PartTable<int> tab;
     fill_parts(&tab, fptr, base, P);

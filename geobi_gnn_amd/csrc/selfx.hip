@@ -22,7 +22,7 @@
 // n <= kTile; a pair row is written only below max_pairs; cnt / offs are indexed f * S + slice with f < F, slice < S.
 #include "common.h"
 #include "pair_slices.h"
-#include "rocprim_temp.h"
+#include "device_steps.h"
 #include "../../include/geobi_hip.h"
 
 #include <math.h>
@@ -303,11 +303,11 @@ __global__ __launch_bounds__(kThreads) void selfx_totals_kernel(const int* __res
 struct SelfxBuffers {
   int* incl;
   long long *cnt, *offs;        // [F * S], face-major and slice-minor
-  SubWs scan;
+  ExclusiveScan<long long> scan;
 };
 SelfxBuffers carve_selfx(Arena& a, int64_t F, int slices) {
   const size_t n = (size_t)F * slices;
-  return {a.take<int>(F), a.take<long long>(n), a.take<long long>(n), a.take_ws(scan_temp_bytes<long long>(n))};
+  return {a.take<int>(F), a.take<long long>(n), a.take<long long>(n), ExclusiveScan<long long>::take(a, n)};
 }
 
 Slicing selfx_slices(int64_t F) { return choose_slices(F, F, kQpl, kTile); }
@@ -353,8 +353,7 @@ int geobi_self_intersections(const float* verts, const int32_t* faces, const int
   GEOBI_LAUNCH_OK();
   selfx_walk_kernel<false><<<grid, kThreads, 0, s>>>(verts, faces, b.incl, n, sl.tiles_per_slice, hits, b.cnt, nullptr, nullptr, 0, c);
   GEOBI_LAUNCH_OK();
-  size_t tb = b.scan.bytes;
-  GEOBI_HIP(rocprim::exclusive_scan(b.scan.p, tb, b.cnt, b.offs, 0ll, (size_t)cells, rocprim::plus<long long>(), s, false));
+  GEOBI_TRY(b.scan.run(b.cnt, b.offs, s));
   if (max_pairs > 0) {
     selfx_walk_kernel<true><<<grid, kThreads, 0, s>>>(verts, faces, b.incl, n, sl.tiles_per_slice, nullptr, nullptr, b.offs, pairs,
                                                       (long long)max_pairs, nullptr);

@@ -261,15 +261,14 @@ struct SubdivBuffers {
   // scratch of the plan
   uint64_t* p_in;
   int* children;
-  SubWs pair_sort_temp, slot_scan_temp, face_scan_temp;
+  KeySort<uint64_t> pair_sort; ExclusiveScan<int> slot_scan, face_scan;
 };
 SubdivBuffers carve_subdiv(Arena& a, int64_t F) {
   return {carve_tables<false, false>(a, F),
           a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(3 * F), a.take<int>(F), a.take<int>(kCounts),
           a.take<uint64_t>(6 * F),
           a.take<uint64_t>(6 * F), a.take<int>(F),
-          a.take_ws(sort_keys_temp_bytes<uint64_t>(6 * F, kPairBits)),
-          a.take_ws(scan_temp_bytes<int>(3 * F)), a.take_ws(scan_temp_bytes<int>(F))};
+          KeySort<uint64_t>::take(a, 6 * F, kPairBits), ExclusiveScan<int>::take(a, 3 * F), ExclusiveScan<int>::take(a, F)};
 }
 
 int subdiv_buffers(const char* what, int64_t F, void* ws, size_t ws_bytes, SubdivBuffers& b) {
@@ -335,22 +334,18 @@ int geobi_subdiv_plan(const int32_t* faces, const float* points, int64_t F, int6
   GEOBI_HIP(hipMemsetAsync(b.counts, 0, sizeof(int) * kCounts, s));
   subdiv_flags_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, n, points, adaptive, L2, b.split, b.counts);
   GEOBI_LAUNCH_OK();
-  size_t tb = b.slot_scan_temp.bytes;
-  GEOBI_HIP(rocprim::exclusive_scan(b.slot_scan_temp.p, tb, b.split, b.rank, 0, (size_t)n, rocprim::plus<int>(), s, false));
+  GEOBI_TRY(b.slot_scan.run(b.split, b.rank, s));
   subdiv_slot_mid_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, b.t.v_out, n, points, adaptive, L2, b.split, b.rank, b.slot_mid);
   GEOBI_LAUNCH_OK();
   subdiv_child_count_kernel<<<cdiv(F, kT), kT, 0, s>>>(b.slot_mid, (int)F, b.children);
   GEOBI_LAUNCH_OK();
-  tb = b.face_scan_temp.bytes;
-  GEOBI_HIP(rocprim::exclusive_scan(b.face_scan_temp.p, tb, b.children, b.first_child, 0, (size_t)F, rocprim::plus<int>(), s,
-                                    false));
+  GEOBI_TRY(b.face_scan.run(b.children, b.first_child, s));
   subdiv_totals_kernel<<<1, 1, 0, s>>>(b.children, b.first_child, (int)F, (int)V, loop != 0 ? 1 : 0, b.counts);
   GEOBI_LAUNCH_OK();
   if (loop != 0) {
     subdiv_pairs_kernel<<<cdiv(n, kT), kT, 0, s>>>(b.t.k_out, n, b.p_in);
     GEOBI_LAUNCH_OK();
-    tb = b.pair_sort_temp.bytes;
-    GEOBI_HIP(rocprim::radix_sort_keys(b.pair_sort_temp.p, tb, b.p_in, b.p_out, (size_t)(2 * n), 0u, kPairBits, s, false));
+    GEOBI_TRY(b.pair_sort.run(b.p_in, b.p_out, s));
   }
   GEOBI_HIP(hipMemcpyAsync(counts, b.counts, sizeof(int) * kCounts, hipMemcpyDeviceToDevice, s));
   GEOBI_TRY(timer.mark());

@@ -313,13 +313,14 @@ def case_grid(dev):
 
 
 def test_guard_band_and_short_workspace(dev, monkeypatch):
-    W.CASES['grid'] = case_grid
+    name = 'grid_left_over'                          # a case of this module's beside that module's own 'grid'
+    W.CASES[name] = case_grid
     try:
-        W.test_guard_band('grid', dev, monkeypatch)
-        W.test_short_workspace('grid', dev, monkeypatch)
+        W.test_guard_band(name, dev, monkeypatch)
+        W.test_short_workspace(name, dev, monkeypatch)
     finally:
-        del W.CASES['grid']
-        W._REF.pop('grid', None)
+        del W.CASES[name]
+        W._REF.pop(name, None)
 
 
 def test_a_guard_band_around_the_outputs(dev):

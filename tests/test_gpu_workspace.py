@@ -16,8 +16,8 @@ Short        request k of a case gets its first nbytes - 512 bytes (the requests
 
 Shapes: the icosphere of meshgen.icosphere(2) (42 vertices, 80 faces), for subdivide, decimate and the remeshing steps with its
 vertices jittered by a fixed seed, so that edges are short and long and (after the collapses) valences flip; node, edge, row and segment counts of 63, 64 and 65
-(4 n crosses a 256-byte line between 64 and 65); 2^18 + 1 for relabel, match_coarsen, vertex_faces and segment_csr,
-whose scan or sort temporary comes from rocPRIM above 2^18; 33 parts (two launches of 32) for the part tables; FeaSt at
+(4 n crosses a 256-byte line between 64 and 65); 2^18 + 1 for relabel, match_coarsen, vertex_faces, segment_csr and the
+grid search, whose scan or sort temporary comes from rocPRIM above 2^18; 33 parts (two launches of 32) for the part tables; FeaSt at
 (6, 32) and (128, 128) with 65 nodes; the heads at the fused width (32, 1024) and at (8, 2048), 65 rows; row_loss also at
 65 * 1024 + 1 rows, the first count whose workspace is larger than 512 bytes."""
 import re
@@ -196,6 +196,54 @@ def case_remesh(dev):
             meshremesh.mesh_stats(pts, faces, low, high, device=dev)]
 
 
+def case_fill(dev):
+    """the sphere without three faces: three loops, found alone and then closed"""
+    from geobi_gnn_amd import meshfill
+    pts, faces = _sphere(dev)
+    faces = faces[[f for f in range(faces.shape[0]) if f not in (0, 30, 60)]]
+    loops = meshfill.boundary_loops(faces, pts.shape[0], device=dev)
+    r = meshfill.fill_holes(pts, faces, device=dev)
+    assert loops.counts['loops'] > 0 and r.counts['filled_loops'] > 0
+    return [loops, r.points, r.faces, r.new_vertex_loop, r.new_face_loop, r.loops, r.counts]      # not r.ws, the plan's memory
+
+
+def case_selfx(dev):
+    """the sphere and two triangles that pass through it (and through each other)"""
+    from geobi_gnn_amd import meshselfx
+    pts, faces = _sphere(dev)
+    V = pts.shape[0]
+    extra = _t([[-2, -2, 0.1], [2, -2, 0.1], [0, 3, 0.1], [0.2, -2, -2], [0.2, 2, -2], [0.2, 0, 3]], dev, torch.float32)
+    crossing = _t([[V, V + 1, V + 2], [V + 3, V + 4, V + 5]], dev, torch.int64)
+    r = meshselfx.self_intersections(torch.cat([pts, extra]), torch.cat([faces, crossing]), max_pairs=65, device=dev)
+    assert r.counts['pairs'] > 0
+    return r
+
+
+def case_sample(dev):
+    from geobi_gnn_amd import meshsample
+    pts, faces = _sphere(dev)
+    out = [meshsample.sample_surface(pts, faces, 65, seed=11)]
+    # 33 strips of 1 .. 3 faces over vertices of their own: two launches of the 32-part table
+    n_faces = [1 + (k % 3) for k in range(33)]
+    fptr = [0] + [int(v) for v in np.cumsum(n_faces)]
+    first_vertex = np.cumsum([0] + [n + 2 for n in n_faces])
+    union = torch.cat([_strip(n + 2, dev) + int(v0) for n, v0 in zip(n_faces, first_vertex)])
+    out.append(meshsample.sample_surface_parts(_rand(dev, 8, int(first_vertex[-1]), 3), union, fptr, 5, seed=11,
+                                               stream_ids=list(range(33))))
+    return out
+
+
+def case_grid(dev):
+    """both grids over the sphere, 65 queries each; 2^18 + 1 queries: the rank scan of the search takes its temporary from
+    rocPRIM"""
+    from geobi_gnn_amd import meshgrid
+    pts, faces = _sphere(dev)
+    points, triangles = meshgrid.PointGrid(pts), meshgrid.TriangleGrid(pts, faces)
+    q = _rand(dev, 9, 65, 3)
+    return [points.cell_start, points.order, triangles.cell_start, triangles.order, triangles.records,
+            points.nearest(q), triangles.nearest(q), points.nearest(_rand(dev, 10, BIG, 3))]
+
+
 def case_meshprep(dev):
     from geobi_gnn_amd import meshprep
     out = []
@@ -370,7 +418,8 @@ def case_row_loss(dev):
     return [ops.row_loss(_rand(dev, n, n, 3), _rand(dev, n + 1, n, 3), 0) for n in COUNTS + (65 * 1024 + 1,)]
 
 
-CASES = {f.__name__[5:]: f for f in (case_clean, case_topo, case_subdiv, case_decim, case_remesh, case_meshprep, case_submesh, case_mesheval, case_parts,
+CASES = {f.__name__[5:]: f for f in (case_clean, case_topo, case_subdiv, case_decim, case_remesh, case_fill, case_selfx, case_sample,
+                                     case_grid, case_meshprep, case_submesh, case_mesheval, case_parts,
                                      case_filters, case_vertex_update, case_graph, case_pool, case_pool_big,
                                      case_feast_small, case_feast_wide, case_head_fused, case_head_unfused, case_row_loss)}
 
