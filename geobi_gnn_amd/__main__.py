@@ -9,10 +9,11 @@
   python -m geobi_gnn_amd noise --data_dir DIR [--levels 0.1,0.2,0.3] [--kind gaussian] [--direction normal] [--seed 1]
   python -m geobi_gnn_amd clean --data_dir DIR [--out_dir DIR/clean] [--weld_tol 0] [--no_weld] [--no_manifold]
   python -m geobi_gnn_amd denoise ... --clean [--weld_tol 0] [--no_weld] [--no_manifold] [--orient] [--min_component N]
-  python -m geobi_gnn_amd clean ... [--orient] [--min_component N] [--drop_intersecting]
-  python -m geobi_gnn_amd info --data_dir DIR [--weld_tol 0] [--no_weld] [--intersections] [--gpu -1]
+  python -m geobi_gnn_amd clean ... [--orient] [--min_component N] [--drop_intersecting] [--outward]
+  python -m geobi_gnn_amd info --data_dir DIR [--weld_tol 0] [--no_weld] [--intersections] [--solid] [--gpu -1]
   python -m geobi_gnn_amd sample --data_dir DIR [--out_dir DIR/samples] --n N [--seed 1] [--normals] [--gpu -1]
   python -m geobi_gnn_amd eval ... --free --samples N [--seed 1]
+  python -m geobi_gnn_amd eval ... --free --signed
   python -m geobi_gnn_amd align ... --samples N [--seed 1]
   python -m geobi_gnn_amd subdivide --data_dir DIR [--out_dir DIR/subdivided] [--levels 1] [--scheme midpoint|loop]
   python -m geobi_gnn_amd subdivide --data_dir DIR (--max_edge L | --max_edge_diag R) [--max_rounds 16]
@@ -213,8 +214,9 @@ def evaluate(opt):
     stats = {}
     t0 = time.time()
     try:
+        more = {'signed': True} if opt.signed else {}
         rows, _ = mesheval.eval_dirs(opt.result_dir, opt.original_dir, device=dev, stats=stats, align=opt.align, free=opt.free,
-                                     estimate_scale=opt.scale, samples=opt.samples, seed=opt.seed, index=_index_of(opt))
+                                     estimate_scale=opt.scale, samples=opt.samples, seed=opt.seed, index=_index_of(opt), **more)
     except (ValueError, OSError, GeobiError) as e:
         print('eval failed: %s' % e, file=sys.stderr)
         return 1
@@ -339,8 +341,11 @@ def _weld_tol(opt):
 
 def _topo_args(opt):
     """--orient / --min_component / --drop_intersecting as clean_mesh takes them (none is in the options without its flag)"""
-    return {'orient': getattr(opt, 'orient', False), 'min_component': getattr(opt, 'min_component', 0),
+    args = {'orient': getattr(opt, 'orient', False), 'min_component': getattr(opt, 'min_component', 0),
             'drop_intersecting': getattr(opt, 'drop_intersecting', False)}
+    if getattr(opt, 'outward', False):         # --outward (meshwind.py): the key exists only with the flag
+        args['outward'] = True
+    return args
 
 
 def _host_mesh(result):
@@ -358,6 +363,8 @@ def _clean_line(cleaned, V, F, out_file):
             ('flipped', 'flipped'), ('nonorientable', 'nonorientable'), ('components', 'components'), ('small', 'faces_dropped')))
     if 'intersecting' in c:    # only with --drop_intersecting
         line += ',  intersecting: %d' % c['intersecting']
+    if t is not None and 'turned' in t:        # only with --outward
+        line += ',  turned: %d,  open_components: %d' % (t['turned'], t['open_components'])
     return line
 
 
@@ -436,6 +443,7 @@ def fill(opt):
 INFO_KEYS = ('vertices_used', 'faces', 'degenerate', 'edges', 'boundary_edges', 'complex_edges', 'inconsistent_edges',
              'components', 'orient_components', 'nonorientable', 'would_flip', 'euler')
 INTERSECTION_KEYS = ('intersecting_pairs', 'intersecting_faces', 'folded_pairs')      # info --intersections
+SOLID_KEYS = ('closed_components', 'inward_components')                                # info --solid, behind volume
 
 
 def info(opt):
@@ -449,12 +457,15 @@ def info(opt):
 
     def one(path, skip):
         points, faces = meshio.read_obj(path)
-        r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev, intersections=opt.intersections)
+        more = {'solid': True} if opt.solid else {}
+        r = meshtopo.mesh_report(points, faces, weld_tol=weld_tol, device=dev, intersections=opt.intersections, **more)
         line = ("V: %7d,  F: %7d,  %s,  closed: %s,  '%s'"
                 % (points.shape[0], faces.shape[0], ',  '.join('%s: %d' % (k, r[k]) for k in INFO_KEYS),
                    'yes' if r['closed'] else 'no', os.path.basename(path)))
         if opt.intersections:
             line += ',  ' + ',  '.join('%s: %d' % (k, r[k]) for k in INTERSECTION_KEYS)
+        if opt.solid:
+            line += ',  volume: %.9g,  ' % r['volume'] + ',  '.join('%s: %d' % (k, r[k]) for k in SOLID_KEYS)
         print(line, flush=True)
 
     return folders.walk(files, one)
@@ -675,6 +686,9 @@ def _add_clean_flags(p, given=False):
     p.add_argument('--drop_intersecting', action=_TrueGiven, default=argparse.SUPPRESS,
                    help='drop the faces that intersect another face (all pairs, on the welded table); `fill` closes the '
                         'holes this opens')
+    p.add_argument('--outward', action=_TrueGiven, default=argparse.SUPPRESS,
+                   help='--orient, and then every closed part is wound so that its normals point out of the solid: a part of '
+                        'negative volume is turned, and a part nested at odd depth in the others (a cavity) is turned back')
 
 
 def build_parser():
@@ -716,6 +730,9 @@ def build_parser():
     e.add_argument('--samples', type=_samples_arg, default=0, metavar='N',
                    help='with --free: also score from N points drawn by area on each surface; writes ErrorInfo_sampled.txt '
                         '(with --align the ground truth is aligned to as its vertices plus its samples)')
+    e.add_argument('--signed', action='store_true',
+                   help="with --free: also the mean SIGNED distance of the result's vertices to the ground truth (negative "
+                        'inside), the share of vertices inside and the volume ratio; writes ErrorInfo_signed.txt')
     e.add_argument('--seed', type=int, default=1, help='with --samples: the seed of the draw')
     e.add_argument('--index', type=str, choices=('none', 'grid'), default='none',
                    help='none: the searches walk all pairs; grid: a uniform grid in front of them, the same bits (DESIGN.md 4u)')
@@ -768,6 +785,9 @@ def build_parser():
     i.add_argument('--intersections', action='store_true',
                    help='also count the pairs of faces that intersect, the faces in such a pair and the pairs folded flat onto '
                         'each other (all pairs of faces: F * F box tests)')
+    i.add_argument('--solid', action='store_true',
+                   help='also the volume the closed parts enclose as the file winds them, their number, and how many of them '
+                        '`clean --outward` would turn (all pairs of parts and faces)')
     i.add_argument('--gpu', type=int, default=-1)
     i.set_defaults(fn=info)
     u = sub.add_parser('subdivide', help='make every mesh denser on the device: midpoint or Loop passes, or split the edges '
@@ -857,7 +877,7 @@ def parse_args(argv=None):
         if opt.method in ('bnf', 'gnf') and (opt.normal_iters < 0 or not opt.sigma_r > 0 or not opt.sigma_s > 0 or opt.n_iter < 0):
             ap.error('denoise: --normal_iters and --n_iter are not negative, --sigma_r and --sigma_s positive')
         if not opt.clean:
-            for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component', 'drop_intersecting'):
+            for flag in ('weld_tol', 'no_weld', 'no_manifold', 'orient', 'min_component', 'drop_intersecting', 'outward'):
                 if getattr(opt, flag + '_given', False):
                     ap.error('denoise: --%s needs --clean' % flag)
     if opt.command == 'remesh' and opt.index != 'none' and not opt.project:
@@ -866,6 +886,8 @@ def parse_args(argv=None):
         ap.error('eval: --scale needs --align')
     if opt.command == 'eval' and opt.samples and not opt.free:
         ap.error('eval: --samples needs --free')
+    if opt.command == 'eval' and opt.signed and not opt.free:
+        ap.error('eval: --signed needs --free')
     if opt.command in ('eval', 'align', 'sample') and not 0 <= opt.seed < 2 ** 64:
         ap.error('%s: --seed is a 64-bit number that is not negative, got %d' % (opt.command, opt.seed))
     if opt.command == 'align':

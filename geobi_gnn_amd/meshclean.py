@@ -41,7 +41,7 @@ class CleanResult(object):
     vertex_src [V'] (input index of every cleaned vertex), face_map [F'] (input index of every kept face), canon [V];
     counts: welded, degenerate, nonmanifold, unreferenced, rounds (and intersecting with ``drop_intersecting``).  With ``orient`` / ``min_component``: topology, a dict of
     flipped, nonorientable, orient_components, orient_rounds (orient) and components, components_dropped, faces_dropped,
-    component_rounds (min_component), else None; face_flip [F] (input numbering: 1 where the winding was reversed)."""
+    component_rounds (min_component), turned and open_components (outward), else None; face_flip [F] (input numbering: 1 where the winding was reversed)."""
 
     def __init__(self, points, faces, vertex_map, vertex_src, face_map, canon, counts, topology=None, face_flip=None):
         self.points, self.faces = points, faces
@@ -130,7 +130,7 @@ def check_weld_tol(what, weld_tol):
 
 
 def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, device=None, orient=False, min_component=0,
-               drop_intersecting=False):
+               drop_intersecting=False, outward=False):
     """(points [V, 3], faces [F, 3]) -> CleanResult, on the device.  ValueError: non-finite points, a face index outside
     [0, V), weld_tol < 0, max_rounds < 1, min_component < 0.  GeobiError: the library's errors -- a grid quotient outside
     int32, more than ``max_rounds`` rounds of the half-edge rule (a chain of faces that each share a directed edge with the
@@ -141,8 +141,11 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
     edge-connected part of fewer than m faces are dropped (a face they displaced under the rule does not come back).
     ``drop_intersecting``: after the rule and before ``min_component``, every kept face that intersects another kept face
     (``meshselfx``, DESIGN.md 4t) is dropped -- all of them together, in one pass -- and counted under ``intersecting``;
-    ``meshfill`` closes the holes this opens."""
+    ``meshfill`` closes the holes this opens.  ``outward``: implies ``orient``, and ``meshwind.outward_device`` stands in
+    ``orient_device``'s place: every closed part is then wound so that its normals point out of the solid (DESIGN.md 4v);
+    ``face_flip`` carries both flips, ``topology`` gains ``turned`` and ``open_components``."""
     dev = meshin.default_device(device)
+    orient = orient or bool(outward)
     check_weld_tol('clean_mesh', weld_tol)
     if int(max_rounds) < 1:
         raise ValueError('clean_mesh: max_rounds = %r (at least 1)' % (max_rounds,))
@@ -164,7 +167,15 @@ def clean_mesh(points, faces, weld_tol=0.0, manifold=True, max_rounds=1024, devi
         # the stages hand on tables padded to one row for F == 0: only their F rows [:F] are a mesh
         if orient:
             fc, _, _ = resolve_faces(fv, canon, V, False, max_rounds)           # the corners through canon
-            oriented, face_flip, _, ocounts, orient_rounds = meshtopo.orient_device(fc[:F], V)
+            if outward and F > 0:
+                from . import meshwind
+                oriented, face_flip, _, wcounts_host = meshwind.outward_device(pts, fc[:F].contiguous(), V)
+                ocounts = torch.tensor([wcounts_host[k] for k in ('components', 'nonorientable', 'flipped')], dtype=torch.int32,
+                                       device=dev)
+                orient_rounds = wcounts_host['rounds']
+                topology['turned'], topology['open_components'] = wcounts_host['turned'], wcounts_host['open_components']
+            else:
+                oriented, face_flip, _, ocounts, orient_rounds = meshtopo.orient_device(fc[:F], V)
             fv = oriented[:F]
             tcounts.append(ocounts)
             topology['orient_rounds'] = orient_rounds

@@ -227,6 +227,61 @@ def eval_free(result_points, result_faces, gt_points, gt_faces, device=None, ali
     return row
 
 
+def eval_signed(result_points, result_faces, gt_points, gt_faces, device=None, index=None):
+    """Which SIDE of the ground truth a result lies on (meshwind) -- what no unsigned distance shows of a
+    result that shrank.  Sizes may differ, as for eval_free.  Returns a dict:
+
+      num_v, signed (mean over the result's vertices of their distance to the ground-truth surface, NEGATIVE for a vertex
+      inside it: winding number above 1/2), signed_norm (over scale, the ground truth's mean edge length), inside (the share
+      of vertices inside), volume, volume_gt (the volume the closed components enclose as each file winds them),
+      volume_ratio (result over ground truth; None when either mesh has a component that is not closed or the ground
+      truth encloses nothing), scale.
+
+    The distances are point_to_mesh's (index='grid': through a grid, the same bits); the two sums go through
+    dist_summary."""
+    from . import meshwind
+    index = meshgrid.check_index_word(index, 'eval_signed')
+    dev = meshin.default_device(device, result_points)
+    pr, fr = meshin.finite_mesh(result_points, result_faces, dev, 'eval_signed')
+    po, fo = meshin.finite_mesh(gt_points, gt_faces, dev, 'eval_signed')
+    if min(pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]) == 0:
+        raise ValueError('eval_signed: empty mesh (result V = %d, F = %d, ground truth V = %d, F = %d)'
+                         % (pr.shape[0], fr.shape[0], po.shape[0], fo.shape[0]))
+    with torch.cuda.device(dev):
+        dist, _ = point_to_mesh(pr, po, fo, index=index)
+        within = meshwind.winding_device(pr, po, fo) > 0.5
+        zero = torch.zeros_like(dist)
+        scale = mean_edge_length(po, fo)
+        host = torch.cat([scale.double(), dist_summary(torch.where(within, zero, dist)), dist_summary(torch.where(within, dist, zero)),
+                          within.sum().double().reshape(1)]).tolist()
+        vol_r, closed_r, parts_r = meshwind.enclosed_volume(pr, fr)
+        vol_o, closed_o, parts_o = meshwind.enclosed_volume(po, fo)
+    V, scale = pr.shape[0], host[0]
+    signed = (host[1] - host[3]) / V
+    ratio = vol_r / vol_o if closed_r == parts_r and closed_o == parts_o and vol_o != 0.0 else None
+    return {'num_v': V, 'signed': signed, 'signed_norm': signed / scale, 'inside': host[5] / V, 'volume': vol_r,
+            'volume_gt': vol_o, 'volume_ratio': ratio, 'scale': scale}
+
+
+_SIGNED_COLUMNS = ('num_v', 'signed', 'signed_norm', 'inside', 'volume_ratio')
+_SIGNED_FMT = '{0:<{1}}  {2:>7}  {3:10.6f}  {4:9.6f}  {5:.6f}  {6}\n'
+
+
+def _ratio_text(ratio):
+    return '-' if ratio is None else '%.6f' % ratio
+
+
+def signed_totals(rows):
+    """Vertex-count weighted means of eval_signed's columns; volume_ratio is the ratio of the summed volumes over the files
+    that have one (None when none has)."""
+    n = sum(r['num_v'] for r in rows)
+    tot = {k: sum(r[k] * r['num_v'] for r in rows) / n for k in ('signed', 'signed_norm', 'inside')}
+    with_ratio = [r for r in rows if r['volume_ratio'] is not None]
+    tot.update(num_v=n, volume_ratio=(sum(r['volume'] for r in with_ratio) / sum(r['volume_gt'] for r in with_ratio)
+                                      if with_ratio and sum(r['volume_gt'] for r in with_ratio) != 0.0 else None))
+    return tot
+
+
 def eval_sampled(result_points, result_faces, gt_points, gt_faces, n_samples, seed=1, stream_id=0, device=None, index=None):
     """eval_free's distances measured from points drawn by area on the two SURFACES (meshsample.sample_surface) instead of
     from their vertices: two meshes that share every vertex and differ inside their triangles are `surf = 0` to eval_free
@@ -335,7 +390,7 @@ def align_line(name, width, info):
 
 
 def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, free=False, estimate_scale=False, samples=0,
-              seed=1, index=None):
+              seed=1, index=None, signed=False):
     """eval_denoising_result(dir_result, dir_original): every pair of pair_files scored with eval_pair, the per-file
     and totals lines printed and written to dir_result/ErrorInfo_h.txt in the reference's format with three columns
     appended (surf, surf_norm, hausdorff).  A result whose V or F differs from its ground truth is a ValueError naming
@@ -349,11 +404,16 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
     as well, the alignment target is the ground truth's vertices followed by its draw-0 samples (align(samples=)), which
     is another alignment and so other numbers in both files.  Returns (rows, totals) -- rows carry 'file', and with
     samples eval_sampled's keys.  index='grid': the scoring searches go through grids (eval_pair, eval_free, eval_sampled);
-    every file keeps its bytes."""
+    every file keeps its bytes.  signed (with free): every pair is ALSO scored with eval_signed and
+    dir_result/ErrorInfo_signed.txt is written beside ErrorInfo_free.txt, whose bytes the flag does not change; the signed
+    keys of a row and of the totals carry the suffix _sd where eval_free has a key of that name."""
     import time
     index = meshgrid.check_index_word(index, 'eval')
     if samples and not free:
         raise ValueError('eval: samples need the free scoring (eval_free pairs nothing by index; neither do samples)')
+    if signed and not free:
+        raise ValueError('eval: signed needs the free scoring (eval_signed pairs nothing by index)')
+    signed_rows = []
     pairs = pair_files(dir_result, dir_original)
     if not pairs:
         print('--- empty data ---')
@@ -380,6 +440,9 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
         if samples:
             sampled = eval_sampled(pr, fr, po, fo, samples, seed=seed, stream_id=stream_id, device=dev, index=index)
             row.update((k, sampled[k]) for k in _SAMPLED_COLUMNS)
+        if signed:
+            signed_rows.append(eval_signed(pr, fr, po, fo, device=dev, index=index))
+            row.update((k, signed_rows[-1][k]) for k in _SIGNED_COLUMNS[1:])
         if align:
             row.update((k, infos[-1][k]) for k in _ALIGN_KEYS)
         row['file'] = os.path.basename(file_r)
@@ -422,6 +485,17 @@ def eval_dirs(dir_result, dir_original, device=None, stats=None, align=False, fr
                 f.write('\n')
                 for row in rows:
                     f.write(_SAMPLED_FMT.format(row['file'], width, *[row[k] for k in _SAMPLED_COLUMNS]))
+            print('%s saved.' % file_txt)
+        if signed:
+            tot_sd = signed_totals(signed_rows)
+            tot.update((k, tot_sd[k]) for k in _SIGNED_COLUMNS[1:])
+            file_txt = os.path.join(dir_result, 'ErrorInfo_signed.txt')
+            with open(file_txt, 'w') as f:
+                f.write('Error_signed:  num_v  signed  signed_norm  inside  volume_ratio \n')
+                f.write(_SIGNED_FMT.format('', width, *[tot_sd[k] for k in _SIGNED_COLUMNS[:-1]] + [_ratio_text(tot_sd['volume_ratio'])]))
+                f.write('\n')
+                for row, sd in zip(rows, signed_rows):
+                    f.write(_SIGNED_FMT.format(row['file'], width, *[sd[k] for k in _SIGNED_COLUMNS[:-1]] + [_ratio_text(sd['volume_ratio'])]))
             print('%s saved.' % file_txt)
         return rows, tot
     tot = totals(rows)

@@ -113,13 +113,15 @@ def face_components(faces, V, state=None, min_component=0, max_rounds=256, devic
                                               'faces_dropped': faces_dropped, 'rounds': rounds})
 
 
-def mesh_report(points, faces, weld_tol=0.0, max_rounds=256, device=None, intersections=False):
+def mesh_report(points, faces, weld_tol=0.0, max_rounds=256, device=None, intersections=False, solid=False):
     """(points [V, 3], faces [F, 3]) -> dict: vertices_used, faces, degenerate; edges, boundary_edges, complex_edges,
     inconsistent_edges; components, orient_components, nonorientable, would_flip; euler = vertices_used - edges + faces;
     closed = no boundary and no complex edge.  Computed after the weld (``weld_tol`` as in ``clean_mesh``), degenerate
     faces excluded and no face dropped for its half-edges.  ``intersections``: also intersecting_pairs, intersecting_faces
     and folded_pairs (pairs that share an edge and lie flat on each other), from ``meshselfx``'s all-pairs search on the
-    same welded table."""
+    same welded table.  ``solid``: also volume (the sum of volume6 / 6 over the closed components as the file
+    winds them), closed_components and inward_components (the components ``meshwind.orient_outward`` would leave reversed),
+    from ``meshwind`` on the same welded table."""
     _check_rounds('mesh_report', max_rounds)
     dev = meshin.default_device(device)
     meshclean.check_weld_tol('mesh_report', weld_tol)
@@ -141,9 +143,21 @@ def mesh_report(points, faces, weld_tol=0.0, max_rounds=256, device=None, inters
         if intersections:
             from . import meshselfx
             x = dict(zip(meshselfx.COUNT_KEYS, L.read_i64(meshselfx.search_device(pts, fc[:F], state[:F] if F else None)[2])))
+        if solid:
+            from . import meshwind
+            s = {'volume': 0.0, 'closed_components': 0, 'inward_components': 0}
+            if F:
+                _, _, label, wc = meshwind.outward_device(pts, fc[:F].contiguous(), V, state[:F].contiguous(), max_rounds)
+                # the file's own winding: the volume of a component the file winds inconsistently is not counted
+                v6, is_closed, consistent = meshwind.part_solids_device(pts, fc[:F].contiguous(), label, state[:F].contiguous())
+                whole = (is_closed[:F] != 0) & (consistent[:F] != 0) & (label == torch.arange(F, dtype=torch.int32, device=dev))
+                s = {'volume': float((v6[:F] * whole).sum() / 6.0), 'closed_components': wc['closed_components'],
+                     'inward_components': wc['turned']}
     report = {'vertices_used': c[4], 'faces': c[5], 'degenerate': c[6], 'edges': c[0], 'boundary_edges': c[1],
             'complex_edges': c[2], 'inconsistent_edges': c[3], 'components': c[7], 'orient_components': c[8],
             'nonorientable': c[9], 'would_flip': c[10], 'euler': c[4] - c[0] + c[5], 'closed': c[1] == 0 and c[2] == 0}
     if intersections:
         report.update(intersecting_pairs=x['pairs'], intersecting_faces=x['faces_hit'], folded_pairs=x['pairs_k2'])
+    if solid:
+        report.update(s)
     return report

@@ -1174,6 +1174,44 @@ int geobi_self_intersections(const float* verts, const int32_t* faces, const int
                              int32_t* hits, int32_t* pairs, int64_t max_pairs, void* counts, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---------------------------------------------------------------- winding numbers ----
+ * The generalised winding number (Jacobson et al. 2013) of query points q [Q, 3] float32 against the mesh (verts [V, 3]
+ * float32, faces [F, 3] int32 range-checked by the caller): the sum of the signed solid angles of the faces seen from the
+ * query, over 4 pi.  On a closed surface wound counter-clockwise seen from outside it is 1 inside and 0 outside; it needs
+ * neither a closed nor a clean surface.  All pairs (csrc/winding.hip); tests/wind_model.py restates every rule in numpy.
+ *   faces        a face takes part when its state is 1 (state == NULL: all), its three ids differ and lie in [0, V).
+ *                With face_part [F] and query_part [Q] both given, a pair whose parts are equal is skipped.
+ *   term         a, b, c = the fp64 differences of the float32 corners and the float32 query (exact), no FMA contraction:
+ *                det = (ax*(by*cz - bz*cy) + ay*(bz*cx - bx*cz)) + az*(bx*cy - by*cx);  (u . w) = (ux*wx + uy*wy) + uz*wz;
+ *                la = sqrt(a . a), lb, lc likewise;  den = (la*(lb*lc) + (b . c)*la) + ((a . b)*lc + (c . a)*lb);
+ *                theta = 2 * atan2(det, den).  det == 0: the term is 0 (a query in the face's plane, on the face included:
+ *                the principal value).  den is symmetric in b and c: a reversed face gives the negated term exactly.
+ *   sum          integers: term = llrint(theta / (4 pi) * 2^40), |term| <= 2^39; the terms are added as int64 and
+ *                w [Q] (DEVICE fp64) = sum * 2^-40.  The answer therefore does not depend on the slicing of the faces
+ *                (geobi_winding_number_slices(Q, F): the rule of geobi_nearest_slices, a pure host function): a query gets
+ *                the same bits alone and in a batch.  F <= 2^23 (|sum| <= 2^62) -- more is refused; Q, V <= GEOBI_MAX_NODES.
+ * Q == 0 does nothing; F == 0 answers zeros; neither needs a workspace.
+ *   geobi_part_solids  per component of geobi_topo_orient's label [F] (the lowest face of the component, -1 for a face
+ *                that is not included; state as given to it), at the rows x == label[x] (the other rows: 0):
+ *                volume6 [F] fp64 = the sum over the component's faces of det(v0 - o, v1 - o, v2 - o), det as above on fp64
+ *                differences of float32 corners, o the first corner of face x; the faces in ascending order, face rank r
+ *                into partial sum r mod 64, then the 64 partial sums added in ascending order from 0.0 (one wave, no
+ *                float atomics).  closed [F] int32 = 1 iff every edge of the component has exactly two claimants;
+ *                consistent [F] int32 = 1 iff no edge with exactly two claimants is walked the same way by both.
+ *   geobi_flip_faces   faces_out (may be faces) = faces with corners 1 and 2 swapped where flip_of_label[label[f]] != 0
+ *                (label outside [0, F): never), and flip_io[f] ^= 1 there.                                                */
+int geobi_winding_number_slices(int64_t Q, int64_t F);
+size_t geobi_winding_number_ws_bytes(int64_t Q, int64_t F);
+int geobi_winding_number(const float* q, const float* verts, const int32_t* faces, const int32_t* state,
+                         const int32_t* face_part, const int32_t* query_part, int64_t Q, int64_t V, int64_t F, void* w,
+                         void* ws, size_t ws_bytes, void* stream);
+size_t geobi_part_solids_ws_bytes(int64_t F);
+int geobi_part_solids(const float* verts, const int32_t* faces, const int32_t* state, const int32_t* label, int64_t V,
+                      int64_t F, void* volume6, int32_t* closed, int32_t* consistent, void* ws, size_t ws_bytes,
+                      void* stream);
+int geobi_flip_faces(const int32_t* faces, const int32_t* label, const int32_t* flip_of_label, int64_t F,
+                     int32_t* faces_out, int32_t* flip_io, void* stream);
+
 /* ---------------------------------------------------------------- dense helpers ------------
  * Plain fp32 MFMA GEMMs used by the layers above, exported for tests and profiling.            */
 int geobi_gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N,
