@@ -12,7 +12,7 @@ mkdir -p "$HERE/build"
 # every header is a dependency of every object (feast_dev.h is shared by feast.hip and feast_fused.hip; a stale
 # object would ship in the in-tree .so), and so is this script (compiler flags)
 HDRS=("$HERE"/*.h "$HERE/../../include"/*.h "$HERE/build.sh")
-for f in capi executor graph gemm feast feast_fused pool geom head_fused meshprep patch dist chamfer reg icp noise sample surfpoints filter guided clean topo subdiv decim remesh fill project selfx grid winding; do
+for f in capi executor graph gemm feast feast_fused pool scan geom head_fused meshprep patch dist chamfer reg icp noise sample surfpoints filter guided clean topo subdiv decim remesh fill project selfx grid winding; do
   src="$HERE/$f.hip"; obj="$HERE/build/$f.o"
   stale=0
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ]; then stale=1; fi

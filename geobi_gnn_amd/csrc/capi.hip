@@ -336,6 +336,14 @@ int geobi_debug_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, v
   GEOBI_REQUIRE(ws_bytes >= scan_ws_bytes(n), "%s: workspace too small (%zu < %zu)", __func__, ws_bytes, scan_ws_bytes(n));
   return scan_exclusive_i32(ws, ws_bytes, in, out, n, as_stream(stream));
 }
+int geobi_debug_scan_exclusive_i32_pair(const int32_t* in_a, const int32_t* in_b, int32_t* out_a, int32_t* out_b, int64_t n,
+                                        void* stream) {
+  GEOBI_SIZES(0, n);
+  if (n <= 0) return 0;
+  GEOBI_NOTNULL(in_a); GEOBI_NOTNULL(in_b); GEOBI_NOTNULL(out_a); GEOBI_NOTNULL(out_b);
+  GEOBI_REQUIRE(n <= kSmallScan, "%s: n = %lld, the pair scan takes at most 2^18 elements", __func__, (long long)n);
+  return scan_exclusive_i32_pair(in_a, in_b, out_a, out_b, n, as_stream(stream));
+}
 
 size_t geobi_relabel_ws_bytes(int64_t N) { return relabel_ws_bytes(N); }
 int geobi_relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t* cnew, int32_t* count,

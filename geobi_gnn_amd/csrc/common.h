@@ -212,7 +212,7 @@ __device__ __forceinline__ double fold_ascending(const double* __restrict__ part
 
 // ---- optional per-kernel timing for bench.py's roofline object (events on the launch stream)
 enum ProfKernel { PROF_NONE = 0, PROF_AGG_FWD = 1, PROF_AGG_BWD = 2, PROF_ROWPASS = 3, PROF_GEMM = 4, PROF_POOL_FORM = 5 };
-// tags of PROF_POOL_FORM (pool.hip): which form of a scan / of match_coarsen's tail a call took
+// tags of PROF_POOL_FORM (scan.hip, pool.hip):which form of a scan / of match_coarsen's tail a call took
 enum PoolForm {
   POOL_FORM_SCAN_ONE_BLOCK = 1, POOL_FORM_SCAN_LOOKBACK = 2, POOL_FORM_SCAN_ROCPRIM = 3,
   POOL_FORM_MATCH_SCANFREE = 4, POOL_FORM_MATCH_TWOPASS_DUAL = 5
@@ -414,8 +414,7 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
 int match_heavy_edge(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, int rounds, int init,
                      int32_t* cluster, int32_t* cluster_final, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
 void set_match_round_cap(int cap);
-void set_match_scanfree(int on);      // test hooks: 1 / 0 force the form, < 0 = as the environment says
-void set_scan_lookback(int on);
+void set_match_scanfree(int on);      // test hook: 1 / 0 force the form, < 0 = as the environment says
 size_t relabel_ws_bytes(int64_t N);
 int relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t* cnew, int32_t* count, void* ws,
                     size_t ws_bytes,
@@ -455,9 +454,13 @@ size_t pool_edge_ws_bytes(int64_t E);
 int pool_edge(const int32_t* cnew, const int32_t* row, const int32_t* col, const float* w, int64_t E, int64_t nmax,
               int32_t* rowptr_c, int32_t* row_c, int32_t* col_c, float* w_c, int32_t* count, void* ws,
               size_t ws_bytes, hipStream_t s);
-// pool.hip: exclusive int scan shared with meshprep.hip (single launch below 2^18 elements)
+// scan.hip: the library's exclusive int scan, run through IntScan of device_steps.h (its own kernels, one launch and a
+// 16-byte temporary, up to kSmallScan elements; rocPRIM above), and two scans of n <= kSmallScan elements in one launch
+constexpr int64_t kSmallScan = 1 << 18;
 size_t scan_ws_bytes(int64_t n);
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s);
+int scan_exclusive_i32_pair(const int* in_a, const int* in_b, int* out_a, int* out_b, int64_t n, hipStream_t s);
+void set_scan_lookback(int on);       // test hook: 1 / 0 force the look-back form, < 0 = as the environment says
 // capi.hip: the one check of host part pointers (P >= 1, not NULL, start >= 0, no empty part, GEOBI_MAX_NODES rows);
 // the entry points that take a union batch (dist.hip, chamfer.hip, icp.hip) run it first and rely on it
 int parts_check(const char* fn, const int64_t* qptr, const int64_t* tptr, int P);

@@ -77,8 +77,9 @@ struct PrimScan {
 template <typename T> using ExclusiveScan = PrimScan<T, false>;
 template <typename T> using InclusiveScan = PrimScan<T, true>;
 
-// ---- the library's own exclusive int scan (pool.hip): one block, look-back or rocPRIM by size.  Not ExclusiveScan<int>:
-// below 2^18 elements another kernel runs and the temporary is 16 bytes.
+// ---- the library's own exclusive int scan (scan.hip): one block up to 2^14 elements, the look-back kernel up to 2^18,
+// rocPRIM (ExclusiveScan<int>'s call and size) above.  Not ExclusiveScan<int>: below 2^18 elements another kernel runs
+// and the temporary is 16 bytes.
 struct IntScan {
   SubWs temp; int64_t n;
   int run(const int* in, int* out, int64_t n_run, hipStream_t s) const {

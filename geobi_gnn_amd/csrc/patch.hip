@@ -7,6 +7,7 @@
 // visiting order); since round 4 it runs on the device as well, ring by ring, with the visiting order recovered from
 // slot numbers (patch_grow_kernel).  Its sequential statement lives with the test infrastructure (oracle/oracle_c.c).
 
+#include "block_scan.h"
 #include "common.h"
 #include "device_steps.h"
 #include "../../include/geobi_hip.h"
@@ -196,12 +197,7 @@ __device__ __forceinline__ int grow_tab_rest(int* t_id, int* t_val, int size, un
 
 // exclusive prefix of one int per lane over the wave; total = the wave's sum
 __device__ __forceinline__ int grow_wave_scan(int c, int lane, int& total) {
-  int incl = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
+  const int incl = wave_inclusive_scan(c, lane);
   total = __shfl(incl, 63, 64);
   return incl - c;
 }

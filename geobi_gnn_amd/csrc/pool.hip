@@ -14,6 +14,10 @@
 // (weight desc, min(u,v) asc, max(u,v) asc) -- i.e. greedy matching in globally descending edge
 // order, computed by rounds of mutual proposals.  oracle/oracle_c.c:oracle_greedy_sorted is the
 // sequential statement of the same rule.
+//
+// The count-to-offset scans of these steps are IntScan records (device_steps.h) and scan_exclusive_i32_pair; their
+// kernels live in scan.hip.  Only the scan-free matching pair scans in place, with block_scan.h.
+#include "block_scan.h"
 #include "common.h"
 #include "device_steps.h"
 
@@ -27,8 +31,8 @@ namespace {
 
 constexpr uint64_t kSentinel = ~0ull;
 
-// A/B knobs with a test hook: the environment decides (unset or non-zero = on) until geobi_set_* forces a form
-Knob g_scan_lookback{"GEOBI_SCAN_LOOKBACK", 1}, g_match_scanfree{"GEOBI_MATCH_SCANFREE", 1};
+// A/B knob with a test hook: the environment decides (unset or non-zero = on) until geobi_set_match_scanfree forces a form
+Knob g_match_scanfree{"GEOBI_MATCH_SCANFREE", 1};
 
 static inline int key_bits(int64_t N) {   // (1 << bits) > N: see graph.hip
   int b = 1;
@@ -281,25 +285,6 @@ __global__ void match_lists_kernel(const int* __restrict__ state, const int* __r
 // three, and no single-workgroup walk over the whole array.
 constexpr int kMaxScanBlocks = 4096;
 
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int* s_wave, int& total) {
-  // 256 threads = 4 waves; returns the exclusive prefix of v inside the block and the block total
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    int t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) { const int t = s_wave[w]; off += w < wave ? t : 0; tot += t; }
-  __syncthreads();
-  total = tot;
-  return off + inc - v;
-}
-
 __global__ __launch_bounds__(256) void match_commit_scan_kernel(const int* __restrict__ prop, int N,
                                                                 int* __restrict__ cluster, int* __restrict__ remaining,
                                                                 int* __restrict__ final, int* __restrict__ lrank,
@@ -323,8 +308,8 @@ __global__ __launch_bounds__(256) void match_commit_scan_kernel(const int* __res
     size = rep ? ((st >= 0 && st != u) ? 2 : 1) : 0;
   }
   int tr, to;
-  const int pr = block_exclusive_scan_256(rep, s_wave, tr);
-  const int po = block_exclusive_scan_256(size, s_wave, to);
+  const int pr = block_exclusive_scan<4>(rep, s_wave, tr);
+  const int po = block_exclusive_scan<4>(size, s_wave, to);
   if (u < N) { lrank[u] = pr; loffs[u] = po; }
   if (threadIdx.x == 0) { bt_rank[blockIdx.x] = tr; bt_offs[blockIdx.x] = to; }
 }
@@ -345,8 +330,8 @@ __global__ __launch_bounds__(256) void match_lists_scan_kernel(const int* __rest
     const int i = base + threadIdx.x;
     const int vr = i < nblocks ? bt_rank[i] : 0, vo = i < nblocks ? bt_offs[i] : 0;
     int tr, to;
-    const int pr = block_exclusive_scan_256(vr, s_wave, tr);
-    const int po = block_exclusive_scan_256(vo, s_wave, to);
+    const int pr = block_exclusive_scan<4>(vr, s_wave, tr);
+    const int po = block_exclusive_scan<4>(vo, s_wave, to);
     if (i < nblocks) { s_rank[i] = carry_r + pr; s_offs[i] = carry_o + po; }
     carry_r += tr; carry_o += to;
   }
@@ -837,315 +822,7 @@ __global__ void gather_f32_kernel(const float* __restrict__ src, const int* __re
   if (i < n) { int k = idx[i]; dst[i] = k >= 0 ? src[k] : 0.f; }
 }
 
-// Exclusive scan of up to a few hundred thousand ints in ONE launch (one 1024-thread block walking the
-// array with a running carry).  The graph levels of this path have <= ~10^5 nodes, where two rocPRIM
-// launches (init + lookback) cost more in launch latency than the scan itself.  Each thread owns 16
-// consecutive ints per step (16 K per step for the block); the loads of the next step are issued before
-// the current one is scanned, the carry lives in a register and the wave sums are double-buffered, so
-// a step costs one barrier.
-__global__ __launch_bounds__(1024) void small_exclusive_scan_kernel(const int* __restrict__ in, int* __restrict__ out,
-                                                                    int64_t n) {
-  constexpr int EPT = 16, CHUNK = 1024 * EPT;
-  __shared__ int wsum[2][16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool vec = ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0;
-  int cur[EPT], nxt[EPT];
-  auto load = [&](int64_t base, int* v) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * EPT;
-    if (vec && i0 + EPT <= n) {
-#pragma unroll
-      for (int q = 0; q < EPT / 4; ++q) {
-        int4 t = *reinterpret_cast<const int4*>(in + i0 + 4 * q);
-        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < EPT; ++q) v[q] = (i0 + q < n) ? in[i0 + q] : 0;
-    }
-  };
-  int carry = 0, buf = 0;
-  load(0, cur);
-  for (int64_t base = 0; base < n; base += CHUNK, buf ^= 1) {
-    if (base + CHUNK < n) load(base + CHUNK, nxt);
-    int tsum = 0;
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) tsum += cur[q];
-    int inc = tsum;                                   // inclusive scan of thread sums inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      int t = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += t;
-    }
-    if (lane == 63) wsum[buf][wave] = inc;
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const int t = wsum[buf][w];
-      woff += w < wave ? t : 0;
-      total += t;
-    }
-    int ex = carry + woff + inc - tsum;               // exclusive prefix of this thread's first element
-    carry += total;
-    const int64_t i0 = base + (int64_t)threadIdx.x * EPT;
-    if (vec && i0 + EPT <= n) {
-#pragma unroll
-      for (int q = 0; q < EPT / 4; ++q) {
-        int4 t;
-        t.x = ex; ex += cur[4 * q];
-        t.y = ex; ex += cur[4 * q + 1];
-        t.z = ex; ex += cur[4 * q + 2];
-        t.w = ex; ex += cur[4 * q + 3];
-        *reinterpret_cast<int4*>(out + i0 + 4 * q) = t;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < EPT; ++q) {
-        if (i0 + q < n) out[i0 + q] = ex;
-        ex += cur[q];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) cur[q] = nxt[q];
-  }
-}
-
-// Two independent exclusive scans in one launch: the walk of small_exclusive_scan_kernel over two arrays
-// (16 ints per thread, array and step; the next step's loads in flight while this one is scanned).
-__global__ __launch_bounds__(1024) void small_exclusive_scan2_kernel(const int* __restrict__ in_a,
-                                                                     const int* __restrict__ in_b,
-                                                                     int* __restrict__ out_a, int* __restrict__ out_b,
-                                                                     int64_t n) {
-  constexpr int EPT = 16, CHUNK = 1024 * EPT;
-  __shared__ int wsum[2][2][16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool vec = ((((uintptr_t)in_a) | ((uintptr_t)in_b) | ((uintptr_t)out_a) | ((uintptr_t)out_b)) & 15) == 0;
-  int ca[EPT], cb[EPT], na[EPT], nb[EPT];
-  auto load = [&](const int* __restrict__ in, int64_t base, int* v) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * EPT;
-    if (vec && i0 + EPT <= n) {
-#pragma unroll
-      for (int q = 0; q < EPT / 4; ++q) {
-        int4 t = *reinterpret_cast<const int4*>(in + i0 + 4 * q);
-        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < EPT; ++q) v[q] = (i0 + q < n) ? in[i0 + q] : 0;
-    }
-  };
-  auto store = [&](int* __restrict__ out, int64_t base, const int* v, int ex) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * EPT;
-    if (vec && i0 + EPT <= n) {
-#pragma unroll
-      for (int q = 0; q < EPT / 4; ++q) {
-        int4 t;
-        t.x = ex; ex += v[4 * q];
-        t.y = ex; ex += v[4 * q + 1];
-        t.z = ex; ex += v[4 * q + 2];
-        t.w = ex; ex += v[4 * q + 3];
-        *reinterpret_cast<int4*>(out + i0 + 4 * q) = t;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < EPT; ++q) {
-        if (i0 + q < n) out[i0 + q] = ex;
-        ex += v[q];
-      }
-    }
-  };
-  int carry_a = 0, carry_b = 0, buf = 0;
-  load(in_a, 0, ca);
-  load(in_b, 0, cb);
-  for (int64_t base = 0; base < n; base += CHUNK, buf ^= 1) {
-    if (base + CHUNK < n) { load(in_a, base + CHUNK, na); load(in_b, base + CHUNK, nb); }
-    int ta = 0, tb = 0;
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) { ta += ca[q]; tb += cb[q]; }
-    int ia = ta, ib = tb;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      int xa = __shfl_up(ia, d, 64), xb = __shfl_up(ib, d, 64);
-      if (lane >= d) { ia += xa; ib += xb; }
-    }
-    if (lane == 63) { wsum[buf][0][wave] = ia; wsum[buf][1][wave] = ib; }
-    __syncthreads();
-    int woa = 0, wob = 0, tota = 0, totb = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const int xa = wsum[buf][0][w], xb = wsum[buf][1][w];
-      woa += w < wave ? xa : 0; wob += w < wave ? xb : 0;
-      tota += xa; totb += xb;
-    }
-    store(out_a, base, ca, carry_a + woa + ia - ta);
-    store(out_b, base, cb, carry_b + wob + ib - tb);
-    carry_a += tota; carry_b += totb;
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) { ca[q] = na[q]; cb[q] = nb[q]; }
-  }
-}
-
-constexpr int64_t kSmallScan = 1 << 18;
-constexpr int64_t kOneBlockScan = 1 << 14;        // up to here the one-block walk is a single step
-
-// Exclusive scan of 16 K .. 256 K ints in ONE launch of several blocks (decoupled look-back): the one-block walk above
-// is bound by a single CU's memory throughput (3.3 us per 16 K ints: 20 us for the 82 K-entry row pointers of the
-// facet level).  Blocks take their index from a ticket (so every predecessor of a block is already running: the
-// look-back cannot wait on a block that has not started), publish (epoch | flag | value) as one 64-bit word -- flag 1:
-// the block's own sum, flag 2: the inclusive prefix up to and including it -- and wave 0 of each block inspects 64
-// predecessors at a time.  The state words carry the call's epoch, so the buffer is never cleared between calls.
-// Library-global state: one scan at a time (every scan of this path runs on the caller's stream, in order).
-__device__ __forceinline__ unsigned long long scan_pack(unsigned epoch, unsigned flag, int value) {
-  return ((unsigned long long)((epoch << 2) | flag) << 32) | (unsigned)value;
-}
-
-__global__ __launch_bounds__(256) void lookback_exclusive_scan_kernel(const int* __restrict__ in, int* __restrict__ out,
-                                                                      int64_t n, unsigned long long* state, int* ticket,
-                                                                      unsigned epoch, int nblocks) {
-  constexpr int EPT = 16, CHUNK = 256 * EPT;
-  __shared__ int s_bid, s_prefix, wsum[4];
-  if (threadIdx.x == 0) s_bid = atomicAdd(ticket, 1);
-  __syncthreads();
-  const int b = s_bid;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t i0 = (int64_t)b * CHUNK + (int64_t)threadIdx.x * EPT;
-  const bool vec = ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0 && i0 + EPT <= n;
-  int v[EPT];
-  if (vec) {
-#pragma unroll
-    for (int q = 0; q < EPT / 4; ++q) {
-      const int4 t = *reinterpret_cast<const int4*>(in + i0 + 4 * q);
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) v[q] = (i0 + q < n) ? in[i0 + q] : 0;
-  }
-  int tsum = 0;
-#pragma unroll
-  for (int q = 0; q < EPT; ++q) tsum += v[q];
-  int inc = tsum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int woff = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const int t = wsum[w];
-    woff += w < wave ? t : 0;
-    total += t;
-  }
-  if (wave == 0) {
-    int prefix = 0;
-    if (b > 0) {
-      if (lane == 0) __hip_atomic_store(state + b, scan_pack(epoch, 1, total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      for (int hi = b - 1; hi >= 0; hi -= 64) {
-        const int pidx = hi - lane;
-        unsigned flag = 2;
-        int val = 0;
-        if (pidx >= 0) {
-          unsigned long long st;
-          int spins = 0;
-          do {
-            st = __hip_atomic_load(state + pidx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-          } while (((unsigned)(st >> 34) != epoch || ((st >> 32) & 3) == 0) && ++spins < (1 << 26));
-          flag = (unsigned)(st >> 32) & 3;
-          val = (int)(unsigned)st;
-        }
-        const unsigned long long done = __ballot(flag == 2);
-        const int first = done ? __ffsll((long long)done) - 1 : 64;       // nearest predecessor with a full prefix
-        int c = lane <= first ? val : 0;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-        prefix += c;
-        if (done) break;
-      }
-    }
-    if (lane == 0) {
-      __hip_atomic_store(state + b, scan_pack(epoch, 2, prefix + total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      s_prefix = prefix;
-      if (b == nblocks - 1) *ticket = 0;                                   // every ticket of this call is taken
-    }
-  }
-  __syncthreads();
-  int ex = s_prefix + woff + inc - tsum;
-  if (vec) {
-#pragma unroll
-    for (int q = 0; q < EPT / 4; ++q) {
-      int4 t;
-      t.x = ex; ex += v[4 * q];
-      t.y = ex; ex += v[4 * q + 1];
-      t.z = ex; ex += v[4 * q + 2];
-      t.w = ex; ex += v[4 * q + 3];
-      *reinterpret_cast<int4*>(out + i0 + 4 * q) = t;
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) {
-      if (i0 + q < n) out[i0 + q] = ex;
-      ex += v[q];
-    }
-  }
-}
-
-// persistent look-back state (zeroed once; see the kernel).  One per host thread: a thread drives one stream at a time
-// (one mesh group of a concurrent step, executor.hip), so two scans in flight never share state words.
-static thread_local unsigned long long* g_scan_state = nullptr;
-static thread_local int* g_scan_ticket = nullptr;
-static thread_local unsigned g_scan_epoch = 0;
-
-static hipError_t lookback_scan(const int* in, int* out, int64_t n, hipStream_t s) {
-  if (g_scan_state == nullptr) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, 4096 * sizeof(unsigned long long) + 256);
-    if (e != hipSuccess) return e;
-    // zeroed ON THE LAUNCH STREAM: a null-stream memset is not ordered against a non-blocking stream, and a host thread
-    // that starts later (one context per thread) initialises its state while other threads' kernels are in flight
-    e = hipMemsetAsync(p, 0, 4096 * sizeof(unsigned long long) + 256, s);
-    if (e != hipSuccess) return e;
-    g_scan_state = (unsigned long long*)p;
-    g_scan_ticket = (int*)((char*)p + 4096 * sizeof(unsigned long long));
-  }
-  g_scan_epoch = (g_scan_epoch + 1) & 0x3fffffffu;
-  if (g_scan_epoch == 0) g_scan_epoch = 1;
-  const int nblocks = cdiv(n, 4096);
-  lookback_exclusive_scan_kernel<<<nblocks, 256, 0, s>>>(in, out, n, g_scan_state, g_scan_ticket, g_scan_epoch, nblocks);
-  return hipGetLastError();
-}
-
-
-static hipError_t exclusive_scan_int(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s) {
-  if (n <= kSmallScan) {
-    const bool lookback = g_scan_lookback.on();
-    if (lookback && n > kOneBlockScan) {
-      prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_LOOKBACK);
-      const hipError_t e = lookback_scan(in, out, n, s);
-      prof_end(PROF_POOL_FORM, s);
-      return e;
-    }
-    prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_ONE_BLOCK);
-    small_exclusive_scan_kernel<<<1, 1024, 0, s>>>(in, out, n);
-    prof_end(PROF_POOL_FORM, s);
-    return hipGetLastError();
-  }
-  prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_SCAN_ROCPRIM);
-  const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, out, 0, (size_t)n, rocprim::plus<int>(), s, false);
-  prof_end(PROF_POOL_FORM, s);
-  return e;
-}
-
 }  // namespace
-
-size_t scan_ws_bytes(int64_t n) { return n <= kSmallScan ? 16 : ExclusiveScan<int>::temp_bytes(n); }
-
-int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s) {
-  GEOBI_HIP(exclusive_scan_int(temp, temp_bytes, in, out, n, s));
-  return 0;
-}
 
 int edge_weight_t10(const float* x, int C, const int32_t* row, const int32_t* col, const float* w_in, int64_t E,
                     float* w_out, hipStream_t s, int32_t* zero8) {
@@ -1188,10 +865,9 @@ int expand_rowptr(const int32_t* rowptr, int64_t N, int32_t* row, hipStream_t s)
 static Knob g_round_cap{nullptr, 0};
 void set_match_round_cap(int cap) { g_round_cap.set(cap > 0 ? cap : 0); }
 
-// Test hooks (geobi_set_match_scanfree / geobi_set_scan_lookback): 1 / 0 force the form, a negative value goes back to
-// what the environment says.  Without a call nothing changes.
+// Test hook (geobi_set_match_scanfree): 1 / 0 force the form, a negative value goes back to what the environment says.
+// Without a call nothing changes.
 void set_match_scanfree(int on) { if (on < 0) g_match_scanfree.reset(); else g_match_scanfree.set(on != 0); }
-void set_scan_lookback(int on) { if (on < 0) g_scan_lookback.reset(); else g_scan_lookback.set(on != 0); }
 
 static void launch_match_rounds(const int32_t* rowptr, const int32_t* col, const float* w, int N, int rounds, int init,
                                 int32_t* cluster, int32_t* status, int*& pp, int*& pn, hipStream_t s) {
@@ -1283,9 +959,9 @@ int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int
   GEOBI_LAUNCH_OK();
   if (N + 1 <= kSmallScan) {
     prof_begin(PROF_POOL_FORM, s, 0.0, POOL_FORM_MATCH_TWOPASS_DUAL);
-    small_exclusive_scan2_kernel<<<1, 1024, 0, s>>>(flag, sz, rank, offs, N + 1);
+    const int rc = scan_exclusive_i32_pair(flag, sz, rank, offs, N + 1, s);
     prof_end(PROF_POOL_FORM, s);
-    GEOBI_LAUNCH_OK();
+    GEOBI_TRY(rc);
   } else {
     GEOBI_TRY(b.scan_a.run(flag, rank, s));
     GEOBI_TRY(b.scan_b.run(sz, offs, s));

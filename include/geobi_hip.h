@@ -1378,9 +1378,13 @@ int geobi_prof_enable(int kernel);
  * differences to the row maximum, i.e. FINITE and <= 0: <= 2 ulp against exp, results below 2^-126 flush to 0; a
  * non-finite argument is outside its contract).  Exposed so that a test can check it in isolation.              */
 int geobi_debug_exp_le0(const float* x, float* y, int64_t n, void* stream);
-/* diagnostic entries of the pooling front end (csrc/pool.hip), for tests: forms that otherwise only the executor calls.
+/* diagnostic entries of the pooling front end (csrc/pool.hip, csrc/scan.hip), for tests: forms that otherwise only the
+ * executor calls.
  *   geobi_debug_scan_exclusive_i32     : the library's exclusive int scan (out[i] = in[0] + ... + in[i-1]); workspace of
  *                                        geobi_debug_scan_ws_bytes(n) bytes
+ *   geobi_debug_scan_exclusive_i32_pair: two such scans of n <= 2^18 elements each in one launch (the dual scan of
+ *                                        geobi_match_coarsen's two-pass tail), out_a from in_a and out_b from in_b; a
+ *                                        larger n is refused.  No workspace; the pointers need no alignment beyond 4 bytes
  *   geobi_debug_segment_max2_fwd / _bwd: max over the composition of two clusterings in one pass (segptr1 / members1:
  *                                        fine -> mid lists, segptr2 / members2: mid -> coarse, every mid segment
  *                                        non-empty); arg12 [nseg2, C] = fine row of the maximum (-1: empty); the
@@ -1394,6 +1398,8 @@ int geobi_debug_exp_le0(const float* x, float* y, int64_t n, void* stream);
  *                                        E_fine = fine edge count (> 0), rowinfo_in = the array above or NULL           */
 size_t geobi_debug_scan_ws_bytes(int64_t n);
 int geobi_debug_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, void* ws, size_t ws_bytes, void* stream);
+int geobi_debug_scan_exclusive_i32_pair(const int32_t* in_a, const int32_t* in_b, int32_t* out_a, int32_t* out_b, int64_t n,
+                                        void* stream);
 int geobi_debug_segment_max2_fwd(const float* x, int C, const int32_t* segptr1, const int32_t* members1,
                                  const int32_t* segptr2, const int32_t* members2, int64_t nseg2, float* out,
                                  int32_t* arg12, void* stream);

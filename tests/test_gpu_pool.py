@@ -268,6 +268,56 @@ def test_exclusive_scan_forms(dev, n, lookback):
     assert np.array_equal(_np(out), want)
 
 
+def _scan_buffers(dev, v, in_off, out_off):
+    """v in a buffer `in_off` ints behind a 16-byte boundary, an output range of -1 sentinels `out_off` ints behind one
+    with a guard element on either side -> (in view, out view, whole output buffer, index of out[0] in it)"""
+    n = len(v)
+    src = torch.zeros(n + 4, dtype=torch.int32, device=dev)
+    buf = torch.full((n + 8,), -1, dtype=torch.int32, device=dev)
+    assert src.data_ptr() % 16 == 0 and buf.data_ptr() % 16 == 0
+    o0 = 4 + out_off                                     # one whole int4 of guards in front of an aligned range
+    a, o = src[in_off:in_off + n], buf[o0:o0 + n]
+    a.copy_(torch.from_numpy(v))
+    assert a.data_ptr() % 16 == 4 * in_off and o.data_ptr() % 16 == 4 * out_off
+    return a, o, buf, o0
+
+
+def _check_scan(buf, o0, v, what):
+    got = _np(buf)
+    n = len(v)
+    assert np.array_equal(got[o0:o0 + n], np.cumsum(v.astype(np.int64)) - v), what
+    assert (got[:o0] == -1).all() and (got[o0 + n:] == -1).all(), what + ': wrote outside out[0 .. n)'
+
+
+def test_exclusive_scan_unaligned(dev):
+    """Pointers 4 bytes behind a 16-byte boundary take the scalar loads and stores of load_chunk / store_chunk, which no
+    torch allocation reaches: the single scan in both look-back settings with in and out = buf[1:1 + n] (and once with
+    only out so) at one int, either side of a thread's 16, a full step plus one (4097 look-back / 16 385 walk) and
+    20 000 (five look-back blocks with a tail); the pair scan (one kernel, vec = all four pointers aligned) aligned and
+    with only out_b off.  List b has other values than list a (seed n + 1): a carry or wave sum taken from the wrong
+    list shows.  The elements around every output range keep their -1."""
+    L = _L()
+    try:
+        for lookback in (0, 1):
+            L.call('geobi_set_scan_lookback', lookback)
+            for n, in_off in [(m, 1) for m in (1, 15, 17, 4097, 16385, 20000)] + [(20000, 0)]:
+                v = M.scan_case(n)
+                a, o, buf, o0 = _scan_buffers(dev, v, in_off, 1)
+                ws = L.workspace(L.lib().geobi_debug_scan_ws_bytes(n), dev)
+                L.call('geobi_debug_scan_exclusive_i32', L.ptr(a), L.ptr(o), n, L.ptr(ws), ws.numel(), L.stream())
+                _check_scan(buf, o0, v, 'n %d, look-back %d, in +%d ints, out +1' % (n, lookback, in_off))
+    finally:
+        L.call('geobi_set_scan_lookback', -1)
+    for n in (1, 16, 16385, 20000):
+        va, vb = M.scan_case(n), M.scan_case(n + 1)[:n]
+        for off_b in (0, 1):
+            a, oa, buf_a, a0 = _scan_buffers(dev, va, 0, 0)
+            b, ob, buf_b, b0 = _scan_buffers(dev, vb, 0, off_b)
+            L.call('geobi_debug_scan_exclusive_i32_pair', L.ptr(a), L.ptr(b), L.ptr(oa), L.ptr(ob), n, L.stream())
+            _check_scan(buf_a, a0, va, 'pair, n %d, list a, out_b +%d ints' % (n, off_b))
+            _check_scan(buf_b, b0, vb, 'pair, n %d, list b, out_b +%d ints' % (n, off_b))
+
+
 # ================================================================================================ edge coarsening
 def _rows_form(g, cnew, segptr, members, nc, w, onepass, rowinfo_in=None):
     """geobi_pool_edge_rows (two passes) or geobi_debug_pool_edge_rows_onepass -> (rowptr_c, row_c, col_c, w_c, count, overflow)"""
