@@ -1,5 +1,5 @@
 // Block-wide exclusive int scan in pieces (device only): the wave ladder, the fold of the wave sums through LDS, and the
-// load / store of a thread's chunk of consecutive ints.  scan.hip builds the library's scan kernels from them and pool.hip
+// load / store of a thread's chunk of consecutive ints.  scan.hip builds the library's scan kernels from them and match.hip
 // the scan-free matching pair.  patch.hip's grow_wave_scan is the same ladder, so it calls wave_inclusive_scan; what it
 // adds (the total by a lane-63 broadcast, the exclusive value) stays there.  Blocks are 64 * WAVES threads wide, one
 // dimension; s_wave arrays have WAVES entries per list and are indexed by threadIdx.x >> 6.

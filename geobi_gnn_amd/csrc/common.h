@@ -212,7 +212,7 @@ __device__ __forceinline__ double fold_ascending(const double* __restrict__ part
 
 // ---- optional per-kernel timing for bench.py's roofline object (events on the launch stream)
 enum ProfKernel { PROF_NONE = 0, PROF_AGG_FWD = 1, PROF_AGG_BWD = 2, PROF_ROWPASS = 3, PROF_GEMM = 4, PROF_POOL_FORM = 5 };
-// tags of PROF_POOL_FORM (scan.hip, pool.hip):which form of a scan / of match_coarsen's tail a call took
+// tags of PROF_POOL_FORM (scan.hip, match.hip): which form of a scan / of match_coarsen's tail a call took
 enum PoolForm {
   POOL_FORM_SCAN_ONE_BLOCK = 1, POOL_FORM_SCAN_LOOKBACK = 2, POOL_FORM_SCAN_ROCPRIM = 3,
   POOL_FORM_MATCH_SCANFREE = 4, POOL_FORM_MATCH_TWOPASS_DUAL = 5
@@ -238,12 +238,14 @@ Fork fork_side_stream(hipStream_t main);       // side stream waits for everythi
 int join_side_stream(const Fork& f, hipStream_t main);   // `main` waits for the side stream
 int side_wait_main(const Fork& f, hipStream_t main);     // side stream waits for `main` as of now
 
-// ---- launchers that ANOTHER translation unit calls (all enqueue on `s`, never sync).  A launcher only its own entry point
-// reaches has no prototype here: it is the body of that entry point
-// graph.hip (also called by executor.hip)
+// ---- launchers that ANOTHER translation unit calls, grouped by the unit that defines them (all enqueue on `s`, never
+// sync).  A launcher only its own entry point reaches has no prototype here: it is the body of that entry point
+
+// ---- graph.hip; called by executor.hip
 int csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int32_t* col, int64_t E, int32_t* pos_rev,
                       int32_t* flag, hipStream_t s);
-// gemm.hip
+
+// ---- gemm.hip; called by feast.hip and geom.hip
 struct GemmEpilogue {
   const float* bias = nullptr;  // [N] added per column
   float slope = 1.0f;           // leaky-relu negative slope (1 = identity)
@@ -259,14 +261,53 @@ static inline size_t gemm_nn_ws_bytes(int64_t M, int N) {
   return (M * N < (int64_t)2200000) ? align_up((size_t)8 * M * N * sizeof(float)) + 256 : 256;
 }
 // forward GEMM of a FeaSt layer: the split is a function of the layer shape only
-// packed-weight buffer shared by forward and backward: Wf [ldz(Cin), Cout] for z Wf / g Wf^T, then
-// W' [ldr(Cout), Cin] = [lin.weight ; u.weight ; 0] for dx = r' W'
-// feast_fused.hip: the fused (aggregate -> LDS tile -> MFMA) kernels and their packed weights
-int feast_fused_nt(int nout);
+static inline int feast_fwd_slices(int Kp, int Cout) { return Kp >= 1024 ? 4 : ((Kp >= 512 && Cout >= 64) ? 2 : 1); }
+static inline size_t gemm_nn_fixed_ws_bytes(int64_t M, int N, int slices) {
+  size_t b = (size_t)slices * M * N * sizeof(float);
+  return (slices > 1 && b <= ((size_t)256 << 20)) ? align_up(b) + 256 : 256;
+}
+// What a gemm_nn call decided on the host (the launch follows it; geobi_debug_gemm_nn reports it).  shape: the tile shape
+// by its GEOBI_NN_CFG number, 0 = nothing was launched; slices > 1: split-K through ep.ws and the reduce kernel.
+struct NnPlan { int fast = 0, shape = 0, wm = 0, wn = 0, tm = 0, tn = 0, bk = 0, slices = 0, k_chunk = 0, wide = 0; };
+// cfg != 0: this call's tile shape, as GEOBI_NN_CFG of that value forces it for the process; ran: the plan that ran
+int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N, int K,
+            const GemmEpilogue& ep, hipStream_t s, int cfg = 0, NnPlan* ran = nullptr);
+size_t gemm_tn_ws_bytes(int I, int J, int64_t M);
+size_t gemm_tn_ws_bytes_any_width(int I, int J, int64_t M);   // max over column widths 1..J
+enum TnOut { TN_PLAIN = 0, TN_LIN_UNPACK = 1, TN_DU_DC = 2, TN_RPRIME = 3 };
+struct TnOutput {
+  int mode = TN_PLAIN;
+  float* C = nullptr;   // primary output
+  int ldc = 0;
+  float* C2 = nullptr;  // secondary output (bias gradient / c gradient)
+  int Cin = 0, Cout = 0;
+  int extra_row = 0, extra_col = 0;  // TN_PLAIN: last row / column is the implicit-ones one -> C2
+  int accumulate = 0;   // != 0: add to what C / C2 hold (gradient accumulation) instead of overwriting
+  // TN_RPRIME ([x | 1]^T [r | dp | dcs]): C = dlin, C2 = dbias, C3 = du, C4 = dc; col0 = first input channel of
+  // this A operand (split inputs issue one GEMM per half)
+  float* C3 = nullptr;
+  float* C4 = nullptr;
+  int col0 = 0;
+};
+// I, J: logical output sizes INCLUDING an implicit ones row / column when ones_row / ones_col >= 0, or the column-sums
+// row (sum_row == I - 1: the sums of B's columns over the M rows, formed on the VALU beside the MFMAs; TnOutput.extra_row
+// routes it).
+// What a gemm_tn call decided on the host: the kernel instance <ti, tj, u, va> (va: the vector-A kernel), its grid
+// (tiles_i x tiles_j output tiles, blocks_y blocks of four node slices of m_per_slice rows each = blocks_y slabs) and the
+// extra bias blocks of the reduce kernel.  All zero: nothing was launched.
+struct TnPlan {
+  int ti = 0, tj = 0, va = 0, u = 0, tiles_i = 0, tiles_j = 0, slices = 0, blocks_y = 0, bias_blocks = 0;
+  int64_t m_per_slice = 0;
+};
+int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, int ones_row, int ones_col,
+            const TnOutput& o, void* ws, size_t ws_bytes, hipStream_t s, int sum_row = -1, TnPlan* ran = nullptr);
+
+// ---- feast_fused.hip: the fused (aggregate -> LDS tile -> MFMA) kernels and their packed weights; called by feast.hip,
+// the pack sizes and feast_fused_pack_batch by executor.hip too
 size_t feast_fused_fwd_pack_floats(int Cin, int Cout);
 size_t feast_fused_dx_pack_floats(int Cin, int Cout);
 int feast_fused_pack_fwd(const float* lin_w, const float* c, int Cin, int Cout, float* bp, hipStream_t s);
-// one launch for the packed forms of several layers (feast_fused.hip)
+// one launch for the packed forms of several layers
 constexpr int kMaxPackBatch = 8;
 struct FusedPackItem {
   const float* lin_w;
@@ -282,7 +323,7 @@ int feast_fused_pack_dx(const float* lin_w, const float* u_w, const float* c, in
 int feast_fused_pack_all(const float* lin_w, const float* u_w, const float* c, int Cin, int Cout, int Kp, float* wf,
                          float* bf, float* bdx, hipStream_t s);
 double feast_fused_bytes(int64_t N, int64_t E, int C, int nout);
-// ---- launch records: host-side only, filled by field name, passed by const reference down to the one
+// launch records: host-side only, filled by field name, passed by const reference down to the one
 // place that spells a kernel's argument list.
 // the layer input as every FeaSt kernel sees it; a second one describes the transposed graph the dx side walks
 struct FeastIn {
@@ -327,11 +368,11 @@ int feast_fused_dx(const FeastIn& gin, const int* rowptr_in, const int* pos, con
                    const float* xl, const float* dpd, const float* Bp, int Cin, float* dxa, int Ca, float* dxb, int Cb,
                    float* tile_out, hipStream_t s);
 bool feast_rowpass_fused_supported(int Cin, int Cb, int Cout);
-int set_tile_rows(int rows);
-int set_rowpass_form(int staged, int chunked64);
-int set_column_parts(int parts);
 int feast_rowpass_fused(const FeastIn& in, int Cin, int Cout, const RowpassLaunch& r, hipStream_t s);
-// packed-weight buffer layout: [Wf | W' | Bf (fused forward) | Bdx (fused dx)]
+
+// ---- feast.hip; called by executor.hip (feast_ldz by feast_fused.hip)
+// packed-weight buffer shared by forward and backward: [Wf | W' | Bf (fused forward) | Bdx (fused dx)], with
+// Wf [ldz(Cin), Cout] for z Wf / g Wf^T and W' [ldr(Cout), Cin] = [lin.weight ; u.weight ; 0] for dx = r' W'
 static inline size_t feast_wpack_plain_floats(int Cin, int Cout) {
   return (size_t)((GEOBI_H * Cin + 3) / 4 * 4) * Cout + (size_t)(GEOBI_H * Cout + 2 * GEOBI_HP) * Cin;
 }
@@ -339,49 +380,6 @@ static inline size_t feast_wpack_floats(int Cin, int Cout) {
   return feast_wpack_plain_floats(Cin, Cout) + feast_fused_fwd_pack_floats(Cin, Cout) +
          feast_fused_dx_pack_floats(Cin, Cout);
 }
-static inline int feast_fwd_slices(int Kp, int Cout) { return Kp >= 1024 ? 4 : ((Kp >= 512 && Cout >= 64) ? 2 : 1); }
-static inline size_t gemm_nn_fixed_ws_bytes(int64_t M, int N, int slices) {
-  size_t b = (size_t)slices * M * N * sizeof(float);
-  return (slices > 1 && b <= ((size_t)256 << 20)) ? align_up(b) + 256 : 256;
-}
-// What a gemm_nn call decided on the host (the launch follows it; geobi_debug_gemm_nn reports it).  shape: the tile shape
-// by its GEOBI_NN_CFG number, 0 = nothing was launched; slices > 1: split-K through ep.ws and the reduce kernel.
-struct NnPlan { int fast = 0, shape = 0, wm = 0, wn = 0, tm = 0, tn = 0, bk = 0, slices = 0, k_chunk = 0, wide = 0; };
-// cfg != 0: this call's tile shape, as GEOBI_NN_CFG of that value forces it for the process; ran: the plan that ran
-int gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N, int K,
-            const GemmEpilogue& ep, hipStream_t s, int cfg = 0, NnPlan* ran = nullptr);
-size_t gemm_tn_ws_bytes(int I, int J, int64_t M);
-size_t gemm_tn_ws_bytes_any_width(int I, int J, int64_t M);   // max over column widths 1..J
-enum TnOut { TN_PLAIN = 0, TN_LIN_UNPACK = 1, TN_DU_DC = 2, TN_RPRIME = 3 };
-struct TnOutput {
-  int mode = TN_PLAIN;
-  float* C = nullptr;   // primary output
-  int ldc = 0;
-  float* C2 = nullptr;  // secondary output (bias gradient / c gradient)
-  int Cin = 0, Cout = 0;
-  int extra_row = 0, extra_col = 0;  // TN_PLAIN: last row / column is the implicit-ones one -> C2
-  int accumulate = 0;   // != 0: add to what C / C2 hold (gradient accumulation) instead of overwriting
-  // TN_RPRIME ([x | 1]^T [r | dp | dcs]): C = dlin, C2 = dbias, C3 = du, C4 = dc; col0 = first input channel of
-  // this A operand (split inputs issue one GEMM per half)
-  float* C3 = nullptr;
-  float* C4 = nullptr;
-  int col0 = 0;
-};
-// I, J: logical output sizes INCLUDING an implicit ones row / column when ones_row / ones_col >= 0, or the column-sums
-// row (sum_row == I - 1: the sums of B's columns over the M rows, formed on the VALU beside the MFMAs; TnOutput.extra_row
-// routes it).
-// What a gemm_tn call decided on the host: the kernel instance <ti, tj, u, va> (va: the vector-A kernel), its grid
-// (tiles_i x tiles_j output tiles, blocks_y blocks of four node slices of m_per_slice rows each = blocks_y slabs) and the
-// extra bias blocks of the reduce kernel.  All zero: nothing was launched.
-struct TnPlan {
-  int ti = 0, tj = 0, va = 0, u = 0, tiles_i = 0, tiles_j = 0, slices = 0, blocks_y = 0, bias_blocks = 0;
-  int64_t m_per_slice = 0;
-};
-int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, int ones_row, int ones_col,
-            const TnOutput& o, void* ws, size_t ws_bytes, hipStream_t s, int sum_row = -1, TnPlan* ran = nullptr);
-
-// feast.hip
-int exp_le0_probe(const float* x, float* y, int64_t n, hipStream_t s);
 int feast_ldz(int Cin);
 size_t feast_fwd_ws_bytes(int64_t N, int Cin, int Cout);
 int feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64_t E, const int32_t* rowptr_in,
@@ -396,54 +394,30 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
               const float* gout, const float* p, const float* z, const float* wf_saved, float* dxa, float* dxb,
               float* dlin_w, float* du_w, float* dc, float* dbias, int accumulate, void* ws, size_t ws_bytes,
               hipStream_t s);
-struct CopySeg { const void* src; void* dst; int64_t n; int32_t add; float value; };     // = geobi_copy_seg_t
-int concat32(const CopySeg* segs, int n_segs, int is_float, hipStream_t s);
-// pool.hip
+
+// ---- match.hip; called by executor.hip
 int edge_weight_t10(const float* x, int C, const int32_t* row, const int32_t* col, const float* w_in, int64_t E,
                     float* w_out, hipStream_t s, int32_t* zero8 = nullptr);
-int edge_weight_att(const float* x, int C, const float* att_l, const float* att_r, const int32_t* row, const int32_t* col,
-                    const float* w_in, int64_t N, int64_t E, float* node_ws, float* w_out, hipStream_t s);
-int gather_f32(const float* src, const int32_t* idx, int64_t n, float* dst, hipStream_t s);
-int expand_rowptr(const int32_t* rowptr, int64_t N, int32_t* row, hipStream_t s);
-size_t match_ws_bytes(int64_t N);
 size_t match_coarsen_ws_bytes(int64_t N);
 int match_coarsen(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, int rounds, int init,
                   int32_t* state, int32_t* cluster_final, int32_t* cnew, int32_t* segptr, int32_t* members,
                   int32_t* counters, void* ws, size_t ws_bytes, hipStream_t s, void* rowinfo_out = nullptr,
                   bool* rowinfo_made = nullptr);
-int match_heavy_edge(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, int rounds, int init,
-                     int32_t* cluster, int32_t* cluster_final, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
-void set_match_round_cap(int cap);
-void set_match_scanfree(int on);      // test hook: 1 / 0 force the form, < 0 = as the environment says
-size_t relabel_ws_bytes(int64_t N);
-int relabel_compact(const int32_t* cluster, int64_t N, int rep_is_self, int32_t* cnew, int32_t* count, void* ws,
-                    size_t ws_bytes,
-                    hipStream_t s);
-size_t segment_csr_ws_bytes(int64_t n);
-int segment_csr(const int32_t* seg, int64_t n, int64_t nseg, int32_t* segptr, int32_t* members, void* ws,
-                size_t ws_bytes, hipStream_t s);
-size_t segment_pairs_ws_bytes(int64_t nseg);
-int segment_csr_pairs(const int32_t* cnew, const int32_t* raw, int64_t N, int64_t nseg, int32_t* segptr,
-                      int32_t* members, void* ws, size_t ws_bytes, hipStream_t s);
-int segment_csr_compose(const int32_t* segptr1, const int32_t* members1, const int32_t* segptr2,
-                        const int32_t* members2, int64_t nseg2, int64_t n_fine, int32_t* segptr12,
-                        int32_t* members12, void* ws, size_t ws_bytes, hipStream_t s);
-int segment_max_fwd(const float* x, int C, const int32_t* segptr, const int32_t* members, int64_t nseg, float* out,
-                    int32_t* arg, hipStream_t s);
+
+// ---- segment.hip; called by executor.hip
 int segment_sum2(const float* x, int C, const int32_t* segptr1, const int32_t* members1, const int32_t* segptr2,
                  const int32_t* members2, int64_t nseg2, float* out, hipStream_t s);
 int segment_max2_fwd(const float* x, int C, const int32_t* segptr1, const int32_t* members1, const int32_t* segptr2,
                      const int32_t* members2, int64_t nseg2, float* out, int32_t* arg12, hipStream_t s);
 int segment_max2_bwd(const float* gout, const int32_t* arg12, const int32_t* seg12, int C, int64_t nseg2, int64_t n_fine,
                      float* gx, int add, hipStream_t s);
-int segment_max_bwd(const float* gout, const int32_t* arg, const int32_t* seg, int C, int64_t nseg, int64_t n_fine,
-                    float* gx, hipStream_t s);
 int segment_sum(const float* x, int C, const int32_t* segptr, const int32_t* members, int64_t nseg, int mean,
                 float* out, hipStream_t s);
 int segment_mean_bwd(const float* gout, const int32_t* seg, const int32_t* segptr, int C, int64_t n_fine, float* gx,
                      hipStream_t s);
 int gather_rows(const float* x, const int32_t* idx, int C, int64_t n_out, float* out, hipStream_t s);
-size_t pool_edge_rows_ws_bytes(int64_t nbound);
+
+// ---- pool.hip; called by executor.hip
 size_t pool_edge_rows_ws_bytes_onepass(int64_t nbound, int64_t E);
 int pool_edge_rows(const int32_t* cnew, const int32_t* segptr, const int32_t* members, const int32_t* rowptr,
                    const int32_t* col, const float* w, const int32_t* ncount, int64_t nbound, int32_t* rowptr_c,
@@ -454,20 +428,24 @@ size_t pool_edge_ws_bytes(int64_t E);
 int pool_edge(const int32_t* cnew, const int32_t* row, const int32_t* col, const float* w, int64_t E, int64_t nmax,
               int32_t* rowptr_c, int32_t* row_c, int32_t* col_c, float* w_c, int32_t* count, void* ws,
               size_t ws_bytes, hipStream_t s);
-// scan.hip: the library's exclusive int scan, run through IntScan of device_steps.h (its own kernels, one launch and a
-// 16-byte temporary, up to kSmallScan elements; rocPRIM above), and two scans of n <= kSmallScan elements in one launch
+
+// ---- scan.hip: the library's exclusive int scan (its own kernels, one launch and a 16-byte temporary, up to kSmallScan
+// elements; rocPRIM above) and two scans of n <= kSmallScan elements in one launch.  The first two are what IntScan of
+// device_steps.h runs, in every unit that carves one; the pair scan is called by match.hip
 constexpr int64_t kSmallScan = 1 << 18;
 size_t scan_ws_bytes(int64_t n);
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s);
 int scan_exclusive_i32_pair(const int* in_a, const int* in_b, int* out_a, int* out_b, int64_t n, hipStream_t s);
-void set_scan_lookback(int on);       // test hook: 1 / 0 force the look-back form, < 0 = as the environment says
-// capi.hip: the one check of host part pointers (P >= 1, not NULL, start >= 0, no empty part, GEOBI_MAX_NODES rows);
-// the entry points that take a union batch (dist.hip, chamfer.hip, icp.hip) run it first and rely on it
+
+// ---- capi.hip: the one check of host part pointers (P >= 1, not NULL, start >= 0, no empty part, GEOBI_MAX_NODES rows);
+// the entry points that take a union batch (dist.hip, chamfer.hip, icp.hip, sample.hip) run it first and rely on it
 int parts_check(const char* fn, const int64_t* qptr, const int64_t* tptr, int P);
-// filter.hip (also called by guided.hip)
+
+// ---- filter.hip; called by guided.hip
 int bnf_spatial_factors(const float* rec_c, const int32_t* rowptr, const int32_t* col, int64_t F, int64_t E,
                         const float* inv2ss, float* wsp, hipStream_t s);
-// geom.hip
+
+// ---- geom.hip; called by executor.hip
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s);
 int face_geom_bwd(const float* verts, const int32_t* fv, const float* g, int64_t F, float* corner_grad,
@@ -475,23 +453,18 @@ int face_geom_bwd(const float* verts, const int32_t* fv, const float* g, int64_t
 int head_fwd(const float* x, int Cin, int64_t N, const float* w1, const float* b1, int K, const float* w2,
              const float* b2, int nout, float slope, int mode, const float* dd, const float* resid, int ld_resid,
              float* h, float* raw, float* out, hipStream_t s);
+size_t head_bwd_ws_bytes(int64_t N, int Cin, int K);
+int head_bwd(const float* x, int Cin, int64_t N, const float* w1, const float* b1, int K, const float* w2, int nout,
+             float slope, int mode, const float* dd, const float* h, const float* raw, const float* gout, float* dx, float* dw1,
+             float* db1, float* dw2, float* db2, int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
 size_t row_loss_ws_bytes(int64_t n);
 int row_loss_fwd(const float* a, const float* b, const float* w, int64_t n, int kind, float scale, float* out,
                  void* ws, size_t ws_bytes, hipStream_t s);
 int row_loss_bwd(const float* a, const float* b, const float* w, const float* gout, int64_t n, int kind,
                  float scale, float* ga, hipStream_t s);
-int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-              float bias_corr1, float bias_corr2, hipStream_t s);
-int rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
-                 hipStream_t s);
-size_t update_position_ws_bytes(int64_t V, int64_t F);
-int update_position2(const float* points, const int32_t* fv, const int32_t* vf, int maxval, const float* normals,
-                     const float* dd, int64_t V, int64_t F, int n_iter, float* out, void* ws, size_t ws_bytes,
-                     hipStream_t s);
-size_t head_bwd_ws_bytes(int64_t N, int Cin, int K);
-// head_fused.hip
+
+// ---- head_fused.hip; called by geom.hip
 bool head_fused_supported(int Cin, int K, int nout);
-int set_head_precision(int mode);
 int head_fwd_fused(const float* x, int64_t N, const float* w1, const float* b1, const float* w2, const float* b2,
                    int nout, float slope, int mode, const float* dd, const float* resid, int ld_resid, float* raw,
                    float* out, hipStream_t s);
@@ -499,8 +472,5 @@ size_t head_bwd_fused_ws_bytes(int64_t N);
 int head_bwd_fused(const float* x, int64_t N, const float* w1, const float* b1, const float* w2, int nout,
                    float slope, const float* graw, float* dx, float* dw1, float* db1, float* dw2, float* db2,
                    int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
-int head_bwd(const float* x, int Cin, int64_t N, const float* w1, const float* b1, int K, const float* w2, int nout,
-             float slope, int mode, const float* dd, const float* h, const float* raw, const float* gout, float* dx, float* dw1,
-             float* db1, float* dw2, float* db2, int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace geobi

@@ -90,4 +90,18 @@ struct IntScan {
   static IntScan take(Arena& a, int64_t n) { return {a.take_ws(scan_ws_bytes(n)), n}; }
 };
 
+// ---- n counts (or flags) and the scan over them: the count-to-offset step of match.hip, segment.hip and pool.hip
+struct CountScan { int* cnt; IntScan scan; };
+static inline CountScan carve_count_scan(Arena& a, int64_t n) { return {a.take<int>(n), IntScan::take(a, n)}; }
+
+// ---- 64-bit sort keys (a << bits) | b of graph.hip, segment.hip and pool.hip, with (1 << bits) > N: the radix sort only
+// has to look at 2 * bits bits (34 for the 82 k-node level-0 facet graph) instead of 64.  The sentinel (all ones) still
+// sorts last because every valid key is < 2^(2 bits) - 1.
+constexpr uint64_t kSentinel = ~0ull;
+static inline int key_bits(int64_t N) {
+  int b = 1;
+  while ((1ll << b) <= N) ++b;
+  return b;
+}
+
 }  // namespace geobi

@@ -309,7 +309,7 @@ int pool_layer(Bump& b, const Level& g, const float* x, int C, int pool_mean, Po
     GEOBI_TRY(segment_sum(x1, C, segptr[1], members[1], R2, 1, x2, s));
   } else {
     // both matching steps in one pass over the composed segments: same values and the same arg-max routing as two
-    // segment_max passes (pool.hip), the step-one maxima are never written
+    // segment_max passes (segment.hip), the step-one maxima are never written
     GEOBI_TRY(segment_max2_fwd(x, C, segptr[0], members[0], segptr[1], members[1], R2, x2, arg2, s));
   }
   if (save) {

@@ -13,6 +13,8 @@
 //   dz = g W_packed^T;  row pass over targets: s_ijh = dz_i[h,:].x_j, softmax backward -> dl_ij;
 //   column pass over sources j: r_j[h,:] = sum_i q_ijh/deg_i g_i  (same gather kernel, transposed CSR);
 //   dx = [r | dp] [lin.weight ; u.weight];  dW = z^T g;  du = dp^T x;  dc, dbias column sums.
+#include "../../include/geobi_hip.h"
+
 #include <algorithm>
 #include <cstdlib>
 
@@ -643,13 +645,6 @@ int launch_logits(int C, const FeastIn& in, float* p, hipStream_t s) {
 
 }  // namespace
 
-int exp_le0_probe(const float* x, float* y, int64_t n, hipStream_t s) {
-  if (n <= 0) return 0;
-  exp_le0_probe_kernel<<<cdiv(n, 256), 256, 0, s>>>(x, y, n);
-  GEOBI_LAUNCH_OK();
-  return 0;
-}
-
 int feast_ldz(int Cin) { return (H * Cin + 3) / 4 * 4; }
 int feast_ldr(int Cout) { return H * Cout + 2 * HP; }   // [r | dp(12) | dcs(12)]
 
@@ -993,3 +988,64 @@ int feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64
 }
 
 }  // namespace geobi
+
+using namespace geobi;
+
+static int check_channels(const char* fn, int Cin, int Cout) {
+  bool in_ok = Cin == 6 || Cin == 12 || Cin == 32 || Cin == 64 || Cin == 128;
+  bool out_ok = Cout == 32 || Cout == 64 || Cout == 128;
+  if (!in_ok || !out_ok) return set_error("%s: unsupported channels Cin=%d Cout=%d", fn, Cin, Cout);
+  return 0;
+}
+
+extern "C" {
+
+int geobi_debug_exp_le0(const float* x, float* y, int64_t n, void* stream) {
+  GEOBI_NOTNULL(x); GEOBI_NOTNULL(y);
+  hipStream_t s = as_stream(stream);
+  if (n <= 0) return 0;
+  exp_le0_probe_kernel<<<cdiv(n, 256), 256, 0, s>>>(x, y, n);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+size_t geobi_feast_wpack_floats(int Cin, int Cout) { return feast_wpack_floats(Cin, Cout); }
+
+int geobi_feast_ldz(int Cin) { return feast_ldz(Cin); }
+size_t geobi_feast_fwd_ws_bytes(int64_t N, int Cin, int Cout) { return feast_fwd_ws_bytes(N, Cin, Cout); }
+
+int geobi_feast_fwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64_t E,
+                    const int32_t* rowptr_in, const int32_t* col_in, const float* lin_w, const float* u_w,
+                    const float* c, const float* bias, int Cout, float slope, float* out, float* p, float* z,
+                    float* wf, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(N, E);
+  GEOBI_NOTNULL(xa); GEOBI_NOTNULL(rowptr_in); GEOBI_NOTNULL(lin_w); GEOBI_NOTNULL(u_w); GEOBI_NOTNULL(c); GEOBI_NOTNULL(bias);
+  GEOBI_NOTNULL(out); GEOBI_NOTNULL(p);
+  if (Cb > 0) GEOBI_NOTNULL(xb);
+  if (E > 0) GEOBI_NOTNULL(col_in);
+  GEOBI_TRY(check_channels(__func__, Ca + Cb, Cout));
+  return feast_fwd(xa, Cb > 0 ? xb : nullptr, Ca, Cb, N, E, rowptr_in, col_in, lin_w, u_w, c, bias, Cout, slope, out,
+                   p, z, wf, ws, ws_bytes, as_stream(stream));
+}
+
+size_t geobi_feast_bwd_ws_bytes(int64_t N, int64_t E, int Cin, int Cout) { return feast_bwd_ws_bytes(N, E, Cin, Cout); }
+
+int geobi_feast_bwd(const float* xa, const float* xb, int Ca, int Cb, int64_t N, int64_t E,
+                    const int32_t* rowptr_in, const int32_t* col_in, const int32_t* rowptr_out,
+                    const int32_t* col_out, const int32_t* pos_in, const float* lin_w, const float* u_w,
+                    const float* c, int Cout, float slope, const float* out, const float* gout, const float* p,
+                    const float* z, const float* wf, float* dxa, float* dxb, float* dlin_w, float* du_w, float* dc,
+                    float* dbias, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(N, E);
+  GEOBI_NOTNULL(xa); GEOBI_NOTNULL(rowptr_in); GEOBI_NOTNULL(rowptr_out); GEOBI_NOTNULL(lin_w); GEOBI_NOTNULL(u_w); GEOBI_NOTNULL(c);
+  GEOBI_NOTNULL(gout); GEOBI_NOTNULL(p); GEOBI_NOTNULL(dlin_w); GEOBI_NOTNULL(du_w); GEOBI_NOTNULL(dc); GEOBI_NOTNULL(dbias);
+  if (slope != 1.0f) GEOBI_NOTNULL(out);
+  if (Cb > 0) { GEOBI_NOTNULL(xb); if (dxa) GEOBI_NOTNULL(dxb); }
+  if (E > 0) { GEOBI_NOTNULL(col_in); GEOBI_NOTNULL(col_out); GEOBI_NOTNULL(pos_in); }
+  GEOBI_TRY(check_channels(__func__, Ca + Cb, Cout));
+  return feast_bwd(xa, Cb > 0 ? xb : nullptr, Ca, Cb, N, E, rowptr_in, col_in, rowptr_out, col_out, pos_in, lin_w,
+                   u_w, c, Cout, slope, out, gout, p, z, wf, dxa, dxb, dlin_w, du_w, dc, dbias, accumulate, ws, ws_bytes,
+                   as_stream(stream));
+}
+
+}  // extern "C"

@@ -26,6 +26,8 @@
 //                    once for the weight-gradient product.
 // The backward's first half (g, dz = g Wf^T on the matrix cores, per-edge softmax backward) is
 // feast_rowpass_fused_kernel / feast_rowpass_fused128_kernel below.
+#include "../../include/geobi_hip.h"
+
 #include "common.h"
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -37,6 +39,9 @@ namespace geobi { namespace { __device__ unsigned long long g_stamps_bwd[16384][
 #include "feast_dev.h"
 
 namespace geobi {
+
+// column tiles of 32 per workgroup
+static int feast_fused_nt(int nout) { return nout <= 32 ? 1 : (nout <= 64 ? 2 : 4); }
 
 namespace {
 
@@ -1281,29 +1286,6 @@ int launch_rowpass_fused128(const FeastIn& in, const RowpassLaunch& r, hipStream
 }
 }  // namespace
 
-// column parts of the fused kernel from one process (parity tests, A/B timing): 1 / 2, 0 = chosen per launch
-int set_column_parts(int parts) {
-  if (parts < 0 || parts > 2) return set_error("fused kernel column parts: 1, 2 or 0 (per launch), got %d", parts);
-  g_col_parts.set(parts);
-  return 0;
-}
-
-// forms of the 64-channel backward row pass from one process (parity tests, A/B timing): 1 / 0, -1 = default
-int set_rowpass_form(int staged, int chunked64) {
-  if (staged < -1 || staged > 1 || chunked64 < -1 || chunked64 > 1)
-    return set_error("row-pass form: staged and chunked64 are 1, 0 or -1 (default), got %d, %d", staged, chunked64);
-  if (staged < 0) g_rp_staged.reset(); else g_rp_staged.set(staged);
-  if (chunked64 < 0) g_rp_chunked.reset(); else g_rp_chunked.set(chunked64);
-  return 0;
-}
-
-// both tile geometries from one process (parity tests, A/B timing): rows = 16 / 32, 0 = back to GEOBI_TILE16
-int set_tile_rows(int rows) {
-  if (rows != 0 && rows != 16 && rows != 32) return set_error("tile rows: 16, 32 or 0 (environment default), got %d", rows);
-  if (rows == 0) g_tile16.reset(); else g_tile16.set(rows == 16);
-  return 0;
-}
-
 // split inputs: the row is read in batches of 16 channels (32 at 128 channels), so the first part must end on such a
 // boundary; 128 channels: Cout 64 or 128 (GEOBI_ROWPASS_FUSED128=0: the GEMM + standalone row pass)
 static Knob g_rowpass_fused128{"GEOBI_ROWPASS_FUSED128", 1};   // A/B knob
@@ -1338,7 +1320,6 @@ int feast_rowpass_fused(const FeastIn& in, int Cin, int Cout, const RowpassLaunc
   return rc == kNoCase ? set_error("feast fused row pass: unsupported Cin=%d (per-edge logit channels %d)", Cin, in.LC) : rc;
 }
 
-int feast_fused_nt(int nout) { return nout <= 32 ? 1 : (nout <= 64 ? 2 : 4); }
 // packed weights + the QSELF floats softmax(c) behind them
 size_t feast_fused_fwd_pack_floats(int Cin, int Cout) { return (size_t)fused_k(Cin, 0) * 32 * feast_fused_nt(Cout) + QSELF; }
 size_t feast_fused_dx_pack_floats(int Cin, int Cout) { return (size_t)fused_k(Cout, 1) * 32 * feast_fused_nt(Cin) + QSELF; }
@@ -1434,3 +1415,32 @@ int feast_fused_dx(const FeastIn& gin, const int* rowptr_in, const int* pos, con
 }
 
 }  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+// both tile geometries from one process (parity tests, A/B timing): rows = 16 / 32, 0 = back to GEOBI_TILE16
+int geobi_set_tile_rows(int rows) {
+  if (rows != 0 && rows != 16 && rows != 32) return set_error("tile rows: 16, 32 or 0 (environment default), got %d", rows);
+  if (rows == 0) g_tile16.reset(); else g_tile16.set(rows == 16);
+  return 0;
+}
+
+// forms of the 64-channel backward row pass from one process (parity tests, A/B timing): 1 / 0, -1 = default
+int geobi_set_rowpass_form(int staged, int chunked64) {
+  if (staged < -1 || staged > 1 || chunked64 < -1 || chunked64 > 1)
+    return set_error("row-pass form: staged and chunked64 are 1, 0 or -1 (default), got %d, %d", staged, chunked64);
+  if (staged < 0) g_rp_staged.reset(); else g_rp_staged.set(staged);
+  if (chunked64 < 0) g_rp_chunked.reset(); else g_rp_chunked.set(chunked64);
+  return 0;
+}
+
+// column parts of the fused kernel from one process (parity tests, A/B timing): 1 / 2, 0 = chosen per launch
+int geobi_set_column_parts(int parts) {
+  if (parts < 0 || parts > 2) return set_error("fused kernel column parts: 1, 2 or 0 (per launch), got %d", parts);
+  g_col_parts.set(parts);
+  return 0;
+}
+
+}  // extern "C"

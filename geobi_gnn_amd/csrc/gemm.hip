@@ -7,6 +7,8 @@
 //   gemm_tn : C[I,J] = sum_m A[m,I] * B[m,J]   (weight gradients; the reduction runs over the
 //             node dimension, split across workgroups into partial slabs that a second kernel
 //             adds in a fixed order -> deterministic, no float atomics).
+#include "../../include/geobi_hip.h"
+
 #include "common.h"
 
 #include <algorithm>
@@ -795,3 +797,65 @@ int gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, 
 }
 
 }  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+int geobi_gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N,
+                  int K, const float* bias, float slope, void* stream) {
+  GEOBI_NOTNULL(A); GEOBI_NOTNULL(B); GEOBI_NOTNULL(C);
+  GemmEpilogue ep;
+  ep.bias = bias;
+  ep.slope = slope;
+  return gemm_nn(A, lda, B, ldb, transB, C, ldc, M, N, K, ep, as_stream(stream));
+}
+size_t geobi_gemm_tn_ws_bytes(int I, int J, int64_t M) { return gemm_tn_ws_bytes(I, J, M); }
+int geobi_gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, float* C, int ldc,
+                  void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_NOTNULL(A); GEOBI_NOTNULL(B); GEOBI_NOTNULL(C);
+  TnOutput o;
+  o.C = C;
+  o.ldc = ldc;
+  return gemm_tn(A, lda, B, ldb, M, I, J, -1, -1, o, ws, ws_bytes, as_stream(stream));
+}
+
+// The two products with every argument their launchers take, and what the launcher decided (include/geobi_hip.h)
+int geobi_debug_gemm_nn(const float* A, int lda, const float* B, int ldb, int transB, float* C, int ldc, int M, int N,
+                        int K, const float* bias, float slope, float* C1, int split, int ldc1, void* ws, size_t ws_bytes,
+                        int fixed_slices, int cfg, int64_t* plan, void* stream) {
+  GEOBI_NOTNULL(A); GEOBI_NOTNULL(B); GEOBI_NOTNULL(C); GEOBI_NOTNULL(plan);
+  GEOBI_REQUIRE(cfg >= 0 && cfg <= 5, "%s: cfg = %d (0: the launcher's choice, 1..5: a GEOBI_NN_CFG shape)", __func__, cfg);
+  GEOBI_REQUIRE(C1 == nullptr || (split >= 0 && split <= N && ldc1 >= N - split && ldc >= split),
+                "%s: split = %d, ldc = %d, ldc1 = %d do not hold N = %d columns", __func__, split, ldc, ldc1, N);
+  GemmEpilogue ep;
+  ep.bias = bias; ep.slope = slope;
+  ep.C1 = C1; ep.split = split; ep.ldc1 = ldc1;
+  ep.ws = ws; ep.ws_bytes = ws_bytes; ep.fixed_slices = fixed_slices;
+  NnPlan p;
+  const int rc = gemm_nn(A, lda, B, ldb, transB, C, ldc, M, N, K, ep, as_stream(stream), cfg, &p);
+  const int64_t v[8] = {p.fast, p.shape, p.wm * 1000 + p.wn * 100 + p.tm * 10 + p.tn, p.bk, p.slices, p.k_chunk, p.wide,
+                        p.slices > 1};
+  for (int i = 0; i < 8; ++i) plan[i] = v[i];
+  return rc;
+}
+int geobi_debug_gemm_tn(const float* A, int lda, const float* B, int ldb, int64_t M, int I, int J, int ones_row,
+                        int ones_col, int sum_row, int mode, float* C, int ldc, float* C2, float* C3, float* C4, int Cin,
+                        int Cout, int col0, int extra_row, int extra_col, int accumulate, void* ws, size_t ws_bytes,
+                        int64_t* plan, void* stream) {
+  GEOBI_NOTNULL(A); GEOBI_NOTNULL(B); GEOBI_NOTNULL(C); GEOBI_NOTNULL(plan);
+  GEOBI_REQUIRE(mode >= TN_PLAIN && mode <= TN_RPRIME, "%s: mode = %d (0 plain, 1 lin-unpack, 2 du/dc, 3 r')", __func__, mode);
+  if (mode == TN_PLAIN && (extra_row || extra_col)) GEOBI_NOTNULL(C2);
+  if (mode == TN_LIN_UNPACK) GEOBI_NOTNULL(C2);
+  TnOutput o;
+  o.mode = mode; o.C = C; o.ldc = ldc; o.C2 = C2; o.C3 = C3; o.C4 = C4;
+  o.Cin = Cin; o.Cout = Cout; o.col0 = col0;
+  o.extra_row = extra_row; o.extra_col = extra_col; o.accumulate = accumulate;
+  TnPlan p;
+  const int rc = gemm_tn(A, lda, B, ldb, M, I, J, ones_row, ones_col, o, ws, ws_bytes, as_stream(stream), sum_row, &p);
+  const int64_t v[8] = {p.va, p.ti, p.tj, p.tiles_i, p.tiles_j, p.blocks_y, p.m_per_slice, p.bias_blocks};
+  for (int i = 0; i < 8; ++i) plan[i] = v[i];
+  return rc;
+}
+
+}  // extern "C"

@@ -3,9 +3,11 @@
 //   face_geom   /root/reference/code/network.py:332-337 + data_util.py:182-198:
 //               x_f = cat(x_f[:, :6], centroid(pred. verts), unit normal(pred. verts));
 //               backward scatters into the vertices through vertex -> (face, corner) inverse
-//               lists (segment_sum in pool.hip), not atomics.
+//               lists (segment_sum in segment.hip), not atomics.
 //   head        network.py:324-343: Linear(32,1024) + leaky_relu(0.2) + Linear(1024, 1|3), then
 //               vertex head: (* depth_direction) + xyz;   face head: F.normalize(dim=1).
+#include "../../include/geobi_hip.h"
+
 #include "common.h"
 
 #include <algorithm>
@@ -326,33 +328,6 @@ int row_loss_bwd(const float* a, const float* b, const float* w, const float* go
 // the second buffer of the ping-pong over the positions
 static float* carve_positions(Arena& a, int64_t V) { return a.take<float>((size_t)V * 3); }
 
-size_t update_position_ws_bytes(int64_t V, int64_t F) {
-  (void)F;
-  return carve_bytes([&](Arena& a) { carve_positions(a, V); });
-}
-
-int update_position2(const float* points, const int32_t* fv, const int32_t* vf, int maxval, const float* normals,
-                     const float* dd, int64_t V, int64_t F, int n_iter, float* out, void* ws, size_t ws_bytes,
-                     hipStream_t s) {
-  GEOBI_REQUIRE(V > 0 && F > 0 && n_iter >= 0, "update_position2: empty mesh");
-  Arena a(ws, ws_bytes);
-  float* tmp = carve_positions(a, V);
-  GEOBI_WS_CHECK("update_position2", a, ws, ws_bytes);
-  // ping-pong so that the LAST iteration lands in `out`
-  const float* src = points;
-  if (n_iter == 0) {
-    GEOBI_HIP(hipMemcpyAsync(out, points, sizeof(float) * V * 3, hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  for (int it = 0; it < n_iter; ++it) {
-    float* dst = ((n_iter - 1 - it) % 2 == 0) ? out : tmp;
-    vertex_update_kernel<<<cdiv(V, 256), 256, 0, s>>>(src, nullptr, fv, normals, vf, maxval, dd, (int)V, dst);
-    src = dst;
-  }
-  GEOBI_LAUNCH_OK();
-  return 0;
-}
-
 int face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
                   hipStream_t s) {
   if (F <= 0) return 0;
@@ -468,17 +443,6 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, c
 }
 }  // namespace
 
-int adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-              float bias_corr1, float bias_corr2, hipStream_t s) {
-  GEOBI_REQUIRE(n > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f, "adam_flat: n = %lld, bias corrections %g, %g", (long long)n,
-                bias_corr1, bias_corr2);
-  GEOBI_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, "adam_flat: 16-byte aligned vectors");
-  adam_flat_kernel<<<cdiv(cdiv(n, 4), 256), 256, 0, s>>>(p, g, m, v, n, lr / bias_corr1, b1, b2, eps, wd,
-                                                         1.0f / sqrtf(bias_corr2));
-  GEOBI_LAUNCH_OK();
-  return 0;
-}
-
 // ---------------------------------------------------------------------------- per-mesh rotation of a union batch
 // code/dataset.py:39-69 turns every training sample by its own random rotation before the loader hands it over; here the
 // samples are already one disjoint-union graph, so part p (rows ptr[p] .. ptr[p + 1]) takes matrix p: out = in @ R.  The
@@ -519,8 +483,86 @@ __global__ __launch_bounds__(256) void rotate_parts_kernel(RotateJob job, float*
 }
 }  // namespace
 
-int rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
-                 hipStream_t s) {
+}  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+int geobi_face_geom_fwd(const float* verts, const int32_t* fv, const float* xf, int ldxf, int64_t F, float* out,
+                        void* stream) {
+  GEOBI_SIZES(F, 0);
+  return face_geom_fwd(verts, fv, xf, ldxf, F, out, as_stream(stream));
+}
+int geobi_face_geom_bwd(const float* verts, const int32_t* fv, const float* gout, int64_t F, float* corner_grad,
+                        void* stream) {
+  GEOBI_SIZES(F, 0);
+  return face_geom_bwd(verts, fv, gout, F, corner_grad, as_stream(stream));
+}
+
+int geobi_head_fwd(const float* x, int Cin, int64_t N, const float* w1, const float* b1, int K, const float* w2,
+                   const float* b2, int nout, float slope, int mode, const float* dd, const float* resid,
+                   int ld_resid, float* h, float* raw, float* out, void* stream) {
+  GEOBI_SIZES(N, 0);
+  GEOBI_NOTNULL(x); GEOBI_NOTNULL(w1); GEOBI_NOTNULL(b1); GEOBI_NOTNULL(w2); GEOBI_NOTNULL(b2);
+  GEOBI_NOTNULL(raw); GEOBI_NOTNULL(out);
+  if (mode == 0) GEOBI_NOTNULL(resid);
+  return head_fwd(x, Cin, N, w1, b1, K, w2, b2, nout, slope, mode, dd, resid, ld_resid, h, raw, out, as_stream(stream));
+}
+size_t geobi_head_bwd_ws_bytes(int64_t N, int Cin, int K) { return head_bwd_ws_bytes(N, Cin, K); }
+int geobi_head_bwd(const float* x, int Cin, int64_t N, const float* w1, const float* b1, int K, const float* w2,
+                   int nout, float slope, int mode, const float* dd, const float* h, const float* raw, const float* gout,
+                   float* dx, float* dw1, float* db1, float* dw2, float* db2, int accumulate, void* ws,
+                   size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(N, 0);
+  GEOBI_NOTNULL(x); GEOBI_NOTNULL(w1); GEOBI_NOTNULL(w2); GEOBI_NOTNULL(raw); GEOBI_NOTNULL(gout);
+  GEOBI_NOTNULL(dw1); GEOBI_NOTNULL(db1); GEOBI_NOTNULL(dw2); GEOBI_NOTNULL(db2);
+  return head_bwd(x, Cin, N, w1, b1, K, w2, nout, slope, mode, dd, h, raw, gout, dx, dw1, db1, dw2, db2, accumulate, ws,
+                  ws_bytes, as_stream(stream));
+}
+
+size_t geobi_row_loss_ws_bytes(int64_t n) { return row_loss_ws_bytes(n); }
+int geobi_row_loss_fwd(const float* a, const float* b, const float* w, int64_t n, int kind, float scale, float* out,
+                       void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(n, 0);
+  GEOBI_NOTNULL(a); GEOBI_NOTNULL(b); GEOBI_NOTNULL(out);
+  return row_loss_fwd(a, b, w, n, kind, scale, out, ws, ws_bytes, as_stream(stream));
+}
+int geobi_row_loss_bwd(const float* a, const float* b, const float* w, const float* gout, int64_t n, int kind,
+                       float scale, float* ga, void* stream) {
+  GEOBI_SIZES(n, 0);
+  GEOBI_NOTNULL(a); GEOBI_NOTNULL(b); GEOBI_NOTNULL(gout); GEOBI_NOTNULL(ga);
+  return row_loss_bwd(a, b, w, gout, n, kind, scale, ga, as_stream(stream));
+}
+
+int geobi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, float bias_corr1, float bias_corr2, void* stream) {
+  GEOBI_NOTNULL(p); GEOBI_NOTNULL(g); GEOBI_NOTNULL(m); GEOBI_NOTNULL(v);
+  hipStream_t s = as_stream(stream);
+  GEOBI_REQUIRE(n > 0 && bias_corr1 > 0.f && bias_corr2 > 0.f, "adam_flat: n = %lld, bias corrections %g, %g", (long long)n,
+                bias_corr1, bias_corr2);
+  GEOBI_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, "adam_flat: 16-byte aligned vectors");
+  adam_flat_kernel<<<cdiv(cdiv(n, 4), 256), 256, 0, s>>>(p, g, m, v, n, lr / bias_corr1, beta1, beta2, eps, weight_decay,
+                                                         1.0f / sqrtf(bias_corr2));
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+int geobi_rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int ldx, int x_triples, float* y, float* dd,
+                       int64_t n, void* stream) {
+  GEOBI_SIZES(n, 0);
+  if (P < 1) return set_error("%s: P = %d parts (at least one)", __func__, P);
+  GEOBI_NOTNULL(part_ptr); GEOBI_NOTNULL(R);
+  if (x_triples < 0 || ldx < 3 * x_triples)
+    return set_error("%s: ldx = %d is shorter than the x_triples = %d column triples to turn", __func__, ldx, x_triples);
+  if (part_ptr[0] != 0 || part_ptr[P] != n)
+    return set_error("%s: part_ptr runs from %lld to %lld, not from 0 to n = %lld", __func__, (long long)part_ptr[0],
+                     (long long)part_ptr[P], (long long)n);
+  for (int p = 0; p < P; ++p)
+    if (part_ptr[p + 1] < part_ptr[p]) return set_error("%s: part_ptr decreases at part %d", __func__, p);
+  if (n == 0) return 0;
+  GEOBI_NOTNULL(x);
+  hipStream_t s = as_stream(stream);
   for (int base = 0; base < P; base += kMaxParts) {
     RotateJob job;
     fill_parts(&job.rows, part_ptr, base, P);
@@ -535,4 +577,34 @@ int rotate_parts(const int64_t* part_ptr, int P, const float* R, float* x, int l
   return 0;
 }
 
-}  // namespace geobi
+size_t geobi_update_position_ws_bytes(int64_t V, int64_t F) {
+  (void)F;
+  return carve_bytes([&](Arena& a) { carve_positions(a, V); });
+}
+
+int geobi_update_position2(const float* points, const int32_t* fv, const int32_t* vf, int maxval,
+                           const float* normals, const float* dd, int64_t V, int64_t F, int n_iter, float* out,
+                           void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(V > F ? V : F, 0);
+  GEOBI_NOTNULL(points); GEOBI_NOTNULL(fv); GEOBI_NOTNULL(vf); GEOBI_NOTNULL(normals); GEOBI_NOTNULL(out);
+  hipStream_t s = as_stream(stream);
+  GEOBI_REQUIRE(V > 0 && F > 0 && n_iter >= 0, "update_position2: empty mesh");
+  Arena a(ws, ws_bytes);
+  float* tmp = carve_positions(a, V);
+  GEOBI_WS_CHECK("update_position2", a, ws, ws_bytes);
+  // ping-pong so that the LAST iteration lands in `out`
+  const float* src = points;
+  if (n_iter == 0) {
+    GEOBI_HIP(hipMemcpyAsync(out, points, sizeof(float) * V * 3, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  for (int it = 0; it < n_iter; ++it) {
+    float* dst = ((n_iter - 1 - it) % 2 == 0) ? out : tmp;
+    vertex_update_kernel<<<cdiv(V, 256), 256, 0, s>>>(src, nullptr, fv, normals, vf, maxval, dd, (int)V, dst);
+    src = dst;
+  }
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+}  // extern "C"

@@ -7,6 +7,9 @@
 // Self loops are dropped here: FeaStConv removes and re-adds exactly one per node, which
 // the conv kernels apply implicitly, and the pooling layer drops them first too
 // (/root/reference/code/net_util.py:163).
+//
+// Also here, with their entry points: the batched union copy (geobi_concat32) and the two index builders of the pooled
+// graphs, geobi_expand_rowptr (CSR row pointers -> one row id per edge) and geobi_gather_f32.
 #include "common.h"
 #include "device_steps.h"
 #include "../../include/geobi_hip.h"
@@ -16,17 +19,6 @@
 namespace geobi {
 
 namespace {
-
-constexpr uint64_t kSentinel = ~0ull;
-
-// Keys are (segment << bits) | neighbour with (1 << bits) > N, so the radix sort only has to look at
-// 2 * bits bits (34 for the 82 k-node level-0 facet graph) instead of 64.  The sentinel (all ones)
-// still sorts last because every valid key is < 2^(2 bits) - 1.
-static inline int key_bits(int64_t N) {
-  int b = 1;
-  while ((1ll << b) <= N) ++b;
-  return b;
-}
 
 __global__ void make_keys_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ nbr, int64_t E,
                                  int64_t N, int drop_self, int bits, uint64_t* __restrict__ keys,
@@ -116,6 +108,46 @@ struct SortBuffers { uint64_t *k_in, *k_out; int32_t *v_in, *v_out; PairSort<uin
 SortBuffers carve_sort(Arena& a, int64_t E) {
   return {a.take<uint64_t>(E), a.take<uint64_t>(E), a.take<int32_t>(E), a.take<int32_t>(E),
           PairSort<uint64_t, int32_t>::take(a, E)};
+}
+
+// ---------------------------------------------------------------- batched union copy (geobi_concat32)
+constexpr int kMaxSegs = 96;
+struct ConcatJob {
+  const uint32_t* src[kMaxSegs];
+  uint32_t* dst[kMaxSegs];
+  int64_t start[kMaxSegs + 1];     // element offsets of the jobs in the launch's index space
+  uint32_t fill[kMaxSegs];         // int32 add, or the bits of the float fill value
+  int n, is_float;
+};
+
+// One launch for every array of a union batch: 4 elements per thread and step; the job of an element is found by a
+// binary search (find_part, common.h) over <= 96 start offsets held in LDS.
+__global__ __launch_bounds__(256) void concat32_kernel(ConcatJob job) {
+  __shared__ int64_t s_start[kMaxSegs + 1];
+  for (int i = threadIdx.x; i <= job.n; i += 256) s_start[i] = job.start[i];
+  __syncthreads();
+  const int64_t total = s_start[job.n];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int lo = find_part(s_start, job.n, i);
+    const int64_t k = i - s_start[lo];
+    const uint32_t* src = job.src[lo];
+    uint32_t v = job.fill[lo];
+    if (src != nullptr) v = job.is_float ? src[k] : src[k] + v;
+    job.dst[lo][k] = v;
+  }
+}
+
+// ---------------------------------------------------------------- index builders of the pooled graphs
+__global__ void expand_rowptr_kernel(const int* __restrict__ rowptr, int N, int* __restrict__ row) {
+  int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  for (int e = rowptr[n]; e < rowptr[n + 1]; ++e) row[e] = n;
+}
+
+__global__ void gather_f32_kernel(const float* __restrict__ src, const int* __restrict__ idx, int64_t n,
+                                  float* __restrict__ dst) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { int k = idx[i]; dst[i] = k >= 0 ? src[k] : 0.f; }
 }
 
 }  // namespace
@@ -210,46 +242,26 @@ int geobi_csr_reverse_index(const int32_t* rowptr, const int32_t* row, const int
   return csr_reverse_index(rowptr, row, col, E, pos_rev, flag, as_stream(stream));
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------- batched union copy (geobi_concat32)
-namespace geobi {
-namespace {
-constexpr int kMaxSegs = 96;
-struct ConcatJob {
-  const uint32_t* src[kMaxSegs];
-  uint32_t* dst[kMaxSegs];
-  int64_t start[kMaxSegs + 1];     // element offsets of the jobs in the launch's index space
-  uint32_t fill[kMaxSegs];         // int32 add, or the bits of the float fill value
-  int n, is_float;
-};
-
-// One launch for every array of a union batch: 4 elements per thread and step; the job of an element is found by a
-// binary search (find_part, common.h) over <= 96 start offsets held in LDS.
-__global__ __launch_bounds__(256) void concat32_kernel(ConcatJob job) {
-  __shared__ int64_t s_start[kMaxSegs + 1];
-  for (int i = threadIdx.x; i <= job.n; i += 256) s_start[i] = job.start[i];
-  __syncthreads();
-  const int64_t total = s_start[job.n];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int lo = find_part(s_start, job.n, i);
-    const int64_t k = i - s_start[lo];
-    const uint32_t* src = job.src[lo];
-    uint32_t v = job.fill[lo];
-    if (src != nullptr) v = job.is_float ? src[k] : src[k] + v;
-    job.dst[lo][k] = v;
-  }
+int geobi_expand_rowptr(const int32_t* rowptr, int64_t N, int32_t* row, void* stream) {
+  GEOBI_SIZES(N, 0);
+  hipStream_t s = as_stream(stream);
+  if (N <= 0) return 0;
+  expand_rowptr_kernel<<<cdiv(N, 256), 256, 0, s>>>(rowptr, (int)N, row);
+  GEOBI_LAUNCH_OK();
+  return 0;
 }
-}  // namespace
 
-int concat32(const CopySeg* segs, int n_segs, int is_float, hipStream_t s) {
+int geobi_concat32(const geobi_copy_seg_t* segs, int n_segs, int is_float, void* stream) {
+  if (n_segs <= 0) return 0;
+  GEOBI_NOTNULL(segs);
+  hipStream_t s = as_stream(stream);
   for (int base = 0; base < n_segs; base += kMaxSegs) {
     ConcatJob job;
     job.n = n_segs - base < kMaxSegs ? n_segs - base : kMaxSegs;
     job.is_float = is_float;
     job.start[0] = 0;
     for (int i = 0; i < job.n; ++i) {
-      const CopySeg& g = segs[base + i];
+      const geobi_copy_seg_t& g = segs[base + i];
       GEOBI_REQUIRE(g.n >= 0 && (g.n == 0 || g.dst != nullptr), "concat32: bad segment %d", base + i);
       job.src[i] = (const uint32_t*)g.src;
       job.dst[i] = (uint32_t*)g.dst;
@@ -268,4 +280,13 @@ int concat32(const CopySeg* segs, int n_segs, int is_float, hipStream_t s) {
   return 0;
 }
 
-}  // namespace geobi
+int geobi_gather_f32(const float* src, const int32_t* idx, int64_t n, float* dst, void* stream) {
+  GEOBI_SIZES(0, n);
+  hipStream_t s = as_stream(stream);
+  if (n <= 0) return 0;
+  gather_f32_kernel<<<cdiv(n, 256), 256, 0, s>>>(src, idx, n, dst);
+  GEOBI_LAUNCH_OK();
+  return 0;
+}
+
+}  // extern "C"

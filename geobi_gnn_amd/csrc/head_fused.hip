@@ -9,6 +9,8 @@
 // Any pairing k(s, half) works as long as A and B agree.  Two pairings are used:
 //   "contiguous"  k(s, half) = 16 half + s      -- both operands are 16 contiguous floats per lane
 //   "accumulator" k(r, half) = row(r, half)     -- a C/D tile is fed back as the B operand as is
+#include "../../include/geobi_hip.h"
+
 #include "common.h"
 
 #include <cstdlib>
@@ -547,11 +549,6 @@ bool head_fused_supported(int Cin, int K, int nout) { return Cin == CIN && K == 
 
 // 0: exact fp32 MFMA (default); 1: the first GEMM of the heads as six bf16 products (head_fwd_fused_bf16x3_kernel)
 static Knob g_head_precision{"GEOBI_HEAD_BF16X3", 0};
-int set_head_precision(int mode) {
-  GEOBI_REQUIRE(mode == 0 || mode == 1, "head precision: 0 (fp32) or 1 (3 x bf16 split, six products)");
-  g_head_precision.set(mode);
-  return 0;
-}
 
 int head_fwd_fused(const float* x, int64_t N, const float* w1, const float* b1, const float* w2, const float* b2,
                    int nout, float slope, int mode, const float* dd, const float* resid, int ld_resid, float* raw,
@@ -623,3 +620,15 @@ int head_bwd_fused(const float* x, int64_t N, const float* w1, const float* b1, 
 }
 
 }  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+int geobi_set_head_precision(int mode) {
+  GEOBI_REQUIRE(mode == 0 || mode == 1, "head precision: 0 (fp32) or 1 (3 x bf16 split, six products)");
+  g_head_precision.set(mode);
+  return 0;
+}
+
+}  // extern "C"

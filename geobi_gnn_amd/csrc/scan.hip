@@ -1,5 +1,5 @@
 // The library's exclusive int scan, out[i] = in[0] + ... + in[i - 1]: what IntScan of device_steps.h runs for every
-// count-to-offset step of clean.hip, grid.hip, meshprep.hip, patch.hip and pool.hip.  Three forms by size:
+// count-to-offset step of clean.hip, grid.hip, meshprep.hip, patch.hip, match.hip, segment.hip and pool.hip.  Three forms:
 //
 //   n <= 2^14           one 1024-thread block, one step                            (walk_exclusive_scan_kernel<1>)
 //   2^14 < n <= 2^18    several 256-thread blocks with decoupled look-back, or -- GEOBI_SCAN_LOOKBACK=0 /
@@ -15,6 +15,8 @@
 // aligned and i0 + 16 <= n, else each int is loaded and stored on its own behind an i < n guard.  The look-back state has
 // 4096 words for at most cdiv(2^18, 4096) = 64 blocks.  The wave-sum arrays have WAVES entries per list (16 for the
 // walk, 4 for the look-back kernel), indexed by threadIdx.x >> 6.
+#include "../../include/geobi_hip.h"
+
 #include "block_scan.h"
 #include "common.h"
 #include "device_steps.h"
@@ -161,9 +163,6 @@ hipError_t lookback_scan(const int* in, int* out, int64_t n, hipStream_t s) {
 
 }  // namespace
 
-// Test hook (geobi_set_scan_lookback): 1 / 0 force the form, a negative value goes back to what the environment says.
-void set_scan_lookback(int on) { if (on < 0) g_scan_lookback.reset(); else g_scan_lookback.set(on != 0); }
-
 size_t scan_ws_bytes(int64_t n) { return n <= kSmallScan ? 16 : ExclusiveScan<int>::temp_bytes(n); }
 
 int scan_exclusive_i32(void* temp, size_t temp_bytes, const int* in, int* out, int64_t n, hipStream_t s) {
@@ -193,3 +192,32 @@ int scan_exclusive_i32_pair(const int* in_a, const int* in_b, int* out_a, int* o
 }
 
 }  // namespace geobi
+
+using namespace geobi;
+
+extern "C" {
+
+// Test hook: 1 / 0 force the look-back form, a negative value goes back to what the environment says.
+int geobi_set_scan_lookback(int on) {
+  if (on < 0) g_scan_lookback.reset(); else g_scan_lookback.set(on != 0);
+  return 0;
+}
+
+size_t geobi_debug_scan_ws_bytes(int64_t n) { return scan_ws_bytes(n); }
+int geobi_debug_scan_exclusive_i32(const int32_t* in, int32_t* out, int64_t n, void* ws, size_t ws_bytes, void* stream) {
+  GEOBI_SIZES(0, n);
+  if (n <= 0) return 0;
+  GEOBI_NOTNULL(in); GEOBI_NOTNULL(out); GEOBI_NOTNULL(ws);
+  GEOBI_REQUIRE(ws_bytes >= scan_ws_bytes(n), "%s: workspace too small (%zu < %zu)", __func__, ws_bytes, scan_ws_bytes(n));
+  return scan_exclusive_i32(ws, ws_bytes, in, out, n, as_stream(stream));
+}
+int geobi_debug_scan_exclusive_i32_pair(const int32_t* in_a, const int32_t* in_b, int32_t* out_a, int32_t* out_b, int64_t n,
+                                        void* stream) {
+  GEOBI_SIZES(0, n);
+  if (n <= 0) return 0;
+  GEOBI_NOTNULL(in_a); GEOBI_NOTNULL(in_b); GEOBI_NOTNULL(out_a); GEOBI_NOTNULL(out_b);
+  GEOBI_REQUIRE(n <= kSmallScan, "%s: n = %lld, the pair scan takes at most 2^18 elements", __func__, (long long)n);
+  return scan_exclusive_i32_pair(in_a, in_b, out_a, out_b, n, as_stream(stream));
+}
+
+}  // extern "C"

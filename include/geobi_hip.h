@@ -1378,8 +1378,8 @@ int geobi_prof_enable(int kernel);
  * differences to the row maximum, i.e. FINITE and <= 0: <= 2 ulp against exp, results below 2^-126 flush to 0; a
  * non-finite argument is outside its contract).  Exposed so that a test can check it in isolation.              */
 int geobi_debug_exp_le0(const float* x, float* y, int64_t n, void* stream);
-/* diagnostic entries of the pooling front end (csrc/pool.hip, csrc/scan.hip), for tests: forms that otherwise only the
- * executor calls.
+/* diagnostic entries of the pooling front end (csrc/match.hip, segment.hip, pool.hip, scan.hip), for tests: forms that
+ * otherwise only the executor calls.
  *   geobi_debug_scan_exclusive_i32     : the library's exclusive int scan (out[i] = in[0] + ... + in[i-1]); workspace of
  *                                        geobi_debug_scan_ws_bytes(n) bytes
  *   geobi_debug_scan_exclusive_i32_pair: two such scans of n <= 2^18 elements each in one launch (the dual scan of

@@ -1,4 +1,4 @@
-"""The index builders under every kernel (csrc/graph.hip, the tail of csrc/pool.hip, capi.hip) stated in plain numpy:
+"""The index builders under every kernel (csrc/graph.hip, with their entry points) stated in plain numpy:
 int64, loops and np.lexsort.  One function per entry point, its contract written out from include/geobi_hip.h and the
 kernels; the device tests (tests/test_gpu_graph.py) compare with it exactly, tests/test_graph_model_host.py pins the
 model itself to a dense adjacency count on a CPU-only machine.  The inputs of the device tests live here too, so that

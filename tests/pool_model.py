@@ -1,5 +1,5 @@
-"""The pooling front end (csrc/pool.hip) stated in plain numpy: int64 / fp64, loops where a loop is the clearest
-statement.  Written from the semantics in the file's header and in include/geobi_hip.h, not from the kernels; the device
+"""The pooling front end (csrc/match.hip, csrc/segment.hip, csrc/pool.hip) stated in plain numpy: int64 / fp64, loops where
+a loop is the clearest statement.  Written from the semantics in the files' headers and in include/geobi_hip.h, not from the kernels; the device
 tests (tests/test_gpu_pool.py) compare with it exactly wherever the result is an integer or a selection, and
 tests/test_pool_model_host.py pins the model itself to the oracle's sequential rules on a CPU-only machine.  The inputs
 of the device tests live here too, so that both files see the same ones.

@@ -1,8 +1,8 @@
-"""The pooling front end (csrc/pool.hip) through the C ABI against the plain model of tests/pool_model.py, at the edges
-of its paths: every form of the matching tail and of the scans (forced through geobi_set_match_scanfree /
-geobi_set_scan_lookback), the state of the matching after every call, the bitonic row merge at gathered counts of
-0 / 1 / 31 / 32 / 33 / 63 / 64 / 65, the segment reductions on negative, signed-zero, infinite, tied and empty segments,
-and the edge weights element by element.
+"""The pooling front end (csrc/match.hip, csrc/segment.hip, csrc/pool.hip) through the C ABI against the plain model of
+tests/pool_model.py, at the edges of its paths: every form of the matching tail and of the scans (forced through
+geobi_set_match_scanfree / geobi_set_scan_lookback), the state of the matching after every call, the bitonic row merge
+at gathered counts of 0 / 1 / 31 / 32 / 33 / 63 / 64 / 65, the segment reductions on negative, signed-zero, infinite,
+tied and empty segments, and the edge weights element by element.
 
 Bars: every integer output and every selection (max, arg, routed gradient, merged weight) is compared EXACTLY; sums,
 means and the edge weights have the bounds stated at their tests, each derived from fp32 arithmetic."""

@@ -10,7 +10,7 @@ mkdir -p "$HERE/build/variants"
 bash "$HERE/build.sh" > /dev/null
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function "$@" -c "$HERE/$UNIT.hip" -o "$HERE/build/variants/${UNIT}_$NAME.o" 2>&1 | grep -E "error|Spill: [1-9]" || true
 OBJS=()
-for f in capi executor graph gemm feast feast_fused pool geom head_fused meshprep patch dist; do
+for f in $(bash "$HERE/build.sh" --list-units); do      # the product's unit list, minus the unit replaced
   if [ "$f" = "$UNIT" ]; then OBJS+=("$HERE/build/variants/${UNIT}_$NAME.o"); else OBJS+=("$HERE/build/$f.o"); fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$HERE/build/variants/libgeobi_hip_$NAME.so" "${OBJS[@]}"
